@@ -56,3 +56,46 @@ def test_workloads_and_cli():
     assert out.returncode == 0
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in out.stdout
+
+
+def test_full_and_dump_outputs_flags():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0
+    for flag in ("--full", "--dump-outputs"):
+        assert flag in out.stdout
+
+
+def test_dump_outputs_is_deterministic_and_bounded(tmp_path):
+    """dump_outputs on a small CPU model: float32 / float64 files, the same sample positions on every call, the sample
+    and the norms are the gradients', a parameter without a gradient reads as zeros, and the default sample of a large
+    gradient stays far below 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench()
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(64, 300), torch.nn.ReLU(), torch.nn.Linear(300, 6), torch.nn.Linear(6, 6))
+    x = torch.randn(5, 64)
+    logits = m[2](m[1](m[0](x)))                   # the last Linear gets no gradient
+    loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, (torch.rand(5, 6) > 0.5).float())
+    loss.backward()
+    names = b.dump_outputs(str(tmp_path / "a"), m, logits, loss, n_sample=1000)
+    b.dump_outputs(str(tmp_path / "b"), m, logits, loss, n_sample=1000)
+    assert names == ["grad_norms", "grad_sample", "logits", "loss"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    for n in names:
+        assert got[n].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy")))
+    assert got["logits"].shape == (5, 6) and got["loss"].shape == (1,)
+    assert np.allclose(got["logits"], logits.detach().numpy()) and np.isclose(got["loss"][0], loss.item())
+    params = list(m.parameters())
+    grads = [p.grad.reshape(-1) if p.grad is not None else torch.zeros(p.numel()) for p in params]
+    assert got["grad_norms"].dtype == np.float64 and got["grad_norms"].shape == (len(params),)
+    assert np.allclose(got["grad_norms"], [float(g.double().norm()) for g in grads])
+    assert got["grad_norms"][-1] == 0 and got["grad_norms"][-2] == 0
+    flat = torch.cat(grads)
+    idx = torch.randint(flat.numel(), (1000,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(got["grad_sample"], flat[idx].numpy())
+    big = torch.nn.Linear(4096, 4096, bias=False)
+    big.weight.grad = torch.ones_like(big.weight)
+    b.dump_outputs(str(tmp_path / "c"), big, torch.zeros(2, 6), torch.zeros(()))
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) < 64 << 20

@@ -6,7 +6,7 @@ TAG="$1"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out
 rm -rf $O/prof_$TAG && mkdir -p $O/prof_$TAG
-rocprofv3 -M --kernel-trace --stats --output-format csv -d $O/prof_$TAG/k -o k -- python3 bench.py --steps 10 --warmup 4 --no-cpu-baseline --no-secondary > $O/${TAG}_prof.log 2>&1
+rocprofv3 -M --kernel-trace --stats --output-format csv -d $O/prof_$TAG/k -o k -- python3 bench.py --full --steps 10 --warmup 4 --no-cpu-baseline --no-secondary > $O/${TAG}_prof.log 2>&1
 python3 tools/trace_timeline.py $O/prof_$TAG/k/k_kernel_trace.csv > $O/${TAG}_timeline_h768.txt
 cp $O/prof_$TAG/k/k_kernel_stats.csv $O/${TAG}_kernel_stats_h768.csv
 rm -f $O/prof_$TAG/k/k_kernel_trace.csv
