@@ -51,6 +51,11 @@ constexpr int BPM_ATTN_DQ_W32 = 5;
 constexpr int BPM_ATTN_DQ_W128 = 3;
 constexpr int BPM_ATTN_DQ_W64 = 4;
 constexpr int QT = BPM_ATTN_QT;      // queries per tile (dK/dV): a multiple of 32
+// head_dim 256 tiles: the dQ pass stages 32 keys per tile (K / V staging registers 32 instead of 64 in bf16: 228
+// registers, 2 waves per SIMD without spills); the f32 dK / dV pass stages 32 queries per tile (64 keys spill even at
+// one wave: 128 registers of K / V fragments, 128 of dK / dV accumulators and 128 of Q / dO staging).
+constexpr int BPM_ATTN_KT256_DQ = 32;
+constexpr int BPM_ATTN_QT256_F32 = 32;
 
 // Waves per SIMD each kernel is compiled for (register budget 512 / waves), per kernel (0 forward, 1 dQ, 2 dK/dV),
 // compute type and padded head_dim: the largest occupancy at which the kernel does not spill inside its tile loop.
@@ -58,13 +63,15 @@ constexpr int QT = BPM_ATTN_QT;      // queries per tile (dK/dV): a multiple of 
 // 110 us at 4 waves (12 registers spilled) -> 98 at 3.  Both backward kernels now compute one k-step of their second
 // product at a time (dQ: 112 registers at head_dim 64, 89 at 25, 166 at 128; dK/dV: 154 / 114 / 222), which fits one more
 // wave per SIMD without spills.  The f32 (parity-mode) kernels need
-// one wave fewer.
+// one wave fewer.  Head_dim 256 (bf16 / f32): forward 2 / 1 (244 registers in bf16; the f32 K / V images take 130 KiB of
+// LDS, one workgroup per CU anyway), dQ 2 / 1, dK / dV 1 / 1 (bf16: 256 accumulator + fragment registers spill at 2).
 template <typename CT>
 constexpr int attn_waves(int kernel, int dhp) {
     const bool bf = sizeof(CT) == 2;
     if (dhp <= 32) return kernel == 0 ? (bf ? BPM_ATTN_WF : 4) : (kernel == 2 ? (bf ? BPM_ATTN_DKV_W32 : 3) : (bf ? BPM_ATTN_DQ_W32 : 4));
     if (dhp <= 64) return kernel == 0 ? (bf ? 4 : 3) : kernel == 1 ? (bf ? BPM_ATTN_DQ_W64 : 3) : (bf ? BPM_ATTN_DKV_W64 : 2);
-    return kernel == 0 ? (bf ? 3 : 2) : (kernel == 1 && bf ? BPM_ATTN_DQ_W128 : BPM_ATTN_W128);
+    if (dhp <= 128) return kernel == 0 ? (bf ? 3 : 2) : (kernel == 1 && bf ? BPM_ATTN_DQ_W128 : BPM_ATTN_W128);
+    return kernel == 2 || !bf ? 1 : 2;
 }
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -100,6 +107,8 @@ template <typename CT, int DHP> struct Cfg {
     static constexpr int ROWB = DHP * SZ;                   // bytes per head row
     static constexpr int STRIDE = ROWB + Tr<CT>::TR_PAD_B;  // LDS image row stride
     static constexpr int CPR = ROWB / 16;                   // chunks per row
+    static constexpr int KTQ = DHP <= 128 ? KT : BPM_ATTN_KT256_DQ;   // keys per tile of the dQ pass
+    static constexpr int QTK = DHP <= 128 || SZ == 2 ? QT : BPM_ATTN_QT256_F32;   // queries per tile of the dK / dV pass
 };
 
 // cooperative copy of `rows` head rows (global row index row0.., bound nrows) into an LDS image
@@ -385,7 +394,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
-    char* vimg = smem + KT * C::STRIDE;
+    char* vimg = smem + C::KTQ * C::STRIDE;
 
     const int b = bh / P.H, h = bh % P.H;
     int tid_ = threadIdx.x;
@@ -433,14 +442,14 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
 
     const int q_hi = min(P.T, qb * 64 + 64) - 1;
     const int jend = min(P.S, P.qpos0 + q_hi * P.qstride + P.mask_off);
-    const int ntile = (jend + KT - 1) / KT;
+    const int ntile = (jend + C::KTQ - 1) / C::KTQ;
     const int lim = min(P.S, P.qpos0 + q * P.qstride + P.mask_off);
     const int lim_min = min(P.S, P.qpos0 + q0 * P.qstride + P.mask_off);
     const bool dropping = drop.thresh != 0;
     const uint32_t drow = ((uint32_t)bh * (uint32_t)P.T + (uint32_t)q) * (uint32_t)P.S;
     const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
 
-    RowStage<CT, DHP, KT> kst, vst;
+    RowStage<CT, DHP, C::KTQ> kst, vst;
     if (ntile > 0) { kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid); }
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
@@ -448,14 +457,14 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
         kst.store(kimg, tid);
         vst.store(vimg, tid);
         __syncthreads();
-        if (kt + 1 < ntile) { kst.load(Kh, (kt + 1) * KT, P.S, tid); vst.load(Vh, (kt + 1) * KT, P.S, tid); }
-        const int jb = kt * KT + 4 * g;
-        const bool edge = kt * KT + KT > lim_min;
+        if (kt + 1 < ntile) { kst.load(Kh, (kt + 1) * C::KTQ, P.S, tid); vst.load(Vh, (kt + 1) * C::KTQ, P.S, tid); }
+        const int jb = kt * C::KTQ + 4 * g;
+        const bool edge = kt * C::KTQ + C::KTQ > lim_min;
         const int rel = lim - jb;
         // one k-step of the dQ product (32 keys in bf16, 16 in f32) at a time: its dS lives only until its MFMAs
         constexpr int NPK = Tr<CT>::KSTEP / 16;
 #pragma unroll
-        for (int ks = 0; ks < KT / Tr<CT>::KSTEP; ++ks) {
+        for (int ks = 0; ks < C::KTQ / Tr<CT>::KSTEP; ++ks) {
             f32x4 ds[NPK];
 #pragma unroll
             for (int nn = 0; nn < NPK; ++nn) {
@@ -512,6 +521,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
             if (BPM_ATTN_SETPRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
         }
     }
+    static_assert(2 * C::KTQ * C::STRIDE >= 4 * store_rows16_bytes<CT, DHP>(), "one transpose block per wave in the K / V images");
     __syncthreads();                                   // every wave is done with the K / V images
     if (q0 < P.T)
         store_rows16<CT, DHP>(smem + wave * store_rows16_bytes<CT, DHP>(), (CT*)P.dQ + ((size_t)q0 * P.B + b) * P.lddq + h * P.dh,
@@ -525,7 +535,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
 template <typename CT, int DHP, bool XP>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves<CT>(1, DHP), attn_waves<CT>(1, DHP)))) void attn_bwd_dq_kernel(const AGroup grp) {
     typedef Cfg<CT, DHP> C;
-    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE];
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::KTQ * C::STRIDE];
     if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     const AProb& P = pick(grp, bid);
@@ -547,9 +557,9 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* qimg = smem;
-    char* doimg = smem + QT * C::STRIDE;
-    float* s_lse = (float*)(smem + 2 * QT * C::STRIDE);      // -lse * log2(e)
-    float* s_del = s_lse + QT;
+    char* doimg = smem + C::QTK * C::STRIDE;
+    float* s_lse = (float*)(smem + 2 * C::QTK * C::STRIDE);      // -lse * log2(e)
+    float* s_del = s_lse + C::QTK;
 
     const int b = bh / P.H, h = bh % P.H;
     int tid_ = threadIdx.x;
@@ -579,19 +589,19 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     const int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
     const int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);   // wave-uniform: tiles at or above it need no test
     const int i_first = first_row(kb * 64 - P.mask_off + 1);                                   // first query row that sees any key of the block
-    const int qt_lo = i_first / QT;
-    const int qt_hi = (P.T + QT - 1) / QT;
+    const int qt_lo = i_first / C::QTK;
+    const int qt_hi = (P.T + C::QTK - 1) / C::QTK;
     const bool dropping = drop.thresh != 0;
     const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
 
-    RowStage<CT, DHP, QT> qst, dost;
-    float n_lse = 0.f, n_del = 0.f;                    // threads < QT: next tile's -lse*log2(e) and delta
+    RowStage<CT, DHP, C::QTK> qst, dost;
+    float n_lse = 0.f, n_del = 0.f;                    // threads < QTK: next tile's -lse*log2(e) and delta
     const float* lse_h = P.lse + (size_t)bh * P.T;
     const float* del_h = P.delta + (size_t)bh * P.T;
     auto stage = [&](int qt) {
-        qst.load(Qh, qt * QT, P.T, tid);
-        dost.load(dOh, qt * QT, P.T, tid);
-        const int i = qt * QT + (tid & (QT - 1));
+        qst.load(Qh, qt * C::QTK, P.T, tid);
+        dost.load(dOh, qt * C::QTK, P.T, tid);
+        const int i = qt * C::QTK + (tid & (C::QTK - 1));
         const bool ok = i < P.T;
         const float l = lse_h[ok ? i : 0], dl = del_h[ok ? i : 0];
         n_lse = ok ? -l * LOG2E : 0.f;
@@ -603,15 +613,15 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
         __syncthreads();
         qst.store(qimg, tid);
         dost.store(doimg, tid);
-        if (tid < QT) { s_lse[tid] = n_lse; s_del[tid] = n_del; }
+        if (tid < C::QTK) { s_lse[tid] = n_lse; s_del[tid] = n_del; }
         __syncthreads();
         if (qt + 1 < qt_hi) stage(qt + 1);
-        const bool edge = (qt * QT < ilo_max) || (qt * QT + QT > P.T);
+        const bool edge = (qt * C::QTK < ilo_max) || (qt * C::QTK + C::QTK > P.T);
         // one k-step of the dV / dK products (32 queries in bf16, 16 in f32) at a time: its scores, probabilities and
         // dS live only until its MFMAs (half the registers of doing the whole 64-query tile first)
         constexpr int UPK = Tr<CT>::KSTEP / 16;
 #pragma unroll
-        for (int ks = 0; ks < QT / Tr<CT>::KSTEP; ++ks) {
+        for (int ks = 0; ks < C::QTK / Tr<CT>::KSTEP; ++ks) {
             f32x4 pd[UPK], ds[UPK];
 #pragma unroll
             for (int uu = 0; uu < UPK; ++uu) {
@@ -624,7 +634,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
                 }
                 const f32x4 l4 = *(const f32x4*)(s_lse + 16 * u + 4 * g);
                 const f32x4 d4 = *(const f32x4*)(s_del + 16 * u + 4 * g);
-                const int ib = qt * QT + 16 * u + 4 * g;       // query of element r is ib + r
+                const int ib = qt * C::QTK + 16 * u + 4 * g;       // query of element r is ib + r
                 f32x4 e4 = s_ * LOG2E + l4;
                 if (edge) {
 #pragma unroll
@@ -673,7 +683,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
             if (BPM_ATTN_SETPRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
         }
     }
-    static_assert(2 * QT * C::STRIDE >= 4 * store_rows16_bytes<CT, DHP>(), "one transpose block per wave in the Q / dO images");
+    static_assert(2 * C::QTK * C::STRIDE >= 4 * store_rows16_bytes<CT, DHP>(), "one transpose block per wave in the Q / dO images");
     __syncthreads();                                   // every wave is done with the Q / dO images
     if (j0 < P.S) {
         char* blk = smem + wave * store_rows16_bytes<CT, DHP>();
@@ -690,7 +700,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
 template <typename CT, int DHP>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves<CT>(2, DHP), attn_waves<CT>(2, DHP)))) void attn_bwd_dkv_kernel(const AGroup grp) {
     typedef Cfg<CT, DHP> C;
-    __shared__ __attribute__((aligned(16))) char smem[2 * QT * C::STRIDE + 2 * QT * 4];
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::QTK * C::STRIDE + 2 * C::QTK * 4];
     if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     const AProb& P = pick(grp, bid);
@@ -723,6 +733,7 @@ int fill(AGroup& g, const bpm_attn_problem* probs, int nprob, int blocks_over_S,
         AProb& p = g.p[i];
         if (q.B < 1 || q.H < 1 || q.T < 1 || q.S < 1 || q.dh < 1 || q.dh > q.dhp) return BPM_ERR_ARG;
         if (q.T > (1 << 22) || q.S > (1 << 22)) return BPM_ERR_ARG;      // index arithmetic is 32-bit (rows * 512 B per head fits 31 bits)
+        if ((long)(q.T > q.S ? q.T : q.S) * q.dhp * 4 > (1l << 31)) return BPM_ERR_ARG;   // ... and rows * 1 KiB at head_dim 256 in f32
         if (q.dhp != probs[0].dhp) return BPM_ERR_ARG;
         p.Q = (const char*)q.Q; p.K = (const char*)q.K; p.V = (const char*)q.V;
         p.O = (char*)q.O; p.ldo = q.ldo; p.lse = q.lse;
@@ -794,6 +805,7 @@ int dispatch(int which, int dhp, const AGroup& g, int total, hipStream_t s) {
         BPM_ATTN_CASE(32)
         BPM_ATTN_CASE(64)
         BPM_ATTN_CASE(128)
+        BPM_ATTN_CASE(256)
         default: return BPM_ERR_ARG;
     }
 #undef BPM_ATTN_CASE

@@ -1259,15 +1259,16 @@ extern "C" int bpm_split_rows(const bpm_split_problem* q, int n, void* stream) {
 struct ExpP { const void* q; const void* dO; void* qexp; void* dOexp; const void* Pd; float* dbias; int B, H, T, S, dh, dhp, ld; };
 
 constexpr int EXP_NT = 1024;      // 16 waves, one row each per pass (T*B = 16 rows at the headline: one pass)
+constexpr int EXP_MAXDH = 256;    // head_dim limit: bias sums of columns lane + 64 k, k < EXP_MAXDH / 64, per lane
 
 template <typename CT>
 __global__ __launch_bounds__(EXP_NT) void expand_heads_kernel(const Grp<ExpP> grp) {
-    __shared__ float red[EXP_NT / 64][128];
+    __shared__ float red[EXP_NT / 64][EXP_MAXDH];
     unsigned bid = blockIdx.x, nblk;
     const ExpP& P = pick(grp, bid, nblk);
     const int h = (int)bid, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int c0 = h * P.dh;
-    float acc0 = 0.f, acc1 = 0.f;                         // bias sums of columns lane, lane + 64 of this head
+    float acc[EXP_MAXDH / 64] = {};                       // bias sums of columns lane + 64 k of this head
     for (int tb = wv; tb < P.T * P.B; tb += EXP_NT / 64) {
         const int t = tb / P.B, b = tb - t * P.B;
         const size_t r = (size_t)(h * P.T + t) * P.B + b;
@@ -1283,12 +1284,14 @@ __global__ __launch_bounds__(EXP_NT) void expand_heads_kernel(const Grp<ExpP> gr
             const CT* prow = (const CT*)P.Pd + r * P.S;
             for (int j = lane; j < P.S; j += 64) rs += Tr<CT>::to_f(prow[j]);
             rs = wave_sum(rs);
-            if (lane < P.dh) acc0 += rs * Tr<CT>::to_f(drow[lane]);
-            if (lane + 64 < P.dh) acc1 += rs * Tr<CT>::to_f(drow[lane + 64]);
+#pragma unroll
+            for (int k = 0; k < EXP_MAXDH / 64; ++k)
+                if (lane + 64 * k < P.dh) acc[k] += rs * Tr<CT>::to_f(drow[lane + 64 * k]);
         }
     }
     if (!P.dbias) return;                                 // uniform per block
-    red[wv][lane] = acc0; red[wv][lane + 64] = acc1;
+#pragma unroll
+    for (int k = 0; k < EXP_MAXDH / 64; ++k) red[wv][lane + 64 * k] = acc[k];
     __syncthreads();
     for (int j = threadIdx.x; j < P.dh; j += EXP_NT) {
         float s = 0.f;
@@ -1304,7 +1307,7 @@ extern "C" int bpm_expand_heads(int dtype, const bpm_expand_problem* q, int n, v
     g.n = n; g.blk0[0] = 0; g.seedp = nullptr;
     for (int i = 0; i < n; ++i) {
         const bpm_expand_problem& s = q[i];
-        if (!s.q || !s.dO || !s.qexp || !s.dOexp || s.B < 1 || s.H < 1 || s.T < 1 || s.dh < 1 || s.dh > s.dhp || s.dh > 128 ||
+        if (!s.q || !s.dO || !s.qexp || !s.dOexp || s.B < 1 || s.H < 1 || s.T < 1 || s.dh < 1 || s.dh > s.dhp || s.dh > EXP_MAXDH ||
             s.ld < s.H * s.dh || (s.dbias && (!s.Pd || s.S < 1)))
             return BPM_ERR_ARG;
         ExpP& p = g.p[i];

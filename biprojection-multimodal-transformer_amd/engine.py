@@ -53,7 +53,9 @@ def dhp_for(dh: int) -> int:
         return 64
     if dh <= 128:
         return 128
-    raise ValueError(f"head_dim {dh} > 128 is not supported by the attention kernels")
+    if dh <= 256:
+        return 256
+    raise ValueError(f"head_dim {dh} > 256 is not supported by the attention kernels (limit 256)")
 
 
 _TABLES: Dict[Tuple[int, int, str], torch.Tensor] = {}
@@ -488,7 +490,7 @@ class EncoderGroupPlan:
         # 4096 rows, the merged K = 6144 data gradient, the dK / dV pass).  Equal to the dK / dV route in real arithmetic; the
         # roundings differ (dS instead of dK is rounded to CT), fixtures F7 / F9 / F11 hold both.  Crossmodal groups only.
         self._lowrank = (_LOWRANK and not cfg.biprojection and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs)
-                         and self.dh <= 128)
+                         and self.dh <= 256)
         self.ld, self.ld4 = pad32(d), pad32(4 * d)
         self.scale = self.dh ** -0.5
         dev, ct = store.device, ops.ct_torch(self.dtype)

@@ -121,7 +121,7 @@ int bpm_gemm_grouped(int dtype, int variant, const bpm_gemm_problem* probs /* ho
  * Replaces: torch.bmm / += attn_mask / F.softmax(float) / F.dropout / torch.bmm
  * (multihead_attention.py:110-126), buffered_future_mask (transformer.py:209-216)
  * and their backward.  Q [B,H,T,dhp] (pre-scaled by dh^-0.5), K/V [B,H,S,dhp],
- * dO [B,H,T,dhp]: CT head-major, dhp in {32,64,128}.  O, dQ, dK, dV: CT
+ * dO [B,H,T,dhp]: CT head-major, dhp in {32,64,128,256}.  O, dQ, dK, dV: CT
  * row-major [(t*B+b), ld], column h*dh + c.  lse, delta: fp32 [B,H,T].
  * mask_off: key j visible to query i iff j - i < mask_off (1 + |S-T| with
  * attn_mask; <= 0 means no mask).

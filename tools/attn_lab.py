@@ -18,7 +18,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bpmult_amd  # noqa: E402,F401
 from bpmult_amd import ops  # noqa: E402
+from bpmult_amd.engine import dhp_for  # noqa: E402
 from bpmult_amd.ops import BPM_BF16  # noqa: E402
+
+
+BF16_PEAK_TF = 2500.0     # MI355X dense bf16 MFMA peak (spec)
 
 
 def _time(fn, iters):
@@ -51,7 +55,7 @@ def main():
         from bpmult_amd import _lib
         _lib.check(_lib.lab_library().__enter__().bpm_debug_attn_pair(a.pair), "bpm_debug_attn_pair")   # -DBPM_LAB build only
     B, H, T, S, dh, G = a.B, a.H, a.T, a.S, a.dh, a.G
-    dhp = 32 if dh <= 32 else 64 if dh <= 64 else 128
+    dhp = dhp_for(dh)
     d = H * dh
     off = (1 << 30) if a.no_mask else 1 + abs(S - T)
     g = torch.Generator().manual_seed(3)
@@ -71,7 +75,8 @@ def main():
     res = {"shape": dict(B=B, H=H, T=T, S=S, head_dim=dh, encoders=G, mask=not a.no_mask, drop=a.drop, drop_encoders=a.drop_encoders)}
     for name, fn, fl in (("fwd", ops.attn_fwd, 4), ("bwd_dq", ops.attn_bwd_dq, 6), ("bwd_dkv", ops.attn_bwd_dkv, 8)):
         us = _time(lambda: fn(BPM_BF16, arr, 5), a.iters)
-        res[name] = {"us": round(us, 1), "tflops": round(fl * dh * pairs / us / 1e6, 1)}
+        tf = fl * dh * pairs / us / 1e6
+        res[name] = {"us": round(us, 1), "tflops": round(tf, 1), "bf16_peak_frac": round(tf / BF16_PEAK_TF, 3)}
     print(json.dumps(res))
 
 
