@@ -418,6 +418,9 @@ class GroupCfg:
     embed_dropout: float
     attn_mask: bool
     biprojection: bool
+    # self-attention-only stack, the reference's forward(x) (transformer.py:81-85, 158-159): keys and values are projected
+    # from the query rows' LayerNorm-0 output; no key / value source, no folded key / value state (_build_fwd_self)
+    self_only: bool = False
 
 
 SIDE, JOIN, MARK, WAIT, SIDE2 = "side", "join", "mark", "wait", "side2"
@@ -489,8 +492,8 @@ class EncoderGroupPlan:
         # elimination has T = 2: at hidden 768 this removes 1.5 of the step's 19.4 ms (the key / value weight gradients over
         # 4096 rows, the merged K = 6144 data gradient, the dK / dV pass).  Equal to the dK / dV route in real arithmetic; the
         # roundings differ (dS instead of dK is rounded to CT), fixtures F7 / F9 / F11 hold both.  Crossmodal groups only.
-        self._lowrank = (_LOWRANK and not cfg.biprojection and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs)
-                         and self.dh <= 256)
+        self._lowrank = (_LOWRANK and not cfg.self_only and not cfg.biprojection
+                         and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs) and self.dh <= 256)
         self.ld, self.ld4 = pad32(d), pad32(4 * d)
         self.scale = self.dh ** -0.5
         dev, ct = store.device, ops.ct_torch(self.dtype)
@@ -511,6 +514,9 @@ class EncoderGroupPlan:
             return t
 
         for e in self.encs:
+            if cfg.self_only:
+                self.buf.append(self._alloc_self(e, z, ct))
+                continue
             R, Rk = e.T * B, e.S * B
             tailp = bool(e.tail_rows)
             if tailp and (not cfg.biprojection or e.T < 2 or e.T_full is not None):
@@ -603,7 +609,7 @@ class EncoderGroupPlan:
         # table of the launch that turns folded K/V gradients into in_proj / LayerNorm parameter gradients
         lnK = 1 if cfg.biprojection else 0
         self._unfold = []                                  # one table per layer: its gradients are final with it
-        for i in range(L):
+        for i in range(0 if cfg.self_only else L):
             ud, blk = [], 0
             for e, b in zip(self.encs, self.buf):
                 pn = lambda leaf: self._pn(e, i, leaf)
@@ -624,10 +630,42 @@ class EncoderGroupPlan:
             self._dkv_side = "0"
         self._side_low = d < 512
         self.store.side_low = self._side_low
-        self._fwd = {True: self._build_fwd(True), False: self._build_fwd(False)}
+        build_fwd, build_bwd = (self._build_fwd_self, self._build_bwd_self) if cfg.self_only else (self._build_fwd, self._build_bwd)
+        self._fwd = {True: build_fwd(True), False: build_fwd(False)}
         # backward tables by (training, stores): stores = the first weight-gradient launch of each large matrix writes
         # instead of accumulating (the flat gradient buffer was not cleared: ParamStore.begin_backward(stores=True))
-        self._bwd = {(t, f): self._build_bwd(t, f) for t in (True, False) for f in (True, False)}
+        self._bwd = {(t, f): build_bwd(t, f) for t in (True, False) for f in (True, False)}
+
+    def _alloc_self(self, e: EncoderDesc, z, ct) -> dict:
+        """Buffers of one self-attention-only encoder (GroupCfg.self_only): the query chain of a crossmodal encoder whose
+        keys and values come from the same LayerNorm-0 rows as its queries."""
+        if e.S != e.T or e.tail_rows or e.T_full is not None or e.q_pos0 or e.q_stride != 1:
+            raise ValueError(f"encoder {e.prefix}: a self-attention-only encoder attends over its own {e.T} time steps "
+                             "(S == T, no gathered rows, no tail_rows)")
+        B, d, H, L, ld, ld4, dhp = self.B, self.cfg.d, self.cfg.H, self.cfg.layers, self.ld, self.ld4, self.dhp
+        R = e.T * B
+        b = dict(R=R, Rk=R, Rl=[R] * L, Tl=[e.T] * L, tailp=False)
+        b["x"] = [z(R, d) for _ in range(L + 1)]
+        b["out"] = z(e.T, B, d)
+        b["stf"] = (z(R), z(R))
+        for nm, shape, dt in (("xn", (R, ld), ct), ("qh", (B, H, e.T, dhp), ct), ("kh", (B, H, e.T, dhp), ct),
+                              ("vh", (B, H, e.T, dhp), ct), ("ao", (R, ld), ct), ("lse", (B, H, e.T), torch.float32),
+                              ("xmid", (R, d), torch.float32), ("xn2", (R, ld), ct), ("h1", (R, ld4), ct),
+                              ("st0m", (R,), torch.float32), ("st0r", (R,), torch.float32),
+                              ("st1m", (R,), torch.float32), ("st1r", (R,), torch.float32)):
+            b[nm] = [z(*shape, dt=dt) for _ in range(L)]
+        # backward temporaries: what the side stream's weight gradients read is double-buffered by layer parity (dyf: by
+        # layer mod 3, written one layer early), as in the other layer kinds
+        two = lambda *shape: [z(*shape, dt=ct), z(*shape, dt=ct)]
+        b["dx"], b["dxn"] = z(R, d), z(R, d)
+        b["dy"], b["dh1"] = two(R, ld), two(R, ld4)
+        b["dyf"] = [z(R, ld, dt=ct) for _ in range(3)]
+        # dQ | dK | dV side by side (the [R, 3d] operand of ONE d(xn) product when ld == d; one spare row, see dqkvs above)
+        b["dqkvs"] = two(R + 1, 3 * ld)
+        b["dqs"], b["dks"], b["dvs"] = ([t[:R, w * ld:(w + 1) * ld] for t in b["dqkvs"]] for w in range(3))
+        b["dao"], b["delta"] = z(B, H, e.T, dhp, dt=ct), z(B, H, e.T)      # main stream only: one buffer
+        b["dxq"] = z(e.T, B, d)
+        return b
 
     # -- helpers ----------------------------------------------------------------
     def _mask_off(self, T: int, S: int) -> int:
@@ -851,14 +889,19 @@ class EncoderGroupPlan:
         c, B, d = self.cfg, self.B, self.cfg.d
         p = c.embed_dropout if training else 0.0
         emb = []
+        if c.self_only:                         # one input per encoder (xk / xv are ignored and may be None)
+            xk = xv = [None] * len(self.encs)
         for e, b, q, k, v in zip(self.encs, self.buf, xq, xk, xv):
             for t, n in ((q, e.T), (k, e.S), (v, e.S)):
+                if t is None and c.self_only:
+                    continue
                 if tuple(t.shape) != (n, B, d) or not t.is_contiguous() or t.dtype != torch.float32:
                     raise ValueError(f"encoder {e.prefix}: expected contiguous fp32 [{n},{B},{d}], got {tuple(t.shape)} {t.dtype}")
-            emb += [ops.embed_problem(q, b["x"][0], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q), pos0=e.q_pos0,
-                                      pos_stride=e.q_stride),
-                    ops.embed_problem(k, b["ke"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)),
-                    ops.embed_problem(v, b["ve"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V))]
+            emb.append(ops.embed_problem(q, b["x"][0], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q), pos0=e.q_pos0,
+                                         pos_stride=e.q_stride))
+            if not c.self_only:
+                emb += [ops.embed_problem(k, b["ke"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)),
+                        ops.embed_problem(v, b["ve"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V))]
         ops.embed_pos_fwd(emb, self.table, d, math.sqrt(d), seed)
         self._last = (seed, training)
         self._run(self._fwd[training], seed)
@@ -1075,6 +1118,143 @@ class EncoderGroupPlan:
         steps += [(SIDE, self._gemm(GEMM_TN if self._lowrank else GEMM_NN, dg_kv)), (SIDE, (ops.ln_bwd, A(LnProblem, hat), d)), JOIN]
         return steps
 
+    # -- self-attention-only tables (GroupCfg.self_only) ---------------------------
+    # transformer.py:141-195 with normalize_before and no key / value source, per layer:
+    #   x = x + drop(out_proj(attn(LN0 x)))          (one mask: T x T, offset 1 when attn_mask)
+    #   x = x + drop(fc2(drop(relu(fc1(LN_F x)))))   LN_F = layer_norms.1, or layer_norms.2 in the biprojection kind (its
+    #                                                layer_norms.1 is the identity of maybe_layer_norm(1, after=True): no gradient)
+    def _build_fwd_self(self, training: bool):
+        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
+        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
+        pr = (lambda p: p) if training else (lambda p: 0.0)
+        A = ops.array
+        lnF = 2 if c.biprojection else 1
+        steps = []
+        for i in range(c.layers):
+            ln, qkv, att, outp, ln2, fc1, fc2 = [], [], [], [], [], [], []
+            for e, b in zip(self.encs, self.buf):
+                R, Tn = b["R"], e.T
+                P = lambda leaf: st.p(self._pn(e, i, leaf))
+                ipw = self._pn(e, i, "self_attn.in_proj_weight")
+                ipb = P("self_attn.in_proj_bias")
+                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
+                ln.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), P("layer_norms.0.bias"), b["st0m"][i], b["st0r"][i],
+                                         R, out=b["xn"][i], ldo=ld))
+                for w, dst in enumerate((b["qh"][i], b["kh"][i], b["vh"][i])):      # Q (scaled), K, V: one grouped launch
+                    qkv.append(ops.gemm_problem(b["xn"][i], st.sptr(ipw, w * d * ld), dst, R, d, d, ld, ld, 0,
+                                                bias_n=ipb[w * d:(w + 1) * d], alpha=self.scale if w == 0 else 1.0,
+                                                out_kind=OUT_HEADS, heads=(B, H, Tn, dh, dhp)))
+                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tn, Tn, dh, dhp,
+                                            self._mask_off(Tn, Tn), drop_p=pr(e.attn_dropout),
+                                            drop_site=site(e.enc_id, i, S_ATTN_SELF)))
+                outp.append(ops.gemm_problem(b["ao"][i], st.sptr(wo), b["xmid"][i], R, d, d, ld, ld, d,
+                                             bias_n=P("self_attn.out_proj.bias"), resid=b["x"][i], ldr=d,
+                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES1)))
+                ln2.append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{lnF}.weight"), P(f"layer_norms.{lnF}.bias"),
+                                          b["st1m"][i], b["st1r"][i], R, out=b["xn2"][i], ldo=ld))
+                fc1.append(ops.gemm_problem(b["xn2"][i], st.sptr(w1), b["h1"][i], R, 4 * d, d, ld, ld, ld4, bias_n=P("fc1.bias"),
+                                            flags=F_RELU, drop_p=pr(c.relu_dropout), drop_site=site(e.enc_id, i, S_RELU),
+                                            out_kind=OUT_CT))
+                fc2.append(ops.gemm_problem(b["h1"][i], st.sptr(w2), b["x"][i + 1], R, d, 4 * d, ld4, ld4, d, bias_n=P("fc2.bias"),
+                                            resid=b["xmid"][i], ldr=d, drop_p=pr(c.res_dropout),
+                                            drop_site=site(e.enc_id, i, S_RES2)))
+            steps += [(ops.ln_fwd, self.dtype, A(LnProblem, ln), d),
+                      self._gemm(GEMM_NT, qkv),
+                      (ops.attn_fwd, self.dtype, A(AttnProblem, att)),
+                      self._gemm(GEMM_NT, outp),
+                      (ops.ln_fwd, self.dtype, A(LnProblem, ln2), d),
+                      self._gemm(GEMM_NT, fc1),
+                      self._gemm(GEMM_NT, fc2)]
+        fin = [ops.ln_problem(b["x"][c.layers], st.p(e.prefix + "layer_norm.weight"), st.p(e.prefix + "layer_norm.bias"),
+                              b["stf"][0], b["stf"][1], b["R"], out=b["out"], ldo=d, out_f32=True)
+               for e, b in zip(self.encs, self.buf)]
+        steps.append((ops.ln_fwd, self.dtype, A(LnProblem, fin), d))
+        return steps
+
+    def _build_bwd_self(self, training: bool, stores: bool = False):
+        """Main stream: the data-gradient chain, the attention backward (dK / dV feed the d(xn) product on the critical
+        path, so both passes run here) and the LayerNorm backwards.  Side stream: the weight gradients, up to two layers
+        behind (WAIT i + 2 / MARK i and the parity-buffered operands of the other layer kinds).  stores=True: the
+        weight-gradient launch of fc1 / fc2 / out_proj and of each in_proj_weight row block is its only writer and stores;
+        the small tensors (biases, LayerNorm affines, summed by several launches) are in the store's zero segments."""
+        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
+        ACC1 = 0 if stores else F_ACCUM
+        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
+        pr = (lambda p: p) if training else (lambda p: 0.0)
+        A = ops.array
+        inv_relu = 1.0 / (1.0 - pr(c.relu_dropout))
+        lnF = 2 if c.biprojection else 1
+        steps = []
+        for i in reversed(range(c.layers)):
+            wg_ffn, dg_fc2, dg_fc1, lnf, wg_att, dg_out, att, dg_a, dg_b, dg_c, lnq = ([] for _ in range(11))
+            # bf16x3: only forward activations are listed as already split (their image is this step's forward launch's);
+            # gradients are split again by the weight-gradient launch that reads them
+            pre_ffn, pre_att = [], []
+            for e, b in zip(self.encs, self.buf):
+                R, Tn = b["R"], e.T
+                P = lambda leaf: st.p(self._pn(e, i, leaf))
+                GP = lambda leaf, off=0: st.gptr(self._pn(e, i, leaf), off)
+                ipw = self._pn(e, i, "self_attn.in_proj_weight")
+                ipb_g = self._pn(e, i, "self_attn.in_proj_bias")
+                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
+                par = i & 1
+                dh1, dy, dqkv = b["dh1"][par], b["dy"][par], b["dqkvs"][par]
+                dqs, dks, dvs = b["dqs"][par], b["dks"][par], b["dvs"][par]
+                dx, dyf = b["dx"], b["dyf"][i % 3]
+                nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=ld, cast_colsum=st.gptr(self._pn(e, i - 1, "fc2.bias")),
+                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i - 1, S_RES2))
+                pre_ffn += [b["h1"][i], b["xn2"][i]]
+                pre_att += [b["ao"][i], b["xn"][i]]
+                # ---- FFN
+                wg_ffn.append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, R, ld, ld4, 4 * d, flags=ACC1))
+                dg_fc2.append(ops.gemm_problem(dyf, st.sptr(w2), dh1, R, 4 * d, d, ld, ld4, ld4, gate=b["h1"][i], ldg=ld4,
+                                               gate_scale=inv_relu, colsum=GP("fc1.bias"), out_kind=OUT_CT))
+                wg_ffn.append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, R, ld4, ld, d, flags=ACC1))
+                dg_fc1.append(ops.gemm_problem(dh1, st.sptr(w1), b["dxn"], R, d, 4 * d, ld4, ld, d))
+                lnf.append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{lnF}.weight"), None, b["st1m"][i], b["st1r"][i], R,
+                                          dy=b["dxn"], ldy=d, add=dx, dx=dx, dgamma=GP(f"layer_norms.{lnF}.weight"),
+                                          dbeta=GP(f"layer_norms.{lnF}.bias"), cast=dy, ldc=ld,
+                                          cast_colsum=GP("self_attn.out_proj.bias"), drop_p=pr(c.res_dropout),
+                                          drop_site=site(e.enc_id, i, S_RES1)))
+                # ---- self-attention
+                wg_att.append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, R, ld, ld, d, flags=ACC1))
+                dg_out.append(ops.gemm_problem(dy, st.sptr(wo), b["dao"], R, d, d, ld, ld, 0, out_kind=OUT_HEADS,
+                                               heads=(B, H, Tn, dh, dhp)))
+                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tn, Tn, dh, dhp,
+                                            self._mask_off(Tn, Tn), dO=b["dao"], delta=b["delta"], dQ=dqs, lddq=3 * ld,
+                                            dK=dks, lddk=3 * ld, dV=dvs, lddv=3 * ld, dq_scale=self.scale,
+                                            drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF)))
+                # in_proj_weight row blocks [0, d), [d, 2d), [2d, 3d): one writer each
+                for w, src in enumerate((dqs, dks, dvs)):
+                    wg_att.append(ops.gemm_problem(src, b["xn"][i], st.gptr(ipw, w * d * d), d, d, R, 3 * ld, ld, d, flags=ACC1,
+                                                   colsum_a=st.gptr(ipb_g, w * d)))
+                # d(xn) = dq Wq + dk Wk + dv Wv
+                if ld == d:                                   # one product over K = 3d (see dqkvs)
+                    dg_a.append(ops.gemm_problem(dqkv, st.sptr(ipw, 0), b["dxn"], R, d, 3 * d, 3 * ld, ld, d))
+                else:
+                    dg_a.append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxn"], R, d, d, 3 * ld, ld, d))
+                    dg_b.append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
+                    dg_c.append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
+                lnq.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), None, b["st0m"][i], b["st0r"][i], R, dy=b["dxn"],
+                                          ldy=d, add=dx, dx=dx, dgamma=GP("layer_norms.0.weight"), dbeta=GP("layer_norms.0.bias"),
+                                          **nxt))
+            for group in (lnf, lnq):
+                ops.check_ln_rows(group, d)
+            x3 = st.x3
+            steps += [(WAIT, i + 2),
+                      self._gemm(GEMM_NN, dg_fc2),
+                      (SIDE, self._gemm(GEMM_TN, wg_ffn, background=True, presplit=pre_ffn if x3 else ())),
+                      self._gemm(GEMM_NN, dg_fc1),
+                      (ops.ln_bwd, A(LnProblem, lnf), d),
+                      self._gemm(GEMM_NN, dg_out),
+                      (ops.attn_bwd, self.dtype, A(AttnProblem, att)),
+                      (SIDE, self._gemm(GEMM_TN, wg_att, background=True, presplit=pre_att if x3 else ())),
+                      self._gemm(GEMM_NN, dg_a)] + \
+                     ([self._gemm(GEMM_NN, dg_b), self._gemm(GEMM_NN, dg_c)] if dg_b else []) + \
+                     [(ops.ln_bwd, A(LnProblem, lnq), d),
+                      (MARK, i)]
+        return steps + [JOIN]
+
     @staticmethod
     def store_written(prefix: str, layers: int):
         """Names of the parameters whose gradient the `stores` tables write with a plain store (ParamStore.set_store_written)."""
@@ -1115,9 +1295,12 @@ class EncoderGroupPlan:
         emb = []
         for e, b in zip(self.encs, self.buf):
             emb.append(ops.embed_problem(b["dx"], b["dxq"], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q)))
-            emb.append(ops.embed_problem(b["dke"], b["dxk"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)))
-            emb.append(ops.embed_problem(b["dve"], b["dxv"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V)))
+            if not c.self_only:
+                emb.append(ops.embed_problem(b["dke"], b["dxk"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)))
+                emb.append(ops.embed_problem(b["dve"], b["dxv"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V)))
         ops.embed_pos_bwd(emb, d, math.sqrt(d), seed)
+        if c.self_only:                         # no key / value source: None in its place
+            return [b["dxq"] for b in self.buf], [None] * len(self.buf), [None] * len(self.buf)
         return [b["dxq"] for b in self.buf], [b["dxk"] for b in self.buf], [b["dxv"] for b in self.buf]
 
 

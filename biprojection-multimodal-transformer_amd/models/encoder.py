@@ -61,15 +61,15 @@ class SinusoidalPositionalEmbedding(nn.Module):
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, x_q, x_k, x_v, enc):
+        """x_k / x_v None: the self-attention stack (the encoder's self-only plan; its only input is x_q)."""
         plan = enc._plan_for(x_q, x_k)
         enc._store.refresh_shadows()
         if enc._store.x3:
             from .. import ops
             ops.x3_new_step()
-        out = plan.forward([x_q.detach().contiguous()], [x_k.detach().contiguous()], [x_v.detach().contiguous()],
-                           enc._next_seed(), enc.training)[0]
+        kv = ([None], [None]) if x_k is None else ([x_k.detach().contiguous()], [x_v.detach().contiguous()])
+        out = plan.forward([x_q.detach().contiguous()], *kv, enc._next_seed(), enc.training)[0]
         ctx.enc, ctx.plan = enc, plan
-        ctx.same_kv = x_k is x_v
         return out.detach().clone()
 
     @staticmethod
@@ -78,15 +78,20 @@ class _EncoderFn(torch.autograd.Function):
         enc._store.begin_backward()
         dq, dk, dv = plan.backward([dout])
         enc._store.end_backward()
+        if dk[0] is None:
+            return None, dq[0].clone(), None, None, None
         return None, dq[0].clone(), dk[0].clone(), dv[0].clone(), None
 
 
 class TransformerEncoder(nn.Module):
     """Drop-in for bpmult.models.transformer.TransformerEncoder.
 
-    forward(x_in, x_in_k, x_in_v) on [T,B,d] / [S,B,d] fp32 CUDA tensors.  The
-    self-attention-only call forward(x_in) of the reference (used only by its
-    broken `hybrid` branch) is not part of the hot path."""
+    forward(x_in, x_in_k, x_in_v) on [T,B,d] / [S,B,d] fp32 CUDA tensors: the crossmodal call (the biprojection layer
+    kind: self-attention, then attention over x_in_k / x_in_v).  forward(x_in), or any call with x_in_k or x_in_v None
+    (the reference's condition, transformer.py:71,84): the self-attention stack over x_in's own T time steps, [T,B,d].
+    In the biprojection layer kind that stack follows the reference's layer exactly: its FFN is normalised by
+    layer_norms.2, and layer_norms.1 (maybe_layer_norm(1, after=True), the identity) gets no gradient -- it ends zero.
+    Both call forms run on the HIP engine and share one parameter store; plans are kept per call form and shape."""
 
     def __init__(self, embed_dim, num_heads, layers, attn_dropout=0.0, relu_dropout=0.0, res_dropout=0.0,
                  embed_dropout=0.0, attn_mask=False, biprojection=False):
@@ -107,9 +112,9 @@ class TransformerEncoder(nn.Module):
         self._plans = {}
         self._step = 0
 
-    def group_cfg(self) -> GroupCfg:
+    def group_cfg(self, self_only: bool = False) -> GroupCfg:
         return GroupCfg(self.embed_dim, self.num_heads, len(self.layers), self.relu_dropout, self.res_dropout, self.dropout,
-                        self.attn_mask, self.biprojection)
+                        self.attn_mask, self.biprojection, self_only=self_only)
 
     # -- standalone execution (a group of one) ----------------------------------
     def _apply(self, fn, *a, **k):
@@ -128,11 +133,14 @@ class TransformerEncoder(nn.Module):
         return self._store
 
     def _plan_for(self, x_q, x_k) -> EncoderGroupPlan:
+        """x_k None: the self-attention-only plan of x_q's shape."""
         st = self._ensure_store()
-        key = (x_q.shape[0], x_k.shape[0], x_q.shape[1])
+        T, B = x_q.shape[0], x_q.shape[1]
+        key = ("self", T, B) if x_k is None else (T, x_k.shape[0], B)
         if key not in self._plans:
-            desc = EncoderDesc("", 0, x_q.shape[0], x_k.shape[0], self.attn_dropout)
-            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(), [desc], x_q.shape[1])
+            S = T if x_k is None else x_k.shape[0]
+            desc = EncoderDesc("", 0, T, S, self.attn_dropout)
+            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(self_only=x_k is None), [desc], B)
         return self._plans[key]
 
     def _next_seed(self) -> int:
@@ -140,8 +148,7 @@ class TransformerEncoder(nn.Module):
         return (torch.initial_seed() * 1000003 + self._step) & 0x7FFFFFFFFFFFFFFF      # 63 bits: bit 63 marks a device-resident seed
 
     def forward(self, x_in, x_in_k=None, x_in_v=None):
-        if x_in_k is None or x_in_v is None:
-            raise NotImplementedError("self-attention-only TransformerEncoder.forward(x) is outside the BPMulT hot path "
-                                      "(reference uses it only in the broken --hybrid branch)")
         self._ensure_store()
+        if x_in_k is None or x_in_v is None:           # transformer.py:71,84: the self-attention stack
+            return _EncoderFn.apply(self._anchor, x_in, None, None, self)
         return _EncoderFn.apply(self._anchor, x_in, x_in_k, x_in_v, self)
