@@ -26,6 +26,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import defaultdict
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -419,7 +420,7 @@ class GroupCfg:
     attn_mask: bool
     biprojection: bool
     # self-attention-only stack, the reference's forward(x) (transformer.py:81-85, 158-159): keys and values are projected
-    # from the query rows' LayerNorm-0 output; no key / value source, no folded key / value state (_build_fwd_self)
+    # from the query rows' LayerNorm-0 output; no key / value source, no folded key / value state (EncoderGroupPlan._kv)
     self_only: bool = False
 
 
@@ -471,8 +472,21 @@ def _side_stream(device, which: int = 1, low: bool = True) -> "torch.cuda.Stream
     return _side_streams[key]
 
 
+# buffer keys of the self-attention block: its own in a self-only plan; beside the cross-attention block's (which owns
+# qh / kh / vh / ao / lse / xmid / dy and the parity-buffered dao / delta) in the biprojection layer kind
+_SELF_KEYS = dict(q="qh", k="kh", v="vh", o="ao", lse="lse", mid="xmid", dy="dy", dao="dao", delta="delta")
+_BIP_SELF_KEYS = dict(q="qs", k="ks", v="vs", o="aos", lse="lses", mid="xmid0", dy="dy0", dao="dao0", delta="delta0")
+
+
 class EncoderGroupPlan:
-    """Buffers + launch tables for G encoders x L layers at batch size B."""
+    """Buffers + launch tables for G encoders x L layers at batch size B.
+
+    Three layer kinds, each a fixed sequence of blocks (transformer.py:141-195, normalize_before):
+      self-only (GroupCfg.self_only)  self-attention + FFN
+      crossmodal                      cross-attention + FFN
+      biprojection                    self-attention + cross-attention + FFN
+    The per-block builders below (_ln0_* / _self_attn_* / _cross_attn_* / _ffn_*) append one encoder's problems of one
+    layer to that layer's launch lists; _build_fwd / _build_bwd wire their operands and order the launches per kind."""
 
     def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int):
         self.store, self.cfg, self.encs, self.B = store, cfg, list(encs), B
@@ -482,6 +496,9 @@ class EncoderGroupPlan:
             raise ValueError("embed_dim must be divisible by num_heads")
         self.dh = d // H
         self.dhp = dhp_for(self.dh)
+        # key / value source: every kind but the self-attention-only stack, whose keys and values are projected from the
+        # query rows' LayerNorm-0 output -- no key / value-side state, steps or unfold tables without one
+        self._kv = not cfg.self_only
         # LOW-RANK KEY SIDE.  With T query time steps dK = dS^T Q and dV = Pd^T dO have rank T per (batch element, head), and
         # every key / value-side product of the backward factors through the [H T, S] matrices dS, Pd (written by the dQ
         # pass) instead of the [S B, d] matrices dK, dV:
@@ -492,116 +509,20 @@ class EncoderGroupPlan:
         # elimination has T = 2: at hidden 768 this removes 1.5 of the step's 19.4 ms (the key / value weight gradients over
         # 4096 rows, the merged K = 6144 data gradient, the dK / dV pass).  Equal to the dK / dV route in real arithmetic; the
         # roundings differ (dS instead of dK is rounded to CT), fixtures F7 / F9 / F11 hold both.  Crossmodal groups only.
-        self._lowrank = (_LOWRANK and not cfg.self_only and not cfg.biprojection
+        self._lowrank = (_LOWRANK and self._kv and not cfg.biprojection
                          and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs) and self.dh <= 256)
         self.ld, self.ld4 = pad32(d), pad32(4 * d)
         self.scale = self.dh ** -0.5
-        dev, ct = store.device, ops.ct_torch(self.dtype)
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
+        # FFN LayerNorm: layer_norms.2 in the biprojection kind (its layer_norms.1 normalises the key / value source, or is
+        # the identity of maybe_layer_norm(1, after=True) in the self-attention-only stack: no gradient)
+        self._lnF = 2 if cfg.biprojection else 1
+        dev = store.device
         L = cfg.layers
-        self.buf: List[dict] = []
         # accumulators that every backward starts from zero (d(khat), d(vhat), folded bias sums): ONE buffer, one fill
         nacc = sum(L * 2 * d + 16 for e in self.encs)
         self._acc0 = torch.zeros(nacc, device=dev, dtype=torch.float32)
-        acc_off = [0]
-
-        def carve(*shape):
-            n = 1
-            for v in shape:
-                n *= v
-            t = self._acc0[acc_off[0]: acc_off[0] + n].view(*shape)
-            acc_off[0] += (n + 15) // 16 * 16
-            return t
-
-        for e in self.encs:
-            if cfg.self_only:
-                self.buf.append(self._alloc_self(e, z, ct))
-                continue
-            R, Rk = e.T * B, e.S * B
-            tailp = bool(e.tail_rows)
-            if tailp and (not cfg.biprojection or e.T < 2 or e.T_full is not None):
-                raise ValueError("tail_rows: biprojection encoders with at least two query rows (crossmodal encoders gather their rows)")
-            # query-side rows / time steps of every layer (the last one shrinks to rows {0, T-1} with tail_rows)
-            Rl, Tl = [R] * L, [e.T] * L
-            if tailp:
-                Rl[-1], Tl[-1] = 2 * B, 2
-            b = dict(R=R, Rk=Rk, Rl=Rl, Tl=Tl, tailp=tailp)
-            b["x"] = [z(R, d) for _ in range(L)] + [z(Rl[-1], d)]
-            b["ke"], b["ve"] = z(Rk, d), z(Rk, d)
-            b["out"] = z(Tl[-1], B, d)
-            b["stf"] = (z(Rl[-1]), z(Rl[-1]))
-            # key / value source, normalised ONCE without affine (the per-layer LayerNorm gain and bias are folded
-            # into the K / V projection weights, see register_encoder_shadows)
-            b["khat"], b["vhat"] = z(Rk, self.ld, dt=ct), z(Rk, self.ld, dt=ct)
-            b["stk"], b["stv"] = (z(Rk), z(Rk)), (z(Rk), z(Rk))
-            # d(khat), d(vhat) = sum over the layers of dK_i Wk'_i, dV_i Wv'_i: ONE product over K = L ld per encoder at the
-            # end of backward (dK_i / dV_i of every layer are kept side by side in dkall / dvall) instead of L products
-            # accumulating into the same fp32 [Rk, d] tensor (8 x 300 MB of read-modify-write per level at hidden 768)
-            b["Gk"], b["Gv"] = z(Rk, d), z(Rk, d)
-            if self._lowrank:
-                HT, Sp = H * e.T, (e.S + 63) // 64 * 64
-                b["Sp"] = Sp
-                # dS / Pd of every layer, [layer][h*T + t][b][key] with zero key padding (never written); the same row
-                # order (h*T + t)*B + b for the expanded head rows and everything computed from them
-                b["dSall"], b["Pdall"] = z(L, HT, B, Sp, dt=ct), z(L, HT, B, Sp, dt=ct)
-                b["qkall"], b["daall"] = z(L, HT * B, self.ld, dt=ct), z(L, HT * B, self.ld, dt=ct)
-                for nm in ("qexp", "doexp", "U", "Av"):
-                    b[nm] = [z(HT * B, self.ld, dt=ct) for _ in range(2)]
-                b["dkall"] = b["dvall"] = None
-            else:
-                b["dkall"], b["dvall"] = z(Rk, L * self.ld, dt=ct), z(Rk, L * self.ld, dt=ct)
-            b["dWf"] = [z(2 * d, d) for _ in range(L)]              # folded K/V weight gradients (per backward)
-            b["dbf"] = carve(L, 2 * d)                              # folded K/V bias gradients (column sums)
-            # per-layer activations: shape(i) -- query-side tensors follow Rl / Tl, key / value-side ones stay full
-            for nm, shape, dt in (("xn", lambda i: (R, self.ld), ct),
-                                  ("qh", lambda i: (B, H, Tl[i], self.dhp), ct), ("kh", lambda i: (B, H, e.S, self.dhp), ct),
-                                  ("vh", lambda i: (B, H, e.S, self.dhp), ct), ("ao", lambda i: (Rl[i], self.ld), ct),
-                                  ("lse", lambda i: (B, H, Tl[i]), torch.float32),
-                                  ("xmid", lambda i: (Rl[i], d), torch.float32), ("xn2", lambda i: (Rl[i], self.ld), ct),
-                                  ("h1", lambda i: (Rl[i], self.ld4), ct),
-                                  ("st0m", lambda i: (R,), torch.float32), ("st0r", lambda i: (R,), torch.float32),
-                                  ("st1m", lambda i: (Rl[i],), torch.float32), ("st1r", lambda i: (Rl[i],), torch.float32)):
-                b[nm] = [z(*shape(i), dt=dt) for i in range(L)]
-            if cfg.biprojection:
-                for nm, shape, dt in (("qs", lambda i: (B, H, Tl[i], self.dhp), ct), ("ks", lambda i: (B, H, e.T, self.dhp), ct),
-                                      ("vs", lambda i: (B, H, e.T, self.dhp), ct), ("aos", lambda i: (Rl[i], self.ld), ct),
-                                      ("lses", lambda i: (B, H, Tl[i]), torch.float32), ("xmid0", lambda i: (Rl[i], d), torch.float32),
-                                      ("xq", lambda i: (Rl[i], self.ld), ct), ("st2m", lambda i: (Rl[i],), torch.float32),
-                                      ("st2r", lambda i: (Rl[i],), torch.float32)):
-                    b[nm] = [z(*shape(i), dt=dt) for i in range(L)]
-            if tailp:
-                # last layer: rows {0, T-1} of its input (fp32) and of LN0(input) (CT), their gradients, and the residual
-                # gradient scattered back into an otherwise-zero [R, d] buffer (only the two row blocks are ever written)
-                b["xg"], b["xng"] = z(2 * B, d), z(2 * B, self.ld, dt=ct)
-                b["dxg"], b["dxng"], b["dxs"] = z(2 * B, d), z(2 * B, d), z(R, d)
-            # backward temporaries (shared by all layers)
-            b["dx"], b["dxn"] = z(R, d), z(R, d)
-            # Off-critical-path work (weight gradients, the key/value-side dgrad + LayerNorm backward) runs on a
-            # side stream up to two layers behind the main chain, so every operand it reads has its own buffer
-            # within a layer (dyf: FFN, dy: attention, dy0/dqs/dks/dvs: biprojection self-attention half) and is
-            # double-buffered by layer parity.
-            two = lambda *shape: [z(*shape, dt=ct), z(*shape, dt=ct)]
-            b["dy"], b["dh1"] = two(R, self.ld), two(R, self.ld4)
-            # dyf[i % 3]: written one layer early (fused into the LayerNorm backward that produces dx)
-            b["dyf"] = [z(R, self.ld, dt=ct) for _ in range(3)]
-            b["dq"] = two(R, self.ld)
-            if cfg.biprojection:
-                b["dy0"] = two(R, self.ld)
-                # dQ | dK | dV of the self-attention half side by side in one [R, 3 ld] buffer: without column padding
-                # (ld == d) that is the [R, 3d] operand of ONE d(xn) = [dq dk dv] in_proj_weight product (K = 3d) instead
-                # of three K = d launches accumulating into the same output
-                # (one spare row: the bounded loaders size their descriptors rows x ld from each VIEW's first element, so
-                # the dK / dV views' ranges reach up to 2 ld elements past row R - 1)
-                b["dqkvs"] = two(R + 1, 3 * self.ld)
-                b["dqs"], b["dks"], b["dvs"] = ([t[:R, w * self.ld:(w + 1) * self.ld] for t in b["dqkvs"]] for w in range(3))
-            # read by the side-stream dK/dV pass of the cross attention: by layer parity like dq/dk/dv
-            b["dao"] = [z(B, H, e.T, self.dhp, dt=ct) for _ in range(2)]
-            b["delta"] = [z(B, H, e.T) for _ in range(2)]
-            if cfg.biprojection:
-                b["dao0"], b["delta0"] = z(B, H, e.T, self.dhp, dt=ct), z(B, H, e.T)
-            b["dke"], b["dve"] = z(Rk, d), z(Rk, d)
-            b["dxq"], b["dxk"], b["dxv"] = z(e.T, B, d), z(e.S, B, d), z(e.S, B, d)
-            self.buf.append(b)
+        self._acc_off = 0
+        self.buf: List[dict] = [self._alloc(e) for e in self.encs]
         if cfg.biprojection and any(e.T_full is not None for e in self.encs):
             raise ValueError("a gathered query subset is only exact for crossmodal (non-biprojection) encoders")
         self.table = sinusoid_table(max(max(e.T_full or e.T, e.S) for e in self.encs) + 2, d, dev)
@@ -609,7 +530,7 @@ class EncoderGroupPlan:
         # table of the launch that turns folded K/V gradients into in_proj / LayerNorm parameter gradients
         lnK = 1 if cfg.biprojection else 0
         self._unfold = []                                  # one table per layer: its gradients are final with it
-        for i in range(0 if cfg.self_only else L):
+        for i in range(L if self._kv else 0):
             ud, blk = [], 0
             for e, b in zip(self.encs, self.buf):
                 pn = lambda leaf: self._pn(e, i, leaf)
@@ -630,40 +551,113 @@ class EncoderGroupPlan:
             self._dkv_side = "0"
         self._side_low = d < 512
         self.store.side_low = self._side_low
-        build_fwd, build_bwd = (self._build_fwd_self, self._build_bwd_self) if cfg.self_only else (self._build_fwd, self._build_bwd)
-        self._fwd = {True: build_fwd(True), False: build_fwd(False)}
+        self._fwd = {True: self._build_fwd(True), False: self._build_fwd(False)}
         # backward tables by (training, stores): stores = the first weight-gradient launch of each large matrix writes
         # instead of accumulating (the flat gradient buffer was not cleared: ParamStore.begin_backward(stores=True))
-        self._bwd = {(t, f): build_bwd(t, f) for t in (True, False) for f in (True, False)}
+        self._bwd = {(t, f): self._build_bwd(t, f) for t in (True, False) for f in (True, False)}
 
-    def _alloc_self(self, e: EncoderDesc, z, ct) -> dict:
-        """Buffers of one self-attention-only encoder (GroupCfg.self_only): the query chain of a crossmodal encoder whose
-        keys and values come from the same LayerNorm-0 rows as its queries."""
-        if e.S != e.T or e.tail_rows or e.T_full is not None or e.q_pos0 or e.q_stride != 1:
+    def _alloc(self, e: EncoderDesc) -> dict:
+        """Buffers of one encoder: the query chain and FFN of every kind, the self-attention block's (self-only and
+        biprojection) and the cross-attention block's key / value-side state (kinds with a key / value source)."""
+        c, B, d, H, L, ld, ld4, dhp = self.cfg, self.B, self.cfg.d, self.cfg.H, self.cfg.layers, self.ld, self.ld4, self.dhp
+        dev, ct = self.store.device, ops.ct_torch(self.dtype)
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
+        if not self._kv and (e.S != e.T or e.tail_rows or e.T_full is not None or e.q_pos0 or e.q_stride != 1):
             raise ValueError(f"encoder {e.prefix}: a self-attention-only encoder attends over its own {e.T} time steps "
                              "(S == T, no gathered rows, no tail_rows)")
-        B, d, H, L, ld, ld4, dhp = self.B, self.cfg.d, self.cfg.H, self.cfg.layers, self.ld, self.ld4, self.dhp
-        R = e.T * B
-        b = dict(R=R, Rk=R, Rl=[R] * L, Tl=[e.T] * L, tailp=False)
-        b["x"] = [z(R, d) for _ in range(L + 1)]
-        b["out"] = z(e.T, B, d)
-        b["stf"] = (z(R), z(R))
-        for nm, shape, dt in (("xn", (R, ld), ct), ("qh", (B, H, e.T, dhp), ct), ("kh", (B, H, e.T, dhp), ct),
-                              ("vh", (B, H, e.T, dhp), ct), ("ao", (R, ld), ct), ("lse", (B, H, e.T), torch.float32),
-                              ("xmid", (R, d), torch.float32), ("xn2", (R, ld), ct), ("h1", (R, ld4), ct),
-                              ("st0m", (R,), torch.float32), ("st0r", (R,), torch.float32),
-                              ("st1m", (R,), torch.float32), ("st1r", (R,), torch.float32)):
-            b[nm] = [z(*shape, dt=dt) for _ in range(L)]
-        # backward temporaries: what the side stream's weight gradients read is double-buffered by layer parity (dyf: by
-        # layer mod 3, written one layer early), as in the other layer kinds
-        two = lambda *shape: [z(*shape, dt=ct), z(*shape, dt=ct)]
+        has_self = c.biprojection or not self._kv
+        R, Rk = e.T * B, e.S * B
+        tailp = bool(e.tail_rows)
+        if tailp and (not c.biprojection or e.T < 2 or e.T_full is not None):
+            raise ValueError("tail_rows: biprojection encoders with at least two query rows (crossmodal encoders gather their rows)")
+        # query-side rows / time steps of every layer (the last one shrinks to rows {0, T-1} with tail_rows)
+        Rl, Tl = [R] * L, [e.T] * L
+        if tailp:
+            Rl[-1], Tl[-1] = 2 * B, 2
+        b = dict(R=R, Rk=Rk, Rl=Rl, Tl=Tl, tailp=tailp)
+        b["x"] = [z(R, d) for _ in range(L)] + [z(Rl[-1], d)]
+        b["out"] = z(Tl[-1], B, d)
+        b["stf"] = (z(Rl[-1]), z(Rl[-1]))
+        if self._kv:
+            b["ke"], b["ve"] = z(Rk, d), z(Rk, d)
+            # key / value source, normalised ONCE without affine (the per-layer LayerNorm gain and bias are folded
+            # into the K / V projection weights, see register_encoder_shadows)
+            b["khat"], b["vhat"] = z(Rk, ld, dt=ct), z(Rk, ld, dt=ct)
+            b["stk"], b["stv"] = (z(Rk), z(Rk)), (z(Rk), z(Rk))
+            # d(khat), d(vhat) = sum over the layers of dK_i Wk'_i, dV_i Wv'_i: ONE product over K = L ld per encoder at the
+            # end of backward (dK_i / dV_i of every layer are kept side by side in dkall / dvall) instead of L products
+            # accumulating into the same fp32 [Rk, d] tensor (8 x 300 MB of read-modify-write per level at hidden 768)
+            b["Gk"], b["Gv"] = z(Rk, d), z(Rk, d)
+            if self._lowrank:
+                HT, Sp = H * e.T, (e.S + 63) // 64 * 64
+                b["Sp"] = Sp
+                # dS / Pd of every layer, [layer][h*T + t][b][key] with zero key padding (never written); the same row
+                # order (h*T + t)*B + b for the expanded head rows and everything computed from them
+                b["dSall"], b["Pdall"] = z(L, HT, B, Sp, dt=ct), z(L, HT, B, Sp, dt=ct)
+                b["qkall"], b["daall"] = z(L, HT * B, ld, dt=ct), z(L, HT * B, ld, dt=ct)
+                for nm in ("qexp", "doexp", "U", "Av"):
+                    b[nm] = [z(HT * B, ld, dt=ct) for _ in range(2)]
+                b["dkall"] = b["dvall"] = None
+            else:
+                b["dkall"], b["dvall"] = z(Rk, L * ld, dt=ct), z(Rk, L * ld, dt=ct)
+            b["dWf"] = [z(2 * d, d) for _ in range(L)]              # folded K/V weight gradients (per backward)
+            b["dbf"] = self._acc0[self._acc_off: self._acc_off + L * 2 * d].view(L, 2 * d)   # folded K/V bias gradients
+            self._acc_off += (L * 2 * d + 15) // 16 * 16
+        # per-layer activations: shape(i) -- query-side tensors follow Rl / Tl, key / value-side ones stay full (qh .. lse:
+        # the cross-attention block's, or the self-attention block's in a self-only plan, where S == T)
+        acts = [("xn", lambda i: (R, ld), ct),
+                ("qh", lambda i: (B, H, Tl[i], dhp), ct), ("kh", lambda i: (B, H, e.S, dhp), ct),
+                ("vh", lambda i: (B, H, e.S, dhp), ct), ("ao", lambda i: (Rl[i], ld), ct),
+                ("lse", lambda i: (B, H, Tl[i]), torch.float32),
+                ("xmid", lambda i: (Rl[i], d), torch.float32), ("xn2", lambda i: (Rl[i], ld), ct),
+                ("h1", lambda i: (Rl[i], ld4), ct),
+                ("st0m", lambda i: (R,), torch.float32), ("st0r", lambda i: (R,), torch.float32),
+                ("st1m", lambda i: (Rl[i],), torch.float32), ("st1r", lambda i: (Rl[i],), torch.float32)]
+        if self._kv and c.biprojection:
+            acts += [("qs", lambda i: (B, H, Tl[i], dhp), ct), ("ks", lambda i: (B, H, e.T, dhp), ct),
+                     ("vs", lambda i: (B, H, e.T, dhp), ct), ("aos", lambda i: (Rl[i], ld), ct),
+                     ("lses", lambda i: (B, H, Tl[i]), torch.float32), ("xmid0", lambda i: (Rl[i], d), torch.float32),
+                     ("xq", lambda i: (Rl[i], ld), ct), ("st2m", lambda i: (Rl[i],), torch.float32),
+                     ("st2r", lambda i: (Rl[i],), torch.float32)]
+        for nm, shape, dt in acts:
+            b[nm] = [z(*shape(i), dt=dt) for i in range(L)]
+        if tailp:
+            # last layer: rows {0, T-1} of its input (fp32) and of LN0(input) (CT), their gradients, and the residual
+            # gradient scattered back into an otherwise-zero [R, d] buffer (only the two row blocks are ever written)
+            b["xg"], b["xng"] = z(2 * B, d), z(2 * B, ld, dt=ct)
+            b["dxg"], b["dxng"], b["dxs"] = z(2 * B, d), z(2 * B, d), z(R, d)
+        # backward temporaries (shared by all layers)
         b["dx"], b["dxn"] = z(R, d), z(R, d)
+        # Off-critical-path work (weight gradients, the key/value-side dgrad + LayerNorm backward) runs on a
+        # side stream up to two layers behind the main chain, so every operand it reads has its own buffer
+        # within a layer (dyf: FFN, dy: attention, dy0/dqs/dks/dvs: biprojection self-attention half) and is
+        # double-buffered by layer parity.
+        two = lambda *shape: [z(*shape, dt=ct), z(*shape, dt=ct)]
         b["dy"], b["dh1"] = two(R, ld), two(R, ld4)
+        # dyf[i % 3]: written one layer early (fused into the LayerNorm backward that produces dx)
         b["dyf"] = [z(R, ld, dt=ct) for _ in range(3)]
-        # dQ | dK | dV side by side (the [R, 3d] operand of ONE d(xn) product when ld == d; one spare row, see dqkvs above)
-        b["dqkvs"] = two(R + 1, 3 * ld)
-        b["dqs"], b["dks"], b["dvs"] = ([t[:R, w * ld:(w + 1) * ld] for t in b["dqkvs"]] for w in range(3))
-        b["dao"], b["delta"] = z(B, H, e.T, dhp, dt=ct), z(B, H, e.T)      # main stream only: one buffer
+        if self._kv:
+            b["dq"] = two(R, ld)
+        if self._kv and c.biprojection:
+            b["dy0"] = two(R, ld)
+        if has_self:
+            # dQ | dK | dV of the self-attention block side by side in one [R, 3 ld] buffer: without column padding
+            # (ld == d) that is the [R, 3d] operand of ONE d(xn) = [dq dk dv] in_proj_weight product (K = 3d) instead
+            # of three K = d launches accumulating into the same output
+            # (one spare row: the bounded loaders size their descriptors rows x ld from each VIEW's first element, so
+            # the dK / dV views' ranges reach up to 2 ld elements past row R - 1)
+            b["dqkvs"] = two(R + 1, 3 * ld)
+            b["dqs"], b["dks"], b["dvs"] = ([t[:R, w * ld:(w + 1) * ld] for t in b["dqkvs"]] for w in range(3))
+        if self._kv:
+            # read by the side-stream dK/dV pass of the cross attention: by layer parity like dq/dk/dv
+            b["dao"] = [z(B, H, e.T, dhp, dt=ct) for _ in range(2)]
+            b["delta"] = [z(B, H, e.T) for _ in range(2)]
+        if has_self:                                       # the self-attention backward runs on the main stream: one buffer
+            k = _BIP_SELF_KEYS if self._kv else _SELF_KEYS
+            b[k["dao"]], b[k["delta"]] = z(B, H, e.T, dhp, dt=ct), z(B, H, e.T)
+        if self._kv:
+            b["dke"], b["dve"] = z(Rk, d), z(Rk, d)
+            b["dxk"], b["dxv"] = z(e.S, B, d), z(e.S, B, d)
         b["dxq"] = z(e.T, B, d)
         return b
 
@@ -688,114 +682,277 @@ class EncoderGroupPlan:
         arr.x3_presplit = frozenset(t.data_ptr() for t in presplit)
         return (ops.gemm_grouped, self.dtype, variant, arr)
 
+    def _tail(self, b: dict, i: int) -> bool:
+        """Layer i runs on rows {0, T-1} only (EncoderDesc.tail_rows, last layer)."""
+        return b["tailp"] and i == self.cfg.layers - 1
+
+    # -- per-block problem builders -------------------------------------------------
+    # Each appends encoder e's problems of layer i to the layer's launch lists t[name] (one launch per name, problems in
+    # encoder order).  The caller passes what differs between the layer kinds: inputs, residuals, first-writer flags, drop
+    # sites, buffer keys.  pr(p): the dropout probability p in training, 0 in eval.
+    def _proj(self, e, i, Ain, rows, which, Cout, Tlen):
+        """Q (which 0, scaled), K (1) or V (2) projection of in_proj_weight into head-major Cout."""
+        d, ld = self.cfg.d, self.ld
+        return ops.gemm_problem(Ain, self.store.sptr(self._pn(e, i, "self_attn.in_proj_weight"), which * d * ld), Cout, rows, d, d,
+                                ld, ld, 0, bias_n=self.store.p(self._pn(e, i, "self_attn.in_proj_bias"))[which * d:(which + 1) * d],
+                                alpha=self.scale if which == 0 else 1.0, out_kind=OUT_HEADS,
+                                heads=(self.B, self.cfg.H, Tlen, self.dh, self.dhp))
+
+    def _ln0_fwd(self, t, e, b, i):
+        P = lambda leaf: self.store.p(self._pn(e, i, leaf))
+        t["ln0"].append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), P("layer_norms.0.bias"), b["st0m"][i], b["st0r"][i],
+                                       b["R"], out=b["xn"][i], ldo=self.ld))
+
+    def _ln0_bwd(self, t, e, b, i, pr):
+        """LayerNorm-0 backward over all rows from d(xn), added to the residual gradient (the gathered rows' one, scattered
+        into dxs, in a tail_rows last layer) into the dense dx the layers below continue from.  Hand-off to the next layer
+        down (i-1): its FFN-output gradient dyf = dropmask(dx) and fc2.bias gradient are fused into this launch."""
+        st, c, d = self.store, self.cfg, self.cfg.d
+        nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=self.ld, cast_colsum=st.gptr(self._pn(e, i - 1, "fc2.bias")),
+                                     drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i - 1, S_RES2))
+        t["ln0"].append(ops.ln_problem(b["x"][i], st.p(self._pn(e, i, "layer_norms.0.weight")), None, b["st0m"][i], b["st0r"][i],
+                                       b["R"], dy=b["dxn"], ldy=d, add=b["dxs"] if self._tail(b, i) else b["dx"], dx=b["dx"],
+                                       dgamma=st.gptr(self._pn(e, i, "layer_norms.0.weight")),
+                                       dbeta=st.gptr(self._pn(e, i, "layer_norms.0.bias")), **nxt))
+
+    def _self_attn_fwd(self, t, e, b, i, pr, k, res_site):
+        """Self-attention over LN0(x) (transformer.py:158-159): keys / values from every row, queries from the layer's
+        query rows; b[k["mid"]] = x + drop(out_proj(attention)) (dropout site res_site).  LN0 is _ln0_fwd."""
+        st, c, B, d, H, ld = self.store, self.cfg, self.B, self.cfg.d, self.cfg.H, self.ld
+        R, Rq, Tq = b["R"], b["Rl"][i], b["Tl"][i]
+        x_in, xn = b["x"][i], b["xn"][i]
+        xq_in, res_in = xn, x_in                           # query operand, its residual
+        tail = self._tail(b, i)
+        if tail:
+            # time steps 0 and T-1 are the first and the last B rows of a [T, B, .] tensor: two block copies
+            for j, r0 in ((0, 0), (1, R - B)):
+                t["s.gather"].append(ops.cast_problem(x_in[r0:r0 + B], d, B, d, dst_f32=b["xg"][j * B:(j + 1) * B], ldf=d))
+                t["s.gather"].append(ops.cast_problem(xn[r0:r0 + B], ld, B, d, a_is_ct=True, dst_ct=b["xng"][j * B:(j + 1) * B],
+                                                      ldd=ld))
+            xq_in, res_in = b["xng"], b["xg"]
+        q, kk, v, o, lse = (b[k[n]][i] for n in ("q", "k", "v", "o", "lse"))
+        t["s.qkv"] += [self._proj(e, i, xq_in, Rq, 0, q, Tq), self._proj(e, i, xn, R, 1, kk, e.T), self._proj(e, i, xn, R, 2, v, e.T)]
+        t["s.att"].append(ops.attn_problem(q, kk, v, o, ld, lse, B, H, Tq, e.T, self.dh, self.dhp, self._mask_off(e.T, e.T),
+                                           drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF),
+                                           **(dict(q_pos0=0, q_stride=e.T - 1) if tail else {})))
+        t["s.out"].append(ops.gemm_problem(o, st.sptr(self._pn(e, i, "self_attn.out_proj.weight")), b[k["mid"]][i], Rq, d, d, ld, ld,
+                                           d, bias_n=st.p(self._pn(e, i, "self_attn.out_proj.bias")), resid=res_in, ldr=d,
+                                           drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, res_site)))
+
+    def _self_attn_bwd(self, t, e, b, i, pr, k, first, acc1, cast=None):
+        """Backward of _self_attn_fwd down to d(xn) (dQ | dK | dV side by side in dqkvs); LN0 is _ln0_bwd.  first: flags of
+        the out_proj.weight / in_proj_weight rows [0, d) gradients (accumulating when another block wrote them first);
+        acc1: those of rows [d, 3d).  cast = (dx, res_site): d(out_proj output) is dropmask(dx), not the FFN's hand-off."""
+        st, c, B, d, H, ld = self.store, self.cfg, self.B, self.cfg.d, self.cfg.H, self.ld
+        R, Rq, Tq = b["R"], b["Rl"][i], b["Tl"][i]
+        GP = lambda leaf, off=0: st.gptr(self._pn(e, i, leaf), off)
+        ipw, wo = self._pn(e, i, "self_attn.in_proj_weight"), self._pn(e, i, "self_attn.out_proj.weight")
+        par = i & 1
+        dy, dqs, dks, dvs = b[k["dy"]][par], b["dqs"][par], b["dks"][par], b["dvs"][par]
+        q, kk, v, o, lse, dao, delta = (b[k[n]] for n in ("q", "k", "v", "o", "lse", "dao", "delta"))
+        q, kk, v, o, lse = q[i], kk[i], v[i], o[i], lse[i]
+        tail = self._tail(b, i)
+        xn = b["xn"][i]
+        xq_in = b["xng"] if tail else xn
+        if cast is not None:
+            t["s.cast"].append(ops.cast_problem(cast[0], d, Rq, d, dst_ct=dy, ldd=ld, colsum=GP("self_attn.out_proj.bias"),
+                                                drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, cast[1])))
+        t["s.acts"] += [o, xq_in, xn]
+        t["s.wg"].append(ops.gemm_problem(dy, o, GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=first))
+        t["s.dgout"].append(ops.gemm_problem(dy, st.sptr(wo), dao, Rq, d, d, ld, ld, 0, out_kind=OUT_HEADS,
+                                             heads=(B, H, Tq, self.dh, self.dhp)))
+        t["s.att"].append(ops.attn_problem(q, kk, v, o, ld, lse, B, H, Tq, e.T, self.dh, self.dhp, self._mask_off(e.T, e.T),
+                                           dO=dao, delta=delta, dQ=dqs, lddq=3 * ld, dK=dks, lddk=3 * ld, dV=dvs, lddv=3 * ld,
+                                           dq_scale=self.scale, drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF),
+                                           **(dict(q_pos0=0, q_stride=e.T - 1) if tail else {})))
+        # in_proj_weight row blocks [0, d), [d, 2d), [2d, 3d) (with a key / value source, unfold_grads comes after this
+        # launch and adds to rows [d, 3d))
+        for w, src, xin, rows in ((0, dqs, xq_in, Rq), (1, dks, xn, R), (2, dvs, xn, R)):
+            t["s.wg"].append(ops.gemm_problem(src, xin, st.gptr(ipw, w * d * d), d, d, rows, 3 * ld, ld, d,
+                                              flags=first if w == 0 else acc1,
+                                              colsum_a=GP("self_attn.in_proj_bias", w * d)))
+        # d(xn) = dq Wq + dk Wk + dv Wv: three launches (plain store, then two +=) -- one owner per
+        # output tile in each launch, no atomics (per-lane-scattered float atomics run ~17x below store rate)
+        if tail:
+            # keys / values come from every row, the query only from rows {0, T-1}: d(xn) over all rows is the
+            # K / V part; the query part is a [2B, d] product whose row blocks are added into it, and the
+            # gathered rows' residual gradient goes to the same two row blocks of the otherwise-zero dxs
+            if ld == d:
+                t["s.dg_a"].append(ops.gemm_problem(b["dqkvs"][par][:R, ld:], st.sptr(ipw, d * ld), b["dxn"], R, d, 2 * d,
+                                                    3 * ld, ld, d))
+            else:
+                t["s.dg_a"].append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d))
+                t["s.dg_b"].append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
+            t["s.dgq"].append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxng"], Rq, d, d, 3 * ld, ld, d))
+            for j, r0 in ((0, 0), (1, R - B)):
+                blk = slice(j * B, (j + 1) * B)
+                t["s.scatter"].append(ops.addn_problem(b["dxn"][r0:r0 + B], [b["dxn"][r0:r0 + B], b["dxng"][blk]]))
+                t["s.scatter"].append(ops.addn_problem(b["dxs"][r0:r0 + B], [b["dxg"][blk]]))
+        elif ld == d:                                   # one product over K = 3d (see the dqkvs buffer)
+            t["s.dg_a"].append(ops.gemm_problem(b["dqkvs"][par], st.sptr(ipw, 0), b["dxn"], R, d, 3 * d, 3 * ld, ld, d))
+        else:
+            t["s.dg_a"].append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxn"], R, d, d, 3 * ld, ld, d))
+            t["s.dg_b"].append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
+            t["s.dg_c"].append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
+
+    def _cross_attn_fwd(self, t, e, b, i, pr, q_src, resid):
+        """Cross attention: queries projected from q_src (CT), keys / values from the normalised key / value source through
+        the LayerNorm-folded K / V weights (on the side stream, t["c.kv"]); xmid = resid + drop(out_proj(attention))."""
+        st, c, B, d, H, ld = self.store, self.cfg, self.B, self.cfg.d, self.cfg.H, self.ld
+        Rq, Tq = b["Rl"][i], b["Tl"][i]
+        qpos = dict(q_pos0=0, q_stride=e.T - 1) if self._tail(b, i) else dict(q_pos0=e.q_pos0, q_stride=e.q_stride)
+        kvf = self._pn(e, i, KVF)
+        t["c.q"].append(self._proj(e, i, q_src, Rq, 0, b["qh"][i], Tq))
+        for w, hat, dst in ((0, b["khat"], b["kh"][i]), (1, b["vhat"], b["vh"][i])):    # folded: khat (W_k * gamma)^T + (W_k beta + b_k)
+            t["c.kv"].append(ops.gemm_problem(hat, st.sptr(kvf + (".v" if w else ".k")), dst, b["Rk"], d, d, ld, ld, 0,
+                                              bias_n=st.fold(kvf, w * d, d), out_kind=OUT_HEADS, heads=(B, H, e.S, self.dh, self.dhp)))
+        t["c.att"].append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tq, e.S, self.dh,
+                                           self.dhp, self._mask_off(e.T_full or e.T, e.S), drop_p=pr(e.attn_dropout),
+                                           drop_site=site(e.enc_id, i, S_ATTN), **qpos))
+        t["c.out"].append(ops.gemm_problem(b["ao"][i], st.sptr(self._pn(e, i, "self_attn.out_proj.weight")), b["xmid"][i], Rq, d, d,
+                                           ld, ld, d, bias_n=st.p(self._pn(e, i, "self_attn.out_proj.bias")), resid=resid, ldr=d,
+                                           drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES1)))
+
+    def _cross_attn_bwd(self, t, e, b, i, pr, acc1, q_src, dq_out, dq_flags):
+        """Backward of _cross_attn_fwd: d(query operand) into dq_out (dq_flags), the key side as dK / dV blocks of dkall /
+        dvall or low-rank (_lowrank), the folded K / V gradients into dWf / dbf (unfolded per layer by unfold_grads)."""
+        st, c, B, d, H, ld = self.store, self.cfg, self.B, self.cfg.d, self.cfg.H, self.ld
+        Rq, Tq, Rk = b["Rl"][i], b["Tl"][i], b["Rk"]
+        qpos = dict(q_pos0=0, q_stride=e.T - 1) if self._tail(b, i) else dict(q_pos0=e.q_pos0, q_stride=e.q_stride)
+        GP = lambda leaf, off=0: st.gptr(self._pn(e, i, leaf), off)
+        ipw = self._pn(e, i, "self_attn.in_proj_weight")
+        lr = self._lowrank
+        par = i & 1
+        dy, dq, dao, delta = (b[n][par] for n in ("dy", "dq", "dao", "delta"))
+        ldk = c.layers * ld                       # layer i's dK / dV: column block i of dkall / dvall
+        dk, dv = (None, None) if lr else (b["dkall"][:, i * ld:(i + 1) * ld], b["dvall"][:, i * ld:(i + 1) * ld])
+        t["c.grads"] += [dy, dq]
+        t["c.acts"] += [b["ao"][i], q_src] + ([] if lr else [b["khat"], b["vhat"]])
+        # (the first writer of out_proj.weight / in_proj_weight rows [0, d) on the side stream; a biprojection
+        # self-attention block below comes second and accumulates)
+        t["c.wg"].append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=acc1))
+        t["c.dgout"].append(ops.gemm_problem(dy, st.sptr(self._pn(e, i, "self_attn.out_proj.weight")), dao, Rq, d, d, ld, ld, 0,
+                                             out_kind=OUT_HEADS, heads=(B, H, Tq, self.dh, self.dhp)))
+        lrx = {}
+        if lr:
+            HT, Sp = H * Tq, b["Sp"]
+            rows = HT * B                        # row (h*T + t)*B + b everywhere below
+            lrx = dict(dS=b["dSall"][i], Pd=b["Pdall"][i], xs=(Sp, Tq * B * Sp, B * Sp))
+        t["c.att"].append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tq, e.S, self.dh,
+                                           self.dhp, self._mask_off(e.T_full or e.T, e.S), dO=dao, delta=delta, dQ=dq, lddq=ld,
+                                           dK=dk, lddk=ldk, dV=dv, lddv=ldk, dq_scale=self.scale,
+                                           drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN), **qpos, **lrx))
+        # query projection: gradients go straight to the parameters.  Key / value projections ran with the
+        # LayerNorm folded in: their bias column sums and weight gradients (against khat / vhat) land in
+        # per-layer scratch and are unfolded into in_proj / LayerNorm gradients by one launch at the end.
+        # (the bias column sums ride on the weight-gradient GEMMs: colsum_a, one extra MFMA against ones)
+        t["c.wg"].append(ops.gemm_problem(dq, q_src, st.gptr(ipw, 0), d, d, Rq, ld, ld, d, flags=acc1,
+                                          colsum_a=GP("self_attn.in_proj_bias")))
+        if lr:
+            qexp, doexp, U, Av = (b[n][par] for n in ("qexp", "doexp", "U", "Av"))
+            # heads' q / dO vectors as block rows; the folded value-bias gradient = sum rowsum(Pd) dO (the folded key
+            # bias gets none: the rows of dS sum to zero -- dbf's key half stays at the zero every backward starts from)
+            t["c.expand"].append(ops.expand_problem(b["qh"][i], dao, qexp, doexp, B, H, Tq, self.dh, self.dhp, ld, Pd=b["Pdall"][i],
+                                                    S=Sp, dbias=b["dbf"][i][d:]))
+            for src, stack, dst in ((qexp, KSTACK, b["qkall"][i]), (doexp, VSTACK, b["daall"][i])):
+                t["c.lrqk"].append(ops.gemm_problem(src, st.sptr(e.prefix + stack, i * ld * ld), dst, rows, d, d, ld, ld, ld,
+                                                    out_kind=OUT_CT))
+            # per batch element: [H T, S] x [S, d]; the rows of a batch element are B rows apart in all three tensors
+            for mat, hat_, dst in ((b["dSall"][i], b["khat"], U), (b["Pdall"][i], b["vhat"], Av)):
+                t["c.lrqk"].append(ops.gemm_problem(mat, hat_, dst, HT, d, e.S, B * Sp, B * ld, B * ld, out_kind=OUT_CT,
+                                                    flags=F_CT_NARROW, batch=(B, Sp, ld, ld)))
+            t["c.wg"].append(ops.gemm_problem(qexp, U, b["dWf"][i][:d], d, d, rows, ld, ld, d))
+            t["c.wg"].append(ops.gemm_problem(doexp, Av, b["dWf"][i][d:], d, d, rows, ld, ld, d))
+        else:
+            t["c.wg"].append(ops.gemm_problem(dk, b["khat"], b["dWf"][i][:d], d, d, Rk, ldk, ld, d, colsum_a=b["dbf"][i][:d]))
+            t["c.wg"].append(ops.gemm_problem(dv, b["vhat"], b["dWf"][i][d:], d, d, Rk, ldk, ld, d, colsum_a=b["dbf"][i][d:]))
+        t["c.dgq"].append(ops.gemm_problem(dq, st.sptr(ipw, 0), dq_out, Rq, d, d, ld, ld, d, flags=dq_flags))
+
+    def _ffn_fwd(self, t, e, b, i, pr, stats):
+        """x[i+1] = xmid + drop(fc2(drop(relu(fc1(LN_F xmid))))); stats: LN_F's mean / rstd buffers."""
+        st, c, d, ld, ld4 = self.store, self.cfg, self.cfg.d, self.ld, self.ld4
+        P = lambda leaf: st.p(self._pn(e, i, leaf))
+        Rq = b["Rl"][i]
+        t["f.ln"].append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{self._lnF}.weight"), P(f"layer_norms.{self._lnF}.bias"),
+                                        stats[0], stats[1], Rq, out=b["xn2"][i], ldo=ld))
+        t["f.fc1"].append(ops.gemm_problem(b["xn2"][i], st.sptr(self._pn(e, i, "fc1.weight")), b["h1"][i], Rq, 4 * d, d, ld, ld, ld4,
+                                           bias_n=P("fc1.bias"), flags=F_RELU, drop_p=pr(c.relu_dropout),
+                                           drop_site=site(e.enc_id, i, S_RELU), out_kind=OUT_CT))
+        t["f.fc2"].append(ops.gemm_problem(b["h1"][i], st.sptr(self._pn(e, i, "fc2.weight")), b["x"][i + 1], Rq, d, 4 * d, ld4, ld4, d,
+                                           bias_n=P("fc2.bias"), resid=b["xmid"][i], ldr=d, drop_p=pr(c.res_dropout),
+                                           drop_site=site(e.enc_id, i, S_RES2)))
+
+    def _ffn_bwd(self, t, e, b, i, pr, acc1, dx, stats):
+        """Backward of _ffn_fwd from dyf (written by the layer above) down to xmid; the LN_F backward adds into the residual
+        gradient dx and hands d(out_proj output) = dropmask(dx) (site S_RES1) to the attention block below as dy."""
+        st, c, d, ld, ld4 = self.store, self.cfg, self.cfg.d, self.ld, self.ld4
+        GP = lambda leaf: st.gptr(self._pn(e, i, leaf))
+        Rq = b["Rl"][i]
+        dh1, dy, dyf = b["dh1"][i & 1], b["dy"][i & 1], b["dyf"][i % 3]
+        inv_relu = 1.0 / (1.0 - pr(c.relu_dropout))
+        t["f.grads"] += [dyf, dh1]
+        t["f.acts"] += [b["h1"][i], b["xn2"][i]]
+        t["f.wg"].append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, Rq, ld, ld4, 4 * d, flags=acc1))
+        t["f.dg2"].append(ops.gemm_problem(dyf, st.sptr(self._pn(e, i, "fc2.weight")), dh1, Rq, 4 * d, d, ld, ld4, ld4,
+                                           gate=b["h1"][i], ldg=ld4, gate_scale=inv_relu, colsum=GP("fc1.bias"), out_kind=OUT_CT))
+        t["f.wg"].append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, Rq, ld4, ld, d, flags=acc1))
+        t["f.dg1"].append(ops.gemm_problem(dh1, st.sptr(self._pn(e, i, "fc1.weight")), b["dxn"], Rq, d, 4 * d, ld4, ld, d))
+        lnF = self._lnF
+        t["f.ln"].append(ops.ln_problem(b["xmid"][i], st.p(self._pn(e, i, f"layer_norms.{lnF}.weight")), None, stats[0], stats[1], Rq,
+                                        dy=b["dxn"], ldy=d, add=dx, dx=dx, dgamma=GP(f"layer_norms.{lnF}.weight"),
+                                        dbeta=GP(f"layer_norms.{lnF}.bias"), cast=dy, ldc=ld,
+                                        cast_colsum=GP("self_attn.out_proj.bias"), drop_p=pr(c.res_dropout),
+                                        drop_site=site(e.enc_id, i, S_RES1)))
+
     # -- forward tables ---------------------------------------------------------
     def _build_fwd(self, training: bool):
-        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
-        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
+        c, st, d, A = self.cfg, self.store, self.cfg.d, ops.array
         pr = (lambda p: p) if training else (lambda p: 0.0)
-        A = ops.array
-        hat = []
-        for e, b in zip(self.encs, self.buf):
-            hat += [ops.ln_problem(b["ke"], self._ones, self._zeros, b["stk"][0], b["stk"][1], b["Rk"], out=b["khat"], ldo=ld),
-                    ops.ln_problem(b["ve"], self._ones, self._zeros, b["stv"][0], b["stv"][1], b["Rk"], out=b["vhat"], ldo=ld)]
-        steps, kv_steps = [], [(SIDE, (ops.ln_fwd, self.dtype, A(LnProblem, hat), d)), (MARK, "hat")]
+        ln = lambda probs: (ops.ln_fwd, self.dtype, A(LnProblem, probs), d)
+        nt = lambda probs: self._gemm(GEMM_NT, probs)
+        attn = lambda probs: (ops.attn_fwd, self.dtype, A(AttnProblem, probs))
+        steps, kv_steps = [], []
+        if self._kv:
+            hat = []
+            for b in self.buf:
+                hat += [ops.ln_problem(b["ke"], self._ones, self._zeros, b["stk"][0], b["stk"][1], b["Rk"], out=b["khat"], ldo=self.ld),
+                        ops.ln_problem(b["ve"], self._ones, self._zeros, b["stv"][0], b["stv"][1], b["Rk"], out=b["vhat"], ldo=self.ld)]
+            kv_steps = [(SIDE, ln(hat)), (MARK, "hat")]
         for i in range(c.layers):
-            ln, qkv, att, outp, ln2, fc1, fc2 = [], [], [], [], [], [], []
-            kvp = []
-            pre = dict(ln=[], gather=[], qkv=[], att=[], outp=[], cast=[])      # biprojection self-attention half
+            t = defaultdict(list)
             for e, b in zip(self.encs, self.buf):
-                R, Rk = b["R"], b["Rk"]
-                Rq, Tq = b["Rl"][i], b["Tl"][i]                        # query-side rows / time steps of this layer
-                tail = b["tailp"] and i == c.layers - 1                # rows {0, T-1} only (EncoderDesc.tail_rows)
-                qpos = dict(q_pos0=0, q_stride=e.T - 1) if tail else dict(q_pos0=e.q_pos0, q_stride=e.q_stride)
-                P = lambda leaf: st.p(self._pn(e, i, leaf))
-                ipw = self._pn(e, i, "self_attn.in_proj_weight")
-                ipb = P("self_attn.in_proj_bias")
-                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
-                g0, b0 = P("layer_norms.0.weight"), P("layer_norms.0.bias")
-                g1, b1 = P("layer_norms.1.weight"), P("layer_norms.1.bias")
-
-                def proj(Ain, rows, which, Cout, Tlen):
-                    return ops.gemm_problem(Ain, st.sptr(ipw, which * d * ld), Cout, rows, d, d, ld, ld, 0,
-                                            bias_n=ipb[which * d:(which + 1) * d], alpha=self.scale if which == 0 else 1.0,
-                                            out_kind=OUT_HEADS, heads=(B, H, Tlen, dh, dhp))
-
-                def proj_kv(Ain, which, Cout):       # folded: khat (W_k * gamma)^T + (W_k beta + b_k)
-                    kvf = self._pn(e, i, KVF)
-                    return ops.gemm_problem(Ain, st.sptr(kvf + (".k" if which == 1 else ".v")), Cout, Rk, d, d, ld, ld, 0,
-                                            bias_n=st.fold(kvf, (which - 1) * d, d), out_kind=OUT_HEADS,
-                                            heads=(B, H, e.S, dh, dhp))
-
-                x_in = b["x"][i]
-                if c.biprojection:
-                    g2, b2 = P("layer_norms.2.weight"), P("layer_norms.2.bias")
-                    pre["ln"].append(ops.ln_problem(x_in, g0, b0, b["st0m"][i], b["st0r"][i], R, out=b["xn"][i], ldo=ld))
-                    xq_in, res_in = b["xn"][i], x_in                   # self-attention query operand, its residual
-                    if tail:
-                        # time steps 0 and T-1 are the first and the last B rows of a [T, B, .] tensor: two block copies
-                        for j, r0 in ((0, 0), (1, R - B)):
-                            pre["gather"].append(ops.cast_problem(x_in[r0:r0 + B], d, B, d, dst_f32=b["xg"][j * B:(j + 1) * B], ldf=d))
-                            pre["gather"].append(ops.cast_problem(b["xn"][i][r0:r0 + B], ld, B, d, a_is_ct=True,
-                                                                  dst_ct=b["xng"][j * B:(j + 1) * B], ldd=ld))
-                        xq_in, res_in = b["xng"], b["xg"]
-                    pre["qkv"] += [proj(xq_in, Rq, 0, b["qs"][i], Tq), proj(b["xn"][i], R, 1, b["ks"][i], e.T),
-                                   proj(b["xn"][i], R, 2, b["vs"][i], e.T)]
-                    pre["att"].append(ops.attn_problem(b["qs"][i], b["ks"][i], b["vs"][i], b["aos"][i], ld, b["lses"][i], B, H,
-                                                       Tq, e.T, dh, dhp, self._mask_off(e.T, e.T),
-                                                       drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF),
-                                                       **(qpos if tail else {})))
-                    pre["outp"].append(ops.gemm_problem(b["aos"][i], st.sptr(wo), b["xmid0"][i], Rq, d, d, ld, ld, d,
-                                                        bias_n=P("self_attn.out_proj.bias"), resid=res_in, ldr=d,
-                                                        drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES0)))
-                    pre["cast"].append(ops.cast_problem(b["xmid0"][i], d, Rq, d, dst_ct=b["xq"][i], ldd=ld))
-                    q_src, resid_src = b["xq"][i], b["xmid0"][i]
-                    gf, bf = g2, b2
-                    stf = (b["st2m"][i], b["st2r"][i])
-                else:
-                    ln.append(ops.ln_problem(x_in, g0, b0, b["st0m"][i], b["st0r"][i], R, out=b["xn"][i], ldo=ld))
-                    q_src, resid_src = b["xn"][i], x_in
-                    gf, bf = g1, b1
-                    stf = (b["st1m"][i], b["st1r"][i])
-                qkv.append(proj(q_src, Rq, 0, b["qh"][i], Tq))
-                kvp.append(proj_kv(b["khat"], 1, b["kh"][i]))
-                kvp.append(proj_kv(b["vhat"], 2, b["vh"][i]))
-                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tq, e.S, dh, dhp,
-                                            self._mask_off(e.T_full or e.T, e.S), drop_p=pr(e.attn_dropout),
-                                            drop_site=site(e.enc_id, i, S_ATTN), **qpos))
-                outp.append(ops.gemm_problem(b["ao"][i], st.sptr(wo), b["xmid"][i], Rq, d, d, ld, ld, d,
-                                             bias_n=P("self_attn.out_proj.bias"), resid=resid_src, ldr=d,
-                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES1)))
-                ln2.append(ops.ln_problem(b["xmid"][i], gf, bf, stf[0], stf[1], Rq, out=b["xn2"][i], ldo=ld))
-                fc1.append(ops.gemm_problem(b["xn2"][i], st.sptr(w1), b["h1"][i], Rq, 4 * d, d, ld, ld, ld4, bias_n=P("fc1.bias"),
-                                            flags=F_RELU, drop_p=pr(c.relu_dropout), drop_site=site(e.enc_id, i, S_RELU),
-                                            out_kind=OUT_CT))
-                fc2.append(ops.gemm_problem(b["h1"][i], st.sptr(w2), b["x"][i + 1], Rq, d, 4 * d, ld4, ld4, d, bias_n=P("fc2.bias"),
-                                            resid=b["xmid"][i], ldr=d, drop_p=pr(c.res_dropout),
-                                            drop_site=site(e.enc_id, i, S_RES2)))
-            if c.biprojection:
-                steps += [(ops.ln_fwd, self.dtype, A(LnProblem, pre["ln"]), d)] + \
-                         ([(ops.rows_cast, self.dtype, A(CastProblem, pre["gather"]))] if pre["gather"] else []) + \
-                         [self._gemm(GEMM_NT, pre["qkv"]),
-                          (ops.attn_fwd, self.dtype, A(AttnProblem, pre["att"])),
-                          self._gemm(GEMM_NT, pre["outp"]),
-                          (ops.rows_cast, self.dtype, A(CastProblem, pre["cast"]))]
+                self._ln0_fwd(t, e, b, i)
+                if not self._kv:                           # self-only: self + FFN
+                    self._self_attn_fwd(t, e, b, i, pr, _SELF_KEYS, S_RES1)
+                    self._ffn_fwd(t, e, b, i, pr, (b["st1m"][i], b["st1r"][i]))
+                elif c.biprojection:                       # self + cross (queries: the self block's output, not normalised) + FFN
+                    self._self_attn_fwd(t, e, b, i, pr, _BIP_SELF_KEYS, S_RES0)
+                    t["s.cast"].append(ops.cast_problem(b["xmid0"][i], d, b["Rl"][i], d, dst_ct=b["xq"][i], ldd=self.ld))
+                    self._cross_attn_fwd(t, e, b, i, pr, b["xq"][i], b["xmid0"][i])
+                    self._ffn_fwd(t, e, b, i, pr, (b["st2m"][i], b["st2r"][i]))
+                else:                                      # crossmodal: cross (queries: LN0(x)) + FFN
+                    self._cross_attn_fwd(t, e, b, i, pr, b["xn"][i], b["x"][i])
+                    self._ffn_fwd(t, e, b, i, pr, (b["st1m"][i], b["st1r"][i]))
+            self_half = lambda: [ln(t["ln0"])] + ([(ops.rows_cast, self.dtype, A(CastProblem, t["s.gather"]))] if t["s.gather"] else []) \
+                + [nt(t["s.qkv"]), attn(t["s.att"]), nt(t["s.out"])]
             # K/V side of every layer depends only on the (embedded) key/value sources: the side stream runs it
             # ahead of the query chain; the main stream waits for layer i's K/V heads just before attention i.
-            kv_steps += [(SIDE, self._gemm(GEMM_NT, kvp)), (MARK, i)]
-            if ln:
-                steps.append((ops.ln_fwd, self.dtype, A(LnProblem, ln), d))
-            steps += [self._gemm(GEMM_NT, qkv),
-                      (WAIT, i),
-                      (ops.attn_fwd, self.dtype, A(AttnProblem, att)),
-                      self._gemm(GEMM_NT, outp)]
-            steps += [(ops.ln_fwd, self.dtype, A(LnProblem, ln2), d),
-                      self._gemm(GEMM_NT, fc1),
-                      self._gemm(GEMM_NT, fc2)]
+            cross = lambda: [nt(t["c.q"]), (WAIT, i), attn(t["c.att"]), nt(t["c.out"])]
+            ffn = [ln(t["f.ln"]), nt(t["f.fc1"]), nt(t["f.fc2"])]
+            if not self._kv:
+                steps += self_half() + ffn
+            elif c.biprojection:
+                steps += self_half() + [(ops.rows_cast, self.dtype, A(CastProblem, t["s.cast"]))] + cross() + ffn
+            else:
+                steps += [ln(t["ln0"])] + cross() + ffn
+            if self._kv:
+                kv_steps += [(SIDE, nt(t["c.kv"])), (MARK, i)]
         fin = [ops.ln_problem(b["x"][c.layers], st.p(e.prefix + "layer_norm.weight"), st.p(e.prefix + "layer_norm.bias"),
                               b["stf"][0], b["stf"][1], b["Rl"][-1], out=b["out"], ldo=d, out_f32=True)
                for e, b in zip(self.encs, self.buf)]
-        steps.append((ops.ln_fwd, self.dtype, A(LnProblem, fin), d))
-        return kv_steps + steps + [JOIN]
+        steps.append(ln(fin))
+        return kv_steps + steps + ([JOIN] if self._kv else [])
+
 
     def _exec(self, s, seed: int) -> None:
         fn = s[0]
@@ -889,17 +1046,15 @@ class EncoderGroupPlan:
         c, B, d = self.cfg, self.B, self.cfg.d
         p = c.embed_dropout if training else 0.0
         emb = []
-        if c.self_only:                         # one input per encoder (xk / xv are ignored and may be None)
+        if not self._kv:                        # one input per encoder (xk / xv are ignored and may be None)
             xk = xv = [None] * len(self.encs)
         for e, b, q, k, v in zip(self.encs, self.buf, xq, xk, xv):
-            for t, n in ((q, e.T), (k, e.S), (v, e.S)):
-                if t is None and c.self_only:
-                    continue
+            for t, n in ((q, e.T), (k, e.S), (v, e.S))[:3 if self._kv else 1]:
                 if tuple(t.shape) != (n, B, d) or not t.is_contiguous() or t.dtype != torch.float32:
                     raise ValueError(f"encoder {e.prefix}: expected contiguous fp32 [{n},{B},{d}], got {tuple(t.shape)} {t.dtype}")
             emb.append(ops.embed_problem(q, b["x"][0], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q), pos0=e.q_pos0,
                                          pos_stride=e.q_stride))
-            if not c.self_only:
+            if self._kv:
                 emb += [ops.embed_problem(k, b["ke"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)),
                         ops.embed_problem(v, b["ve"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V))]
         ops.embed_pos_fwd(emb, self.table, d, math.sqrt(d), seed)
@@ -909,351 +1064,99 @@ class EncoderGroupPlan:
 
     # -- backward tables --------------------------------------------------------
     def _build_bwd(self, training: bool, stores: bool = False):
-        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
+        c, st, d, A = self.cfg, self.store, self.cfg.d, ops.array
         ACC1 = 0 if stores else F_ACCUM          # flags of the FIRST writer of a large weight gradient in a step
-        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
         pr = (lambda p: p) if training else (lambda p: 0.0)
-        A = ops.array
-        G = len(self.encs)
+        nn = lambda probs: self._gemm(GEMM_NN, probs)
+        wg = lambda probs, presplit: (SIDE, self._gemm(GEMM_TN, probs, background=True, presplit=presplit))
+        ln = lambda probs: (ops.ln_bwd, A(LnProblem, probs), d)
+        x3, lr = st.x3, self._lowrank
         steps = []
-        inv_relu = 1.0 / (1.0 - pr(c.relu_dropout))
         for i in reversed(range(c.layers)):
-            wg_ffn, dg_fc2, dg_fc1, lnf = [], [], [], []
-            wg_att, dg_out, att, dg_q, lnq = [], [], [], [], []
-            s_cast0, s_dgout0, s_att0, s_wg0, s_dg0a, s_dg0b, s_dg0c, s_ln0 = [], [], [], [], [], [], [], []
-            s_dgq, s_scatter = [], []                 # tail_rows (last layer): d(LN0 rows {0, T-1}) and the scatter back to [R, d]
-            lr = self._lowrank
-            lr_exp, lr_qk = [], []                    # low-rank key side: head expansion; Qexp W' and dS khat / Pd vhat products
-            pre_ffn, pre_att = [], []                 # bf16x3: operands of the weight gradients whose split image already exists
+            t = defaultdict(list)
             for e, b in zip(self.encs, self.buf):
-                R, Rk = b["R"], b["Rk"]
-                Rq, Tq = b["Rl"][i], b["Tl"][i]                        # query-side rows / time steps of this layer
-                tail = b["tailp"] and i == c.layers - 1
-                qpos = dict(q_pos0=0, q_stride=e.T - 1) if tail else dict(q_pos0=e.q_pos0, q_stride=e.q_stride)
-                P = lambda leaf: st.p(self._pn(e, i, leaf))
-                GP = lambda leaf, off=0: st.gptr(self._pn(e, i, leaf), off)
-                ipw = self._pn(e, i, "self_attn.in_proj_weight")
-                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
-                lnF = 2 if c.biprojection else 1      # FFN LayerNorm index
-                lnK = 1 if c.biprojection else 0      # key/value LayerNorm index
-                stF = (b["st2m"][i], b["st2r"][i]) if c.biprojection else (b["st1m"][i], b["st1r"][i])
                 # residual-stream gradient of this layer's query rows: the two gathered rows in a tail_rows last layer
                 # (its LayerNorm-0 backward over all rows then writes the dense dx the layers below continue from)
-                dx = b["dxg"] if tail else b["dx"]
-                par = i & 1
-                dh1, dy, dq, dao, delta = (b[n][par] for n in ("dh1", "dy", "dq", "dao", "delta"))
-                ldk = c.layers * ld                       # layer i's dK / dV: column block i of dkall / dvall
-                dk, dv = (None, None) if lr else (b["dkall"][:, i * ld:(i + 1) * ld], b["dvall"][:, i * ld:(i + 1) * ld])
-                dyf = b["dyf"][i % 3]
-                # hand-off to the next layer down (i-1): its FFN-output gradient dyf = dropmask(dx) and fc2.bias
-                # gradient are produced by whichever LayerNorm backward finishes this layer's dx
-                nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=ld, cast_colsum=st.gptr(self._pn(e, i - 1, "fc2.bias")),
-                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i - 1, S_RES2))
-                if c.biprojection:
-                    dy0, dqs, dks, dvs = (b[n][par] for n in ("dy0", "dqs", "dks", "dvs"))
-                pre_ffn += [dyf, dh1, b["h1"][i], b["xn2"][i]]
-                pre_att += [dy, dq, b["ao"][i], b["xq"][i] if c.biprojection else b["xn"][i]] + ([] if lr else [b["khat"], b["vhat"]])
-                # ---- FFN
-                wg_ffn.append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, Rq, ld, ld4, 4 * d,
-                                               flags=ACC1))
-                dg_fc2.append(ops.gemm_problem(dyf, st.sptr(w2), dh1, Rq, 4 * d, d, ld, ld4, ld4, gate=b["h1"][i], ldg=ld4,
-                                               gate_scale=inv_relu, colsum=GP("fc1.bias"), out_kind=OUT_CT))
-                wg_ffn.append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, Rq, ld4, ld, d,
-                                               flags=ACC1))
-                dg_fc1.append(ops.gemm_problem(dh1, st.sptr(w1), b["dxn"], Rq, d, 4 * d, ld4, ld, d))
-                lnf.append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{lnF}.weight"), None, stF[0], stF[1], Rq, dy=b["dxn"], ldy=d,
-                                          add=dx, dx=dx, dgamma=GP(f"layer_norms.{lnF}.weight"), dbeta=GP(f"layer_norms.{lnF}.bias"),
-                                          cast=dy, ldc=ld, cast_colsum=GP("self_attn.out_proj.bias"), drop_p=pr(c.res_dropout),
-                                          drop_site=site(e.enc_id, i, S_RES1)))
-                # ---- (cross) attention block
-                # (cross-attention half: the first writer of out_proj.weight / in_proj_weight rows [0, d) on the side stream; the
-                # biprojection self-attention half below comes second and accumulates)
-                wg_att.append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d,
-                                               flags=ACC1))
-                dg_out.append(ops.gemm_problem(dy, st.sptr(wo), dao, Rq, d, d, ld, ld, 0, out_kind=OUT_HEADS,
-                                               heads=(B, H, Tq, dh, dhp)))
-                lrx = {}
-                if lr:
-                    HT, Sp = H * Tq, b["Sp"]
-                    rows = HT * B                        # row (h*T + t)*B + b everywhere below
-                    lrx = dict(dS=b["dSall"][i], Pd=b["Pdall"][i], xs=(Sp, Tq * B * Sp, B * Sp))
-                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tq, e.S, dh, dhp,
-                                            self._mask_off(e.T_full or e.T, e.S), dO=dao, delta=delta, dQ=dq, lddq=ld,
-                                            dK=dk, lddk=ldk, dV=dv, lddv=ldk, dq_scale=self.scale,
-                                            drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN), **qpos, **lrx))
-                ipb_g = self._pn(e, i, "self_attn.in_proj_bias")
-                # query projection: gradients go straight to the parameters.  Key / value projections ran with the
-                # LayerNorm folded in: their bias column sums and weight gradients (against khat / vhat) land in
-                # per-layer scratch and are unfolded into in_proj / LayerNorm gradients by one launch at the end.
-                # (the bias column sums ride on the weight-gradient GEMMs: colsum_a, one extra MFMA against ones)
-                q_src = b["xq"][i] if c.biprojection else b["xn"][i]
-                wg_att.append(ops.gemm_problem(dq, q_src, st.gptr(ipw, 0), d, d, Rq, ld, ld, d, flags=ACC1,
-                                               colsum_a=st.gptr(ipb_g, 0)))
-                if lr:
-                    qexp, doexp, U, Av = (b[n][par] for n in ("qexp", "doexp", "U", "Av"))
-                    # heads' q / dO vectors as block rows; the folded value-bias gradient = sum rowsum(Pd) dO (the folded key
-                    # bias gets none: the rows of dS sum to zero -- dbf's key half stays at the zero every backward starts from)
-                    lr_exp.append(ops.expand_problem(b["qh"][i], dao, qexp, doexp, B, H, Tq, dh, dhp, ld, Pd=b["Pdall"][i], S=Sp,
-                                                     dbias=b["dbf"][i][d:]))
-                    for src, stack, dst in ((qexp, KSTACK, b["qkall"][i]), (doexp, VSTACK, b["daall"][i])):
-                        lr_qk.append(ops.gemm_problem(src, st.sptr(e.prefix + stack, i * ld * ld), dst, rows, d, d, ld, ld, ld,
-                                                      out_kind=OUT_CT))
-                    # per batch element: [H T, S] x [S, d]; the rows of a batch element are B rows apart in all three tensors
-                    for mat, hat_, dst in ((b["dSall"][i], b["khat"], U), (b["Pdall"][i], b["vhat"], Av)):
-                        lr_qk.append(ops.gemm_problem(mat, hat_, dst, HT, d, e.S, B * Sp, B * ld, B * ld, out_kind=OUT_CT,
-                                                      flags=F_CT_NARROW, batch=(B, Sp, ld, ld)))
-                    wg_att.append(ops.gemm_problem(qexp, U, b["dWf"][i][:d], d, d, rows, ld, ld, d))
-                    wg_att.append(ops.gemm_problem(doexp, Av, b["dWf"][i][d:], d, d, rows, ld, ld, d))
+                dx = b["dxg"] if self._tail(b, i) else b["dx"]
+                if not self._kv:                           # self-only: self + FFN, every block the first writer
+                    self._ffn_bwd(t, e, b, i, pr, ACC1, dx, (b["st1m"][i], b["st1r"][i]))
+                    self._self_attn_bwd(t, e, b, i, pr, _SELF_KEYS, ACC1, ACC1)
+                elif c.biprojection:
+                    # query was not normalised: its gradient joins the residual stream directly; the self-attention block
+                    # comes second on out_proj.weight / in_proj_weight rows [0, d) and accumulates
+                    self._ffn_bwd(t, e, b, i, pr, ACC1, dx, (b["st2m"][i], b["st2r"][i]))
+                    self._cross_attn_bwd(t, e, b, i, pr, ACC1, b["xq"][i], dx, F_ACCUM)
+                    self._self_attn_bwd(t, e, b, i, pr, _BIP_SELF_KEYS, F_ACCUM, ACC1, cast=(dx, S_RES0))
                 else:
-                    wg_att.append(ops.gemm_problem(dk, b["khat"], b["dWf"][i][:d], d, d, Rk, ldk, ld, d, colsum_a=b["dbf"][i][:d]))
-                    wg_att.append(ops.gemm_problem(dv, b["vhat"], b["dWf"][i][d:], d, d, Rk, ldk, ld, d, colsum_a=b["dbf"][i][d:]))
-                if c.biprojection:   # query was not normalised: its gradient joins the residual stream directly
-                    dg_q.append(ops.gemm_problem(dq, st.sptr(ipw, 0), dx, Rq, d, d, ld, ld, d, flags=F_ACCUM))
-                else:
-                    dg_q.append(ops.gemm_problem(dq, st.sptr(ipw, 0), b["dxn"], Rq, d, d, ld, ld, d))
-                    lnq.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), None, b["st0m"][i], b["st0r"][i], Rq, dy=b["dxn"],
-                                              ldy=d, add=dx, dx=dx, dgamma=GP("layer_norms.0.weight"), dbeta=GP("layer_norms.0.bias"),
-                                              **nxt))
-                if c.biprojection:
-                    # ---- self-attention half (same attention parameters)
-                    s_cast0.append(ops.cast_problem(dx, d, Rq, d, dst_ct=dy0, ldd=ld, colsum=GP("self_attn.out_proj.bias"),
-                                                    drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES0)))
-                    s_wg0.append(ops.gemm_problem(dy0, b["aos"][i], GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d,
-                                                  flags=F_ACCUM))
-                    s_dgout0.append(ops.gemm_problem(dy0, st.sptr(wo), b["dao0"], Rq, d, d, ld, ld, 0, out_kind=OUT_HEADS,
-                                                     heads=(B, H, Tq, dh, dhp)))
-                    s_att0.append(ops.attn_problem(b["qs"][i], b["ks"][i], b["vs"][i], b["aos"][i], ld, b["lses"][i], B, H, Tq, e.T,
-                                                   dh, dhp, self._mask_off(e.T, e.T), dO=b["dao0"], delta=b["delta0"], dQ=dqs,
-                                                   lddq=3 * ld, dK=dks, lddk=3 * ld, dV=dvs, lddv=3 * ld, dq_scale=self.scale,
-                                                   drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF),
-                                                   **(qpos if tail else {})))
-                    # in_proj_weight rows [d, 3d): this launch is their first writer (unfold_grads comes after it and adds)
-                    xq_in = b["xng"] if tail else b["xn"][i]
-                    for w, src, xin, rows in ((0, dqs, xq_in, Rq), (1, dks, b["xn"][i], R), (2, dvs, b["xn"][i], R)):
-                        s_wg0.append(ops.gemm_problem(src, xin, st.gptr(ipw, w * d * d), d, d, rows, 3 * ld, ld, d,
-                                                      flags=F_ACCUM if w == 0 else ACC1, colsum_a=st.gptr(ipb_g, w * d)))
-                    # d(xn) = dq Wq + dk Wk + dv Wv: three launches (plain store, then two +=) -- one owner per
-                    # output tile in each launch, no atomics (per-lane-scattered float atomics run ~17x below store rate)
-                    if tail:
-                        # keys / values come from every row, the query only from rows {0, T-1}: d(xn) over all rows is the
-                        # K / V part; the query part is a [2B, d] product whose row blocks are added into it, and the
-                        # gathered rows' residual gradient goes to the same two row blocks of the otherwise-zero dxs
-                        if ld == d:
-                            s_dg0a.append(ops.gemm_problem(b["dqkvs"][par][:R, ld:], st.sptr(ipw, d * ld), b["dxn"], R, d, 2 * d,
-                                                           3 * ld, ld, d))
-                        else:
-                            s_dg0a.append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d))
-                            s_dg0b.append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
-                        s_dgq.append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxng"], Rq, d, d, 3 * ld, ld, d))
-                        for j, r0 in ((0, 0), (1, R - B)):
-                            blk = slice(j * B, (j + 1) * B)
-                            s_scatter.append(ops.addn_problem(b["dxn"][r0:r0 + B], [b["dxn"][r0:r0 + B], b["dxng"][blk]]))
-                            s_scatter.append(ops.addn_problem(b["dxs"][r0:r0 + B], [b["dxg"][blk]]))
-                    elif ld == d:                                   # one product over K = 3d (see the dqkvs buffer)
-                        s_dg0a.append(ops.gemm_problem(b["dqkvs"][par], st.sptr(ipw, 0), b["dxn"], R, d, 3 * d, 3 * ld, ld, d))
-                    else:
-                        s_dg0a.append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxn"], R, d, d, 3 * ld, ld, d))
-                        s_dg0b.append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
-                        s_dg0c.append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
-                    s_ln0.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), None, b["st0m"][i], b["st0r"][i], R,
-                                                dy=b["dxn"], ldy=d, add=b["dxs"] if tail else dx, dx=b["dx"],
-                                                dgamma=GP("layer_norms.0.weight"), dbeta=GP("layer_norms.0.bias"), **nxt))
-            for group in (lnf, lnq, s_ln0):               # each LayerNorm-backward launch owns its gradient rows exactly once
+                    self._ffn_bwd(t, e, b, i, pr, ACC1, dx, (b["st1m"][i], b["st1r"][i]))
+                    self._cross_attn_bwd(t, e, b, i, pr, ACC1, b["xn"][i], b["dxn"], 0)
+                self._ln0_bwd(t, e, b, i, pr)
+            for group in (t["f.ln"], t["ln0"]):              # each LayerNorm-backward launch owns its gradient rows exactly once
                 ops.check_ln_rows(group, d)
+
+            def ffn(presplit, wg_late):
+                w = wg(t["f.wg"], presplit)
+                return [nn(t["f.dg2"])] + ([] if wg_late else [w]) + [nn(t["f.dg1"])] + ([w] if wg_late else []) + [ln(t["f.ln"])]
+
+            def self_half(presplit):
+                return [nn(t["s.dgout"]), (ops.attn_bwd, self.dtype, A(AttnProblem, t["s.att"])), wg(t["s.wg"], presplit),
+                        nn(t["s.dg_a"])] + ([nn(t["s.dg_b"])] if t["s.dg_b"] else []) + ([nn(t["s.dg_c"])] if t["s.dg_c"] else []) + \
+                    ([nn(t["s.dgq"]), (ops.add_n, A(AddnProblem, t["s.scatter"]))] if t["s.dgq"] else []) + [ln(t["ln0"])]
+
+            if not self._kv:
+                # Main stream: the data-gradient chain, the attention backward (dK / dV feed the d(xn) product on the
+                # critical path, so both passes run here) and the LayerNorm backwards.  Side stream: the weight gradients.
+                # bf16x3: only forward activations are listed as already split (their image is this step's forward
+                # launch's); gradients are split again by the weight-gradient launch that reads them
+                steps += [(WAIT, i + 2)] + ffn(t["f.acts"] if x3 else (), False) + self_half(t["s.acts"] if x3 else ()) + [(MARK, i)]
+                continue
             # Ownership of parameter-gradient words (bpm_ln_bwd_ws adds its row sums with a plain read-modify-write):
             # layer_norms.* / out_proj.bias / fc2.bias gradients are written by the MAIN stream's LayerNorm backward
             # launches only, except layer_norms.{lnK} which unfold_grads (side stream) also adds to -- that launch is
-            # ordered behind lnq(i) / s_ln0(i) by the main_dirty event recorded before every SIDE step, and the next
-            # main-stream writer of the same words is the NEXT step's backward (behind the JOIN).  Keep it that way.
+            # ordered behind the LayerNorm-0 backward of layer i by the main_dirty event recorded before every SIDE step,
+            # and the next main-stream writer of the same words is the NEXT step's backward (behind the JOIN).  Keep it
+            # that way.
             # Side stream (SIDE): weight gradients and the key/value-side dgrad + LayerNorm backward -- nothing on
             # the backward critical path consumes them.  Temporaries are double-buffered by layer parity, so the
             # main chain only waits (WAIT) for the side work of two layers ago before overwriting them.
-            x3 = st.x3
-            wg_ffn_step = (SIDE, self._gemm(GEMM_TN, wg_ffn, background=True, presplit=pre_ffn if x3 else ()))
-            wg_att_step = (SIDE, self._gemm(GEMM_TN, wg_att, background=True, presplit=pre_att if x3 else ()))
+            wg_att = wg(t["c.wg"], t["c.grads"] + t["c.acts"] if x3 else ())
+            dkv = (ops.attn_bwd_dkv, self.dtype, A(AttnProblem, t["c.att"]))
             # (bf16x3: the weight gradients are launched BEHIND the data-gradient products that split the same gradients --
             # dg_fc1 splits dh1, dg_q splits dq -- so that the side stream finds those images instead of splitting again)
-            steps += [(WAIT, i + 2),
-                      self._gemm(GEMM_NN, dg_fc2)] + ([] if x3 else [wg_ffn_step]) + \
-                     [self._gemm(GEMM_NN, dg_fc1)] + ([wg_ffn_step] if x3 else []) + \
-                     [(ops.ln_bwd, A(LnProblem, lnf), d),
-                      self._gemm(GEMM_NN, dg_out),
-                      (ops.attn_bwd_dq, self.dtype, A(AttnProblem, att)),
-                      # dK / dV feed only side work: beside the main chain where the side stream has slack (see _DKV_SIDE_ENV)
-                      ((SIDE if self._dkv_side == "1" else SIDE2, (ops.attn_bwd_dkv, self.dtype, A(AttnProblem, att)))
-                       if self._dkv_side in ("1", "2") else (ops.attn_bwd_dkv, self.dtype, A(AttnProblem, att)))][:3 if lr else 4] + \
-                     ([] if x3 or lr else [wg_att_step]) + [self._gemm(GEMM_NN, dg_q)] + ([wg_att_step] if x3 and not lr else [])
-            if lnq:
-                steps.append((ops.ln_bwd, A(LnProblem, lnq), d))
+            steps += [(WAIT, i + 2)] + ffn(t["f.grads"] + t["f.acts"] if x3 else (), x3) + \
+                [nn(t["c.dgout"]), (ops.attn_bwd_dq, self.dtype, A(AttnProblem, t["c.att"]))] + \
+                ([] if lr else [(SIDE if self._dkv_side == "1" else SIDE2, dkv) if self._dkv_side in ("1", "2") else dkv]) + \
+                ([] if x3 or lr else [wg_att]) + [nn(t["c.dgq"])] + ([wg_att] if x3 and not lr else [])
+            # dK / dV (above) feed only side work: beside the main chain where the side stream has slack (see _DKV_SIDE_ENV)
+            if c.biprojection:
+                steps += [(ops.rows_cast, self.dtype, A(CastProblem, t["s.cast"]))] + self_half(())
+            else:
+                steps.append(ln(t["ln0"]))
             if lr:
                 # low-rank key side: no dK / dV pass; the side stream continues from the dS / Pd the dQ pass wrote.  Issued
                 # BEHIND the rest of the layer's main chain
-                steps += [(SIDE, (ops.expand_heads, self.dtype, A(ExpandProblem, lr_exp))), (SIDE, self._gemm(GEMM_NN, lr_qk)),
-                          wg_att_step]
-            if c.biprojection:
-                steps += [(ops.rows_cast, self.dtype, A(CastProblem, s_cast0)),
-                          self._gemm(GEMM_NN, s_dgout0),
-                          (ops.attn_bwd, self.dtype, A(AttnProblem, s_att0)),
-                          (SIDE, self._gemm(GEMM_TN, s_wg0, background=True)),
-                          self._gemm(GEMM_NN, s_dg0a)] + \
-                         ([self._gemm(GEMM_NN, s_dg0b)] if s_dg0b else []) + ([self._gemm(GEMM_NN, s_dg0c)] if s_dg0c else []) + \
-                         ([self._gemm(GEMM_NN, s_dgq), (ops.add_n, A(AddnProblem, s_scatter))] if s_dgq else []) + \
-                         [(ops.ln_bwd, A(LnProblem, s_ln0), d)]
+                steps += [(SIDE, (ops.expand_heads, self.dtype, A(ExpandProblem, t["c.expand"]))), (SIDE, nn(t["c.lrqk"])), wg_att]
             # folded K/V gradients of this layer -> in_proj / LayerNorm parameter gradients; with it every gradient of
             # layer i is final once the side stream reaches MARK i and the main stream this point (all-reduce hook)
             steps += [(SIDE, (ops.unfold_grads,) + self._unfold[i] + (stores and not c.biprojection,)), (MARK, i)]
+        if not self._kv:
+            return steps + [JOIN]
         # d(khat), d(vhat): all layers' dK / dV against the stacked projection weights, one product over K = L ld per
         # encoder; then -> d(embedded key / value source): LayerNorm backward without affine
         hat, dg_kv = [], []
         for e, b in zip(self.encs, self.buf):
-            if self._lowrank:        # d(khat) of batch element bb = dS_all[:, bb]^T (Qexp W_k')_all[:, bb], K = layers H T
-                KK, Sp = c.layers * H * e.T, b["Sp"]
+            if lr:                   # d(khat) of batch element bb = dS_all[:, bb]^T (Qexp W_k')_all[:, bb], K = layers H T
+                KK, Sp = c.layers * c.H * e.T, b["Sp"]
                 for mat, prod, G_ in ((b["dSall"], b["qkall"], b["Gk"]), (b["Pdall"], b["daall"], b["Gv"])):
-                    dg_kv.append(ops.gemm_problem(mat, prod, G_, e.S, d, KK, B * Sp, B * ld, B * d, batch=(B, Sp, ld, d)))
+                    dg_kv.append(ops.gemm_problem(mat, prod, G_, e.S, d, KK, self.B * Sp, self.B * self.ld, self.B * d,
+                                                  batch=(self.B, Sp, self.ld, d)))
             else:
-                dg_kv += [ops.gemm_problem(b["dkall"], st.sptr(e.prefix + KSTACK), b["Gk"], b["Rk"], d, c.layers * ld, c.layers * ld, ld, d),
-                          ops.gemm_problem(b["dvall"], st.sptr(e.prefix + VSTACK), b["Gv"], b["Rk"], d, c.layers * ld, c.layers * ld, ld, d)]
+                for all_, stack, G_ in ((b["dkall"], KSTACK, b["Gk"]), (b["dvall"], VSTACK, b["Gv"])):
+                    dg_kv.append(ops.gemm_problem(all_, st.sptr(e.prefix + stack), G_, b["Rk"], d, c.layers * self.ld, c.layers * self.ld,
+                                                  self.ld, d))
             hat += [ops.ln_problem(b["ke"], self._ones, None, b["stk"][0], b["stk"][1], b["Rk"], dy=b["Gk"], ldy=d, dx=b["dke"]),
                     ops.ln_problem(b["ve"], self._ones, None, b["stv"][0], b["stv"][1], b["Rk"], dy=b["Gv"], ldy=d, dx=b["dve"])]
-        steps += [(SIDE, self._gemm(GEMM_TN if self._lowrank else GEMM_NN, dg_kv)), (SIDE, (ops.ln_bwd, A(LnProblem, hat), d)), JOIN]
-        return steps
-
-    # -- self-attention-only tables (GroupCfg.self_only) ---------------------------
-    # transformer.py:141-195 with normalize_before and no key / value source, per layer:
-    #   x = x + drop(out_proj(attn(LN0 x)))          (one mask: T x T, offset 1 when attn_mask)
-    #   x = x + drop(fc2(drop(relu(fc1(LN_F x)))))   LN_F = layer_norms.1, or layer_norms.2 in the biprojection kind (its
-    #                                                layer_norms.1 is the identity of maybe_layer_norm(1, after=True): no gradient)
-    def _build_fwd_self(self, training: bool):
-        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
-        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
-        pr = (lambda p: p) if training else (lambda p: 0.0)
-        A = ops.array
-        lnF = 2 if c.biprojection else 1
-        steps = []
-        for i in range(c.layers):
-            ln, qkv, att, outp, ln2, fc1, fc2 = [], [], [], [], [], [], []
-            for e, b in zip(self.encs, self.buf):
-                R, Tn = b["R"], e.T
-                P = lambda leaf: st.p(self._pn(e, i, leaf))
-                ipw = self._pn(e, i, "self_attn.in_proj_weight")
-                ipb = P("self_attn.in_proj_bias")
-                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
-                ln.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), P("layer_norms.0.bias"), b["st0m"][i], b["st0r"][i],
-                                         R, out=b["xn"][i], ldo=ld))
-                for w, dst in enumerate((b["qh"][i], b["kh"][i], b["vh"][i])):      # Q (scaled), K, V: one grouped launch
-                    qkv.append(ops.gemm_problem(b["xn"][i], st.sptr(ipw, w * d * ld), dst, R, d, d, ld, ld, 0,
-                                                bias_n=ipb[w * d:(w + 1) * d], alpha=self.scale if w == 0 else 1.0,
-                                                out_kind=OUT_HEADS, heads=(B, H, Tn, dh, dhp)))
-                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tn, Tn, dh, dhp,
-                                            self._mask_off(Tn, Tn), drop_p=pr(e.attn_dropout),
-                                            drop_site=site(e.enc_id, i, S_ATTN_SELF)))
-                outp.append(ops.gemm_problem(b["ao"][i], st.sptr(wo), b["xmid"][i], R, d, d, ld, ld, d,
-                                             bias_n=P("self_attn.out_proj.bias"), resid=b["x"][i], ldr=d,
-                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, S_RES1)))
-                ln2.append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{lnF}.weight"), P(f"layer_norms.{lnF}.bias"),
-                                          b["st1m"][i], b["st1r"][i], R, out=b["xn2"][i], ldo=ld))
-                fc1.append(ops.gemm_problem(b["xn2"][i], st.sptr(w1), b["h1"][i], R, 4 * d, d, ld, ld, ld4, bias_n=P("fc1.bias"),
-                                            flags=F_RELU, drop_p=pr(c.relu_dropout), drop_site=site(e.enc_id, i, S_RELU),
-                                            out_kind=OUT_CT))
-                fc2.append(ops.gemm_problem(b["h1"][i], st.sptr(w2), b["x"][i + 1], R, d, 4 * d, ld4, ld4, d, bias_n=P("fc2.bias"),
-                                            resid=b["xmid"][i], ldr=d, drop_p=pr(c.res_dropout),
-                                            drop_site=site(e.enc_id, i, S_RES2)))
-            steps += [(ops.ln_fwd, self.dtype, A(LnProblem, ln), d),
-                      self._gemm(GEMM_NT, qkv),
-                      (ops.attn_fwd, self.dtype, A(AttnProblem, att)),
-                      self._gemm(GEMM_NT, outp),
-                      (ops.ln_fwd, self.dtype, A(LnProblem, ln2), d),
-                      self._gemm(GEMM_NT, fc1),
-                      self._gemm(GEMM_NT, fc2)]
-        fin = [ops.ln_problem(b["x"][c.layers], st.p(e.prefix + "layer_norm.weight"), st.p(e.prefix + "layer_norm.bias"),
-                              b["stf"][0], b["stf"][1], b["R"], out=b["out"], ldo=d, out_f32=True)
-               for e, b in zip(self.encs, self.buf)]
-        steps.append((ops.ln_fwd, self.dtype, A(LnProblem, fin), d))
-        return steps
-
-    def _build_bwd_self(self, training: bool, stores: bool = False):
-        """Main stream: the data-gradient chain, the attention backward (dK / dV feed the d(xn) product on the critical
-        path, so both passes run here) and the LayerNorm backwards.  Side stream: the weight gradients, up to two layers
-        behind (WAIT i + 2 / MARK i and the parity-buffered operands of the other layer kinds).  stores=True: the
-        weight-gradient launch of fc1 / fc2 / out_proj and of each in_proj_weight row block is its only writer and stores;
-        the small tensors (biases, LayerNorm affines, summed by several launches) are in the store's zero segments."""
-        c, st, B, d, H = self.cfg, self.store, self.B, self.cfg.d, self.cfg.H
-        ACC1 = 0 if stores else F_ACCUM
-        ld, ld4, dh, dhp = self.ld, self.ld4, self.dh, self.dhp
-        pr = (lambda p: p) if training else (lambda p: 0.0)
-        A = ops.array
-        inv_relu = 1.0 / (1.0 - pr(c.relu_dropout))
-        lnF = 2 if c.biprojection else 1
-        steps = []
-        for i in reversed(range(c.layers)):
-            wg_ffn, dg_fc2, dg_fc1, lnf, wg_att, dg_out, att, dg_a, dg_b, dg_c, lnq = ([] for _ in range(11))
-            # bf16x3: only forward activations are listed as already split (their image is this step's forward launch's);
-            # gradients are split again by the weight-gradient launch that reads them
-            pre_ffn, pre_att = [], []
-            for e, b in zip(self.encs, self.buf):
-                R, Tn = b["R"], e.T
-                P = lambda leaf: st.p(self._pn(e, i, leaf))
-                GP = lambda leaf, off=0: st.gptr(self._pn(e, i, leaf), off)
-                ipw = self._pn(e, i, "self_attn.in_proj_weight")
-                ipb_g = self._pn(e, i, "self_attn.in_proj_bias")
-                wo, w1, w2 = (self._pn(e, i, n) for n in ("self_attn.out_proj.weight", "fc1.weight", "fc2.weight"))
-                par = i & 1
-                dh1, dy, dqkv = b["dh1"][par], b["dy"][par], b["dqkvs"][par]
-                dqs, dks, dvs = b["dqs"][par], b["dks"][par], b["dvs"][par]
-                dx, dyf = b["dx"], b["dyf"][i % 3]
-                nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=ld, cast_colsum=st.gptr(self._pn(e, i - 1, "fc2.bias")),
-                                             drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i - 1, S_RES2))
-                pre_ffn += [b["h1"][i], b["xn2"][i]]
-                pre_att += [b["ao"][i], b["xn"][i]]
-                # ---- FFN
-                wg_ffn.append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, R, ld, ld4, 4 * d, flags=ACC1))
-                dg_fc2.append(ops.gemm_problem(dyf, st.sptr(w2), dh1, R, 4 * d, d, ld, ld4, ld4, gate=b["h1"][i], ldg=ld4,
-                                               gate_scale=inv_relu, colsum=GP("fc1.bias"), out_kind=OUT_CT))
-                wg_ffn.append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, R, ld4, ld, d, flags=ACC1))
-                dg_fc1.append(ops.gemm_problem(dh1, st.sptr(w1), b["dxn"], R, d, 4 * d, ld4, ld, d))
-                lnf.append(ops.ln_problem(b["xmid"][i], P(f"layer_norms.{lnF}.weight"), None, b["st1m"][i], b["st1r"][i], R,
-                                          dy=b["dxn"], ldy=d, add=dx, dx=dx, dgamma=GP(f"layer_norms.{lnF}.weight"),
-                                          dbeta=GP(f"layer_norms.{lnF}.bias"), cast=dy, ldc=ld,
-                                          cast_colsum=GP("self_attn.out_proj.bias"), drop_p=pr(c.res_dropout),
-                                          drop_site=site(e.enc_id, i, S_RES1)))
-                # ---- self-attention
-                wg_att.append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, R, ld, ld, d, flags=ACC1))
-                dg_out.append(ops.gemm_problem(dy, st.sptr(wo), b["dao"], R, d, d, ld, ld, 0, out_kind=OUT_HEADS,
-                                               heads=(B, H, Tn, dh, dhp)))
-                att.append(ops.attn_problem(b["qh"][i], b["kh"][i], b["vh"][i], b["ao"][i], ld, b["lse"][i], B, H, Tn, Tn, dh, dhp,
-                                            self._mask_off(Tn, Tn), dO=b["dao"], delta=b["delta"], dQ=dqs, lddq=3 * ld,
-                                            dK=dks, lddk=3 * ld, dV=dvs, lddv=3 * ld, dq_scale=self.scale,
-                                            drop_p=pr(e.attn_dropout), drop_site=site(e.enc_id, i, S_ATTN_SELF)))
-                # in_proj_weight row blocks [0, d), [d, 2d), [2d, 3d): one writer each
-                for w, src in enumerate((dqs, dks, dvs)):
-                    wg_att.append(ops.gemm_problem(src, b["xn"][i], st.gptr(ipw, w * d * d), d, d, R, 3 * ld, ld, d, flags=ACC1,
-                                                   colsum_a=st.gptr(ipb_g, w * d)))
-                # d(xn) = dq Wq + dk Wk + dv Wv
-                if ld == d:                                   # one product over K = 3d (see dqkvs)
-                    dg_a.append(ops.gemm_problem(dqkv, st.sptr(ipw, 0), b["dxn"], R, d, 3 * d, 3 * ld, ld, d))
-                else:
-                    dg_a.append(ops.gemm_problem(dqs, st.sptr(ipw, 0), b["dxn"], R, d, d, 3 * ld, ld, d))
-                    dg_b.append(ops.gemm_problem(dks, st.sptr(ipw, d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
-                    dg_c.append(ops.gemm_problem(dvs, st.sptr(ipw, 2 * d * ld), b["dxn"], R, d, d, 3 * ld, ld, d, flags=F_ACCUM))
-                lnq.append(ops.ln_problem(b["x"][i], P("layer_norms.0.weight"), None, b["st0m"][i], b["st0r"][i], R, dy=b["dxn"],
-                                          ldy=d, add=dx, dx=dx, dgamma=GP("layer_norms.0.weight"), dbeta=GP("layer_norms.0.bias"),
-                                          **nxt))
-            for group in (lnf, lnq):
-                ops.check_ln_rows(group, d)
-            x3 = st.x3
-            steps += [(WAIT, i + 2),
-                      self._gemm(GEMM_NN, dg_fc2),
-                      (SIDE, self._gemm(GEMM_TN, wg_ffn, background=True, presplit=pre_ffn if x3 else ())),
-                      self._gemm(GEMM_NN, dg_fc1),
-                      (ops.ln_bwd, A(LnProblem, lnf), d),
-                      self._gemm(GEMM_NN, dg_out),
-                      (ops.attn_bwd, self.dtype, A(AttnProblem, att)),
-                      (SIDE, self._gemm(GEMM_TN, wg_att, background=True, presplit=pre_att if x3 else ())),
-                      self._gemm(GEMM_NN, dg_a)] + \
-                     ([self._gemm(GEMM_NN, dg_b), self._gemm(GEMM_NN, dg_c)] if dg_b else []) + \
-                     [(ops.ln_bwd, A(LnProblem, lnq), d),
-                      (MARK, i)]
-        return steps + [JOIN]
+        return steps + [(SIDE, self._gemm(GEMM_TN if lr else GEMM_NN, dg_kv)), (SIDE, ln(hat)), JOIN]
 
     @staticmethod
     def store_written(prefix: str, layers: int):
@@ -1295,13 +1198,12 @@ class EncoderGroupPlan:
         emb = []
         for e, b in zip(self.encs, self.buf):
             emb.append(ops.embed_problem(b["dx"], b["dxq"], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q)))
-            if not c.self_only:
+            if self._kv:
                 emb.append(ops.embed_problem(b["dke"], b["dxk"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)))
                 emb.append(ops.embed_problem(b["dve"], b["dxv"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V)))
         ops.embed_pos_bwd(emb, d, math.sqrt(d), seed)
-        if c.self_only:                         # no key / value source: None in its place
-            return [b["dxq"] for b in self.buf], [None] * len(self.buf), [None] * len(self.buf)
-        return [b["dxq"] for b in self.buf], [b["dxk"] for b in self.buf], [b["dxv"] for b in self.buf]
+        kv = lambda n: [b[n] if self._kv else None for b in self.buf]       # no key / value source: None in its place
+        return [b["dxq"] for b in self.buf], kv("dxk"), kv("dxv")
 
 
 KVF = "self_attn.in_proj_weight#kvf"      # key suffix of the folded key/value shadow and bias
