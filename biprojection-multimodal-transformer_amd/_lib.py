@@ -21,7 +21,7 @@ SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "tail.hip", "frontend.hip"
 HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
-              "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
+              "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
 
 ABI_VERSION = 3                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
@@ -129,6 +129,12 @@ class AttnProblem(C.Structure):
                 ("dS", C.c_void_p), ("Pd", C.c_void_p), ("xs_b", C.c_int), ("xs_h", C.c_int), ("xs_q", C.c_int)]
 
 
+class AttnMapProblem(C.Structure):
+    _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("lse", C.c_void_p), ("W", C.c_void_p), ("ldw", C.c_int),
+                ("B", C.c_int), ("H", C.c_int), ("T", C.c_int), ("S", C.c_int), ("dh", C.c_int), ("dhp", C.c_int),
+                ("mask_off", C.c_int), ("q_pos0", C.c_int), ("q_stride", C.c_int)]
+
+
 class PackProblem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("g", C.c_void_p), ("ldg", C.c_int), ("dsrc", C.c_void_p),
                 ("B", C.c_int), ("T", C.c_int), ("C", C.c_int), ("ld", C.c_int),
@@ -233,6 +239,7 @@ SIGNATURES = {
     "bpm_attn_bwd": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
     "bpm_attn_bwd_dq": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
     "bpm_attn_bwd_dkv": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
+    "bpm_attn_maps": [_I, C.POINTER(AttnMapProblem), _I, _P],
     "bpm_pack_rows_fwd": [_I, C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_rows_bwd": [C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_weights": [_I, _P, _I, C.c_uint, _P],

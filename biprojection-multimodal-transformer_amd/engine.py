@@ -28,7 +28,7 @@ import math
 import os
 from collections import defaultdict
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -425,6 +425,14 @@ class GroupCfg:
 
 
 SIDE, JOIN, MARK, WAIT, SIDE2 = "side", "join", "mark", "wait", "side2"
+
+
+class AttentionMap(NamedTuple):
+    """One head-averaged attention map (EncoderGroupPlan.attention_maps).  weights: fp32 [B, Tq, S], the caller's own
+    tensor.  query_steps: None when the Tq rows are all T time steps of the encoder's query sequence, else the time step
+    of each row (layers that only compute a few query rows: a gathered subset, or rows {0, T-1} of a tail_rows layer)."""
+    weights: torch.Tensor
+    query_steps: Optional[Tuple[int, ...]]
 _SIDE = os.environ.get("BPMULT_SIDE", "1") != "0"
 # dK/dV attention pass: "0" main stream, "1" side stream, "2" a third stream, "auto": side stream.
 # dK / dV feed only side-stream work (weight gradients, key/value dgrad).  At hidden 768 the main stream is the longer one
@@ -552,6 +560,9 @@ class EncoderGroupPlan:
         self._side_low = d < 512
         self.store.side_low = self._side_low
         self._fwd = {True: self._build_fwd(True), False: self._build_fwd(False)}
+        # Q / K / LSE of every layer hold one complete forward pass (attention_maps): cleared while a forward is being
+        # launched, set when its last launch is enqueued (or its captured graph has been replayed: maps_ready)
+        self._maps_ok = False
         # backward tables by (training, stores): stores = the first weight-gradient launch of each large matrix writes
         # instead of accumulating (the flat gradient buffer was not cleared: ParamStore.begin_backward(stores=True))
         self._bwd = {(t, f): self._build_bwd(t, f) for t in (True, False) for f in (True, False)}
@@ -1057,10 +1068,92 @@ class EncoderGroupPlan:
             if self._kv:
                 emb += [ops.embed_problem(k, b["ke"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)),
                         ops.embed_problem(v, b["ve"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V))]
+        self._maps_ok = False
         ops.embed_pos_fwd(emb, self.table, d, math.sqrt(d), seed)
         self._last = (seed, training)
         self._run(self._fwd[training], seed)
+        self._maps_ok = True
         return [b["out"] for b in self.buf]
+
+    # -- attention maps -----------------------------------------------------------
+    def _map_blocks(self, e: EncoderDesc, b: dict, i: int):
+        """(block name, Q, K, lse, S, mask_off, q_pos0, q_stride, query_steps) of layer i's attention blocks, in the order
+        the layer runs them: the operands and the visibility rule of the forward problem (_self_attn_fwd / _cross_attn_fwd)."""
+        Tq = b["Tl"][i]
+        tail = self._tail(b, i)
+        if tail:
+            qpos, steps = (0, e.T - 1), (0, e.T - 1)
+        else:
+            qpos = (e.q_pos0, e.q_stride)
+            steps = None if e.T_full is None else tuple(e.q_pos0 + r * e.q_stride for r in range(Tq))
+        out = []
+        if self.cfg.biprojection or not self._kv:
+            k = _BIP_SELF_KEYS if self._kv else _SELF_KEYS
+            out.append(("self", b[k["q"]][i], b[k["k"]][i], b[k["lse"]][i], e.T, self._mask_off(e.T, e.T),
+                        *((0, e.T - 1) if tail else (0, 1)), steps))
+        if self._kv:
+            out.append(("cross", b["qh"][i], b["kh"][i], b["lse"][i], e.S, self._mask_off(e.T_full or e.T, e.S), *qpos, steps))
+        return out
+
+    def maps_ready(self) -> None:
+        """A captured graph of this plan's forward has just been replayed (no Python of forward() ran)."""
+        self._maps_ok = True
+
+    def attention_maps(self, encoders=None, layers=None) -> List[List[Dict[str, AttentionMap]]]:
+        """Head-averaged attention maps of the LAST forward of this plan: for each selected encoder (index or parameter
+        prefix; None = all, in plan order) a list over the selected layers (None = all) of {block: AttentionMap}, block
+        "cross" (crossmodal), "self" (self-only) or both (biprojection with a key / value source; self [B, Tq, T], cross
+        [B, Tq, S]).  W[b, i, j] = (1/H) sum_h softmax(scores)[b, h, i, j]: the probabilities BEFORE attention dropout --
+        the reference's second MultiheadAttention return value in eval mode and whenever attn_dropout == 0 -- and exactly 0
+        where the mask hides key j.  Detached fp32 tensors, freshly allocated, contiguous [B, Tq, S].
+
+        Nothing is kept for this by the forward: the maps are recomputed from the layer's Q / K / LSE buffers (bpm_attn_maps),
+        in launches of up to BPM_MAX_GROUP problems on the current stream -- the stream the forward ran on, which its last
+        step (JOIN) has made wait for the side stream's key / value projections.  Every backward builder only READS these
+        three buffers (_self_attn_bwd / _cross_attn_bwd pass them as Q / K / lse inputs of the attention problems; the
+        low-rank route also reads qh in bpm_expand_heads; gradients go to dq / dqkvs / dao / delta / dkall / dSall ...),
+        for every layer kind, so maps may be taken before or after backward(), until the plan's next forward.  Before any
+        forward, or after one that did not finish launching, this raises RuntimeError."""
+        if not self._maps_ok:
+            raise RuntimeError("attention_maps: no finished forward pass of this plan (its Q / K / LSE buffers hold nothing to "
+                               "compute the maps from); run forward first")
+        L = self.cfg.layers
+        if encoders is None:
+            eidx = list(range(len(self.encs)))
+        else:
+            eidx = []
+            for n in encoders:
+                if isinstance(n, str):
+                    pf = [k for k, e in enumerate(self.encs) if e.prefix in (n, n + ".")]
+                    if not pf:
+                        raise ValueError(f"attention_maps: no encoder {n!r} in this plan ({[e.prefix for e in self.encs]})")
+                    eidx.append(pf[0])
+                else:
+                    if not 0 <= n < len(self.encs):
+                        raise IndexError(f"attention_maps: encoder index {n} out of range ({len(self.encs)} encoders)")
+                    eidx.append(n)
+        lidx = list(range(L)) if layers is None else list(layers)
+        for i in lidx:
+            if not isinstance(i, int) or not 0 <= i < L:
+                raise IndexError(f"attention_maps: layer {i!r} out of range ({L} layers)")
+        dev = self.store.device
+        probs, res = [], []
+        for k in eidx:
+            e, b = self.encs[k], self.buf[k]
+            per_layer = []
+            for i in lidx:
+                maps = {}
+                for name, q, kk, lse, S, moff, p0, st_, steps in self._map_blocks(e, b, i):
+                    Tq = b["Tl"][i]
+                    W = torch.empty(self.B, Tq, S, device=dev, dtype=torch.float32)
+                    probs.append(ops.attn_map_problem(q, kk, lse, W, S, self.B, self.cfg.H, Tq, S, self.dh, self.dhp, moff,
+                                                      q_pos0=p0, q_stride=st_))
+                    maps[name] = AttentionMap(W, steps)
+                per_layer.append(maps)
+            res.append(per_layer)
+        if probs:
+            ops.attn_maps(self.dtype, probs)
+        return res
 
     # -- backward tables --------------------------------------------------------
     def _build_bwd(self, training: bool, stores: bool = False):

@@ -683,6 +683,8 @@ class _Trunk:
             ent["extra"].copy_(extra)
         self._seed_handle(seed)
         ent["graph"].replay()
+        self.plan1.maps_ready()                      # (no Python of EncoderGroupPlan.forward ran: attention_maps)
+        self.plan2.maps_ready()
         self._px_rows = {k: feats[k].shape[1] for k in ("l", "v", "a")}
         return ent["out"][0], ent["out"][1], key
 
@@ -772,6 +774,7 @@ class _ModelFn(torch.autograd.Function):
         else:
             logits, z, ctx.fkey = ran
         trunk.stamp = getattr(trunk, "stamp", 0) + 1
+        model._last_trunk = trunk
         ctx.trunk, ctx.seed, ctx.stamp, ctx.extra, ctx.params = trunk, seed, trunk.stamp, ex, tail_params
         ctx.need = {"l": x_l.requires_grad, "v": x_v.requires_grad, "a": x_a.requires_grad}
         return logits.detach().clone(), z.detach().clone()
@@ -857,7 +860,45 @@ class _BPMulTBase(nn.Module):
         self._store = None
         return r
 
+    def attention_maps(self, names=None, layers=None):
+        """Head-averaged attention maps of the most recent forward call: a dict from encoder name (the reference's
+        attribute names, "trans_l_with_a", ..., "trans_v_with_a2l"; `names` = None: all twelve) to a list with one entry
+        per selected layer (`layers` = None: all), each a dict from attention block to engine.AttentionMap(weights,
+        query_steps): {"cross": [B, Tq, S]} for a crossmodal encoder, {"self": [B, Tq, T], "cross": [B, Tq, S]} for the
+        4-modal model's biprojection level-2 encoders.  These are what forward hooks on `<encoder>.layers[i].self_attn`
+        read off the reference (second return value, multihead_attention.py:132-135): the softmax probabilities averaged
+        over the heads, BEFORE attention dropout -- equal to the reference's in eval mode and whenever the attention
+        dropout rate is 0 (in training with dropout the reference returns the dropped, rescaled matrix) -- exactly 0 at
+        masked keys, detached (no gradient flows through them; the reference's layers discard them).
+
+        Under dead-row elimination (the default schedule) some layers only compute two query rows: their maps have
+        Tq = 2 and query_steps == (0, N - 1) (the rows' time steps); otherwise query_steps is None and Tq = N.  All maps of
+        the headline model are 12 x 8 maps of 8 MB: select with `names` / `layers` -- nothing is computed for the rest,
+        and nothing at all unless this is called (the step itself is unchanged).  Works in both schedules, after eager
+        launches and after a graph replay (the maps launch itself is never captured), in train and eval mode, under
+        no_grad or not, before or after backward(), until the next forward call of this model; RuntimeError before the
+        first forward and after .to() / set_prune_unused_rows() dropped the activation buffers."""
+        trunk = getattr(self, "_last_trunk", None)
+        if trunk is None:
+            raise RuntimeError("attention_maps: no forward pass to take the maps of (call forward first; .to() and "
+                               "set_prune_unused_rows() drop the activation buffers)")
+        names = list(ENC_ORDER) if names is None else list(names)
+        for n in names:
+            if n not in ENC_ORDER:
+                raise ValueError(f"attention_maps: unknown encoder {n!r}; the encoders are {ENC_ORDER}")
+        L = self.layers
+        for i in (range(L) if layers is None else layers):
+            if not isinstance(i, int) or not 0 <= i < L:
+                raise IndexError(f"attention_maps: layer {i!r} out of range ({L} layers)")
+        out = {}
+        for plan, level in ((trunk.plan1, LEVEL1), (trunk.plan2, LEVEL2)):
+            sel = [n for n in names if n in level]
+            if sel:
+                out.update(zip(sel, plan.attention_maps(sel, layers)))
+        return {n: out[n] for n in names}
+
     def _drop_trunks(self) -> None:
+        self._last_trunk = None
         for t in getattr(self, "_trunks", {}).values():
             t.retire_graphs()
         self._trunks = {}

@@ -70,6 +70,7 @@ class _EncoderFn(torch.autograd.Function):
         kv = ([None], [None]) if x_k is None else ([x_k.detach().contiguous()], [x_v.detach().contiguous()])
         out = plan.forward([x_q.detach().contiguous()], *kv, enc._next_seed(), enc.training)[0]
         ctx.enc, ctx.plan = enc, plan
+        enc._last_plan = plan
         return out.detach().clone()
 
     @staticmethod
@@ -110,6 +111,7 @@ class TransformerEncoder(nn.Module):
         self.precision: Optional[str] = None          # None -> config.precision() at first use
         self._store: Optional[ParamStore] = None
         self._plans = {}
+        self._last_plan: Optional[EncoderGroupPlan] = None      # plan of the most recent forward call (attention_maps)
         self._step = 0
 
     def group_cfg(self, self_only: bool = False) -> GroupCfg:
@@ -119,7 +121,7 @@ class TransformerEncoder(nn.Module):
     # -- standalone execution (a group of one) ----------------------------------
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
-        self._store, self._plans = None, {}
+        self._store, self._plans, self._last_plan = None, {}, None
         return r
 
     def _ensure_store(self) -> ParamStore:
@@ -128,7 +130,7 @@ class TransformerEncoder(nn.Module):
             self._store = ParamStore(list(self.named_parameters()), config.dtype_code(prec), x3=config.is_x3(prec))
             register_encoder_shadows(self._store, "", self.embed_dim, len(self.layers), biprojection=self.biprojection)
             self._store.finalize_shadows()
-            self._plans = {}
+            self._plans, self._last_plan = {}, None
             self._anchor = torch.zeros(1, device=self._store.device, requires_grad=True)
         return self._store
 
@@ -152,3 +154,19 @@ class TransformerEncoder(nn.Module):
         if x_in_k is None or x_in_v is None:           # transformer.py:71,84: the self-attention stack
             return _EncoderFn.apply(self._anchor, x_in, None, None, self)
         return _EncoderFn.apply(self._anchor, x_in, x_in_k, x_in_v, self)
+
+    def attention_maps(self, layers=None):
+        """Head-averaged attention maps of the most recent forward call (either call form): a list with one entry per
+        selected layer (None = all), each a dict from attention block to engine.AttentionMap(weights, query_steps) --
+        {"cross": [B, T, S]} for the crossmodal call of a plain encoder, {"self": [B, T, T], "cross": [B, T, S]} for a
+        biprojection one, {"self": [B, T, T]} for forward(x).  What a forward hook on layers[i].self_attn reads off the
+        reference (the second return value of its MultiheadAttention, multihead_attention.py:132-135), with one stated
+        difference: these are the softmax probabilities BEFORE attention dropout, equal to the reference's in eval mode
+        and whenever attn_dropout == 0 (in training with dropout the reference returns the dropped, rescaled matrix).
+        Detached fp32 tensors owned by the caller; nothing is computed for layers that are not selected, and nothing at
+        all unless this is called.  Valid in train and eval mode, under no_grad or not, before or after backward(),
+        until the next forward call; RuntimeError before the first one (or after .to() / .cuda() dropped the buffers)."""
+        if self._last_plan is None:
+            raise RuntimeError("attention_maps: no forward pass to take the maps of (call forward first; .to() / .cuda() drop "
+                               "the activation buffers)")
+        return self._last_plan.attention_maps(None, layers)[0]

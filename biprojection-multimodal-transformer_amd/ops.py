@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import (BPM_BF16, BPM_BF16X3, BPM_F32, F_ACCUM, F_ATOMIC, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, GEMM_MAX_GROUP, MAX_GROUP, OUT_CT,
-                   OUT_F32, OUT_HEADS, AttnProblem, CastProblem, EmbedProblem, GemmProblem, GmuProblem,
+                   OUT_F32, OUT_HEADS, AttnMapProblem, AttnProblem, CastProblem, EmbedProblem, GemmProblem, GmuProblem,
                    LnProblem, PackProblem)
 
 
@@ -51,6 +51,8 @@ def _seed(seed: int) -> int:
 # tests/test_plan_tables_cpu.py only: lets the launch TABLES (host logic: pointers, shapes, flags) be built from host
 # tensors without a GPU.  Nothing can be launched from them -- every bpm_* entry point needs device pointers.
 _DRY_RUN = False
+# ... and the calls that are issued outside a plan's step tables (attn_maps) are recorded here instead of being launched
+_DRY_LAUNCHES: list = []
 
 
 def _p(t) -> Optional[int]:
@@ -307,6 +309,26 @@ def attn_bwd_dkv(dtype: int, probs, seed: int = 0) -> None:
     L, s = _lib.lib(), _stream()
     for sub, k in _chunks(arr, AttnProblem, None):
         _lib.check(L.bpm_attn_bwd_dkv(dtype, sub, k, _seed(seed), s), "bpm_attn_bwd_dkv")
+
+
+def attn_map_problem(Q, K, lse, W, ldw, B, H, T, S, dh, dhp, mask_off, *, q_pos0=0, q_stride=1) -> AttnMapProblem:
+    """One head-averaged attention map (bpm_attn_maps): Q / K / lse as attn_problem's after its forward, W fp32 [B, T, ldw]
+    receives (1/H) sum_h softmax probabilities (before dropout; exactly 0 where the mask hides the key)."""
+    p = AttnMapProblem()
+    p.Q, p.K, p.lse, p.W, p.ldw = _p(Q), _p(K), _f32(lse, "lse"), _f32(W, "W"), ldw
+    p.B, p.H, p.T, p.S, p.dh, p.dhp, p.mask_off = B, H, T, S, dh, dhp, mask_off
+    p.q_pos0, p.q_stride = q_pos0, q_stride
+    return p
+
+
+def attn_maps(dtype: int, probs) -> None:
+    arr = _as_array(AttnMapProblem, probs)
+    if _DRY_RUN:
+        _DRY_LAUNCHES.append((attn_maps, dtype, arr))
+        return
+    L, s = _lib.lib(), _stream()
+    for sub, k in _chunks(arr, AttnMapProblem, None):
+        _lib.check(L.bpm_attn_maps(dtype, sub, k, s), "bpm_attn_maps")
 
 
 # ----------------------------------------------------------------------------

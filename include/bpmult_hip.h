@@ -158,6 +158,24 @@ int bpm_attn_bwd(int dtype, const bpm_attn_problem* probs /* host */, int nprob,
 int bpm_attn_bwd_dq(int dtype, const bpm_attn_problem* probs /* host */, int nprob, uint64_t seed, void* stream);
 int bpm_attn_bwd_dkv(int dtype, const bpm_attn_problem* probs /* host */, int nprob, uint64_t seed, void* stream);
 
+/* Head-averaged attention maps of a finished forward pass: the reference's second return value
+ * (multihead_attention.py:132-135, attn_weights.sum(dim=1) / num_heads), which the fused kernels never materialise.
+ * Recomputed from the Q / K images and the lse that bpm_attn_fwd left:
+ *   W[b][i][j] = (1/H) sum_h exp(Q[b,h,i,:] . K[b,h,j,:] - lse[b,h,i])   for a visible key, exactly 0.0f for a masked one
+ * -- the softmax probabilities BEFORE attention dropout (what the reference returns in eval mode and with dropout 0).
+ * Exponentials and the head sum in fp32; only [B,T,S] is written (columns S .. ldw-1 of a row are left untouched).
+ * Q, K: 16-byte aligned; all problems of a launch share dhp. */
+typedef struct bpm_attn_map_problem {
+    const void* Q; const void* K;   /* CT, [B,H,T,dhp] (pre-scaled) / [B,H,S,dhp], as bpm_attn_problem */
+    const float* lse;               /* [B,H,T], as written by bpm_attn_fwd */
+    float* W; int ldw;              /* out: fp32 [B,T,ldw], ldw >= S */
+    int B, H, T, S, dh, dhp;
+    int mask_off;                   /* same visibility rule as bpm_attn_problem */
+    int q_pos0, q_stride;
+} bpm_attn_map_problem;
+
+int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs /* host */, int nprob, void* stream);
+
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,
  * problem arrays live in HOST memory and are copied into the kernel arguments.

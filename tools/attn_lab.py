@@ -6,6 +6,11 @@ shapes -- six lock-stepped encoders, B=8, H=12 heads of 64, T=S=512, future mask
   python tools/attn_lab.py [--H 12 --dh 64 --T 512 --S 512 --B 8 --G 6 --no-mask --drop 0.1]
   rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES ... -- python3 tools/attn_lab.py --iters 3     (counters per kernel)
 
+--maps: also the head-averaged attention-map launch (bpm_attn_maps: one problem per encoder, fp32 [B, T, S] out) beside the
+forward launch of the same shapes in the same run -- it does one of the forward's two products and the same exponentials,
+so the forward time is its yardstick.  Shapes on record: the default (headline), the kernel point
+`--H 6 --dh 128 --T 50 --S 50 --B 64`, and head_dim 256 `--H 6 --dh 256`.
+
 Algorithmic FLOPs per visible (query, key) pair and head: forward 4 dh, dQ pass 6 dh (S, dP, dQ), dK/dV pass 8 dh."""
 import argparse
 import json
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--drop", type=float, default=0.1)
     ap.add_argument("--drop-encoders", type=int, default=2, help="how many of the G encoders have attention dropout")
     ap.add_argument("--no-mask", action="store_true")
+    ap.add_argument("--maps", action="store_true", help="also time bpm_attn_maps at the same shapes (after the forward has written LSE)")
     ap.add_argument("--pair", type=int, default=-1, help="tuning hook: bit k = kernel k (fwd, dQ, dK/dV) takes two blocks per workgroup")
     a = ap.parse_args()
     dev, ct = "cuda", torch.bfloat16
@@ -77,6 +83,23 @@ def main():
         us = _time(lambda: fn(BPM_BF16, arr, 5), a.iters)
         tf = fl * dh * pairs / us / 1e6
         res[name] = {"us": round(us, 1), "tflops": round(tf, 1), "bf16_peak_frac": round(tf / BF16_PEAK_TF, 3)}
+    if a.maps:
+        # LSE of the last forward launch above is in place; maps and forward alternate in one timing loop each, three rounds
+        wts = [torch.empty(B, T, S, device=dev) for _ in range(G)]
+        mp = [ops.attn_map_problem(t["q"], t["k"], t["lse"], w, S, B, H, T, S, dh, dhp, off) for t, w in zip(keep, wts)]
+        marr = ops.array(ops.AttnMapProblem, mp)
+        ops.attn_fwd(BPM_BF16, arr, 5)
+        rounds = []
+        for _ in range(3):
+            rounds.append((_time(lambda: ops.attn_fwd(BPM_BF16, arr, 5), a.iters), _time(lambda: ops.attn_maps(BPM_BF16, marr), a.iters)))
+        f_us, m_us = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
+        out_bytes = G * B * T * S * 4
+        in_bytes = G * B * H * ((T + S) * dhp * 2 + T * 4)
+        rowsum = float((wts[0].double().sum(-1) - 1.0).abs().max())
+        res["maps"] = {"us": round(m_us, 1), "fwd_us_same_run": round(f_us, 1), "maps_over_fwd": round(m_us / f_us, 3),
+                       "rounds_fwd_maps_us": [[round(x, 1) for x in r] for r in rounds],
+                       "out_mbytes": round(out_bytes / 1e6, 1), "hbm_gbytes_per_s": round((out_bytes + in_bytes) / m_us / 1e3, 1),
+                       "tflops": round(2 * dh * B * H * G * T * S / m_us / 1e6, 1), "max_row_sum_error": rowsum}
     print(json.dumps(res))
 
 
