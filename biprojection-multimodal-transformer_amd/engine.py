@@ -1295,6 +1295,10 @@ class EncoderGroupPlan:
                 emb.append(ops.embed_problem(b["dke"], b["dxk"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)))
                 emb.append(ops.embed_problem(b["dve"], b["dxv"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V)))
         ops.embed_pos_bwd(emb, d, math.sqrt(d), seed)
+        return self.input_grads()
+
+    def input_grads(self):
+        """The plan-owned buffers backward() leaves the query, key and value source gradients in (three lists)."""
         kv = lambda n: [b[n] if self._kv else None for b in self.buf]       # no key / value source: None in its place
         return [b["dxq"] for b in self.buf], kv("dxk"), kv("dxv")
 

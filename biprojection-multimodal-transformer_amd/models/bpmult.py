@@ -26,8 +26,10 @@ import torch
 from torch import nn
 
 from .. import config, ops
-from .._lib import BPM_F32, F_ACCUM, GEMM_NN, GEMM_NT, GEMM_TN, CastProblem, GemmProblem, GmuProblem, TailDesc, TailGrads
+from .._lib import (BPM_F32, F_ACCUM, GEMM_NN, GEMM_NT, GEMM_TN, AddnProblem, CastProblem, GemmProblem, GmuProblem, TailDesc,
+                    TailGrads)
 from ..engine import SITE_TEXT, EncoderDesc, EncoderGroupPlan, GroupCfg, ParamStore, register_encoder_shadows
+from ..graphs import _RETIRED_GRAPHS, GraphCache  # noqa: F401  (_RETIRED_GRAPHS: read through this module too)
 from ..ops import pad32
 from .encoder import TransformerEncoder
 
@@ -112,11 +114,8 @@ class BertEncoder(nn.Module):
 
 
 # ----------------------------------------------------------------------------
-_RETIRED_GRAPHS: list = []       # captured graphs of dropped trunks: kept alive, never replayed (see _Trunk.MAX_GRAPHS)
-
-
-class _Trunk:
-    """Device buffers + launch tables of the hot path for one batch size."""
+class _Trunk(GraphCache):
+    """Device buffers + launch tables of the hot path for one batch size; its captured graphs (GraphCache)."""
 
     def __init__(self, model: "_BPMulTBase", B: int):
         self.m, self.B = model, B
@@ -188,7 +187,10 @@ class _Trunk:
                                            ag=z(R, d), out=z(self.Ng[tgt], B, d), da1=z(R, self.ld, dt=ct),
                                            da2=z(R, self.ld, dt=ct), dag=z(R, self.ld, dt=ct), dx1=z(R, d), dx2=z(R, d))
         self._build_gmu()
+        self._build_time()
+        self._build_sums()
         self._conv_cache = {}
+        self._conv: Dict[str, dict] = {}                           # what conv_forward leaves for conv_backward
         self._px_rows: Dict[str, int] = {k: 0 for k in self.N}     # rows of px[k] written by the previous input
         # ---- [B,d] tail (token pick, final n-way GMU, residual head): activations kept for its backward + scratch
         n = 4 if model.four_modal else 3
@@ -196,6 +198,9 @@ class _Trunk:
         self.tail = dict(n=n, C=Cn, **{k: z(B, n * d) for k in ("x", "z", "t", "dzp", "dtp", "dx")},
                          **{k: z(B, d) for k in ("h", "p1", "y", "dy", "dp1", "dh")}, logits=z(B, Cn),
                          dextra=z(B, d) if n == 4 else None)
+        self._tail_desc: Optional[TailDesc] = None                 # what tail_forward leaves for tail_backward
+        GraphCache.__init__(self, dev)
+        self.stamp = 0                                             # forward passes run (_ModelFn: a backward must be the last one's)
 
     # -- temporal 1x1 projections (mmtr.py:456-469 / 748-761) -----------------------
     def conv_forward(self, feats: Dict[str, torch.Tensor], seed: int, training: bool) -> None:
@@ -213,7 +218,7 @@ class _Trunk:
             # rows [T, last) hold an earlier, longer input: clear them (rows past every input so far are still the zeros
             # they were allocated as).  While capturing a graph: always the whole tail -- a replay must leave px right
             # whatever ran before it
-            last = self.N[k] if getattr(self, "_capturing", False) else self._px_rows.get(k, self.N[k])
+            last = self.N[k] if self.capturing else self._px_rows[k]
             if T < last:
                 px[T:last].zero_()
             self._px_rows[k] = T
@@ -268,46 +273,44 @@ class _Trunk:
         return res
 
     # -- time-axis Linear (4-modal) --------------------------------------------------
-    def _time_forward(self) -> None:
-        if not self.tmap:
-            return
+    def _build_time(self) -> None:
+        """Forward: out = W h + bias per map.  Backward: dout (fp32 [Td,B,d], or rows {0, Td-1} of it) of every map ->
+        weight / bias gradients and dh (fp32 [Ts,B,d]).  (Exact fp32 products in bf16x3 mode: the tables are not tagged.)"""
         B, d, st = self.B, self.d, self.st
         BD = B * d
-        casts, gemms = [], []
-        for (tgt, src), t in self.tmap.items():
-            casts.append(ops.cast_problem(self.out1[src], BD, t["Ts"], BD, dst_ct=t["h_ct"], ldd=t["ldbd"]))
-            ldw = pad32(t["Ts"])
-            if self.prune:            # output rows {0, Td-1} only: one single-row product each (the row's own bias entry)
-                for j, r in enumerate((0, t["Td"] - 1)):
-                    gemms.append(ops.gemm_problem(st.sptr(t["lin"] + ".weight", r * ldw), t["h_ct"], t["out"][j], 1, BD, t["Ts"], ldw,
-                                                  t["ldbd"], BD, bias_m=st.p(t["lin"] + ".bias").data_ptr() + 4 * r))
-            else:
-                gemms.append(ops.gemm_problem(st.sptr(t["lin"] + ".weight"), t["h_ct"], t["out"], t["Td"], BD, t["Ts"], ldw,
-                                              t["ldbd"], BD, bias_m=st.p(t["lin"] + ".bias")))
-        ops.rows_cast(self.dtype, casts, 0)
-        ops.gemm_grouped(self.dtype, GEMM_NN, gemms, 0)
-
-    def _time_backward(self) -> None:
-        """dout (fp32 [Td,B,d], or rows {0, Td-1} of it) of every map -> weight / bias gradients and dh (fp32 [Ts,B,d])."""
-        if not self.tmap:
-            return
-        B, d, st = self.B, self.d, self.st
-        BD = B * d
-        casts, wg, dg = [], [], []
+        A = ops.array
+        casts, gemms, bw_casts, bw_wg, bw_dg = [], [], [], [], []
         for (tgt, src), t in self.tmap.items():
             Ts, Td, ldbd = t["Ts"], t["Td"], t["ldbd"]
             ldw = pad32(Ts)
             W, bias = t["lin"] + ".weight", t["lin"] + ".bias"
-            casts.append(ops.cast_problem(t["dout"], BD, t["dout"].shape[0], BD, dst_ct=t["dout_ct"], ldd=ldbd))
-            if self.prune:            # rows {0, Td-1} of the weight / bias gradient (the other rows' are zero: cleared with the
-                for j, r in enumerate((0, Td - 1)):          # small tensors); dh = W[{0, Td-1}]^T dout: k = the two rows, Td-1 apart
-                    wg.append(ops.gemm_problem(t["dout_ct"][j], t["h_ct"], st.gptr(W, r * Ts), 1, Ts, BD, ldbd, ldbd, Ts, flags=F_ACCUM))
-                    wg.append(ops.gemm_problem(t["dout_ct"][j], self.ones_bd, st.gptr(bias, r), 1, 1, BD, ldbd, ldbd, 1, flags=F_ACCUM))
-                dg.append(ops.gemm_problem(st.sptr(W), t["dout_ct"], t["dh"], Ts, BD, 2, (Td - 1) * ldw, ldbd, BD))
+            casts.append(ops.cast_problem(self.out1[src], BD, Ts, BD, dst_ct=t["h_ct"], ldd=ldbd))
+            bw_casts.append(ops.cast_problem(t["dout"], BD, t["dout"].shape[0], BD, dst_ct=t["dout_ct"], ldd=ldbd))
+            if self.prune:
+                # output rows {0, Td-1} only: one single-row product each (the row's own bias entry).  Backward: rows
+                # {0, Td-1} of the weight / bias gradient (the other rows' are zero: cleared with the small tensors);
+                # dh = W[{0, Td-1}]^T dout: k = the two rows, Td-1 apart
+                for j, r in enumerate((0, Td - 1)):
+                    gemms.append(ops.gemm_problem(st.sptr(W, r * ldw), t["h_ct"], t["out"][j], 1, BD, Ts, ldw, ldbd, BD,
+                                                  bias_m=st.p(bias).data_ptr() + 4 * r))
+                    bw_wg.append(ops.gemm_problem(t["dout_ct"][j], t["h_ct"], st.gptr(W, r * Ts), 1, Ts, BD, ldbd, ldbd, Ts, flags=F_ACCUM))
+                    bw_wg.append(ops.gemm_problem(t["dout_ct"][j], self.ones_bd, st.gptr(bias, r), 1, 1, BD, ldbd, ldbd, 1, flags=F_ACCUM))
+                bw_dg.append(ops.gemm_problem(st.sptr(W), t["dout_ct"], t["dh"], Ts, BD, 2, (Td - 1) * ldw, ldbd, BD))
             else:
-                wg.append(ops.gemm_problem(t["dout_ct"], t["h_ct"], st.gptr(W), Td, Ts, BD, ldbd, ldbd, Ts, flags=F_ACCUM))
-                wg.append(ops.gemm_problem(t["dout_ct"], self.ones_bd, st.gptr(bias), Td, 1, BD, ldbd, ldbd, 1, flags=F_ACCUM))
-                dg.append(ops.gemm_problem(st.sptr(W), t["dout_ct"], t["dh"], Ts, BD, Td, ldw, ldbd, BD))
+                gemms.append(ops.gemm_problem(st.sptr(W), t["h_ct"], t["out"], Td, BD, Ts, ldw, ldbd, BD, bias_m=st.p(bias)))
+                bw_wg.append(ops.gemm_problem(t["dout_ct"], t["h_ct"], st.gptr(W), Td, Ts, BD, ldbd, ldbd, Ts, flags=F_ACCUM))
+                bw_wg.append(ops.gemm_problem(t["dout_ct"], self.ones_bd, st.gptr(bias), Td, 1, BD, ldbd, ldbd, 1, flags=F_ACCUM))
+                bw_dg.append(ops.gemm_problem(st.sptr(W), t["dout_ct"], t["dh"], Ts, BD, Td, ldw, ldbd, BD))
+        self._time_fwd = (A(CastProblem, casts), A(GemmProblem, gemms))
+        self._time_bwd = (A(CastProblem, bw_casts), A(GemmProblem, bw_wg), A(GemmProblem, bw_dg))
+
+    def _time_forward(self) -> None:
+        casts, gemms = self._time_fwd
+        ops.rows_cast(self.dtype, casts, 0)
+        ops.gemm_grouped(self.dtype, GEMM_NN, gemms, 0)
+
+    def _time_backward(self) -> None:
+        casts, wg, dg = self._time_bwd
         ops.rows_cast(self.dtype, casts, 0)
         ops.gemm_grouped(self.dtype, GEMM_NT, wg, 0)
         ops.gemm_grouped(self.dtype, GEMM_TN, dg, 0)
@@ -396,7 +399,8 @@ class _Trunk:
             q2 = [px[q] for (q, src, _) in LEVEL2.values()]
         k2 = [self.out1[src] for (q, src, _) in LEVEL2.values()]
         self.plan2.forward(q2, k2, k2, seed, training)
-        self._time_forward()
+        if self.tmap:
+            self._time_forward()
         self.gmu_forward()
         return [self.g[(t, k)]["out"] for t in ("l", "a", "v") for k in ("top", "mid")]
 
@@ -453,96 +457,60 @@ class _Trunk:
         ops.tail_bwd(self._tail_desc, gr)
         return grads, tl["dextra"]
 
-    def backward(self, grads: Optional[Sequence[Optional[torch.Tensor]]], seed: int, need_dx: Dict[str, bool],
-                 stores: Optional[bool] = None):
-        """grads: d(top_l), d(mid_l), d(top_a), d(mid_a), d(top_v), d(mid_v); None: the `dout` buffers of the GMU units
-        already hold them (written by tail_backward).  When the gradients are unset (zero_grad / `p.grad = None`) the flat
-        gradient buffer is NOT cleared as a whole: the encoders' large weight gradients are written by their first
-        launch (`stores` launch tables) and one table-driven launch clears the rest.  stores given (captured graphs: it is
-        part of the graph's key): the caller attaches the .grad views afterwards."""
-        st = self.st
-        attach = stores is None
-        if stores is None:
-            stores = st.begin_backward(stores=True)
-        elif stores:
-            ops.zero_segments(*st._zero_table)
-        it = iter(grads) if grads is not None else None
-        for t in ("l", "a", "v"):
-            for k in ("top", "mid"):
-                if it is None:
-                    continue
-                g = next(it)
-                if g is None:
-                    self.g[(t, k)]["dout"].zero_()
-                else:
-                    self.g[(t, k)]["dout"].copy_(g)
-        self.gmu_backward()
-        # gradient of every level-2 output (top GMU operand) and level-1 output (middle + top GMU operands, and -- after the
-        # level-2 backward -- its key / value gradients): summed by grouped bpm_add_n launches into static buffers
-        d2: Dict[str, torch.Tensor] = {}
-        d1: Dict[str, torch.Tensor] = {}
-        gmu_terms: Dict[str, List[torch.Tensor]] = {}
-        to_tmap = []
+    # -- gradient sums between the levels ------------------------------------------------
+    def _build_sums(self) -> None:
+        """Grouped bpm_add_n tables of backward(), all operands static.  d(level-2 output) = the top GMU's operand gradient;
+        d(level-1 output) = its middle + top GMU operand terms (through the time map where it is consumed through one: summed
+        into the map's dout, the term is then the map's dh) + its key / value gradients from level 2; d(projected input) =
+        the gradients of every encoder that reads it.  Whole-tensor terms are summed by one grouped launch, two-row terms
+        (pruned schedule: rows 0 and N-1) added on top (_rows2_tables)."""
+        A, shp = ops.array, lambda k: (self.Ng[k], self.B, self.d)
+        whole, rows, d2, to_tmap = {}, {}, {}, []        # level-1 name -> its whole-tensor / two-row GMU terms; level-2 name -> d
         for tgt in ("l", "a", "v"):
             l2a, l1a, l2b, l1b = FUSE[tgt]
             top, mid = self.g[(tgt, "top")], self.g[(tgt, "mid")]
-            shp = (self.Ng[tgt], self.B, self.d)
-            d2[l2a], d2[l2b] = top["dx1"].view(shp), top["dx2"].view(shp)
+            d2[l2a], d2[l2b] = top["dx1"].view(shp(tgt)), top["dx2"].view(shp(tgt))
             for name, terms in ((l1a, [top["dx1"], mid["dx1"]]), (l1b, [top["dx2"], mid["dx2"]])):
-                if (tgt, name) in self.tmap:
-                    to_tmap.append(ops.addn_problem(self.tmap[(tgt, name)]["dout"], terms))
+                t = self.tmap.get((tgt, name))
+                if t is not None:
+                    to_tmap.append(ops.addn_problem(t["dout"], terms))
+                    whole[name], rows[name] = [t["dh"]], []
                 else:
-                    gmu_terms[name] = terms
-        if to_tmap:
-            ops.add_n(to_tmap)
-        self._time_backward()
-        self._ready("fuse")
-        for (tgt, name), t in self.tmap.items():
-            gmu_terms[name] = [t["dh"]]
-        dq2, dk2, dv2 = self.plan2.backward([d2[n] for n in LEVEL2], self._layer_hook("level2"), stores=stores)
-        # d(level-1 output) = its key / value gradients from level 2 + the GMU terms: whole-tensor terms (dense schedule,
-        # or through a time map) summed by one grouped launch, two-row terms (pruned schedule: rows 0 and N-1) added on top
+                    terms = [x.view(shp(tgt)) for x in terms]
+                    whole[name], rows[name] = (terms, []) if self.Ng[tgt] == self.N[LEVEL1[name][0]] else ([], terms)
+        self._d2 = [d2[n] for n in LEVEL2]
+        self._d1 = [self.d1buf[n] for n in LEVEL1]
+        dq2, dk2, dv2 = self.plan2.input_grads()
         sums, rows2 = [], []
         for (n, (q, src, _)), gk, gv in zip(LEVEL2.items(), dk2, dv2):
-            d1[src] = self.d1buf[src]
-            full = [t for t in gmu_terms[src] if t.numel() == d1[src].numel()]
-            rows2 += [(src, t) for t in gmu_terms[src] if t.numel() != d1[src].numel()]
-            sums.append(ops.addn_problem(d1[src], [t.view(d1[src].shape) for t in full] + [gk, gv]))
-        ops.add_n(sums)
-        self._add_rows2([(d1[src], t) for src, t in rows2])
-        dq1, dk1, dv1 = self.plan1.backward([d1[n] for n in LEVEL1], self._layer_hook("level1"), stores=stores)
+            d1 = self.d1buf[src]
+            rows2 += [(d1, t) for t in rows[src]]
+            sums.append(ops.addn_problem(d1, whole[src] + [gk, gv]))
+        dq1, dk1, dv1 = self.plan1.input_grads()
         acc: Dict[str, List[torch.Tensor]] = {"l": [], "a": [], "v": []}
         for (n, (q, kv, _)), gq, gk, gv in zip(LEVEL1.items(), dq1, dk1, dv1):
             acc[q].append(gq)
             acc[kv] += [gk, gv]
         small: Dict[str, List[torch.Tensor]] = {"l": [], "a": [], "v": []}
-        for (n, (q, src, _)), gq in zip(LEVEL2.items(), dq2):
-            (small if gq.shape[0] != self.N[q] else acc)[q].append(gq)
-        ops.add_n([ops.addn_problem(self.dpx[k], terms) for k, terms in acc.items()])
-        self._add_rows2([(self.dpx[k], gq) for k in acc for gq in small[k]])
-        res = self.conv_backward(seed, need_dx)
-        self._ready("proj")
-        if attach:
-            st.end_backward()
-        return res
+        for (n, (q, src, _)), e, gq in zip(LEVEL2.items(), self.plan2.encs, dq2):     # (3-modal pruned schedule: level 2 has
+            (small if e.T != self.N[q] else acc)[q].append(gq)                          # two query rows)
+        self._sum_tmap = A(AddnProblem, to_tmap)
+        self._sum_d1 = A(AddnProblem, sums)
+        self._rows2_d1 = self._rows2_tables(rows2)
+        self._sum_dpx = A(AddnProblem, [ops.addn_problem(self.dpx[k], terms) for k, terms in acc.items()])
+        self._rows2_dpx = self._rows2_tables([(self.dpx[k], gq) for k in acc for gq in small[k]])
 
-    def _add_rows2(self, pairs) -> None:
-        """dst[0] += t[0], dst[N-1] += t[1] for (dst [N, B, d], t [2, B, d]) pairs -- the two-row terms of the pruned
-        schedule -- as ONE grouped bpm_add_n launch over the row blocks (in place, terms added in list order: the result
-        index_add_ per term gave, which was 18 launches of 5 us and as many dependency gaps per step at hidden 768)."""
-        if not pairs:
-            return
-        B, d = self.B, self.d
-        if (B * d) % 4:                                   # row blocks not 16-byte aligned: the torch path
-            for dst, t in pairs:
-                dst[0] += t.view(2, B, d)[0]
-                dst[-1] += t.view(2, B, d)[1]
-            return
-        terms: Dict[int, list] = {}
+    def _rows2_tables(self, pairs):
+        """dst[0] += t[0], dst[N-1] += t[1] for (dst [N, B, d], t [2, B, d]) pairs as grouped bpm_add_n launches over the row
+        blocks (in place, terms added in list order: the result index_add_ per term gave, which was 18 launches of 5 us and
+        as many dependency gaps per step at hidden 768).  Returns (launch tables, pairs left to torch: unaligned blocks)."""
+        if (self.B * self.d) % 4:
+            return [], pairs
+        terms: Dict[tuple, list] = {}
         for dst, t in pairs:
-            t = t.view(2, B, d)
             for j, r in ((0, 0), (1, dst.shape[0] - 1)):
                 terms.setdefault((dst.data_ptr(), r), [dst[r]]).append(t[j])
+        launches = []
         while terms:                                      # at most 8 inputs per problem (the destination among them), and a
             probs = []                                    # destination once per launch
             for key in list(terms):
@@ -552,188 +520,89 @@ class _Trunk:
                     terms[key] = [out] + ins[7:]
                 else:
                     del terms[key]
-            ops.add_n(probs)
+            launches.append(ops.array(AddnProblem, probs))
+        return launches, []
 
-    # -- captured launch sequences (hipGraph) ---------------------------------------
-    # The ~420 launches of a step are the same every step for a given (mode, input lengths): captured once per key and
-    # replayed.  What changes per step travels through device memory: the inputs (copied into static staging tensors),
-    # the dropout seed (BPM_SEED_INDIRECT: the kernels read it when they run) and the incoming logit gradients.
-    # Host-side decisions stay outside the graph: the weight-shadow refresh, whether the gradients start from zero
-    # (part of the key), attaching .grad views.  Used when nothing needs the eager launch order: no gradient-exchange
-    # hook (GradSync runs eagerly: its all-reduces interleave with backward), launch profiler off.
-    GRAPH_WARMUP = 2            # eager runs of a key before it is captured (lazy allocations, stream creation)
-    # Bounded caches.  The reference collate pads text to the batch's longest sentence and trims audio to its shortest
-    # clip (data/helpers.py:83-102), so real training sees hundreds of (L, V, A) keys, and every captured graph pins its
-    # static inputs / outputs and every allocation made during its capture.  At most MAX_GRAPHS keys are ever captured
-    # (forward graph + its backward graphs): the first ones to recur GRAPH_WARMUP times; every other key runs as eager
-    # launches (the step time is the same: DESIGN.md section 4).  Call counters are kept for MAX_TRACKED keys.
-    # Captured graphs are NEVER DESTROYED while the process lives: on this stack (torch 2.10 + ROCm 7.0/7.2) destroying a
-    # captured graph and then capturing / launching others ends in a host segfault inside hipGraphLaunch
-    # (tools/graph_cache_probe.py, profiles/r04_graph_probe.json: 5 of 5 evicting variants crash -- shared or per-key pool,
-    # with or without a device synchronise, either capture mode -- 0 of 2 non-evicting ones; round 3's capture_end crash
-    # had the same ingredients).  So there is no LRU eviction, and a trunk that is dropped (another batch size, .to())
-    # parks its graph objects in _RETIRED_GRAPHS after releasing their static tensors.
-    MAX_GRAPHS = 4
-    MAX_TRACKED = 64
+    @staticmethod
+    def _add_rows2(tables) -> None:
+        launches, pairs = tables
+        for arr in launches:
+            ops.add_n(arr)
+        for dst, t in pairs:
+            dst[0] += t[0]
+            dst[-1] += t[1]
 
-    def _seed_handle(self, seed: int) -> int:
-        if getattr(self, "_seed_dev", None) is None:
-            self._seed_dev = torch.zeros(1, device=self.st.device, dtype=torch.int64)
-        self._seed_dev.fill_(seed)
-        return ops.DeviceSeed(self._seed_dev)
+    def backward(self, seed: int, need_dx: Dict[str, bool], stores: Optional[bool] = None):
+        """The `dout` buffers of the GMU units hold d(top_l), d(mid_l), ... (written by tail_backward).  When the gradients
+        are unset (zero_grad / `p.grad = None`) the flat gradient buffer is NOT cleared as a whole: the encoders' large
+        weight gradients are written by their first launch (`stores` launch tables) and one table-driven launch clears the
+        rest.  stores given (captured graphs: part of the graph's key): the caller attaches the .grad views afterwards."""
+        st = self.st
+        attach = stores is None
+        if stores is None:
+            stores = st.begin_backward(stores=True)
+        elif stores:
+            ops.zero_segments(*st._zero_table)
+        self.gmu_backward()
+        if self.tmap:
+            ops.add_n(self._sum_tmap)
+            self._time_backward()
+        self._ready("fuse")
+        self.plan2.backward(self._d2, self._layer_hook("level2"), stores=stores)
+        ops.add_n(self._sum_d1)
+        self._add_rows2(self._rows2_d1)
+        self.plan1.backward(self._d1, self._layer_hook("level1"), stores=stores)
+        ops.add_n(self._sum_dpx)
+        self._add_rows2(self._rows2_dpx)
+        res = self.conv_backward(seed, need_dx)
+        self._ready("proj")
+        if attach:
+            st.end_backward()
+        return res
 
-    def _graph_state(self) -> None:
-        if getattr(self, "_fg", None) is None:
-            from collections import OrderedDict
-            self._fg, self._bg, self._gpool = OrderedDict(), OrderedDict(), torch.cuda.graph_pool_handle()
-            self.graph_stats = {"captured": 0, "evicted": 0, "failed": 0}
-            self.MAX_GRAPHS = int(os.environ.get("BPMULT_MAX_GRAPHS", self.MAX_GRAPHS))
-
-    def _evict_graphs(self) -> None:
-        """Forget the oldest call counters of keys that hold no graph (see MAX_TRACKED); captured graphs stay."""
-        idle = [k for k, e in self._fg.items() if "graph" not in e]
-        for k in idle[:max(0, len(idle) - self.MAX_TRACKED)]:
-            del self._fg[k]
-            for bk in [bk for bk in self._bg if bk[0] == k]:
-                del self._bg[bk]
-
-    def _may_capture(self) -> bool:
-        return sum("graph" in e for e in self._fg.values()) < self.MAX_GRAPHS
-
-    def retire_graphs(self) -> None:
-        """This trunk is being dropped: park its captured graphs (never destroyed while the process lives, see above) and
-        release everything else they pinned."""
-        park = os.environ.get("BPMULT_GRAPH_DESTROY", "0") != "1"      # (=1: tools/graph_cache_probe.py reproduces the crash)
-        for table in (getattr(self, "_fg", None) or {}, getattr(self, "_bg", None) or {}):
-            for e in table.values():
-                if "graph" in e and park:
-                    _RETIRED_GRAPHS.append(e["graph"])
-                e.clear()
-        self._fg = self._bg = None
-
-    def _capture(self, fn):
-        """Capture fn() into a new graph.  thread_local error mode: the backward capture runs on the autograd thread while
-        other threads (a DataLoader's pin_memory thread, an asynchronous checkpoint copy) may call into HIP.  Every side
-        stream forked inside the capture must have been joined back when fn returns: an unjoined fork is joined here and
-        reported as a Python error after the capture has ended -- not left for hipStreamEndCapture to trip over.
-        Returns (graph, result) or raises; the caller marks the key non-capturable and goes on eagerly."""
-        from .. import engine as _e
-        from ..engine import open_forks
-        g = torch.cuda.CUDAGraph()
-        left = []
-        _e._OPEN_FORKS.clear()                                    # (forks of earlier eager runs are not this capture's)
-        self._capturing = True
-        try:
-            with torch.cuda.graph(g, pool=self._gpool, capture_error_mode="thread_local"):
-                try:
-                    res = fn()
-                finally:
-                    left = open_forks()
-                    for st_ in left:                              # join, so that the capture can end cleanly
-                        torch.cuda.current_stream().wait_stream(st_)
-        finally:
-            self._capturing = False
-            _e._OPEN_FORKS.clear()
-        if left:
-            raise RuntimeError(f"graph capture: {len(left)} side stream(s) were still forked when the launch sequence ended "
-                               "(a step table without its JOIN)")
-        return g, res
-
-    def graph_forward(self, feats: Dict[str, torch.Tensor], extra: Optional[torch.Tensor], seed: int, training: bool, want_grad: bool):
+    # -- captured launch sequences (GraphCache.replay) ------------------------------------
+    def graph_forward(self, feats: Dict[str, torch.Tensor], extra: Optional[torch.Tensor], seed: int, training: bool):
         """Forward pass through a captured graph when one exists (or can be captured now) for this key; returns
         (logits, z, key) or None (the caller then runs eagerly)."""
         key = (training, tuple(tuple(feats[k].shape) for k in ("l", "v", "a")), extra is not None)
-        self._graph_state()
-        ent = self._fg.setdefault(key, {"calls": 0})
-        self._fg.move_to_end(key)
-        ent["calls"] += 1
-        if ent.get("failed"):
+
+        def run(static, handle):
+            self.forward(static, handle, training)
+            return self.tail_forward(static["extra"], handle, training)
+
+        ent = self.replay(True, key, seed, {k: feats[k] for k in ("l", "v", "a")} | {"extra": extra}, run,
+                              f"BPMulT: graph capture of the forward pass failed for input shapes {key[1]} (%s); "
+                              "this shape runs as eager launches",
+                              on_fail=lambda: self._px_rows.update(self.N))    # nothing of the capture ran: clear the pad rows again
+        if ent is None:
             return None
-        if "graph" not in ent:
-            if ent["calls"] <= self.GRAPH_WARMUP or not self._may_capture():
-                self._evict_graphs()
-                return None
-            ent["in"] = {k: torch.empty_like(feats[k]) for k in ("l", "v", "a")}
-            ent["extra"] = torch.empty_like(extra) if extra is not None else None
-            handle = self._seed_handle(seed)
-
-            def run():
-                self.forward(ent["in"], handle, training)
-                return self.tail_forward(ent["extra"], handle, training)
-
-            try:
-                ent["graph"], ent["out"] = self._capture(run)
-            except Exception as exc:                      # noqa: BLE001 -- any capture failure: this key runs eagerly from now on
-                import warnings
-                ent.clear()
-                ent.update(calls=self.GRAPH_WARMUP + 1, failed=True)
-                self._px_rows = {k: self.N[k] for k in self.N}      # nothing of the capture ran: clear the pad rows again
-                self.graph_stats["failed"] += 1
-                warnings.warn(f"BPMulT: graph capture of the forward pass failed for input shapes {key[1]} ({exc}); "
-                              "this shape runs as eager launches")
-                torch.cuda.synchronize()
-                return None
-            self.graph_stats["captured"] += 1
-            # host-side state a forward leaves for its backward (a replay runs no Python): restored before the backward
-            ent["state"] = (self._conv, self._tail_desc, self.plan1._last, self.plan2._last)
-            self._evict_graphs()
-        for k in ("l", "v", "a"):
-            ent["in"][k].copy_(feats[k])
-        if extra is not None:
-            ent["extra"].copy_(extra)
-        self._seed_handle(seed)
-        ent["graph"].replay()
+        if "state" not in ent:    # host-side state a forward leaves for its backward (a replay runs no Python): restored
+            ent["state"] = (self._conv, self._tail_desc, self.plan1._last, self.plan2._last)      # before the backward
         self.plan1.maps_ready()                      # (no Python of EncoderGroupPlan.forward ran: attention_maps)
         self.plan2.maps_ready()
         self._px_rows = {k: feats[k].shape[1] for k in ("l", "v", "a")}
         return ent["out"][0], ent["out"][1], key
-
-    def restore_forward_state(self, fkey) -> None:
-        """Before the backward (captured or eager) of a forward that was a graph replay."""
-        self._conv, self._tail_desc, self.plan1._last, self.plan2._last = self._fg[fkey]["state"]
 
     def graph_backward(self, fkey, dlogits: torch.Tensor, dz: Optional[torch.Tensor], params, seed: int, need: Dict[str, bool]):
         """Backward of a graph-run forward.  Whether the gradients start from zero (first-writer-stores launch tables +
         the small tensors cleared) or accumulate is part of the key.  Returns (parameter gradients of the tail, d(extra),
         d(features)) as clones of the graph's static outputs, or None before the key is captured (or when its capture
         failed: the caller runs the eager backward -- the forward state has been restored)."""
-        self.restore_forward_state(fkey)
+        self._conv, self._tail_desc, self.plan1._last, self.plan2._last = self._fg[fkey]["state"]
         fresh = self.st._fresh()
         key = (fkey, fresh, dz is not None, tuple(sorted(k for k, v in need.items() if v)))
-        ent = self._bg.setdefault(key, {"calls": 0})
-        ent["calls"] += 1
-        if ent.get("failed"):
+
+        def run(static, handle):
+            pg, dextra = self.tail_backward(static["dlogits"], static["dz"], params)
+            return pg, dextra, self.backward(handle, need, stores=fresh)
+
+        ent = self.replay(False, key, seed, {"dlogits": dlogits, "dz": dz}, run,
+                              "BPMulT: graph capture of the backward pass failed (%s); this key runs as eager launches")
+        if ent is None:
             return None
-        if "graph" not in ent:
-            if ent["calls"] <= 1:
-                return None
-            ent["dlogits"] = torch.empty_like(dlogits)
-            ent["dz"] = torch.empty_like(dz) if dz is not None else None
-            handle = self._seed_handle(seed)
-
-            def run():
-                pg, dextra = self.tail_backward(ent["dlogits"], ent["dz"], params)
-                return pg, dextra, self.backward(None, handle, need, stores=fresh)
-
-            try:
-                g, (pg, dextra, res) = self._capture(run)
-            except Exception as exc:                      # noqa: BLE001
-                import warnings
-                ent.clear()
-                ent.update(calls=2, failed=True)
-                self.graph_stats["failed"] += 1
-                warnings.warn(f"BPMulT: graph capture of the backward pass failed ({exc}); this key runs as eager launches")
-                torch.cuda.synchronize()
-                return None
-            ent.update(graph=g, pg=pg, dextra=dextra, res=res)
-        ent["dlogits"].copy_(dlogits)
-        if dz is not None:
-            ent["dz"].copy_(dz)
-        self._seed_handle(seed)
-        ent["graph"].replay()
         self.st.end_backward()
-        res = {k: (v.clone() if v is not None else None) for k, v in ent["res"].items()}
-        return [t.clone() for t in ent["pg"]], ent["dextra"], res
+        pg, dextra, res = ent["out"]
+        return [t.clone() for t in pg], dextra, {k: (v.clone() if v is not None else None) for k, v in res.items()}
 
     def _ready(self, section: str, events=None) -> None:
         hook = getattr(self.m, "_grad_ready_hook", None)
@@ -766,14 +635,14 @@ class _ModelFn(torch.autograd.Function):
         feats = {"l": x_l.detach().contiguous(), "v": x_v.detach().contiguous(), "a": x_a.detach().contiguous()}
         ex = extra.detach().contiguous() if extra is not None else None
         trunk.st.refresh_shadows()
-        ran = trunk.graph_forward(feats, ex, seed, model.training, model._want_grad) if model._graphs_on() else None
+        ran = trunk.graph_forward(feats, ex, seed, model.training) if model._graphs_on() else None
         if ran is None:
             trunk.forward(feats, seed, model.training)
             logits, z = trunk.tail_forward(ex, seed, model.training)
             ctx.fkey = None
         else:
             logits, z, ctx.fkey = ran
-        trunk.stamp = getattr(trunk, "stamp", 0) + 1
+        trunk.stamp += 1
         model._last_trunk = trunk
         ctx.trunk, ctx.seed, ctx.stamp, ctx.extra, ctx.params = trunk, seed, trunk.stamp, ex, tail_params
         ctx.need = {"l": x_l.requires_grad, "v": x_v.requires_grad, "a": x_a.requires_grad}
@@ -792,7 +661,7 @@ class _ModelFn(torch.autograd.Function):
             pgrads, dextra, res = ran
         else:
             pgrads, dextra = ctx.trunk.tail_backward(dlogits, dz, ctx.params)
-            res = ctx.trunk.backward(None, ctx.seed, ctx.need)
+            res = ctx.trunk.backward(ctx.seed, ctx.need)
         return (None, res["l"], res["v"], res["a"], dextra.clone() if (dextra is not None and ctx.extra is not None) else None,
                 None) + tuple(pgrads)
 
@@ -992,7 +861,7 @@ class _BPMulTBase(nn.Module):
         return (torch.initial_seed() * 1000003 + rank * 0x9E3779B97F4A7C15 + int(self.dropout_step)) & 0x7FFFFFFFFFFFFFFF   # 63 bits: bit 63 marks an indirect seed
 
     def _graphs_on(self) -> bool:
-        """Captured-graph replay of the step (see _Trunk.graph_forward): on unless switched off (`use_graphs`,
+        """Captured-graph replay of the step (_Trunk.graph_forward, graphs.GraphCache): on unless switched off (`use_graphs`,
         BPMULT_GRAPH=0), a gradient-exchange hook needs the eager launch order, or the launch profiler is recording."""
         if not getattr(self, "use_graphs", True) or os.environ.get("BPMULT_GRAPH", "1") == "0":
             return False
@@ -1010,7 +879,6 @@ class _BPMulTBase(nn.Module):
     def _run(self, x_l, x_v, x_a, extra):
         """features -> (logits, gates) through the HIP path (one autograd node)."""
         self._ensure_store()
-        self._want_grad = torch.is_grad_enabled()       # (grad mode is off inside autograd.Function.forward)
         tail = self.tail_parameters()
         for p in tail:
             if p.dtype != torch.float32 or not p.is_contiguous():

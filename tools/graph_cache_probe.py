@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Captured graphs must not be destroyed while the process goes on capturing / launching others (MI355X, torch 2.10 +
-ROCm 7.0/7.2): reproduction and the evidence behind models/bpmult.py's policy (cap instead of LRU eviction, dropped trunks
+ROCm 7.0/7.2): reproduction and the evidence behind graphs.GraphCache's policy (cap instead of LRU eviction, dropped trunks
 park their graphs in _RETIRED_GRAPHS).  A host segfault kills the process, so every variant runs in a child process.
 
   python tools/graph_cache_probe.py            # every variant, one line each; writes gpurun_out/r04_graph_probe.json
@@ -57,8 +57,8 @@ def child_trunks():
                 assert torch.equal(outs[0], outs[1]), (rnd, B, it)
                 n += 1
                 print(f"step {n} round {rnd} B {B} ok", flush=True)
-    from bpmult_amd.models import bpmult as BM
-    print("STATS retired", len(BM._RETIRED_GRAPHS), flush=True)
+    from bpmult_amd.graphs import _RETIRED_GRAPHS
+    print("STATS retired", len(_RETIRED_GRAPHS), flush=True)
 
 
 def child_torch():
