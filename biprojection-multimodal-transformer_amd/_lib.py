@@ -25,7 +25,8 @@ PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd
 
 ABI_VERSION = 3                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
-# that tools/gemm_lab.py, tools/attn_lab.py and three kernel tests use; never loaded by the product path
+# that tools/gemm_lab.py, tools/attn_lab.py and three kernel tests use, the GEMM dispatcher's environment switches and its
+# decision query (bpm_debug_gemm_choice: tools/gemm_choice.py, tests/test_gemm_choice_cpu.py); never loaded by the product path
 LAB_LIB_PATH = os.path.join(_HERE, "..", "build", "lab", "libbpmult_hip_lab.so")
 BPM_F32, BPM_BF16, BPM_BF16X3 = 0, 1, 2      # BPM_BF16X3: bpm_gemm_grouped only (split-bf16 operands, three products)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -310,7 +311,8 @@ def lib() -> C.CDLL:
 
 class lab_library:
     """Context manager for tools/ and tests: route this process's launches through the -DBPM_LAB build (which exports
-    bpm_debug_gemm_force / bpm_debug_attn_pair) and back.  Raises HipLibraryError when that build is absent."""
+    bpm_debug_gemm_force / bpm_debug_gemm_choice / bpm_debug_attn_pair) and back.  Raises HipLibraryError when that build
+    is absent."""
 
     def __enter__(self) -> C.CDLL:
         global _lib
@@ -318,6 +320,8 @@ class lab_library:
         L = load(LAB_LIB_PATH)
         L.bpm_debug_gemm_force.argtypes = [C.c_int]
         L.bpm_debug_attn_pair.argtypes = [C.c_int]
+        # (dtype, variant, problems, nprob, compute units, out[4 + 4 * nprob]): the dispatcher's decision, nothing launched
+        L.bpm_debug_gemm_choice.argtypes = [C.c_int, C.c_int, C.POINTER(GemmProblem), C.c_int, C.c_int, C.POINTER(C.c_int)]
         _lib = L
         return L
 

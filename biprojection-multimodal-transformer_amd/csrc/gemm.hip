@@ -828,85 +828,49 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const Group grp) {
 
 #include "gemm_dma.h"
 
-template <typename CT>
-int launch(int variant, bool fast, bool bm64, const Group& g, hipStream_t s) {
-    dim3 grid(g.total_tiles), block(NTHREADS);
-    if (fast) {
-        switch (variant) {
-            case BPM_GEMM_NT: hipLaunchKernelGGL((gemm_tiled_kernel<CT, true, true, KS_FWD, BPM_DEEP_FWD != 0, true>), grid, block, 0, s, g); break;
-            case BPM_GEMM_NN: hipLaunchKernelGGL((gemm_tiled_kernel<CT, true, false, 1, BPM_DEEP_FWD != 0, true>), grid, block, 0, s, g); break;
-            case BPM_GEMM_TN:
-                if (bm64) hipLaunchKernelGGL((gemm_tiled_kernel<CT, false, false, 1, true, true, 64>), grid, block, 0, s, g);
-                else hipLaunchKernelGGL((gemm_tiled_kernel<CT, false, false, 1, true, true>), grid, block, 0, s, g);
-                break;
-            default: return BPM_ERR_ARG;
-        }
-        BPM_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (variant) {
-        case BPM_GEMM_NT: hipLaunchKernelGGL((gemm_tiled_kernel<CT, true, true, KS_FWD, BPM_DEEP_FWD != 0>), grid, block, 0, s, g); break;
-        case BPM_GEMM_NN: hipLaunchKernelGGL((gemm_tiled_kernel<CT, true, false, 1, BPM_DEEP_FWD != 0>), grid, block, 0, s, g); break;
-        case BPM_GEMM_TN:
-            // measured (MI355X, K = 4096 rows): with at least ~2 workgroups per CU the short stage wins
-            // (more resident workgroups hide the load latency); below that the long stage does
-            if (g.total_tiles >= 2 * 256) hipLaunchKernelGGL((gemm_tiled_kernel<CT, false, false, 1, BPM_DEEP_TN != 0>), grid, block, 0, s, g);
-            else if (BPM_DEEP_TN == 2) hipLaunchKernelGGL((gemm_tiled_kernel<CT, false, false, 1, true>), grid, block, 0, s, g);
-            else hipLaunchKernelGGL((gemm_tiled_kernel<CT, false, false, KS_WGRAD, false>), grid, block, 0, s, g);
-            break;
-        default: return BPM_ERR_ARG;
-    }
-    BPM_CHECK_LAUNCH();
-    return 0;
-}
+// ---------------------------------------------------------------------------
+// host side.  bpm_gemm_grouped is plan_group (check_group -> summarise -> choose -> check_choice -> fill_group), the
+// profiler's work_estimate and launch; everything up to the launch is plain C++ without a HIP call.
+// ---------------------------------------------------------------------------
 
-// LDS-DMA kernel configurations: (waves along m, waves along n, m tiles per wave, stages); X3: split-bf16 operands
-template <int WMD, int WND, int TMW, int NS, bool X3 = false, int DKT = DK>
-int launch_dma_cfg(int variant, const Group& g, hipStream_t s) {
-    dim3 grid(g.total_tiles), block(64 * WMD * WND);
-    switch (variant) {
-        case BPM_GEMM_NT: hipLaunchKernelGGL((gemm_dma_kernel<true, true, WMD, WND, TMW, NS, false, X3, DKT>), grid, block, 0, s, g); break;
-        case BPM_GEMM_NN: hipLaunchKernelGGL((gemm_dma_kernel<true, false, WMD, WND, TMW, NS, false, X3, DKT>), grid, block, 0, s, g); break;
-        case BPM_GEMM_TN:
-            if constexpr ((16 * TMW * WMD) % 128 == 0) {
-                bool xs = false;
-                for (int i = 0; i < g.nprob; ++i) xs = xs || g.p[i].colsum_x != nullptr;
-                if (xs) hipLaunchKernelGGL((gemm_dma_kernel<false, false, WMD, WND, TMW, NS, true, X3, DKT>), grid, block, 0, s, g);
-                else hipLaunchKernelGGL((gemm_dma_kernel<false, false, WMD, WND, TMW, NS, false, X3, DKT>), grid, block, 0, s, g);
-            } else return BPM_ERR_ARG;         // k-strided X: 128-column sub-images only
-            break;
-        default: return BPM_ERR_ARG;
-    }
-    BPM_CHECK_LAUNCH();
-    return 0;
-}
-
+// The kernel family that runs a launch (the variant and the element type pick the instantiation inside it: launch()).
+// 0 .. 6 are the LDS-DMA configurations bpm_debug_gemm_force names, the index of DMA_CFGS.
+enum Kernel {
+    K_NONE = -1,
+    K_DMA_0 = 0,            // 128 x 128,  4 waves, 2 stages (64 KB: 2 per CU)
+    K_DMA_1,                // 256 x 128,  8 waves
+    K_DMA_2,                // 256 x 256,  8 waves of 128 x 64
+    K_DMA_3,                // 256 x 256, 16 waves of 64 x 64
+    K_DMA_4,                // 128 x 128,  3 stages
+    K_DMA_TALL,             // 320 x 256,  8 waves of 160 x 64 (k-contiguous X only)
+    K_DMA_TWO,              // 256 x 128,  8 waves of 64 x 64, 3 stages of 32 k (72 KB): two workgroups per CU (gemm_dma.h)
+    K_X3_2, K_X3_3, K_X3_TALL,      // split-bf16 operands: the configurations the automatic choice picks (fewer instantiations)
+    K_SKINNY,               // 16 x 64, at most 16 rows per problem
+    K_TILED_FAST,           // 128 x 64, hardware-bounded loaders
+    K_TILED_BOUNDED,        // 128 x 64, bounds checked in the loaders (NT / NN)
+    K_TN_64,                // 64 x 64 weight-gradient workgroups, hardware-bounded loaders
+    K_TN_SHORT, K_TN_LONG   // 128 x 64 weight gradients with checked bounds: short / long k stage
+};
+struct Choice { Kernel kernel; int bm, bn; };
 struct DmaCfg { int bm, bn; };
 constexpr DmaCfg DMA_CFGS[] = {{128, 128}, {256, 128}, {256, 256}, {256, 256}, {128, 128}, {320, 256}, {256, 128}};
-constexpr int CFG_TALL = 5;               // 320-row tiles (k-contiguous X only): see the tile choice in bpm_gemm_grouped
-constexpr int CFG_TWO = 6;                // 256 x 128, 32-k stages, three of them: two workgroups per CU (gemm_dma.h)
 constexpr int N_DMA_CFGS = sizeof(DMA_CFGS) / sizeof(DMA_CFGS[0]);
+static_assert(N_DMA_CFGS == K_DMA_TWO + 1, "one tile per LDS-DMA configuration");
+bool is_dma(Kernel k) { return k >= K_DMA_0 && k <= K_X3_TALL; }
 
-int launch_dma(int cfg, int variant, const Group& g, hipStream_t s, bool x3 = false) {
-    if (x3) {                                 // the configurations the automatic choice picks (fewer instantiations)
-        switch (cfg) {
-            case 2: return launch_dma_cfg<2, 4, 8, 2, true>(variant, g, s);
-            case 3: return launch_dma_cfg<4, 4, 4, 2, true>(variant, g, s);
-            case CFG_TALL: return launch_dma_cfg<2, 4, 10, 2, true>(variant, g, s);
-        }
-        return BPM_ERR_ARG;
-    }
-    switch (cfg) {
-        case 0: return launch_dma_cfg<2, 2, 4, 2>(variant, g, s);      // 128 x 128,  4 waves, 2 stages (64 KB: 2 per CU)
-        case 1: return launch_dma_cfg<4, 2, 4, 2>(variant, g, s);      // 256 x 128,  8 waves
-        case 2: return launch_dma_cfg<2, 4, 8, 2>(variant, g, s);      // 256 x 256,  8 waves of 128 x 64
-        case 3: return launch_dma_cfg<4, 4, 4, 2>(variant, g, s);      // 256 x 256, 16 waves of 64 x 64
-        case 4: return launch_dma_cfg<2, 2, 4, 3>(variant, g, s);      // 128 x 128,  3 stages
-        case CFG_TALL: return launch_dma_cfg<2, 4, 10, 2>(variant, g, s);   // 320 x 256, 8 waves of 160 x 64 (NT / NN)
-        case CFG_TWO: return launch_dma_cfg<4, 2, 4, 3, false, 32>(variant, g, s);   // 256 x 128, 8 waves of 64 x 64, 3 stages of 32 k: 72 KB
-    }
-    return BPM_ERR_ARG;
-}
+// Lab switches of the choice: constants in the product library; only a -DBPM_LAB build (build/lab/libbpmult_hip_lab.so:
+// tools/gemm_lab.py, A/B runs, the kernel tests that pin a configuration) can move them.
+struct Lab {
+    int force_dma;          // -1 = automatic choice, -2 = never the LDS-DMA kernel, 0.. = DMA_CFGS[i] where legal (bpm_debug_gemm_force)
+    int two_mask;           // two-resident classes: 1 = FFN weight gradients, 2 = K / V projections, 4 = fc1 (BPMULT_TWO_MASK)
+    bool narrow_dma;        // the two-resident tiles for products that fill 128-wide tiles only (BPMULT_NARROW_DMA)
+};
+#ifdef BPM_LAB
+int env_int(const char* name, int unset) { const char* v = std::getenv(name); return v ? std::atoi(v) : unset; }
+Lab g_lab = {-1, env_int("BPMULT_TWO_MASK", 7), env_int("BPMULT_NARROW_DMA", 1) != 0};
+#else
+constexpr Lab g_lab = {-1, 7, true};
+#endif
 
 int num_cus() {
     static int ncu = 0;
@@ -919,21 +883,323 @@ int num_cus() {
     return ncu;
 }
 
-// tile-configuration override: -1 = automatic choice, -2 = never the LDS-DMA kernel, 0.. = force DMA_CFGS[i] where legal.
-// A constant in the product library; only a -DBPM_LAB build (build/lab/libbpmult_hip_lab.so: tools/gemm_lab.py and the
-// kernel tests that pin a configuration) makes it a process-global switch behind bpm_debug_gemm_force.
-#ifdef BPM_LAB
-int g_force_dma = -1;
-#else
-constexpr int g_force_dma = -1;
-#endif
+// hardware-bounded loader: the problem promises zero k padding, k-contiguous rows are whole k stages and the matrices
+// fit 31-bit byte offsets
+bool bounded_ok(const bpm_gemm_problem& q, int variant, int sz) {
+    const bool xk = variant != BPM_GEMM_TN, yk = variant == BPM_GEMM_NT;
+    const int stage_b = 64 * (variant == BPM_GEMM_NT ? KS_FWD : 1);
+    const bool aov = (q.flags & BPM_GEMM_A_OVERLAP) != 0, bov = (q.flags & BPM_GEMM_B_OVERLAP) != 0;
+    bool ok = (q.flags & BPM_GEMM_KPAD_ZERO) != 0;
+    // overlapping rows: no zero padding behind a row (the next window starts there), so k must end on a stage
+    if (xk) ok = ok && (aov ? q.K % 64 == 0 : ((long)q.lda * sz) % stage_b == 0 && (long)q.K <= q.lda);
+    if (yk) ok = ok && (bov ? q.K % 64 == 0 : ((long)q.ldb * sz) % stage_b == 0 && (long)q.K <= q.ldb);
+    const long bx = ((long)(xk ? q.M : q.K) - 1) * q.lda * sz + (long)(aov ? (xk ? q.K : q.M) : q.lda) * sz;
+    const long by = ((long)(yk ? q.N : q.K) - 1) * q.ldb * sz + (long)(bov ? (yk ? q.K : q.N) : q.ldb) * sz;
+    return ok && bx < (1l << 31) - 65536 && by < (1l << 31) - 65536;
+}
+
+// every argument check that does not depend on the chosen tile
+int check_group(int dtype, int variant, const bpm_gemm_problem* probs, int nprob) {
+    if (nprob < 1 || nprob > BPM_GEMM_MAX_GROUP || !probs) return BPM_ERR_ARG;
+    if (variant != BPM_GEMM_NT && variant != BPM_GEMM_NN && variant != BPM_GEMM_TN) return BPM_ERR_ARG;
+    // BPM_BF16X3: A / B are split-bf16 images (bpm_split_rows: lda / ldb span the hi and the lo plane), K / M / N are those
+    // of the fp32 product, CT outputs and the gate operand are fp32; only the LDS-DMA kernel computes it
+    if (dtype != BPM_F32 && dtype != BPM_BF16 && dtype != BPM_BF16X3) return BPM_ERR_ARG;
+    const int sz = dtype == BPM_F32 ? 4 : 2;
+    bool fast = true, overlap = false;
+    for (int i = 0; i < nprob && fast; ++i) {
+        overlap = overlap || (probs[i].flags & (BPM_GEMM_A_OVERLAP | BPM_GEMM_B_OVERLAP)) != 0;
+        fast = bounded_ok(probs[i], variant, sz);
+    }
+    if (overlap && !fast) return BPM_ERR_ARG;      // only the hardware-bounded loaders address overlapping rows
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_gemm_problem& q = probs[i];
+        if (q.M < 1 || q.N < 1 || q.K < 1 || !q.A || !q.B || !q.C) return BPM_ERR_ARG;
+        // operand leading dims must keep every row 16-byte aligned
+        if ((q.lda * sz) % 16 || (q.ldb * sz) % 16) return BPM_ERR_ALIGN;
+        if (((uintptr_t)q.A | (uintptr_t)q.B) & 15) return BPM_ERR_ALIGN;
+        if (q.colsum_a && (variant != BPM_GEMM_TN || q.splitk > 1)) return BPM_ERR_ARG;
+        if (q.out_kind == BPM_OUT_HEADS && (q.heads_B < 1 || q.heads_dh < 1 || q.heads_H * q.heads_dh != q.N)) return BPM_ERR_ARG;
+        if (q.splitk > 1 && !((q.flags & BPM_GEMM_ATOMIC) && q.out_kind == BPM_OUT_F32)) return BPM_ERR_ARG;
+        if (q.flags & BPM_GEMM_BATCHED) {
+            // `batch` independent products of one shape: operand / output i starts batch_stride_* elements behind i - 1.  The
+            // 128 x 64 kernel only (check_choice); the batch index travels where the split-K slice does, the strides in the
+            // head fields (plain stores through the 4-wide epilogue, no side operands).
+            const uintptr_t al = (uintptr_t)q.C | (uintptr_t)q.bias_n;
+            if (dtype == BPM_BF16X3 || q.batch < 1 || q.batch > 4096 || q.splitk > 1 || q.out_kind == BPM_OUT_HEADS || q.bias_m || q.resid ||
+                q.gate || q.colsum || q.colsum_a || q.drop_p != 0.f || (q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_ACCUM)) ||
+                (q.N & 3) || (q.ldc & 3) || (al & 15) || q.batch_stride_a < 0 || q.batch_stride_b < 0 || q.batch_stride_c < 0 ||
+                ((q.batch_stride_a * sz) & 15) || ((q.batch_stride_b * sz) & 15) || (q.batch_stride_c & 3))
+                return BPM_ERR_ARG;
+        }
+    }
+    return 0;
+}
+
+// what the rules of choose() read, gathered in one pass over the (checked) problems
+struct GroupShape {
+    bool fast = true;       // every problem may take the hardware-bounded loaders (bounded_ok)
+    bool legal = true;      // the LDS-DMA kernel can compute every problem (as bf16 or split-bf16 operands)
+    bool big = true;        // every problem fills 256 x 256 tiles to 80 %
+    bool narrow = true;     // every problem fills 256 x 128 tiles to 75 %
+    bool skinny = true;     // every problem suits the skinny kernel: at most 16 rows, whole 64-byte k-steps
+    bool xs_any = false;    // a problem carries colsum_a
+    long kmin = 1l << 30, kmax = 0, nmax = 0, mmax = 0;
+    long t128 = 0;          // workgroups of the 128 x 64 kernel, split-K slices counted
+    long wg128 = 0;         // ... batches counted too: its grid
+    long t256 = 0, t320 = 0, tiles_narrow = 0;      // tiles of 256 x 256, 320 x 256, 256 x 128
+};
+
+GroupShape summarise(int dtype, int variant, const bpm_gemm_problem* probs, int nprob) {
+    const bool x3 = dtype == BPM_BF16X3, xk = variant != BPM_GEMM_TN, yk = variant == BPM_GEMM_NT;
+    const int sz = dtype == BPM_F32 ? 4 : 2;
+    GroupShape s;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_gemm_problem& q = probs[i];
+        s.fast = s.fast && bounded_ok(q, variant, sz);
+        // LDS-DMA kernel (gemm_dma.h): no split-K, k-contiguous operands hold whole 128-byte stages inside their
+        // zero-padded rows
+        const long kceil = ((long)q.K + DK - 1) / DK * DK;
+        bool legal = q.splitk <= 1 && !(q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_BATCHED)) && (!xk || (q.flags & BPM_GEMM_A_OVERLAP) || kceil <= q.lda) &&
+                     (!yk || (q.flags & BPM_GEMM_B_OVERLAP) || kceil <= q.ldb);
+        if (x3) {       // a plane (half the leading dimension) holds whole k stages / whole 128-column sub-images, no overlap
+            const long pa = q.lda / 2, pb = q.ldb / 2, m128 = ((long)q.M + 127) / 128 * 128, n128 = ((long)q.N + 127) / 128 * 128;
+            legal = legal && !(q.flags & (BPM_GEMM_A_OVERLAP | BPM_GEMM_B_OVERLAP)) && (q.lda & 1) == 0 && (q.ldb & 1) == 0 &&
+                    (xk ? kceil <= pa : m128 <= pa) && (yk ? kceil <= pb : n128 <= pb) && (pa * 2) % 16 == 0 && (pb * 2) % 16 == 0;
+        }
+        // its epilogue is the 4-wide one only (epi_fast_ok, evaluated here on the host)
+        const uintptr_t al = (uintptr_t)q.bias_n | (uintptr_t)q.resid | (uintptr_t)q.C | (uintptr_t)q.gate;
+        s.legal = s.legal && legal && (q.N & 3) == 0 && (al & 15) == 0 && ((q.ldr | q.ldc | q.ldg) & 3) == 0 && !q.bias_m &&
+                  !(q.resid && (q.flags & BPM_GEMM_ACCUM));
+        const long tm = (q.M + 255) / 256, tn = (q.N + 255) / 256, tn_narrow = (q.N + 127) / 128;
+        s.big = s.big && q.M >= 256 && q.N >= 256 && q.K >= 256 && (double)q.M * q.N >= 0.8 * (double)(tm * 256) * (double)(tn * 256);
+        s.narrow = s.narrow && q.M >= 256 && q.N >= 128 && q.K >= 256 && (double)q.M * q.N >= 0.75 * (double)(tm * 256) * (double)(tn_narrow * 128);
+        s.skinny = s.skinny && q.M <= 16 && q.splitk <= 1 &&
+                   !(q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_A_OVERLAP | BPM_GEMM_B_OVERLAP | BPM_GEMM_BATCHED)) &&
+                   ((long)q.lda * sz) % 64 == 0 && (variant != BPM_GEMM_NT || ((long)q.ldb * sz) % 64 == 0);
+        s.xs_any = s.xs_any || q.colsum_a != nullptr;
+        s.kmin = q.K < s.kmin ? q.K : s.kmin;
+        s.kmax = q.K > s.kmax ? q.K : s.kmax;
+        s.nmax = q.N > s.nmax ? q.N : s.nmax;
+        s.mmax = q.M > s.mmax ? q.M : s.mmax;
+        const long t = (long)((q.M + BM - 1) / BM) * ((q.N + BN - 1) / BN);
+        s.t128 += t * (q.splitk > 1 ? q.splitk : 1);
+        s.wg128 += t * ((q.flags & BPM_GEMM_BATCHED) ? q.batch : q.splitk > 1 ? q.splitk : 1);
+        s.t256 += tm * tn;
+        s.t320 += (q.M + 319) / 320 * tn;
+        s.tiles_narrow += tm * tn_narrow;
+    }
+    return s;
+}
+
+// Which kernel runs the group, and with which tile: the rules in the order they apply.  Pure: no HIP call, no environment.
+Choice choose(const GroupShape& s, int dtype, int variant, int nprob, int ncu, const Lab& lab) {
+    const bool x3 = dtype == BPM_BF16X3, tn = variant == BPM_GEMM_TN;
+    // LDS-DMA kernel: bf16 (or split-bf16) operands that the hardware-bounded loaders may address, epilogue 4-wide
+    // (GroupShape::legal).  Measured on MI355X at hidden 768, six problems of 4096 rows per launch (tools/gemm_lab.py, us,
+    // register-staged 128 x 64 kernel -> the configuration chosen below): q 84 -> 55, k/v 154 -> 103, out 80 -> 55, fc1
+    // 267 -> 156, fc2 245 -> 124, d(fc2) 314 -> 181, d(fc1) 185 -> 110, d(out) 82 -> 55, d(q) 63 -> 47, d(k/v) 135 -> 107,
+    // FFN weight gradients 445 -> 322 (8 waves of 128 x 64); the attention weight gradients (768 x 768 x 4096: nine
+    // 256 x 256 tiles per problem) stay on the 128 x 64 kernel (154 against 186).
+    int dma = -1;
+    if ((dtype == BPM_BF16 || x3) && s.fast && s.legal && (lab.force_dma != -2 || x3)) {
+        // weight gradients: one 256 x 256 tile per CU only pays when most CUs get one (measured, 768 x 768 x 4096 problems
+        // with bias column sums: 24 problems = 216 tiles 227 -> 181 us, 18 = 162 tiles 169 -> 156, 12 = 108 tiles 114 -> ~150).
+        // Split operands: the caller (ops.gemm_grouped) sends what ops._X3Plan._eligible accepted
+        const bool big = x3 || (s.big && !(tn && s.t256 * 8 < (long)ncu * 5));
+        if (lab.force_dma >= 0 && !x3) dma = lab.force_dma == K_DMA_TALL && tn ? -1 : lab.force_dma;
+        else if (big) {
+            dma = tn ? K_DMA_2 : K_DMA_3;
+            if (!tn) {
+                // One workgroup per CU: a launch takes ceil(tiles / CUs) rounds of one tile each, and at the model's
+                // shapes the tile count sits just above a multiple of the CU count (six problems of 4096 x 768 are 288
+                // tiles of 256 x 256: a second round for 32 of them).  320-row tiles (13 instead of 16 per 4096 rows: 234
+                // tiles, one round of 1.25x the work) win whenever they save a round; per flop the 16-wave 256-row
+                // kernel is ~5 % faster.
+                const long r256 = (s.t256 + ncu - 1) / ncu, r320 = (s.t320 + ncu - 1) / ncu;
+                if (r320 * 320 * 21 < r256 * 256 * 20) dma = K_DMA_TALL;
+            }
+            // Two resident workgroups per CU (256 x 128 tiles, 32-k stages; gemm_dma.h) where they measured faster than the
+            // one-per-CU tiles (tools/gemm_lab.py, hidden 768, six problems of 4096 rows): the FFN weight gradients
+            // 328 -> 279 us (their k loop is LDS-fill bound: a second workgroup's loads and a third stage fill the gaps);
+            // twelve-problem K / V projections 104 -> 94.  Not for weight gradients that carry the bias column sums (the
+            // extra accumulators spill at 128 registers: 156 -> 253 us) nor for the N = 768 products, where 320 x 256 tiles
+            // fit one round (q 55 -> 59, fc2 124 -> 178).  Inside the step (bench.py, hidden 768, ms per step): none
+            // 19.97-20.03, weight gradients + K / V 19.65-19.82, + fc1 (N >= 2048 forward products) 19.44.  Measured and
+            // rejected, so these run one workgroup per CU: + d(fc2) (NN, N >= 2048) 19.54-19.80, every N = 768 product
+            // 20.22, the attention weight gradients (the spill above).
+            // (hidden 1536, `bench.py --config cfg5`: the weight-gradient and fc1 classes each cost 1 % there -- 70.7 -> 71.4 / 71.6
+            // ms -- so they are tied to hidden <= 1024: weight gradients of at most 1024 rows, forward products of K <= 1024)
+            const bool nt = variant == BPM_GEMM_NT;
+            const bool two_tn = (lab.two_mask & 1) && tn && !s.xs_any && s.kmin >= 1024 && s.mmax <= 1024;
+            const bool kv = (lab.two_mask & 2) && nt && nprob >= 12 && s.nmax <= 1024;
+            const bool fc1 = (lab.two_mask & 4) && nt && s.nmax >= 2048 && s.kmax <= 1024;
+            if (!x3 && (two_tn || kv || fc1)) dma = K_DMA_TWO;
+        }
+        // products whose columns fill 128-wide tiles but not 256-wide ones (hidden 300: 300 / 384 against 300 / 512): the
+        // two-resident 256 x 128 configuration instead of the 128 x 64 kernel
+        else if (lab.narrow_dma && !tn && s.narrow && s.tiles_narrow >= ncu) dma = K_DMA_TWO;
+    }
+    if (dma >= 0) return {x3 ? (dma == K_DMA_2 ? K_X3_2 : dma == K_DMA_3 ? K_X3_3 : K_X3_TALL) : (Kernel)dma, DMA_CFGS[dma].bm, DMA_CFGS[dma].bn};
+    if (x3) return {K_NONE, 0, 0};               // only the LDS-DMA kernel computes split operands
+    // at most 16 rows per problem (level-2 query side under dead-row elimination): the skinny kernel (see there)
+    if (!tn && s.fast && s.skinny) return {K_SKINNY, 16, 64};
+    if (!tn) return {s.fast ? K_TILED_FAST : K_TILED_BOUNDED, BM, BN};
+    // under-filled weight-gradient launches (fewer than two 128-row workgroups per CU) run 64-row workgroups:
+    // measured 98 -> 77 us for the 24 attention weight gradients of a layer (360 -> 600 workgroups)
+    if (s.fast) return s.t128 < 2 * 256 ? Choice{K_TN_64, 64, BN} : Choice{K_TILED_FAST, BM, BN};
+    // measured (MI355X, K = 4096 rows): with at least ~2 workgroups per CU the short stage wins
+    // (more resident workgroups hide the load latency); below that the long stage does
+    return {s.wg128 >= 2 * 256 ? K_TN_SHORT : K_TN_LONG, BM, BN};
+}
+
+// the argument checks that depend on the choice
+int check_choice(const Choice& c, const bpm_gemm_problem* probs, int nprob) {
+    if (c.kernel == K_NONE) return BPM_ERR_ARG;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_gemm_problem& q = probs[i];
+        const int ntiles = (q.N + c.bn - 1) / c.bn;
+        if (q.out_kind == BPM_OUT_CT && !(q.flags & BPM_GEMM_CT_NARROW) && ntiles * c.bn < q.ldc) return BPM_ERR_ARG;
+        if ((q.flags & BPM_GEMM_BATCHED) && (is_dma(c.kernel) || c.kernel == K_SKINNY)) return BPM_ERR_ARG;
+    }
+    return 0;
+}
+
+void fill_group(const Choice& c, const bpm_gemm_problem* probs, int nprob, uint64_t seed, Group& g) {
+    g.seedp = bpm_seed_ptr(seed);
+    g.nprob = nprob;
+    int tile = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_gemm_problem& q = probs[i];
+        Prob& p = g.p[i];
+        p.X = (const char*)q.A; p.Y = (const char*)q.B; p.C = (char*)q.C;
+        p.M = q.M; p.N = q.N; p.K = q.K;
+        p.ldx = q.lda; p.ldy = q.ldb; p.ldc = q.ldc;
+        p.bias_n = q.bias_n; p.bias_m = q.bias_m;
+        p.resid = q.resid; p.ldr = q.ldr;
+        p.gate = (const char*)q.gate; p.ldg = q.ldg; p.gate_scale = q.gate_scale;
+        p.alpha = q.alpha;
+        p.drop = bpm_make_drop(q.drop_p, seed, q.drop_site);
+        p.colsum = q.colsum;
+        p.colsum_x = q.colsum_a;
+        p.flags = q.flags; p.out_kind = q.out_kind;
+        p.hB = q.heads_B; p.hH = q.heads_H; p.hT = q.heads_T; p.hdh = q.heads_dh; p.hdhp = q.heads_dhp;
+        p.tile0 = tile;
+        p.tiles_m = (q.M + c.bm - 1) / c.bm;
+        p.tiles_n = (q.N + c.bn - 1) / c.bn;
+        p.splitk = q.splitk > 1 ? q.splitk : 1;
+        if (q.flags & BPM_GEMM_BATCHED) {          // (check_group)
+            p.splitk = q.batch;
+            p.hB = q.batch_stride_a; p.hH = q.batch_stride_b; p.hT = q.batch_stride_c;
+        }
+        tile += p.tiles_m * p.tiles_n * p.splitk;
+    }
+    g.total_tiles = tile;
+}
+
+// everything bpm_gemm_grouped does before it launches; bpm_debug_gemm_choice reports it.  ncu = 0: the device's count,
+// asked for only once the arguments have passed
+int plan_group(int dtype, int variant, const bpm_gemm_problem* probs, int nprob, uint64_t seed, int ncu, GroupShape& shape, Choice& c, Group& g) {
+    if (const int err = check_group(dtype, variant, probs, nprob)) return err;
+    shape = summarise(dtype, variant, probs, nprob);
+    c = choose(shape, dtype, variant, nprob, ncu ? ncu : num_cus(), g_lab);
+    if (const int err = check_choice(c, probs, nprob)) return err;
+    fill_group(c, probs, nprob, seed, g);
+    return 0;
+}
+
+// the profiler's tallies: flops, and algorithmic HBM bytes (each operand once, the output once, each side operand of
+// the epilogue once)
+void work_estimate(int dtype, const bpm_gemm_problem* probs, int nprob, double& flops, double& bytes) {
+    const int sz = dtype == BPM_F32 ? 4 : 2;
+    flops = bytes = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_gemm_problem& q = probs[i];
+        flops += 2.0 * q.M * (double)q.N * q.K * ((q.flags & BPM_GEMM_BATCHED) ? q.batch : 1);
+        const double mn = (double)q.M * q.N;
+        bytes += ((double)q.M + q.N) * q.K * sz + mn * (q.out_kind == BPM_OUT_F32 ? 4 : sz);
+        if (q.resid) bytes += mn * 4;
+        if (q.gate) bytes += mn * sz;
+        if (q.out_kind == BPM_OUT_F32 && (q.flags & BPM_GEMM_ACCUM)) bytes += mn * 4;
+    }
+}
+
+typedef void (*KernelFn)(const Group);
+
+// the variant picks the instantiation inside a family (nullptr: the family has none for it)
+int launch_variant(int variant, KernelFn nt, KernelFn nn, KernelFn tn, int threads, const Group& g, hipStream_t s) {
+    const KernelFn kernel = variant == BPM_GEMM_NT ? nt : variant == BPM_GEMM_NN ? nn : tn;
+    if (!kernel) return BPM_ERR_ARG;
+    hipLaunchKernelGGL(kernel, dim3(g.total_tiles), dim3(threads), 0, s, g);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+// LDS-DMA kernel configurations: (waves along m, waves along n, m tiles per wave, stages); X3: split-bf16 operands
+template <int WMD, int WND, int TMW, int NS, bool X3 = false, int DKT = DK>
+int launch_dma(int variant, bool xs, const Group& g, hipStream_t s) {
+    KernelFn tn = nullptr;
+    if constexpr ((16 * TMW * WMD) % 128 == 0)          // k-strided X: 128-column sub-images only
+        tn = xs ? gemm_dma_kernel<false, false, WMD, WND, TMW, NS, true, X3, DKT> : gemm_dma_kernel<false, false, WMD, WND, TMW, NS, false, X3, DKT>;
+    return launch_variant(variant, gemm_dma_kernel<true, true, WMD, WND, TMW, NS, false, X3, DKT>,
+                          gemm_dma_kernel<true, false, WMD, WND, TMW, NS, false, X3, DKT>, tn, 64 * WMD * WND, g, s);
+}
+
+// xs: a problem carries colsum_a (GroupShape::xs_any)
+template <typename CT>
+int launch(const Choice& c, int variant, bool xs, const Group& g, hipStream_t s) {
+    switch (c.kernel) {
+        case K_DMA_0: return launch_dma<2, 2, 4, 2>(variant, xs, g, s);
+        case K_DMA_1: return launch_dma<4, 2, 4, 2>(variant, xs, g, s);
+        case K_DMA_2: return launch_dma<2, 4, 8, 2>(variant, xs, g, s);
+        case K_DMA_3: return launch_dma<4, 4, 4, 2>(variant, xs, g, s);
+        case K_DMA_4: return launch_dma<2, 2, 4, 3>(variant, xs, g, s);
+        case K_DMA_TALL: return launch_dma<2, 4, 10, 2>(variant, xs, g, s);
+        case K_DMA_TWO: return launch_dma<4, 2, 4, 3, false, 32>(variant, xs, g, s);
+        case K_X3_2: return launch_dma<2, 4, 8, 2, true>(variant, xs, g, s);
+        case K_X3_3: return launch_dma<4, 4, 4, 2, true>(variant, xs, g, s);
+        case K_X3_TALL: return launch_dma<2, 4, 10, 2, true>(variant, xs, g, s);
+        case K_SKINNY: return launch_variant(variant, gemm_skinny_kernel<CT, true>, gemm_skinny_kernel<CT, false>, nullptr, 256, g, s);
+        case K_TILED_FAST:
+            return launch_variant(variant, gemm_tiled_kernel<CT, true, true, KS_FWD, BPM_DEEP_FWD != 0, true>,
+                                  gemm_tiled_kernel<CT, true, false, 1, BPM_DEEP_FWD != 0, true>,
+                                  gemm_tiled_kernel<CT, false, false, 1, true, true>, NTHREADS, g, s);
+        case K_TILED_BOUNDED:
+            return launch_variant(variant, gemm_tiled_kernel<CT, true, true, KS_FWD, BPM_DEEP_FWD != 0>,
+                                  gemm_tiled_kernel<CT, true, false, 1, BPM_DEEP_FWD != 0>, nullptr, NTHREADS, g, s);
+        case K_TN_64: return launch_variant(variant, nullptr, nullptr, gemm_tiled_kernel<CT, false, false, 1, true, true, 64>, NTHREADS, g, s);
+        case K_TN_SHORT: return launch_variant(variant, nullptr, nullptr, gemm_tiled_kernel<CT, false, false, 1, BPM_DEEP_TN != 0>, NTHREADS, g, s);
+        case K_TN_LONG:
+            return launch_variant(variant, nullptr, nullptr, BPM_DEEP_TN == 2 ? gemm_tiled_kernel<CT, false, false, 1, true>
+                                                                              : gemm_tiled_kernel<CT, false, false, KS_WGRAD, false>, NTHREADS, g, s);
+        case K_NONE: break;
+    }
+    return BPM_ERR_ARG;
+}
 
 }  // namespace
 
 #ifdef BPM_LAB
 extern "C" int bpm_debug_gemm_force(int cfg) {
     if (cfg < -2 || cfg >= N_DMA_CFGS) return BPM_ERR_ARG;
-    g_force_dma = cfg;
+    g_lab.force_dma = cfg;
+    return 0;
+}
+
+// What bpm_gemm_grouped would do with this call on a device of `ncu` compute units, without a device: returns its code up
+// to the launch and writes out[0..3] = kernel (enum Kernel), bm, bn, total_tiles, then tile0, tiles_m, tiles_n, splitk of
+// each problem (4 + 4 * nprob ints).
+extern "C" int bpm_debug_gemm_choice(int dtype, int variant, const bpm_gemm_problem* probs, int nprob, int ncu, int* out) {
+    GroupShape shape;
+    Choice c;
+    Group g;
+    if (ncu < 1 || !out) return BPM_ERR_ARG;
+    if (const int err = plan_group(dtype, variant, probs, nprob, 0, ncu, shape, c, g)) return err;
+    out[0] = c.kernel; out[1] = c.bm; out[2] = c.bn; out[3] = g.total_tiles;
+    for (int i = 0; i < nprob; ++i) {
+        const Prob& p = g.p[i];
+        out[4 + 4 * i] = p.tile0; out[5 + 4 * i] = p.tiles_m; out[6 + 4 * i] = p.tiles_n; out[7 + 4 * i] = p.splitk;
+    }
     return 0;
 }
 #endif
@@ -946,218 +1212,13 @@ extern "C" int bpm_debug_trace(unsigned long long* out, int nblocks) {
 #endif
 
 extern "C" int bpm_gemm_grouped(int dtype, int variant, const bpm_gemm_problem* probs, int nprob, uint64_t seed, void* stream) {
-    if (nprob < 1 || nprob > BPM_GEMM_MAX_GROUP || !probs) return BPM_ERR_ARG;
-    if (variant != BPM_GEMM_NT && variant != BPM_GEMM_NN && variant != BPM_GEMM_TN) return BPM_ERR_ARG;
-    // BPM_BF16X3: A / B are split-bf16 images (bpm_split_rows: lda / ldb span the hi and the lo plane), K / M / N are those
-    // of the fp32 product, CT outputs and the gate operand are fp32; only the LDS-DMA kernel computes it
-    const bool x3 = dtype == BPM_BF16X3;
-    if (dtype != BPM_F32 && dtype != BPM_BF16 && !x3) return BPM_ERR_ARG;
-    const int sz = dtype == BPM_F32 ? 4 : 2;
-    const bool xk = variant != BPM_GEMM_TN, yk = variant == BPM_GEMM_NT;
-    // hardware-bounded loader: every problem promises zero k padding, k-contiguous rows are whole k stages and the
-    // matrices fit 31-bit byte offsets
-    bool fast = true, overlap = false;
-    for (int i = 0; i < nprob && fast; ++i) {
-        const bpm_gemm_problem& q = probs[i];
-        const int stage_b = 64 * (variant == BPM_GEMM_NT ? KS_FWD : 1);
-        const bool aov = (q.flags & BPM_GEMM_A_OVERLAP) != 0, bov = (q.flags & BPM_GEMM_B_OVERLAP) != 0;
-        overlap = overlap || aov || bov;
-        fast = (q.flags & BPM_GEMM_KPAD_ZERO) != 0;
-        // overlapping rows: no zero padding behind a row (the next window starts there), so k must end on a stage
-        if (xk) fast = fast && (aov ? q.K % 64 == 0 : ((long)q.lda * sz) % stage_b == 0 && (long)q.K <= q.lda);
-        if (yk) fast = fast && (bov ? q.K % 64 == 0 : ((long)q.ldb * sz) % stage_b == 0 && (long)q.K <= q.ldb);
-        const long bx = ((long)(xk ? q.M : q.K) - 1) * q.lda * sz + (long)(aov ? (xk ? q.K : q.M) : q.lda) * sz;
-        const long by = ((long)(yk ? q.N : q.K) - 1) * q.ldb * sz + (long)(bov ? (yk ? q.K : q.N) : q.ldb) * sz;
-        fast = fast && bx < (1l << 31) - 65536 && by < (1l << 31) - 65536;
-    }
-    if (overlap && !fast) return BPM_ERR_ARG;      // only the hardware-bounded loaders address overlapping rows
-    // LDS-DMA kernel (gemm_dma.h): bf16, no split-K, k-contiguous operands hold whole 128-byte stages inside their
-    // zero-padded rows, epilogue 4-wide.  Measured on MI355X at hidden 768, six problems of 4096 rows per launch
-    // (tools/gemm_lab.py, us, register-staged 128 x 64 kernel -> the configuration chosen below): q 84 -> 55, k/v 154 ->
-    // 103, out 80 -> 55, fc1 267 -> 156, fc2 245 -> 124, d(fc2) 314 -> 181, d(fc1) 185 -> 110, d(out) 82 -> 55, d(q) 63 ->
-    // 47, d(k/v) 135 -> 107, FFN weight gradients 445 -> 322 (8 waves of 128 x 64); the attention weight gradients
-    // (768 x 768 x 4096: nine 256 x 256 tiles per problem) stay on the 128 x 64 kernel (154 against 186).
-    int dma = -1;
-    if ((dtype == BPM_BF16 || x3) && fast && (g_force_dma != -2 || x3)) {
-        bool legal = true, big = true;
-        long tiles_tn = 0;
-        for (int i = 0; i < nprob && legal; ++i) {
-            const bpm_gemm_problem& q = probs[i];
-            const long kceil = ((long)q.K + DK - 1) / DK * DK;
-            legal = q.splitk <= 1 && !(q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_BATCHED)) && (!xk || (q.flags & BPM_GEMM_A_OVERLAP) || kceil <= q.lda) &&
-                    (!yk || (q.flags & BPM_GEMM_B_OVERLAP) || kceil <= q.ldb);
-            if (x3) {       // a plane (half the leading dimension) holds whole k stages / whole 128-column sub-images, no overlap
-                const long pa = q.lda / 2, pb = q.ldb / 2, m128 = ((long)q.M + 127) / 128 * 128, n128 = ((long)q.N + 127) / 128 * 128;
-                legal = legal && !(q.flags & (BPM_GEMM_A_OVERLAP | BPM_GEMM_B_OVERLAP)) && (q.lda & 1) == 0 && (q.ldb & 1) == 0 &&
-                        (xk ? kceil <= pa : m128 <= pa) && (yk ? kceil <= pb : n128 <= pb) && (pa * 2) % 16 == 0 && (pb * 2) % 16 == 0;
-            }
-            // its epilogue is the 4-wide one only (epi_fast_ok, evaluated here on the host)
-            const uintptr_t al = (uintptr_t)q.bias_n | (uintptr_t)q.resid | (uintptr_t)q.C | (uintptr_t)q.gate;
-            legal = legal && (q.N & 3) == 0 && (al & 15) == 0 && ((q.ldr | q.ldc | q.ldg) & 3) == 0 && !q.bias_m &&
-                    !(q.resid && (q.flags & BPM_GEMM_ACCUM));
-            const long tm = (q.M + 255) / 256, tn = (q.N + 255) / 256;
-            big = big && q.M >= 256 && q.N >= 256 && q.K >= 256 &&
-                  (double)q.M * q.N >= 0.8 * (double)(tm * 256) * (double)(tn * 256);
-            tiles_tn += tm * tn;
-        }
-        // weight gradients: one 256 x 256 tile per CU only pays when most CUs get one (measured, 768 x 768 x 4096 problems
-        // with bias column sums: 24 problems = 216 tiles 227 -> 181 us, 18 = 162 tiles 169 -> 156, 12 = 108 tiles 114 -> ~150)
-        if (variant == BPM_GEMM_TN && tiles_tn * 8 < num_cus() * 5 && !x3) big = false;
-        // products whose columns fill 128-wide tiles but not 256-wide ones (hidden 300: 300 / 384 against 300 / 512): the
-        // two-resident 256 x 128 configuration instead of the 128 x 64 kernel (lab switch BPMULT_NARROW_DMA=0)
-        static const bool narrow_ok = !(std::getenv("BPMULT_NARROW_DMA") && std::atoi(std::getenv("BPMULT_NARROW_DMA")) == 0);
-        bool narrow = narrow_ok && legal && !big && !x3 && variant != BPM_GEMM_TN;
-        long tiles_narrow = 0;
-        for (int i = 0; i < nprob && narrow; ++i) {
-            const bpm_gemm_problem& q = probs[i];
-            const long tm = (q.M + 255) / 256, tn = (q.N + 127) / 128;
-            narrow = q.M >= 256 && q.N >= 128 && q.K >= 256 && (double)q.M * q.N >= 0.75 * (double)(tm * 256) * (double)(tn * 128);
-            tiles_narrow += tm * tn;
-        }
-        narrow = narrow && tiles_narrow >= num_cus();
-        if (x3 && !legal) return BPM_ERR_ARG;
-        if (x3) big = true;                       // the caller (ops.gemm_grouped) sends what bpm_gemm_x3_eligible accepted
-        if (legal && g_force_dma >= 0 && !x3) dma = g_force_dma == CFG_TALL && variant == BPM_GEMM_TN ? -1 : g_force_dma;
-        else if (legal && big) {
-            dma = variant == BPM_GEMM_TN ? 2 : 3;
-            // Two resident workgroups per CU (256 x 128 tiles, 32-k stages; gemm_dma.h) where they measured faster than the
-            // one-per-CU tiles (tools/gemm_lab.py, hidden 768, six problems of 4096 rows): the FFN weight gradients
-            // 328 -> 279 us (their k loop is LDS-fill bound: a second workgroup's loads and a third stage fill the gaps);
-            // twelve-problem K / V projections 104 -> 94.  Not for weight gradients that carry the bias column sums (the
-            // extra accumulators spill at 128 registers: 156 -> 253 us) nor for the N = 768 products, where 320 x 256 tiles
-            // fit one round (q 55 -> 59, fc2 124 -> 178).  Inside the step (bench.py, hidden 768, ms per step; BPMULT_TWO_MASK
-            // is the lab switch for these classes): none 19.97-20.03, weight gradients + K / V 19.65-19.82, + fc1 (N >= 2048
-            // forward products) 19.44, + d(fc2) 19.54-19.80, every N = 768 product 20.22.
-            bool xs_any = false;
-            long kmin = 1l << 30, kmax = 0, nmax = 0, mmax = 0;
-            for (int i = 0; i < nprob; ++i) {
-                xs_any = xs_any || probs[i].colsum_a != nullptr;
-                kmin = probs[i].K < kmin ? probs[i].K : kmin;
-                kmax = probs[i].K > kmax ? probs[i].K : kmax;
-                nmax = probs[i].N > nmax ? probs[i].N : nmax;
-                mmax = probs[i].M > mmax ? probs[i].M : mmax;
-            }
-            static const int two_mask = std::getenv("BPMULT_TWO_MASK") ? std::atoi(std::getenv("BPMULT_TWO_MASK")) : 7;
-            // (hidden 1536, `bench.py --config cfg5`: the weight-gradient and fc1 classes each cost 1 % there -- 70.7 -> 71.4 / 71.6
-            // ms -- so they are tied to hidden <= 1024: weight gradients of at most 1024 rows, forward products of K <= 1024)
-            const bool two_tn = (two_mask & 1) && variant == BPM_GEMM_TN && !xs_any && kmin >= 1024 && mmax <= 1024 && !x3;
-            bool two_kv = (two_mask & 2) && variant == BPM_GEMM_NT && nprob >= 12 && nmax <= 1024 && !x3;
-            if ((two_mask & 4) && variant == BPM_GEMM_NT && nmax >= 2048 && kmax <= 1024 && !x3) two_kv = true;          // fc1
-            if ((two_mask & 8) && variant == BPM_GEMM_NN && nmax >= 2048 && !x3) two_kv = true;          // d(fc2)
-            if ((two_mask & 16) && variant == BPM_GEMM_TN && xs_any && !x3) two_kv = true;               // attention weight gradients
-            if ((two_mask & 32) && variant != BPM_GEMM_TN && nmax <= 1024 && !x3) two_kv = true;         // every N = 768 product
-            if (variant != BPM_GEMM_TN) {
-                // One workgroup per CU: a launch takes ceil(tiles / CUs) rounds of one tile each, and at the model's
-                // shapes the tile count sits just above a multiple of the CU count (six problems of 4096 x 768 are 288
-                // tiles of 256 x 256: a second round for 32 of them).  320-row tiles (13 instead of 16 per 4096 rows: 234
-                // tiles, one round of 1.25x the work) win whenever they save a round; per flop the 16-wave 256-row
-                // kernel is ~5 % faster.
-                const long ncu = num_cus();
-                long t256 = 0, t320 = 0;
-                for (int i = 0; i < nprob; ++i) {
-                    const long tn = (probs[i].N + 255) / 256;
-                    t256 += (probs[i].M + 255) / 256 * tn;
-                    t320 += (probs[i].M + 319) / 320 * tn;
-                }
-                const long r256 = (t256 + ncu - 1) / ncu, r320 = (t320 + ncu - 1) / ncu;
-                if (r320 * 320 * 21 < r256 * 256 * 20) dma = CFG_TALL;
-            }
-            if (two_tn || two_kv) dma = CFG_TWO;
-        } else if (narrow) dma = CFG_TWO;
-    }
-    // at most 16 rows per problem (level-2 query side under dead-row elimination): the skinny kernel (see there)
-    bool skinny = dma < 0 && !x3 && variant != BPM_GEMM_TN && fast;
-    for (int i = 0; i < nprob && skinny; ++i) {
-        const bpm_gemm_problem& q = probs[i];
-        skinny = q.M <= 16 && q.splitk <= 1 && !(q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_A_OVERLAP | BPM_GEMM_B_OVERLAP | BPM_GEMM_BATCHED)) &&
-                 ((long)q.lda * sz) % 64 == 0 && (variant != BPM_GEMM_NT || ((long)q.ldb * sz) % 64 == 0);
-    }
-    // under-filled weight-gradient launches (fewer than two 128-row workgroups per CU) run 64-row workgroups:
-    // measured 98 -> 77 us for the 24 attention weight gradients of a layer (360 -> 600 workgroups)
-    int bm_tile = BM, bn_tile = BN;
-    if (skinny) { bm_tile = 16; bn_tile = 64; }
-    if (dma >= 0) { bm_tile = DMA_CFGS[dma].bm; bn_tile = DMA_CFGS[dma].bn; }
-    else if (variant == BPM_GEMM_TN && fast && BM == 128) {
-        long t128 = 0;
-        for (int i = 0; i < nprob; ++i)
-            t128 += (long)((probs[i].M + BM - 1) / BM) * ((probs[i].N + BN - 1) / BN) * (probs[i].splitk > 1 ? probs[i].splitk : 1);
-        if (t128 < 2 * 256) bm_tile = 64;
-    }
+    GroupShape shape;
+    Choice c;
     Group g;
-    g.seedp = bpm_seed_ptr(seed);
-    g.nprob = nprob;
-    int tile = 0;
-    for (int i = 0; i < nprob; ++i) {
-        const bpm_gemm_problem& q = probs[i];
-        Prob& p = g.p[i];
-        if (q.M < 1 || q.N < 1 || q.K < 1 || !q.A || !q.B || !q.C) return BPM_ERR_ARG;
-        // operand leading dims must keep every row 16-byte aligned
-        if ((q.lda * sz) % 16 || (q.ldb * sz) % 16) return BPM_ERR_ALIGN;
-        if (((uintptr_t)q.A | (uintptr_t)q.B) & 15) return BPM_ERR_ALIGN;
-        p.X = (const char*)q.A; p.Y = (const char*)q.B; p.C = (char*)q.C;
-        p.M = q.M; p.N = q.N; p.K = q.K;
-        p.ldx = q.lda; p.ldy = q.ldb; p.ldc = q.ldc;
-        p.bias_n = q.bias_n; p.bias_m = q.bias_m;
-        p.resid = q.resid; p.ldr = q.ldr;
-        p.gate = (const char*)q.gate; p.ldg = q.ldg; p.gate_scale = q.gate_scale;
-        p.alpha = q.alpha;
-        p.drop = bpm_make_drop(q.drop_p, seed, q.drop_site);
-        p.colsum = q.colsum;
-        p.colsum_x = q.colsum_a;
-        if (q.colsum_a && (variant != BPM_GEMM_TN || q.splitk > 1)) return BPM_ERR_ARG;
-        p.flags = q.flags; p.out_kind = q.out_kind;
-        p.hB = q.heads_B; p.hH = q.heads_H; p.hT = q.heads_T; p.hdh = q.heads_dh; p.hdhp = q.heads_dhp;
-        if (q.out_kind == BPM_OUT_HEADS && (q.heads_B < 1 || q.heads_dh < 1 || q.heads_H * q.heads_dh != q.N)) return BPM_ERR_ARG;
-        const int ntiles = (q.N + bn_tile - 1) / bn_tile;
-        if (q.out_kind == BPM_OUT_CT && !(q.flags & BPM_GEMM_CT_NARROW) && ntiles * bn_tile < q.ldc) return BPM_ERR_ARG;
-        p.tile0 = tile;
-        p.tiles_m = (q.M + bm_tile - 1) / bm_tile;
-        p.tiles_n = ntiles;
-        p.splitk = q.splitk > 1 ? q.splitk : 1;
-        if (p.splitk > 1 && !((q.flags & BPM_GEMM_ATOMIC) && q.out_kind == BPM_OUT_F32)) return BPM_ERR_ARG;
-        if (q.flags & BPM_GEMM_BATCHED) {
-            // `batch` independent products of one shape: operand / output i starts batch_stride_* elements behind i - 1.  The
-            // 128 x 64 kernel only; the batch index travels where the split-K slice does, the strides in the head fields
-            // (plain stores through the 4-wide epilogue, no side operands).
-            const uintptr_t al = (uintptr_t)q.C | (uintptr_t)q.bias_n;
-            if (x3 || dma >= 0 || skinny || q.batch < 1 || q.batch > 4096 || q.splitk > 1 || q.out_kind == BPM_OUT_HEADS || q.bias_m || q.resid ||
-                q.gate || q.colsum || q.colsum_a || q.drop_p != 0.f || (q.flags & (BPM_GEMM_ATOMIC | BPM_GEMM_ACCUM)) ||
-                (q.N & 3) || (q.ldc & 3) || (al & 15) || q.batch_stride_a < 0 || q.batch_stride_b < 0 || q.batch_stride_c < 0 ||
-                ((q.batch_stride_a * sz) & 15) || ((q.batch_stride_b * sz) & 15) || (q.batch_stride_c & 3))
-                return BPM_ERR_ARG;
-            p.splitk = q.batch;
-            p.hB = q.batch_stride_a; p.hH = q.batch_stride_b; p.hT = q.batch_stride_c;
-        }
-        tile += p.tiles_m * p.tiles_n * p.splitk;
-    }
-    g.total_tiles = tile;
+    if (const int err = plan_group(dtype, variant, probs, nprob, seed, 0, shape, c, g)) return err;
+    double flops, bytes;
+    work_estimate(dtype, probs, nprob, flops, bytes);
     hipStream_t s = (hipStream_t)stream;
-    double flops = 0, bytes = 0;
-    for (int i = 0; i < nprob; ++i) {
-        const bpm_gemm_problem& q = probs[i];
-        flops += 2.0 * q.M * (double)q.N * q.K * ((q.flags & BPM_GEMM_BATCHED) ? q.batch : 1);
-        // algorithmic HBM bytes: each operand once, the output once, each side operand of the epilogue once
-        const double mn = (double)q.M * q.N;
-        bytes += ((double)q.M + q.N) * q.K * sz + mn * (q.out_kind == BPM_OUT_F32 ? 4 : sz);
-        if (q.resid) bytes += mn * 4;
-        if (q.gate) bytes += mn * sz;
-        if (q.out_kind == BPM_OUT_F32 && (q.flags & BPM_GEMM_ACCUM)) bytes += mn * 4;
-    }
-    BpmProfScope prof((dma >= 0 ? BPM_K_GEMM_DMA_NT : BPM_K_GEMM_NT) + variant, s, flops, bytes);
-    if (x3 && dma < 0) return BPM_ERR_ARG;
-    if (dma >= 0) return launch_dma(dma, variant, g, s, x3);
-    if (skinny) {
-        dim3 grid(g.total_tiles), block(256);
-        if (dtype == BPM_BF16) {
-            if (variant == BPM_GEMM_NT) hipLaunchKernelGGL((gemm_skinny_kernel<bf16_t, true>), grid, block, 0, s, g);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<bf16_t, false>), grid, block, 0, s, g);
-        } else {
-            if (variant == BPM_GEMM_NT) hipLaunchKernelGGL((gemm_skinny_kernel<float, true>), grid, block, 0, s, g);
-            else hipLaunchKernelGGL((gemm_skinny_kernel<float, false>), grid, block, 0, s, g);
-        }
-        BPM_CHECK_LAUNCH();
-        return 0;
-    }
-    return dtype == BPM_BF16 ? launch<bf16_t>(variant, fast, bm_tile == 64, g, s)
-                             : launch<float>(variant, fast, bm_tile == 64, g, s);
+    BpmProfScope prof((is_dma(c.kernel) ? BPM_K_GEMM_DMA_NT : BPM_K_GEMM_NT) + variant, s, flops, bytes);
+    return dtype == BPM_F32 ? launch<float>(c, variant, shape.xs_any, g, s) : launch<bf16_t>(c, variant, shape.xs_any, g, s);
 }
