@@ -97,6 +97,26 @@ def test_error_strings_and_argument_validation(lib):
     assert lib.bpm_stream_create(1, None) == -1
     e = _lib.EmbedProblem()
     assert lib.bpm_embed_pos_bwd(C.byref(e), 1, 24, 1.0, 0, None) == -1
+    # a valid vector-path backward problem (made-up 16-byte aligned addresses: only rejected calls are made here, a call
+    # that passes validation launches): the workspace must hold 64 ticket words + 3 rows of d floats per block, 16-byte aligned
+    ln.x, ln.gamma, ln.mean, ln.rstd, ln.R = 0x10000, 0x20000, 0x30000, 0x40000, 8
+    ln.dy, ln.ldy, ln.dx, ln.dgamma, ln.dbeta = 0x50000, 768, 0x60000, 0x70000, 0x80000
+    assert lib.bpm_ln_bwd_ws_bytes(1, 768) >= (64 + 3 * 768) * 4
+    assert lib.bpm_ln_bwd_ws(_lib.BPM_BF16, C.byref(ln), 1, 768, 0, 0x90000, 256, None) == -1                 # ws_bytes too small
+    assert lib.bpm_ln_bwd_ws(_lib.BPM_BF16, C.byref(ln), 1, 768, 0, 0x90000, (64 + 3 * 768) * 4 - 1, None) == -1
+    assert lib.bpm_ln_bwd_ws(_lib.BPM_BF16, C.byref(ln), 1, 768, 0, 0x90004, 1 << 20, None) == -1             # ws misaligned
+    assert lib.bpm_ln_bwd_ws(2, C.byref(ln), 1, 768, 0, 0x90000, 1 << 20, None) == -1                         # BPM_BF16X3: GEMM only
+    ad = _lib.AddnProblem()
+    ad.out, ad.n_in, ad.count = 0x10000, 9, 16
+    for j in range(8):
+        ad.src[j] = 0x20000 + 0x1000 * j
+    assert lib.bpm_add_n(C.byref(ad), 1, None) == -1                                                          # n_in > BPM_ADDN_MAX
+    ad.n_in, ad.count = 2, 0
+    assert lib.bpm_add_n(C.byref(ad), 1, None) == -1                                                          # count 0
+    ad.count, ad.src[1] = 16, 0x21004
+    assert lib.bpm_add_n(C.byref(ad), 1, None) == -2                                                          # misaligned input
+    ad.src[1], ad.out = 0x21000, 0x10008
+    assert lib.bpm_add_n(C.byref(ad), 1, None) == -2                                                          # misaligned out
 
 
 def test_no_cpu_fallback():
