@@ -23,7 +23,7 @@ ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
               "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
 
-ABI_VERSION = 3                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
+ABI_VERSION = 4                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
 # that tools/gemm_lab.py, tools/attn_lab.py and three kernel tests use, the GEMM dispatcher's environment switches and its
 # decision query (bpm_debug_gemm_choice: tools/gemm_choice.py, tests/test_gemm_choice_cpu.py); never loaded by the product path
@@ -168,6 +168,10 @@ class AdamSeg(C.Structure):
                 ("rows", C.c_int), ("cols", C.c_int), ("dst_ld", C.c_int), ("pad_", C.c_int)]
 
 
+class SumsqSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("n", C.c_size_t), ("blk0", C.c_uint), ("pad_", C.c_uint)]
+
+
 class SplitProblem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("R", C.c_int), ("C", C.c_int), ("ld", C.c_int), ("ldp", C.c_int)]
 
@@ -269,6 +273,10 @@ SIGNATURES = {
     "bpm_adam_step": [_P, _P, _P, _P, C.c_size_t, _F, _F, _F, _F, _F, _I, _F, _I, _P],
     "bpm_adam_blocks": [C.c_size_t],
     "bpm_adam_step_table": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _I, _P],
+    "bpm_adam_step_table_clip": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P],
+    "bpm_grad_sumsq_blocks": [_P, C.c_size_t],
+    "bpm_grad_sumsq_ws_bytes": [C.c_uint],
+    "bpm_grad_sumsq": [_P, _I, C.c_uint, _F, _F, _P, _P, C.c_size_t, _P, _P],
     "bpm_stream_create": [_I, C.POINTER(C.c_void_p)],
     "bpm_stream_priority_range": [C.POINTER(_I), C.POINTER(_I)],
     "bpm_prof_enable": [C.c_uint],
@@ -294,7 +302,7 @@ def load(path: str) -> C.CDLL:
     for name, args in SIGNATURES.items():
         fn = getattr(L, name)            # AttributeError if the symbol is missing
         fn.argtypes = args
-        fn.restype = C.c_char_p if name == "bpm_error_string" else C.c_size_t if name == "bpm_ln_bwd_ws_bytes" else C.c_int
+        fn.restype = C.c_char_p if name == "bpm_error_string" else C.c_size_t if name.endswith("_ws_bytes") else C.c_int
     v = L.bpm_version()
     if v != ABI_VERSION:
         raise HipLibraryError(f"{path}: ABI version {v}, this package binds version {ABI_VERSION} (include/bpmult_hip.h): rebuild it")

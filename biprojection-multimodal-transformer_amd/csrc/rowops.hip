@@ -203,6 +203,90 @@ __global__ __launch_bounds__(NT) void zero_segments_kernel(const bpm_zero_desc* 
 }
 
 // ---------------------------------------------------------------------------
+// Global gradient norm: sum of squares over a list of fp32 segments (device-resident table), then the norm and torch's
+// clip coefficient, all left on the device (see bpm_grad_sumsq).  Bitwise reproducible: no float atomics, a fixed shape.
+//   block   : one 4096-element window of ONE segment.  Windows start at the 16-byte boundary at or below the segment's
+//             first element, so every quad of a window is aligned whatever the segment's start; a lane owns 4 quads
+//             (f32x4 loads, all issued before the first use).  The at most two quads that straddle the segment's ends
+//             (scalar head and tail) are read element-wise by the lane that owns them, elements outside count as 0.
+//   lane    : <= 16 squares, one fp32 fma chain;   block: 6 shuffle levels + 2 levels over the four waves (fp32);
+//   partial : one float per block into the workspace;  final launch (one block): the partials in fp64, every thread a
+//             fixed strided subset in index order, then a fixed tree.
+// Relative error of the sum of squares <= (1 + 16 + 8) * 2^-24 = 1.5e-6 (square, chain, tree; fp64 above adds nothing
+// visible), half of that under the root, plus the norm's own rounding to fp32.
+// ---------------------------------------------------------------------------
+constexpr int SSQ_ITER = 4;
+constexpr int SSQ_CHUNK = NT * 4 * SSQ_ITER;            // elements per block
+constexpr int SSQ_FINAL_NT = 1024;
+
+BPM_DEV unsigned ssq_lead(const float* p) { return (unsigned)(((uintptr_t)p >> 2) & 3); }      // elements past the 16-byte boundary
+
+__global__ __launch_bounds__(NT) void grad_sumsq_kernel(const bpm_sumsq_seg* __restrict__ tab, int nseg, float* __restrict__ partial) {
+    const bpm_sumsq_seg S = find_desc(tab, nseg, blockIdx.x);
+    const long long n = (long long)S.n;
+    const long long e0 = (long long)(blockIdx.x - S.blk0) * SSQ_CHUNK - ssq_lead(S.p);   // window start, as a segment index
+    f32x4 x[SSQ_ITER];
+#pragma unroll
+    for (int j = 0; j < SSQ_ITER; ++j) {
+        const long long e = e0 + 4 * (j * NT + (int)threadIdx.x);
+        x[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (e >= 0 && e + 4 <= n) {
+            x[j] = *(const f32x4*)(S.p + e);
+        } else if (e > -4 && e < n) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (e + q >= 0 && e + q < n) x[j][q] = S.p[e + q];
+        }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < SSQ_ITER; ++j)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s = fmaf(x[j][q], x[j][q], s);
+    s = wave_sum(s);
+    __shared__ float red[NT / 64];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// out[0] = grad_scale * sqrt(sum of the partials + *extra),  out[1] = min(1, max_norm / (out[0] + 1e-6))  (1 when !clip)
+__global__ __launch_bounds__(SSQ_FINAL_NT) void grad_sumsq_final_kernel(const float* partial, unsigned nblk, float grad_scale,
+                                                                        float max_norm, int clip, const float* extra, float* out) {
+    __shared__ double red[SSQ_FINAL_NT];
+    const unsigned nq = (nblk + 3) / 4;                    // the workspace is 16-byte aligned and sized in whole quads
+    double acc = 0.0;
+    for (unsigned q0 = threadIdx.x; q0 < nq; q0 += SSQ_FINAL_NT * 4) {
+        f32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned q = q0 + j * SSQ_FINAL_NT;
+            v[j] = q < nq ? ((const f32x4*)partial)[q] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned i = 4 * (q0 + j * SSQ_FINAL_NT);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i + e < nblk) acc += (double)v[j][e];  // (past nblk: the quad's unwritten remainder, or a quad not loaded)
+        }
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = SSQ_FINAL_NT / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double tot = red[0] + (extra ? (double)*extra : 0.0);
+        const float norm = (float)((double)grad_scale * sqrt(tot));
+        const float c = max_norm / (norm + 1e-6f);
+        out[0] = norm;
+        out[1] = !clip ? 1.f : c > 1.f ? 1.f : c;          // a NaN coefficient passes through, as torch's clamp lets it
+    }
+}
+
+// ---------------------------------------------------------------------------
 // embedding prologue (reference transformer.py:66-79, position_embedding.py:62-76)
 //   out = dropout(scale * x + table[pos]),  pos = t+1 if x[t,b,0] != 0 else 0
 // backward: dx (+)= scale * drop_mult * dy   (the positional term is detached)
@@ -919,11 +1003,15 @@ extern "C" int bpm_adam_step(float* param, float* grad, float* exp_avg, float* e
 constexpr int ADAM_ITER = 4;
 constexpr int ADAM_CHUNK = NT * ADAM_ITER;             // f32x4 per block
 
-template <typename CT>
+// DEVSCALE (bpm_adam_step_table_clip with a scale_dev): the gradient scale is gscale * (*scale_dev), one uniform read
+// per block of a value an earlier launch on the stream left on the device (the clip coefficient of bpm_grad_sumsq);
+// without it the pointer is not touched and the code is what bpm_adam_step_table has always launched.
+template <typename CT, bool DEVSCALE>
 __global__ __launch_bounds__(NT) void adam_table_kernel(const bpm_adam_seg* __restrict__ tab, int nseg, float* __restrict__ p,
                                                        float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                        float lr_c, float b1, float b2, float eps, float wd, float rsq_bc2,
-                                                       float gscale, int zero_grad) {
+                                                       float gscale, int zero_grad, const float* __restrict__ scale_dev) {
+    if constexpr (DEVSCALE) gscale *= *scale_dev;
     const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
     const size_t base = S.off4 + (size_t)(blockIdx.x - S.blk0) * ADAM_CHUNK;
     const size_t end = S.off4 + S.n4;
@@ -958,17 +1046,30 @@ __global__ __launch_bounds__(NT) void adam_table_kernel(const bpm_adam_seg* __re
 
 extern "C" int bpm_adam_blocks(size_t n4) { return (int)((n4 + ADAM_CHUNK - 1) / ADAM_CHUNK); }
 
+extern "C" int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
+                                        float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                        float weight_decay, int step, float grad_scale, const float* scale_dev, int zero_grad,
+                                        void* stream) {
+    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || step < 1) return BPM_ERR_ARG;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
+    if ((uintptr_t)scale_dev & 3) return BPM_ERR_ALIGN;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    const float lr_c = (float)(lr / bc1), rsq_bc2 = (float)(1.0 / sqrt(bc2));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, param, grad, exp_avg,
+                           exp_avg_sq, lr_c, beta1, beta2, eps, weight_decay, rsq_bc2, grad_scale, zero_grad, scale_dev);
+    };
+    if (dtype == BPM_BF16) scale_dev ? launch(adam_table_kernel<bf16_t, true>) : launch(adam_table_kernel<bf16_t, false>);
+    else scale_dev ? launch(adam_table_kernel<float, true>) : launch(adam_table_kernel<float, false>);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int bpm_adam_step_table(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
                                    float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                                    float weight_decay, int step, float grad_scale, int zero_grad, void* stream) {
-    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || step < 1) return BPM_ERR_ARG;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    BPM_DISPATCH_CT(dtype, adam_table_kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, param, grad,
-                    exp_avg, exp_avg_sq, (float)(lr / bc1), beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), grad_scale,
-                    zero_grad);
-    BPM_CHECK_LAUNCH();
-    return 0;
+    return bpm_adam_step_table_clip(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                                    weight_decay, step, grad_scale, nullptr, zero_grad, stream);
 }
 
 extern "C" int bpm_fold_bias(const bpm_fold_desc* table_dev, int ndesc, unsigned total_blocks, void* stream) {
@@ -990,6 +1091,24 @@ extern "C" int bpm_zero_segment_blocks(unsigned n) { return (int)((n + ZSEG - 1)
 extern "C" int bpm_zero_segments(const bpm_zero_desc* table_dev, int ndesc, unsigned total_blocks, void* stream) {
     if (!table_dev || ndesc < 1 || total_blocks < 1) return BPM_ERR_ARG;
     hipLaunchKernelGGL(zero_segments_kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, ndesc);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bpm_grad_sumsq_blocks(const float* p, size_t n) { return (int)(((((uintptr_t)p >> 2) & 3) + n + SSQ_CHUNK - 1) / SSQ_CHUNK); }
+
+extern "C" size_t bpm_grad_sumsq_ws_bytes(unsigned total_blocks) { return ((size_t)total_blocks + 3) / 4 * 16; }
+
+extern "C" int bpm_grad_sumsq(const bpm_sumsq_seg* table_dev, int nseg, unsigned total_blocks, float grad_scale, float max_norm,
+                              const float* extra_sumsq, void* ws, size_t ws_bytes, float* out, void* stream) {
+    if (!table_dev || nseg < 1 || total_blocks < 1 || !ws || !out) return BPM_ERR_ARG;
+    if (ws_bytes < bpm_grad_sumsq_ws_bytes(total_blocks)) return BPM_ERR_ARG;
+    if (((uintptr_t)ws & 15) || ((uintptr_t)out & 7) || ((uintptr_t)extra_sumsq & 3)) return BPM_ERR_ALIGN;
+    const int clip = max_norm > 0.f && max_norm < INFINITY;          // <= 0, +inf (and NaN): the norm only
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, (float*)ws);
+    BPM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(SSQ_FINAL_NT), 0, (hipStream_t)stream, (const float*)ws, total_blocks,
+                       grad_scale, max_norm, clip, extra_sumsq, out);
     BPM_CHECK_LAUNCH();
     return 0;
 }

@@ -125,6 +125,7 @@ class ParamStore:
         self._fold_table = None
         self.shadow_flat: Optional[torch.Tensor] = None
         self._table = None
+        self._norm_table = None                         # built by the first grad_sumsq()
         self._master_ptr = self.master.data_ptr()
 
     def __del__(self):
@@ -332,14 +333,54 @@ class ParamStore:
         self._adam_table = (ops.device_table(out), len(out), blk)
         self._adam_plain = plain
 
+    def _build_norm_table(self) -> None:
+        """Segment table of the gradient-norm reduction (bpm_grad_sumsq), its workspace and its 2-float result, all
+        allocated once (stable addresses).  The segments are the exact element ranges of the TRAINABLE parameters in
+        gflat, merged where one ends where the next begins: the alignment padding between parameters is left out (nothing
+        promises that a gradient launch never writes there), and so is a frozen parameter's slice, which the backward
+        launches still fill.  Built at the first use, from requires_grad as it is then -- FusedAdam fixes its parameter
+        list the same way -- so a store that never clips or reads the norm allocates nothing."""
+        segs: List[List[int]] = []
+        for n in self.names:
+            p = self.params[n]
+            if not p.requires_grad:
+                continue
+            a, b = self.off[n], self.off[n] + p.numel()
+            if segs and segs[-1][1] == a:
+                segs[-1][1] = b
+            else:
+                segs.append([a, b])
+        if not segs:
+            raise RuntimeError("gradient norm: no trainable parameter in the flat buffers")
+        base = self.gflat.data_ptr()
+        self._norm_table = ops.sumsq_table([(base + 4 * a, b - a) for a, b in segs])
+        self._norm_ws = torch.empty(ops.grad_sumsq_ws_bytes(self._norm_table[2]) // 4, device=self.device, dtype=torch.float32)
+        self._norm_out = torch.zeros(2, device=self.device, dtype=torch.float32)
+
+    def grad_sumsq(self, grad_scale: float = 1.0, max_norm: float = 0.0, extra_sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The global gradient norm without leaving the device: one reduction over the trainable parameters' slices of
+        gflat (+ a tiny fixed-order sum).  Returns the store's persistent result [total_norm, coef]:
+        total_norm = grad_scale * sqrt(sum of squares + extra_sumsq), coef = min(1, max_norm / (total_norm + 1e-6)), or 1
+        when max_norm <= 0 (the norm only).  The next call overwrites it."""
+        if self._norm_table is None:
+            self._build_norm_table()
+        tab, nseg, nblk = self._norm_table
+        ops.grad_sumsq(tab, nseg, nblk, self._norm_ws, self._norm_out, grad_scale, max_norm, extra_sumsq)
+        return self._norm_out
+
     def adam_step(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                  zero_grad: bool) -> None:
+                  zero_grad: bool, scale_dev: Optional[torch.Tensor] = None) -> None:
         """One launch: torch.optim.Adam's update of every trunk parameter (flat master / gradient / moments) AND the CT
         shadows of the plain weight matrices, written from the updated values as they are stored.  What is left for the
-        next forward's refresh_shadows is the small rest (K / V weights with the LayerNorm gain folded in, folded biases)."""
+        next forward's refresh_shadows is the small rest (K / V weights with the LayerNorm gain folded in, folded biases).
+        scale_dev: one device float multiplied into grad_scale by the kernel (the clip coefficient of grad_sumsq)."""
         tab, nseg, nblk = self._adam_table
-        ops.adam_step_table(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
-                            weight_decay, step, grad_scale, zero_grad)
+        if scale_dev is None:
+            ops.adam_step_table(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                                weight_decay, step, grad_scale, zero_grad)
+        else:
+            ops.adam_step_table_clip(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, lr, beta1, beta2,
+                                     eps, weight_decay, step, grad_scale, scale_dev, zero_grad)
         # every plain shadow now holds the CT image of its updated master (whatever was pending before the step); the rest
         # (shadows that mix parameters, folded biases) is stale until the next refresh_shadows
         self._dirty, self._dirty_rest, self._shadow_sig = False, True, self._versions()

@@ -378,6 +378,53 @@ def adam_step_table(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_avg
                "bpm_adam_step_table")
 
 
+def adam_step_table_clip(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
+                         grad_scale, scale_dev, zero_grad) -> None:
+    """adam_step_table with the gradient scale grad_scale * scale_dev[0] (a device float, e.g. grad_sumsq's coefficient)."""
+    for t in (master, grad, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != master.numel():
+            raise ValueError("adam_step_table_clip: flat contiguous float32 buffers of one size")
+    if scale_dev is not None and (scale_dev.dtype != torch.float32 or scale_dev.numel() < 1):
+        raise ValueError("adam_step_table_clip: scale_dev is a float32 device tensor")
+    _lib.check(_lib.lib().bpm_adam_step_table_clip(dtype, table_dev.data_ptr(), nseg, nblk, _p(master), _p(grad), _p(exp_avg),
+                                                   _p(exp_avg_sq), lr, beta1, beta2, eps, weight_decay, step, grad_scale,
+                                                   _p(scale_dev), int(bool(zero_grad)), _stream()),
+               "bpm_adam_step_table_clip")
+
+
+def grad_sumsq_blocks(ptr: int, n: int) -> int:
+    return int(_lib.lib().bpm_grad_sumsq_blocks(ptr, n)) if not _DRY_RUN else ((ptr >> 2 & 3) + n + 4095) // 4096
+
+
+def sumsq_table(segments):
+    """[(device address, element count)] -> (device table, nseg, total blocks) for grad_sumsq."""
+    descs, blk = [], 0
+    for ptr, n in segments:
+        if n < 1 or ptr % 4:
+            raise ValueError("sumsq_table: segments of at least one float at 4-byte aligned addresses")
+        sg = _lib.SumsqSeg()
+        sg.p, sg.n, sg.blk0 = ptr, n, blk
+        blk += grad_sumsq_blocks(ptr, n)
+        descs.append(sg)
+    return device_table(descs), len(descs), blk
+
+
+def grad_sumsq_ws_bytes(total_blocks: int) -> int:
+    return int(_lib.lib().bpm_grad_sumsq_ws_bytes(total_blocks))
+
+
+def grad_sumsq(table_dev: torch.Tensor, nseg: int, total_blocks: int, ws: torch.Tensor, out: torch.Tensor, grad_scale: float = 1.0,
+               max_norm: float = 0.0, extra_sumsq: Optional[torch.Tensor] = None) -> None:
+    """out[0] = grad_scale * sqrt(sum of squares over the table + extra_sumsq), out[1] = torch's clip coefficient for
+    max_norm (1 when max_norm <= 0 or inf); nothing leaves the device."""
+    if out.dtype != torch.float32 or out.numel() < 2 or not out.is_contiguous():
+        raise ValueError("grad_sumsq: out is a contiguous float32 tensor of two elements")
+    if extra_sumsq is not None and (extra_sumsq.dtype != torch.float32 or extra_sumsq.numel() != 1):
+        raise ValueError("grad_sumsq: extra_sumsq is one float32 device value")
+    _lib.check(_lib.lib().bpm_grad_sumsq(table_dev.data_ptr(), nseg, total_blocks, grad_scale, max_norm, _p(extra_sumsq), _p(ws),
+                                         ws.numel() * ws.element_size(), _p(out), _stream()), "bpm_grad_sumsq")
+
+
 def fold_bias(table_dev: torch.Tensor, ndesc: int, total_blocks: int) -> None:
     _lib.check(_lib.lib().bpm_fold_bias(table_dev.data_ptr(), ndesc, total_blocks, _stream()), "bpm_fold_bias")
 

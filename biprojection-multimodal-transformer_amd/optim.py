@@ -9,10 +9,16 @@ outside the trunk (final GMU, head, front-ends) go through an ordinary torch.opt
 
 `FusedAdam` IS a `torch.optim.Optimizer` (one param group holding every model parameter), so LR schedulers and the
 reference's checkpoint code accept it; `param_groups[0]["lr"]` is read at every step.
+
+Global-norm gradient clipping (`max_grad_norm`; upstream MulT calls `torch.nn.utils.clip_grad_norm_(model.parameters(), 0.8)`
+before `optimizer.step()`) is part of the step: one reduction over the flat gradient buffer (`bpm_grad_sumsq`) leaves the
+norm and the clip coefficient on the device, and the Adam kernel multiplies the coefficient into the gradients as it reads
+them -- no second pass over the gradients, no host sync, no per-tensor loop.  `grad_norm(model)` is the readout alone.
 """
 from __future__ import annotations
 
-from typing import Optional
+import math
+from typing import List, Optional
 
 import torch
 
@@ -25,13 +31,23 @@ class FusedAdam(torch.optim.Optimizer):
     Differences from torch.optim.Adam, all deliberate: trunk parameters that never receive a gradient keep a zero
     gradient instead of `None` (their update is exactly zero unless weight_decay > 0); `zero_grad()` clears the flat
     gradient buffer in place (fused into the step when `fused_zero_grad=True`); the moments are two flat buffers
-    (`state_dict()["flat"]`), not per-parameter tensors."""
+    (`state_dict()["flat"]`), not per-parameter tensors.
+
+    `max_grad_norm=c` clips the global gradient norm to c inside the step, as `torch.nn.utils.clip_grad_norm_(
+    model.parameters(), c)` in front of it would (norm over the parameters of `param_groups[0]`, coefficient
+    min(1, c / (norm + 1e-6)), a non-finite norm propagates as with error_if_nonfinite=False).  `grad_scale` (GradSync's
+    1 / world_size) acts BEFORE the clip: after a sum all-reduce the norm is that of the averaged gradient, the same on
+    every rank.  The value lives in `param_groups[0]["max_grad_norm"]` (None: off) and travels with `state_dict()`.
+    `last_grad_norm`: the norm before clipping of the latest clipped step, a 0-dim fp32 DEVICE tensor (None until then);
+    reading it is the caller's sync -- `step()` itself never waits for the device."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fused_zero_grad: bool = False):
+                 fused_zero_grad: bool = False, max_grad_norm: Optional[float] = None):
+        _check_max_norm(max_grad_norm)
         params = [p for p in model.parameters() if p.requires_grad]
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self.model = model
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.fused_zero_grad = fused_zero_grad
         self.step_count = 0
         self.pending_grad_scale: Optional[float] = None      # set by distributed.GradSync.finish(): 1 / world_size
@@ -79,15 +95,29 @@ class FusedAdam(torch.optim.Optimizer):
         n = st.master.numel()
         if n % 4:
             raise RuntimeError("flat parameter buffer is not a multiple of 4 elements")
+        clip = g.get("max_grad_norm")
+        tail = self._tail_opt.param_groups[0]["params"] if self._tail_opt is not None else []
+        coef = None
+        if clip is not None:
+            # the trunk's share: one reduction over gflat; the tail's (PyTorch-owned parameters) through torch; one root.
+            # Norm and coefficient stay on the device: the Adam kernel and the tail multiply read them there.
+            _check_max_norm(clip)
+            tail_grads = [p.grad for p in tail if p.grad is not None]
+            res = st.grad_sumsq(grad_scale, float(clip), _sumsq(tail_grads))
+            self.last_grad_norm = res[0].clone()
+            coef = res[1:2]
         # one launch: the update of every trunk parameter AND the CT shadows of the plain weight matrices, written from
         # the updated masters as they are stored (no second pass over the flat master for the next forward's operands)
         st.adam_step(self._m, self._v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count,
-                     grad_scale, self.fused_zero_grad)
+                     grad_scale, self.fused_zero_grad, scale_dev=coef)
         if self._tail_opt is not None:
             for tg in self._tail_opt.param_groups:
                 tg["lr"], tg["betas"], tg["eps"], tg["weight_decay"] = g["lr"], g["betas"], g["eps"], g["weight_decay"]
-            if grad_scale != 1.0:
-                for p in self._tail_opt.param_groups[0]["params"]:
+            if coef is not None:
+                if tail_grads:
+                    torch._foreach_mul_(tail_grads, coef[0] * grad_scale)      # grad_scale and the clip in one multiply
+            elif grad_scale != 1.0:
+                for p in tail:
                     if p.grad is not None:
                         p.grad.mul_(grad_scale)
             self._tail_opt.step()
@@ -112,3 +142,31 @@ class FusedAdam(torch.optim.Optimizer):
             self.model.dropout_step = int(sd.get("dropout_step", 0))
         for k, v in sd["param_groups"][0].items():
             self.param_groups[0][k] = tuple(v) if k == "betas" else v
+
+
+def _check_max_norm(x) -> None:
+    if x is None:
+        return
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x <= 0:
+        raise ValueError(f"max_grad_norm must be None or a finite number above 0, got {x!r}")
+
+
+def _sumsq(grads: List[torch.Tensor]) -> Optional[torch.Tensor]:
+    """Sum of squares of a list of gradients as one fp32 device scalar (None for an empty list), the way
+    torch.nn.utils.clip_grad_norm_ takes it: per-tensor 2-norms (torch._foreach_norm), then their squares summed."""
+    if not grads:
+        return None
+    return torch.stack(torch._foreach_norm(grads)).float().square().sum().reshape(1)
+
+
+@torch.no_grad()
+def grad_norm(model, grad_scale: float = 1.0) -> torch.Tensor:
+    """Global 2-norm of the model's gradients times grad_scale, as a 0-dim fp32 device tensor: what
+    `torch.nn.utils.clip_grad_norm_(model.parameters(), inf)` would return, without its per-tensor loop over the trunk
+    (one reduction over the flat gradient buffer; the few tail parameters through torch) and without a host sync.
+    Modifies nothing: for logging in loops that keep their own optimizer.  RuntimeError before the first backward."""
+    st = model._ensure_store()
+    tail = [p.grad for n, p in model.named_parameters() if n not in st.params and p.requires_grad and p.grad is not None]
+    if st._fresh():                                        # the flat gradient buffer holds nothing current
+        raise RuntimeError("grad_norm: no gradients yet (call backward first)")
+    return st.grad_sumsq(float(grad_scale), 0.0, _sumsq(tail))[0].clone()

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define BPM_ABI_VERSION 3
+#define BPM_ABI_VERSION 4
 #define BPM_SEED_INDIRECT (1ull << 63) /* seed = BPM_SEED_INDIRECT | (uintptr_t)device pointer to the uint64 seed */
 #define BPM_MAX_GROUP 18 /* problems per grouped launch (6 encoders of a level x 3 projections) */
 #define BPM_GEMM_MAX_GROUP 24 /* bpm_gemm_grouped alone: 6 encoders x (q, k, v, out) weight gradients in one launch */
@@ -430,6 +430,39 @@ int bpm_adam_blocks(size_t n4);
 int bpm_adam_step_table(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
                         float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay,
                         int step, float grad_scale, int zero_grad, void* stream);
+
+/* Global gradient norm and clip coefficient, left ON THE DEVICE.  Together with bpm_adam_step_table_clip this replaces
+ * torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm), which upstream MulT calls between backward() and
+ * optimizer.step(): a foreach norm and a foreach multiply over ~1700 gradient views that read and then rewrite the whole
+ * flat gradient buffer, and a host sync when the norm is logged.  Here the gradients are read once and not rewritten:
+ * the optimizer kernel applies the coefficient as it reads them.
+ * The table (device memory, built once) lists fp32 segments: p = first element (any 4-byte aligned address), n >= 1
+ * elements, blk0 = first block; a segment takes bpm_grad_sumsq_blocks(p, n) blocks (it depends on p's offset inside its
+ * 16-byte line), entries sorted by blk0.  ws: bpm_grad_sumsq_ws_bytes(total_blocks) bytes, 16-byte aligned, contents
+ * irrelevant before and after (one partial sum per block; no state is kept between calls).  Two launches on `stream`.
+ *   out[0] = total_norm = grad_scale * sqrt(sum of squares over the table + *extra_sumsq)
+ *   out[1] = coef = min(1, max_norm / (total_norm + 1e-6))        (torch's formula; NaN propagates)
+ * max_norm <= 0 or +inf: the norm only, coef = 1.  extra_sumsq: NULL, or a device float holding a sum of squares taken
+ * elsewhere (parameters outside the flat buffer), added under the root.  out: 2 floats, 8-byte aligned.
+ * Bitwise reproducible (no float atomics): <= 16 squares per lane and an 8-level tree per block in fp32, one partial per
+ * block, the partials summed in a fixed order in fp64 -- relative error of the norm <= 13 * 2^-24 + one fp32 rounding. */
+typedef struct bpm_sumsq_seg {
+    const float* p;
+    size_t n;
+    unsigned blk0;
+    unsigned pad_;
+} bpm_sumsq_seg;
+int bpm_grad_sumsq_blocks(const float* p, size_t n);
+size_t bpm_grad_sumsq_ws_bytes(unsigned total_blocks);
+int bpm_grad_sumsq(const bpm_sumsq_seg* table_dev, int nseg, unsigned total_blocks, float grad_scale, float max_norm,
+                   const float* extra_sumsq, void* ws, size_t ws_bytes, float* out, void* stream);
+
+/* bpm_adam_step_table with the gradient scale grad_scale * (*scale_dev): scale_dev is a device float written by an earlier
+ * launch on the stream (out + 1 of bpm_grad_sumsq: the clip coefficient), read once per block.  scale_dev = NULL is
+ * bpm_adam_step_table itself (the same kernel); *scale_dev == 1 gives bit-equal results. */
+int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
+                             float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay,
+                             int step, float grad_scale, const float* scale_dev, int zero_grad, void* stream);
 
 /* Engine plumbing (no reference counterpart): a non-blocking HIP stream at the device's lowest priority
  * (low_priority != 0) or at the default priority.  The host engine puts weight-gradient GEMMs and the
