@@ -23,7 +23,7 @@ ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
               "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
 
-ABI_VERSION = 4                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
+ABI_VERSION = 5                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
 # that tools/gemm_lab.py, tools/attn_lab.py and three kernel tests use, the GEMM dispatcher's environment switches and its
 # decision query (bpm_debug_gemm_choice: tools/gemm_choice.py, tests/test_gemm_choice_cpu.py); never loaded by the product path
@@ -38,6 +38,7 @@ LN_OUT_F32 = 2
 MAX_GROUP = 18
 SEED_INDIRECT = 1 << 63          # seed = SEED_INDIRECT | device address of a uint64 (include/bpmult_hip.h)
 GEMM_MAX_GROUP = 24
+ADAM_MAX_GROUPS = 16             # == BPM_ADAM_MAX_GROUPS
 
 
 def build(force: bool = False, verbose: bool = False, out: str | None = None, flags: tuple = (), objdir: str | None = None) -> str:
@@ -165,7 +166,12 @@ class ZeroDesc(C.Structure):
 
 class AdamSeg(C.Structure):
     _fields_ = [("off4", C.c_size_t), ("n4", C.c_uint), ("blk0", C.c_uint), ("dst", C.c_void_p),
-                ("rows", C.c_int), ("cols", C.c_int), ("dst_ld", C.c_int), ("pad_", C.c_int)]
+                ("rows", C.c_int), ("cols", C.c_int), ("dst_ld", C.c_int), ("group", C.c_int)]
+
+
+class AdamGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int), ("step", C.c_int), ("pad_", C.c_int)]
 
 
 class SumsqSeg(C.Structure):
@@ -274,6 +280,7 @@ SIGNATURES = {
     "bpm_adam_blocks": [C.c_size_t],
     "bpm_adam_step_table": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _I, _P],
     "bpm_adam_step_table_clip": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P],
+    "bpm_adam_step_groups": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, C.POINTER(AdamGroup), _I, _F, _P, _P, _P, _P, _I, _P],
     "bpm_grad_sumsq_blocks": [_P, C.c_size_t],
     "bpm_grad_sumsq_ws_bytes": [C.c_uint],
     "bpm_grad_sumsq": [_P, _I, C.c_uint, _F, _F, _P, _P, C.c_size_t, _P, _P],

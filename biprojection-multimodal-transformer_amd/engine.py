@@ -126,6 +126,7 @@ class ParamStore:
         self.shadow_flat: Optional[torch.Tensor] = None
         self._table = None
         self._norm_table = None                         # built by the first grad_sumsq()
+        self._norm_set = None                           # (names, table, workspace, result) of the first grad_sumsq(names=...)
         self._master_ptr = self.master.data_ptr()
 
     def __del__(self):
@@ -304,34 +305,52 @@ class ParamStore:
             blk += (rows * ld + 1023) // 1024
             descs.append(d)
         self._rest_table = (ops.device_table(descs), len(descs), blk) if descs else None
+        self._adam_plain = plain
+        self._adam_table = self._adam_segments(None)
+
+    def _adam_segments(self, group_of: Optional[Dict[str, int]]):
+        """(device table, segments, blocks) over [0, total) in flat order: one segment per parameter with a plain shadow,
+        runs of consecutive parameters without one.  group_of (bpm_adam_step_groups): {parameter name: group index, or -1
+        for a parameter that is not stepped}; a run is then cut wherever the group changes, so that a segment belongs to
+        exactly one group.  A parameter's alignment padding rides with it; offsets are 64-element aligned, so every cut
+        is 16-byte aligned.  None: every segment in group 0 (the tables of bpm_adam_step_table / _clip)."""
+        esz = 2 if self.dtype == BPM_BF16 else 4
+        plain = self._adam_plain
         nblk = ops.adam_blocks
-        segs, blk, run = [], 0, None              # run = [off, end) of consecutive parameters without a plain shadow
+        segs, blk, run = [], 0, None              # run = [off, end, group) of consecutive parameters without a plain shadow
         for n in self.names:
             a = self.off[n]
             b = a + (self.params[n].numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+            gi = 0 if group_of is None else group_of[n]
             if n in plain:
                 if run is not None:
-                    segs.append((run[0], run[1], None))
+                    segs.append((run[0], run[1], None, run[2]))
                     run = None
-                segs.append((a, b, plain[n]))
-            elif run is None:
-                run = [a, b]
+                segs.append((a, b, plain[n], gi))
+            elif run is None or run[2] != gi:
+                if run is not None:
+                    segs.append((run[0], run[1], None, run[2]))
+                run = [a, b, gi]
             else:
                 run[1] = b
         if run is not None:
-            segs.append((run[0], run[1], None))
+            segs.append((run[0], run[1], None, run[2]))
         assert segs and segs[0][0] == 0 and segs[-1][1] == self.total and all(x[1] == y[0] for x, y in zip(segs, segs[1:]))
         out = []
-        for a, b, sh in segs:
+        for a, b, sh, gi in segs:
             sg = AdamSeg()
-            sg.off4, sg.n4, sg.blk0 = a // 4, (b - a) // 4, blk
+            sg.off4, sg.n4, sg.blk0, sg.group = a // 4, (b - a) // 4, blk, gi
             if sh is not None:
                 rows, cols, dst_ld, off = sh
                 sg.dst, sg.rows, sg.cols, sg.dst_ld = self.shadow_flat.data_ptr() + esz * off, rows, cols, dst_ld
             blk += nblk((b - a) // 4)
             out.append(sg)
-        self._adam_table = (ops.device_table(out), len(out), blk)
-        self._adam_plain = plain
+        return ops.device_table(out), len(out), blk
+
+    def adam_group_table(self, group_of: Dict[str, int]):
+        """The grouped segment table (device table, segments, blocks) for {parameter name: group index or -1}; a name the
+        map leaves out is not stepped.  Built on every call: the optimizer keeps it until its groups change."""
+        return self._adam_segments({n: group_of.get(n, -1) for n in self.names})
 
     def _build_norm_table(self) -> None:
         """Segment table of the gradient-norm reduction (bpm_grad_sumsq), its workspace and its 2-float result, all
@@ -340,12 +359,15 @@ class ParamStore:
         promises that a gradient launch never writes there), and so is a frozen parameter's slice, which the backward
         launches still fill.  Built at the first use, from requires_grad as it is then -- FusedAdam fixes its parameter
         list the same way -- so a store that never clips or reads the norm allocates nothing."""
+        self._norm_table, self._norm_ws = self._norm_segments(lambda n: self.params[n].requires_grad)
+        self._norm_out = torch.zeros(2, device=self.device, dtype=torch.float32)
+
+    def _norm_segments(self, counts):
         segs: List[List[int]] = []
         for n in self.names:
-            p = self.params[n]
-            if not p.requires_grad:
+            if not counts(n):
                 continue
-            a, b = self.off[n], self.off[n] + p.numel()
+            a, b = self.off[n], self.off[n] + self.params[n].numel()
             if segs and segs[-1][1] == a:
                 segs[-1][1] = b
             else:
@@ -353,20 +375,28 @@ class ParamStore:
         if not segs:
             raise RuntimeError("gradient norm: no trainable parameter in the flat buffers")
         base = self.gflat.data_ptr()
-        self._norm_table = ops.sumsq_table([(base + 4 * a, b - a) for a, b in segs])
-        self._norm_ws = torch.empty(ops.grad_sumsq_ws_bytes(self._norm_table[2]) // 4, device=self.device, dtype=torch.float32)
-        self._norm_out = torch.zeros(2, device=self.device, dtype=torch.float32)
+        table = ops.sumsq_table([(base + 4 * a, b - a) for a, b in segs])
+        return table, torch.empty(ops.grad_sumsq_ws_bytes(table[2]) // 4, device=self.device, dtype=torch.float32)
 
-    def grad_sumsq(self, grad_scale: float = 1.0, max_norm: float = 0.0, extra_sumsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def grad_sumsq(self, grad_scale: float = 1.0, max_norm: float = 0.0, extra_sumsq: Optional[torch.Tensor] = None,
+                   names: Optional[frozenset] = None) -> torch.Tensor:
         """The global gradient norm without leaving the device: one reduction over the trainable parameters' slices of
         gflat (+ a tiny fixed-order sum).  Returns the store's persistent result [total_norm, coef]:
         total_norm = grad_scale * sqrt(sum of squares + extra_sumsq), coef = min(1, max_norm / (total_norm + 1e-6)), or 1
-        when max_norm <= 0 (the norm only).  The next call overwrites it."""
-        if self._norm_table is None:
-            self._build_norm_table()
-        tab, nseg, nblk = self._norm_table
-        ops.grad_sumsq(tab, nseg, nblk, self._norm_ws, self._norm_out, grad_scale, max_norm, extra_sumsq)
-        return self._norm_out
+        when max_norm <= 0 (the norm only).  The next call overwrites it.
+        names: the parameters that count, instead of requires_grad as it was at the first use -- an optimizer with
+        parameter groups passes the set it steps (a table, workspace and result of its own, rebuilt when the set changes)."""
+        if names is None:
+            if self._norm_table is None:
+                self._build_norm_table()
+            (tab, nseg, nblk), ws, out = self._norm_table, self._norm_ws, self._norm_out
+        else:
+            if self._norm_set is None or self._norm_set[0] != names:
+                self._norm_set = (names,) + self._norm_segments(lambda n: n in names) + (
+                    torch.zeros(2, device=self.device, dtype=torch.float32),)
+            _, (tab, nseg, nblk), ws, out = self._norm_set
+        ops.grad_sumsq(tab, nseg, nblk, ws, out, grad_scale, max_norm, extra_sumsq)
+        return out
 
     def adam_step(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                   zero_grad: bool, scale_dev: Optional[torch.Tensor] = None) -> None:
@@ -383,6 +413,21 @@ class ParamStore:
                                      eps, weight_decay, step, grad_scale, scale_dev, zero_grad)
         # every plain shadow now holds the CT image of its updated master (whatever was pending before the step); the rest
         # (shadows that mix parameters, folded biases) is stale until the next refresh_shadows
+        self._dirty, self._dirty_rest, self._shadow_sig = False, True, self._versions()
+
+    def adam_step_groups(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, table, groups, grad_scale,
+                         zero_grad: bool, scale_dev: Optional[torch.Tensor] = None, norm_dev: Optional[torch.Tensor] = None,
+                         steps_dev: Optional[torch.Tensor] = None, skipped_dev: Optional[torch.Tensor] = None) -> None:
+        """adam_step with parameter groups (bpm_adam_step_groups): table = adam_group_table({parameter name: index into
+        `groups`}); groups = ops.adam_groups(...).  norm_dev: the step is skipped on the device when that norm is not
+        finite.  Still one launch that writes the plain shadows of what it steps."""
+        tab, nseg, nblk = table
+        if getattr(self, "_dirty", True) or self._versions() != getattr(self, "_shadow_sig", None):
+            # a full refresh is pending (the masters were edited), and this launch need not rewrite every plain shadow (a
+            # parameter that is not stepped, a skipped step): derive them now, so that what is left below is the rest
+            self.refresh_shadows()
+        ops.adam_step_groups(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, groups, grad_scale,
+                             zero_grad, scale_dev, norm_dev, steps_dev, skipped_dev)
         self._dirty, self._dirty_rest, self._shadow_sig = False, True, self._versions()
 
     def sptr(self, key: str, elem_off: int = 0) -> int:

@@ -392,6 +392,37 @@ def adam_step_table_clip(dtype, table_dev, nseg, nblk, master, grad, exp_avg, ex
                "bpm_adam_step_table_clip")
 
 
+def adam_groups(groups) -> "C.Array":
+    """[{lr, betas, eps, weight_decay, decoupled_weight_decay, step}] -> the host array bpm_adam_step_groups takes."""
+    if not 1 <= len(groups) <= _lib.ADAM_MAX_GROUPS:
+        raise ValueError(f"adam_groups: 1 .. {_lib.ADAM_MAX_GROUPS} groups, got {len(groups)}")
+    arr = (_lib.AdamGroup * len(groups))()
+    for a, g in zip(arr, groups):
+        a.lr, (a.beta1, a.beta2), a.eps, a.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        a.decoupled, a.step = int(bool(g.get("decoupled_weight_decay", False))), int(g.get("step", 0))
+    return arr
+
+
+def adam_step_groups(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_avg_sq, groups, grad_scale, zero_grad, scale_dev=None,
+                     norm_dev=None, steps_dev=None, skipped_dev=None) -> None:
+    """bpm_adam_step_groups: `groups` from adam_groups(); scale_dev / norm_dev: float32 device values (grad_sumsq's
+    coefficient and norm); steps_dev: int32[len(groups)] device counters of applied steps; skipped_dev: one int32."""
+    for t in (master, grad, exp_avg, exp_avg_sq):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != master.numel():
+            raise ValueError("adam_step_groups: flat contiguous float32 buffers of one size")
+    for t, what in ((scale_dev, "scale_dev"), (norm_dev, "norm_dev")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
+            raise ValueError(f"adam_step_groups: {what} is a float32 device tensor")
+    if steps_dev is not None and (steps_dev.dtype != torch.int32 or steps_dev.numel() < len(groups) or not steps_dev.is_contiguous()):
+        raise ValueError("adam_step_groups: steps_dev is a contiguous int32 device tensor with one counter per group")
+    if skipped_dev is not None and (skipped_dev.dtype != torch.int32 or skipped_dev.numel() < 1):
+        raise ValueError("adam_step_groups: skipped_dev is an int32 device tensor")
+    _lib.check(_lib.lib().bpm_adam_step_groups(dtype, table_dev.data_ptr(), nseg, nblk, _p(master), _p(grad), _p(exp_avg), _p(exp_avg_sq),
+                                               groups, len(groups), grad_scale, _p(scale_dev), _p(norm_dev), _p(steps_dev),
+                                               _p(skipped_dev), int(bool(zero_grad)), _stream()),
+               "bpm_adam_step_groups")
+
+
 def grad_sumsq_blocks(ptr: int, n: int) -> int:
     return int(_lib.lib().bpm_grad_sumsq_blocks(ptr, n)) if not _DRY_RUN else ((ptr >> 2 & 3) + n + 4095) // 4096
 

@@ -7,8 +7,13 @@ master buffer and its gradient a view into one flat gradient buffer (engine.Para
 of the model is ONE streaming kernel (`bpm_adam_step`) instead of a foreach loop over ~1700 tensors; the few parameters
 outside the trunk (final GMU, head, front-ends) go through an ordinary torch.optim.Adam with the same hyper-parameters.
 
-`FusedAdam` IS a `torch.optim.Optimizer` (one param group holding every model parameter), so LR schedulers and the
-reference's checkpoint code accept it; `param_groups[0]["lr"]` is read at every step.
+`FusedAdam` IS a `torch.optim.Optimizer` (by default one param group holding every trainable model parameter), so LR
+schedulers and the reference's checkpoint code accept it; every group's hyper-parameters are read at every step.
+
+Parameter groups (per-group lr / betas / eps / weight decay, L2 or decoupled), parameters left out of every group, and a
+step that skips itself when the gradient norm is not finite all stay ONE launch over the flat buffers
+(`bpm_adam_step_groups`): the segment table carries each segment's group, the groups' constants ride in the kernel
+arguments, and the skip decision is a device float the norm reduction left behind.
 
 Global-norm gradient clipping (`max_grad_norm`; upstream MulT calls `torch.nn.utils.clip_grad_norm_(model.parameters(), 0.8)`
 before `optimizer.step()`) is part of the step: one reduction over the flat gradient buffer (`bpm_grad_sumsq`) leaves the
@@ -22,44 +27,132 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
+
+
+_HYPER = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
 
 
 class FusedAdam(torch.optim.Optimizer):
-    """Drop-in for `torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)` on a `bpmult_amd` model.
+    """Drop-in for `torch.optim.Adam(params, lr, betas, eps, weight_decay, decoupled_weight_decay=...)` on a `bpmult_amd`
+    model.
 
     Differences from torch.optim.Adam, all deliberate: trunk parameters that never receive a gradient keep a zero
     gradient instead of `None` (their update is exactly zero unless weight_decay > 0); `zero_grad()` clears the flat
     gradient buffer in place (fused into the step when `fused_zero_grad=True`); the moments are two flat buffers
     (`state_dict()["flat"]`), not per-parameter tensors.
 
+    `param_groups`: None (one group of every parameter that is trainable at construction), or torch-style dicts
+    `{"params": [...], "lr": ..., "betas": ..., "eps": ..., "weight_decay": ..., "decoupled_weight_decay": ...}`; keys a
+    dict leaves out take the constructor's values.  At most 16 groups; trunk and tail parameters may share one.  Every
+    group keeps its own count of applied steps for the bias corrections (torch keeps one per parameter), so
+    `add_param_group()` after `p.requires_grad_(True)` starts the new group at its step 1 with zero moments.  A model
+    parameter that is in no group is NOT STEPPED: its master, both moments and every weight shadow derived from it keep
+    their bits, and it does not count in the clip norm (its slice of the flat gradient buffer, which the backward
+    launches still fill, is only cleared under `fused_zero_grad`).  `decoupled_weight_decay` (per group): p *= 1 - lr *
+    wd first, then the Adam update on the undecayed gradient -- `torch.optim.AdamW`.  The trunk goes through ONE launch
+    whatever the groups are (`bpm_adam_step_groups`: a block looks up its segment's group); the default construction on
+    a model whose trunk is all trainable launches `bpm_adam_step_table` / `_clip` as it always has.
+
     `max_grad_norm=c` clips the global gradient norm to c inside the step, as `torch.nn.utils.clip_grad_norm_(
-    model.parameters(), c)` in front of it would (norm over the parameters of `param_groups[0]`, coefficient
-    min(1, c / (norm + 1e-6)), a non-finite norm propagates as with error_if_nonfinite=False).  `grad_scale` (GradSync's
+    params, c)` in front of it would: ONE norm over the parameters of all groups, coefficient min(1, c / (norm + 1e-6)),
+    a non-finite norm propagates as with error_if_nonfinite=False (unless `skip_nonfinite`).  `grad_scale` (GradSync's
     1 / world_size) acts BEFORE the clip: after a sum all-reduce the norm is that of the averaged gradient, the same on
-    every rank.  The value lives in `param_groups[0]["max_grad_norm"]` (None: off) and travels with `state_dict()`.
-    `last_grad_norm`: the norm before clipping of the latest clipped step, a 0-dim fp32 DEVICE tensor (None until then);
-    reading it is the caller's sync -- `step()` itself never waits for the device."""
+    every rank.  The value lives in `param_groups[0]["max_grad_norm"]` (None: off) and travels with `state_dict()`; the
+    copies torch's defaults place in the other groups are ignored.
+    `last_grad_norm`: the norm before clipping of the latest step that took it, a 0-dim fp32 DEVICE tensor (None until
+    then); reading it is the caller's sync -- `step()` itself never waits for the device.
+
+    `skip_nonfinite=True`: every step takes the norm (so `last_grad_norm` is set without `max_grad_norm` too), and a
+    step whose norm is NaN or +-inf changes nothing -- no parameter, moment or shadow of any group, trunk or tail, and no
+    group's step count -- except that `skipped_steps` (a 0-dim int32 DEVICE tensor) goes up by one and the flat trunk
+    gradients are still cleared under `fused_zero_grad` (the tail's `.grad`s are the caller's `zero_grad()`, as always;
+    with clipping on they have been multiplied by the NaN / inf coefficient).  The flag is fixed at construction.  The decision, the counters and the bias corrections of later steps live on
+    the device.  The tail then runs torch's FUSED Adam, which honours a device `found_inf` tensor and un-counts the
+    step (what `torch.amp.GradScaler` uses); without the flag the tail is torch's default Adam as before."""
 
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fused_zero_grad: bool = False, max_grad_norm: Optional[float] = None):
+                 fused_zero_grad: bool = False, max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False,
+                 skip_nonfinite: bool = False, param_groups: Optional[List[dict]] = None):
         _check_max_norm(max_grad_norm)
-        params = [p for p in model.parameters() if p.requires_grad]
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self.model = model
+        self._name_of = {id(p): n for n, p in model.named_parameters()}
+        self._group_steps: List[int] = []                    # applied steps per group, see _applied_steps(); add_param_group appends
+        self._stale = True                                   # the groups changed: _regroup() before the next use
+        if param_groups is None:
+            groups = [p for p in model.parameters() if p.requires_grad]
+        else:
+            groups = [dict(g) for g in param_groups]
+            if not groups:
+                raise ValueError("param_groups is an empty list")
+            if len(groups) > _lib.ADAM_MAX_GROUPS:
+                raise ValueError(f"at most {_lib.ADAM_MAX_GROUPS} parameter groups, got {len(groups)}")
+        super().__init__(groups, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
         self.last_grad_norm: Optional[torch.Tensor] = None
         self.fused_zero_grad = fused_zero_grad
-        self.step_count = 0
+        self._skip_nonfinite = bool(skip_nonfinite)
+        self.step_count = 0                                  # calls of step(), skipped ones included
         self.pending_grad_scale: Optional[float] = None      # set by distributed.GradSync.finish(): 1 / world_size
+        # int32[16 + 1] on the device: under skip_nonfinite THE counts of applied steps (started from _group_steps, which
+        # is not advanced from then on), and in its last word the skips
+        self._counters: Optional[torch.Tensor] = None
         self._m: Optional[torch.Tensor] = None
         self._v: Optional[torch.Tensor] = None
         self._store_id = None
         self._tail_opt = None
+        self._tail_gi: List[int] = []                        # tail group -> index of the group it mirrors
 
-    # hyper-parameters live in the param group (what schedulers write)
+    # hyper-parameters live in the param groups (what schedulers write)
     @property
     def lr(self) -> float:
         return self.param_groups[0]["lr"]
+
+    @property
+    def skip_nonfinite(self) -> bool:
+        """Fixed at construction: it decides where the step counts live and which torch Adam steps the tail."""
+        return self._skip_nonfinite
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """Steps skipped for a non-finite gradient norm: a 0-dim int32 device tensor (reading it is the caller's sync)."""
+        self._store()
+        if self._counters is None:
+            self._counters = torch.zeros(_lib.ADAM_MAX_GROUPS + 1, device=self._m.device, dtype=torch.int32)
+        return self._counters[_lib.ADAM_MAX_GROUPS]
+
+    def add_param_group(self, param_group: dict) -> None:
+        """torch's add_param_group with this optimizer's rules (ValueError naming the offender): at most 16 groups, no
+        empty group, parameters of the model only (by identity), each in one group, none with requires_grad == False.
+        A group added after construction starts with zero moments and its own step count 0; the launch table is rebuilt
+        at the next step."""
+        if not isinstance(param_group, dict):
+            raise TypeError(f"param_group must be a dict, got {type(param_group).__name__}")
+        g = dict(param_group)
+        ps = g.get("params")
+        ps = [ps] if isinstance(ps, torch.Tensor) else list(ps if ps is not None else [])
+        gi = len(self.param_groups)
+        if gi >= _lib.ADAM_MAX_GROUPS:
+            raise ValueError(f"at most {_lib.ADAM_MAX_GROUPS} parameter groups: group {gi} is one too many")
+        if not ps:
+            raise ValueError(f"parameter group {gi} is empty")
+        seen = {id(p) for grp in self.param_groups for p in grp["params"]}
+        for p in ps:
+            name = self._name_of.get(id(p)) if isinstance(p, torch.Tensor) else None
+            if name is None:
+                what = f"a tensor of shape {tuple(p.shape)}" if isinstance(p, torch.Tensor) else repr(type(p).__name__)
+                raise ValueError(f"parameter group {gi}: {what} is not a parameter of the model")
+            if id(p) in seen:
+                raise ValueError(f"parameter {name} (group {gi}) is in more than one parameter group")
+            if not p.requires_grad:
+                raise ValueError(f"parameter {name} (group {gi}) has requires_grad == False: leave it out of the groups")
+            seen.add(id(p))
+        g["params"] = ps
+        if "betas" in g:
+            g["betas"] = tuple(g["betas"])
+        super().add_param_group(g)
+        self._group_steps.append(0)
+        self._stale = True
 
     # -- plumbing ---------------------------------------------------------------
     def _store(self):
@@ -68,11 +161,53 @@ class FusedAdam(torch.optim.Optimizer):
             self._m = torch.zeros_like(st.master)
             self._v = torch.zeros_like(st.master)
             self._store_id = id(st)
-            g = self.param_groups[0]
-            tail = [p for n, p in self.model.named_parameters() if n not in st.params and p.requires_grad]
-            self._tail_opt = torch.optim.Adam(tail, lr=g["lr"], betas=g["betas"], eps=g["eps"],
-                                              weight_decay=g["weight_decay"]) if tail else None
+            self._tail_opt, self._tail_gi, self._stale = None, [], True
+        if self._stale:
+            self._regroup(st)
+        if self.skip_nonfinite and self._counters is None:
+            self._counters = torch.zeros(_lib.ADAM_MAX_GROUPS + 1, device=st.master.device, dtype=torch.int32)
+            self._counters[:len(self._group_steps)] = torch.tensor(self._group_steps, dtype=torch.int32)
         return st
+
+    def _regroup(self, st) -> None:
+        """Trunk: {name: group} for the grouped launch table and the norm's parameter set.  Tail: one torch.optim.Adam
+        whose groups mirror the caller's (same membership order); a group added later is added there too, so the state
+        of the earlier ones stays."""
+        group_of = {}
+        for gi, g in enumerate(self.param_groups):
+            tail = []
+            for p in g["params"]:
+                n = self._name_of[id(p)]
+                if n in st.params:
+                    group_of[n] = gi
+                else:
+                    tail.append(p)
+            if not tail or gi in self._tail_gi:
+                continue
+            tg = dict(params=tail, **{k: g[k] for k in _HYPER})
+            if self._tail_opt is None:
+                self._tail_opt = torch.optim.Adam([tg], fused=True) if self.skip_nonfinite else torch.optim.Adam([tg])
+            else:
+                self._tail_opt.add_param_group(tg)
+            self._tail_gi.append(gi)
+        if not group_of:
+            raise ValueError("no parameter of the flat trunk buffers is in any parameter group: FusedAdam steps the trunk "
+                             "(and the tail beside it); for tail parameters alone use torch.optim.Adam")
+        self._group_of = group_of
+        self._group_table = None                           # bpm_adam_step_groups' segment table: built by the first step that needs it
+        self._trunk_set = frozenset(group_of)
+        self._all_trunk = len(group_of) == len(st.params)
+        self._stale = False
+
+    def _grouped(self) -> bool:
+        """False: the one-group L2 step over an all-trainable trunk, which stays on bpm_adam_step_table / _clip."""
+        return (self.skip_nonfinite or len(self.param_groups) > 1 or not self._all_trunk
+                or self.param_groups[0]["decoupled_weight_decay"])
+
+    def _applied_steps(self) -> List[int]:
+        if self._counters is not None and self.skip_nonfinite:
+            return [int(x) for x in self._counters[:len(self.param_groups)].tolist()]      # the caller's sync
+        return list(self._group_steps)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         st = self._store()
@@ -96,23 +231,38 @@ class FusedAdam(torch.optim.Optimizer):
         if n % 4:
             raise RuntimeError("flat parameter buffer is not a multiple of 4 elements")
         clip = g.get("max_grad_norm")
-        tail = self._tail_opt.param_groups[0]["params"] if self._tail_opt is not None else []
-        coef = None
-        if clip is not None:
+        tail = [p for tg in self._tail_opt.param_groups for p in tg["params"]] if self._tail_opt is not None else []
+        grouped = self._grouped()
+        coef = norm = None
+        if clip is not None or self.skip_nonfinite:
             # the trunk's share: one reduction over gflat; the tail's (PyTorch-owned parameters) through torch; one root.
-            # Norm and coefficient stay on the device: the Adam kernel and the tail multiply read them there.
+            # Norm and coefficient stay on the device: the Adam kernel and the tail read them there.
             _check_max_norm(clip)
             tail_grads = [p.grad for p in tail if p.grad is not None]
-            res = st.grad_sumsq(grad_scale, float(clip), _sumsq(tail_grads))
+            res = st.grad_sumsq(grad_scale, float(clip) if clip is not None else 0.0, _sumsq(tail_grads),
+                                names=self._trunk_set if grouped else None)
             self.last_grad_norm = res[0].clone()
-            coef = res[1:2]
+            coef = res[1:2] if clip is not None else None
+            norm = res[0:1] if self.skip_nonfinite else None
         # one launch: the update of every trunk parameter AND the CT shadows of the plain weight matrices, written from
         # the updated masters as they are stored (no second pass over the flat master for the next forward's operands)
-        st.adam_step(self._m, self._v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count,
-                     grad_scale, self.fused_zero_grad, scale_dev=coef)
+        if not grouped:
+            self._group_steps[0] += 1
+            st.adam_step(self._m, self._v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._group_steps[0],
+                         grad_scale, self.fused_zero_grad, scale_dev=coef)
+        else:
+            if norm is None:
+                self._group_steps = [s + 1 for s in self._group_steps]
+            hyper = ops.adam_groups([dict(pg, step=s) for pg, s in zip(self.param_groups, self._group_steps)])
+            if self._group_table is None:
+                self._group_table = st.adam_group_table(self._group_of)
+            st.adam_step_groups(self._m, self._v, self._group_table, hyper, grad_scale, self.fused_zero_grad, scale_dev=coef,
+                                norm_dev=norm, steps_dev=None if norm is None else self._counters,
+                                skipped_dev=None if norm is None else self._counters[_lib.ADAM_MAX_GROUPS:])
         if self._tail_opt is not None:
-            for tg in self._tail_opt.param_groups:
-                tg["lr"], tg["betas"], tg["eps"], tg["weight_decay"] = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+            for tg, gi in zip(self._tail_opt.param_groups, self._tail_gi):
+                for k in _HYPER:
+                    tg[k] = self.param_groups[gi][k]
             if coef is not None:
                 if tail_grads:
                     torch._foreach_mul_(tail_grads, coef[0] * grad_scale)      # grad_scale and the clip in one multiply
@@ -120,28 +270,85 @@ class FusedAdam(torch.optim.Optimizer):
                 for p in tail:
                     if p.grad is not None:
                         p.grad.mul_(grad_scale)
+            if norm is not None:                           # torch's fused Adam: no update and the step un-counted when set
+                self._tail_opt.found_inf = torch.isfinite(res[0]).logical_not().float()
             self._tail_opt.step()
         return loss
 
+    def _load_tail(self, tail_sd) -> None:
+        self._tail_opt.load_state_dict(tail_sd)
+        _tail_flavour(self._tail_opt, self.skip_nonfinite)
+
+    def _group_names(self, gi: int) -> List[str]:
+        return [self._name_of[id(p)] for p in self.param_groups[gi]["params"]]
+
     def state_dict(self):
+        """`step`: the applied steps of group 0; `group_steps`: of every group; `skipped`: the skip count (under
+        skip_nonfinite reading them waits for the device: the caller's checkpoint, not the step); `step_calls`: calls of
+        step(); `param_groups`: one dict per group, the hyper-parameters plus `param_names` (the model's names, in order)."""
         self._store()                                      # the moments exist (zeros) even before the first step
-        g = self.param_groups[0]
-        return {"step": self.step_count, "flat": {"exp_avg": self._m, "exp_avg_sq": self._v},
+        steps = self._applied_steps()
+        skipped = int(self._counters[_lib.ADAM_MAX_GROUPS]) if self._counters is not None else 0
+        return {"step": steps[0], "group_steps": steps, "skipped": skipped, "step_calls": self.step_count,
+                "flat": {"exp_avg": self._m, "exp_avg_sq": self._v},
                 "tail": self._tail_opt.state_dict() if self._tail_opt is not None else None,
                 "dropout_step": int(getattr(self.model, "dropout_step", 0)),
-                "param_groups": [{k: v for k, v in g.items() if k != "params"}]}
+                "param_groups": [dict({k: v for k, v in g.items() if k != "params"}, param_names=self._group_names(gi))
+                                 for gi, g in enumerate(self.param_groups)]}
 
     def load_state_dict(self, sd) -> None:
+        """Restores what state_dict() wrote.  A checkpoint written before parameter groups existed (no `param_names`, no
+        `group_steps`) loads too: every group takes its `step`.  ValueError when the number of groups or a group's
+        parameter names differ from this optimizer's."""
+        groups = sd["param_groups"]
+        if len(groups) != len(self.param_groups):
+            raise ValueError(f"the checkpoint has {len(groups)} parameter groups, this optimizer {len(self.param_groups)}")
+        for gi, theirs in enumerate(groups):
+            if "param_names" in theirs and list(theirs["param_names"]) != self._group_names(gi):
+                raise ValueError(f"parameter group {gi}: the checkpoint's parameter names differ from this optimizer's")
+        steps = sd.get("group_steps")
+        steps = [int(sd["step"])] * len(groups) if steps is None else [int(s) for s in steps]
+        if len(steps) != len(groups):
+            raise ValueError(f"the checkpoint has {len(steps)} group step counts for {len(groups)} parameter groups")
         self._store()
-        self.step_count = sd["step"]
+        self._group_steps = steps
+        self.step_count = int(sd.get("step_calls", sd["step"]))
+        if self._counters is not None or sd.get("skipped"):
+            self.skipped_steps                             # (allocates the counters)
+            self._counters.zero_()
+            self._counters[:len(steps)] = torch.tensor(steps, dtype=torch.int32)
+            self._counters[_lib.ADAM_MAX_GROUPS] = int(sd.get("skipped", 0))
         self._m.copy_(sd["flat"]["exp_avg"])
         self._v.copy_(sd["flat"]["exp_avg_sq"])
         if self._tail_opt is not None and sd.get("tail") is not None:
-            self._tail_opt.load_state_dict(sd["tail"])
+            self._load_tail(sd["tail"])
         if hasattr(self.model, "dropout_step"):
             self.model.dropout_step = int(sd.get("dropout_step", 0))
-        for k, v in sd["param_groups"][0].items():
-            self.param_groups[0][k] = tuple(v) if k == "betas" else v
+        for mine, theirs in zip(self.param_groups, groups):
+            for k, v in theirs.items():
+                if k != "param_names":
+                    mine[k] = tuple(v) if k == "betas" else v
+
+
+def _tail_flavour(opt: torch.optim.Adam, fused: bool) -> None:
+    """torch's load_state_dict takes every group option from the saved groups, `fused` included, and leaves each `step`
+    where that flavour keeps it.  Put the tail back to THIS optimizer's flavour: fused Adam with float32 device steps
+    under skip_nonfinite, the default Adam with host steps otherwise."""
+    for tg in opt.param_groups:
+        tg["fused"], tg["foreach"] = (True if fused else None), None
+        for p in tg["params"]:
+            s = opt.state.get(p)
+            if s and "step" in s:
+                s["step"] = torch.as_tensor(s["step"], dtype=torch.float32).to(p.device if fused else "cpu")
+
+
+def decay_groups(model, weight_decay: float, **overrides) -> List[dict]:
+    """The usual two parameter groups over the model's TRAINABLE parameters: matrices and everything else with
+    ndim >= 2 take `weight_decay`, vectors (ndim <= 1: biases, LayerNorm affines) take 0.  `overrides` (lr, betas, eps,
+    decoupled_weight_decay, ...) go into both dicts."""
+    ps = [p for p in model.parameters() if p.requires_grad]
+    return [dict(overrides, params=[p for p in ps if p.ndim >= 2], weight_decay=weight_decay),
+            dict(overrides, params=[p for p in ps if p.ndim <= 1], weight_decay=0.0)]
 
 
 def _check_max_norm(x) -> None:

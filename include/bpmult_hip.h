@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define BPM_ABI_VERSION 4
+#define BPM_ABI_VERSION 5
 #define BPM_SEED_INDIRECT (1ull << 63) /* seed = BPM_SEED_INDIRECT | (uintptr_t)device pointer to the uint64 seed */
 #define BPM_MAX_GROUP 18 /* problems per grouped launch (6 encoders of a level x 3 projections) */
 #define BPM_GEMM_MAX_GROUP 24 /* bpm_gemm_grouped alone: 6 encoders x (q, k, v, out) weight gradients in one launch */
@@ -417,14 +417,15 @@ int bpm_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, 
  * (device memory, built once) cuts the flat buffer into consecutive segments: off4 / n4 in units of 4 floats (16-byte
  * aligned), blk0 = first block (a segment takes bpm_adam_blocks(n4) blocks; entries sorted by blk0, covering the buffer).
  * dst != NULL: the segment starts with a whole [rows, cols] fp32 matrix (cols % 4 == 0) whose CT shadow is [rows, dst_ld];
- * shadow element (r, c) = CT(updated master (r, c)), pad columns are not touched.  dtype = the shadows' CT. */
+ * shadow element (r, c) = CT(updated master (r, c)), pad columns are not touched.  dtype = the shadows' CT.
+ * group: read by bpm_adam_step_groups only (below); the entries here ignore it, and their tables hold 0 there. */
 typedef struct bpm_adam_seg {
     size_t off4;
     unsigned n4;
     unsigned blk0;
     void* dst;
     int rows, cols, dst_ld;
-    int pad_;
+    int group;
 } bpm_adam_seg;
 int bpm_adam_blocks(size_t n4);
 int bpm_adam_step_table(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
@@ -463,6 +464,38 @@ int bpm_grad_sumsq(const bpm_sumsq_seg* table_dev, int nseg, unsigned total_bloc
 int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
                              float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int step, float grad_scale, const float* scale_dev, int zero_grad, void* stream);
+
+/* The table-driven step with PARAMETER GROUPS, decoupled weight decay and a skip on a non-finite gradient norm: what
+ * torch.optim.Adam(param_groups, decoupled_weight_decay=...) does for the trunk, and what torch.amp.GradScaler makes an
+ * optimizer do when a gradient is inf / NaN.  Still one launch over the flat buffers that writes the CT shadows.
+ * Table: bpm_adam_seg as above, with seg.group = index into `groups` of the group the segment's parameters belong to (a
+ * segment belongs to exactly one group), or -1: NOT STEPPED -- nothing of the segment is loaded and nothing stored (master,
+ * moments and shadow keep their bits), except zeros to its gradients when zero_grad != 0 (a frozen parameter's slice is
+ * still filled by the backward launches and must not grow for ever).  A group index >= ngroups is treated as -1.
+ * groups: HOST array of ngroups (1 .. BPM_ADAM_MAX_GROUPS) entries, copied into the launch.  decoupled == 0: L2 decay,
+ * g = grad * scale + weight_decay * p, the arithmetic of bpm_adam_step_table (one group 0 over the whole table gives
+ * bit-equal results).  decoupled != 0: p *= 1 - lr * weight_decay first, then the Adam update on the undecayed gradient
+ * (torch.optim.AdamW).  step: the group's 1-based step number for the bias corrections when steps_dev == NULL.
+ * scale_dev: NULL or a device float multiplied into grad_scale (the clip coefficient, out + 1 of bpm_grad_sumsq).
+ * norm_dev: NULL or a device float (out of bpm_grad_sumsq); when it is NaN or +-inf the step is SKIPPED: every block
+ * stores nothing but the cleared gradients.  The decision is taken on the device; the host never waits.
+ * steps_dev: NULL or int[ngroups] on the device, the groups' counts of APPLIED steps: the bias corrections then come from
+ * steps_dev[group] + 1 (in double, as the host takes them) and groups[i].step is ignored; after the update a second tiny
+ * launch adds one to every group's count -- or, when the step was skipped, adds one to *skipped_dev (NULL: not counted)
+ * and leaves the counts alone.  Without steps_dev, skipped_dev is still advanced when norm_dev is given.
+ * BPM_ERR_ARG: a NULL table / buffer / groups, ngroups outside 1..16, a host step < 1 when steps_dev == NULL;
+ * BPM_ERR_ALIGN: the four buffers 16-byte, the device scalars 4-byte aligned.  Nothing is launched on an error. */
+#define BPM_ADAM_MAX_GROUPS 16
+typedef struct bpm_adam_group {
+    float lr, beta1, beta2, eps, weight_decay;
+    int decoupled;
+    int step;
+    int pad_;
+} bpm_adam_group;
+int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
+                         float* exp_avg, float* exp_avg_sq, const bpm_adam_group* groups, int ngroups, float grad_scale,
+                         const float* scale_dev, const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad,
+                         void* stream);
 
 /* Engine plumbing (no reference counterpart): a non-blocking HIP stream at the device's lowest priority
  * (low_priority != 0) or at the default priority.  The host engine puts weight-gradient GEMMs and the
