@@ -993,96 +993,29 @@ extern "C" int bpm_adam_step(float* param, float* grad, float* exp_avg, float* e
 }
 
 // ---------------------------------------------------------------------------
-// The same step, table driven, writing the CT weight shadows as it stores the updated masters (no second pass over the
-// flat master for the shadow refresh: 2.7 GB read + 1.35 GB written per optimizer step at hidden 768).  The flat buffer
+// The same step, table driven and with PARAMETER GROUPS, writing the CT weight shadows as it stores the updated masters
+// (no second pass over the flat master for the shadow refresh: 2.7 GB read + 1.35 GB written per optimizer step at
+// hidden 768).  The flat buffer
 // is cut into segments (device-resident table, built once): runs of parameters without a plain shadow, and one segment per
 // parameter that has one -- a whole [rows, cols] matrix whose shadow is [rows, dst_ld], pad columns left as they are
 // (zero since allocation).  A block covers ADAM_CHUNK consecutive f32x4 of ONE segment, so the segment is looked up once
-// per block; every thread has its 4 x 4 loads in flight before the first use.
+// per block; every thread has its 4 x 4 loads in flight before the first use, and the shadow is stored from the updated
+// value.  ONE kernel behind bpm_adam_step_groups, bpm_adam_step_table and bpm_adam_step_table_clip.
+// A segment carries the index of its group (or -1: not stepped), the groups' constants ride in the kernel arguments, and
+// group, skip decision and step number are uniform per block.
+//   L2 group        : g = grad * scale + wd * p                                    (wd_l2 = wd, decay = 1: adam_kernel's arithmetic)
+//   decoupled group : p *= 1 - lr * wd, then the update on g = grad * scale       (wd_l2 = 0, decay = 1 - lr * wd)
+// One expression serves both.  ngroups == 0 (the two table entries): one group, G.g[0], and the segments' group words are
+// not looked at.  A block that is not stepped (group -1, or *norm_dev not finite) loads nothing and stores nothing but
+// zeros to its gradients when zero_grad is set.  scale_dev: the gradient scale is gscale * (*scale_dev), one uniform read
+// per block of a value an earlier launch on the stream left on the device (the clip coefficient of bpm_grad_sumsq).
+// steps_dev: the bias corrections come from steps_dev[group] + 1, in double.
 // ---------------------------------------------------------------------------
 constexpr int ADAM_ITER = 4;
 constexpr int ADAM_CHUNK = NT * ADAM_ITER;             // f32x4 per block
 
-// DEVSCALE (bpm_adam_step_table_clip with a scale_dev): the gradient scale is gscale * (*scale_dev), one uniform read
-// per block of a value an earlier launch on the stream left on the device (the clip coefficient of bpm_grad_sumsq);
-// without it the pointer is not touched and the code is what bpm_adam_step_table has always launched.
-template <typename CT, bool DEVSCALE>
-__global__ __launch_bounds__(NT) void adam_table_kernel(const bpm_adam_seg* __restrict__ tab, int nseg, float* __restrict__ p,
-                                                       float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                       float lr_c, float b1, float b2, float eps, float wd, float rsq_bc2,
-                                                       float gscale, int zero_grad, const float* __restrict__ scale_dev) {
-    if constexpr (DEVSCALE) gscale *= *scale_dev;
-    const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
-    const size_t base = S.off4 + (size_t)(blockIdx.x - S.blk0) * ADAM_CHUNK;
-    const size_t end = S.off4 + S.n4;
-    f32x4 pp[ADAM_ITER], gg[ADAM_ITER], mm[ADAM_ITER], vv[ADAM_ITER];
-#pragma unroll
-    for (int j = 0; j < ADAM_ITER; ++j) {
-        const size_t i = base + j * NT + threadIdx.x;
-        const size_t ic = i < end ? i : S.off4;             // clamped, unconditional loads
-        pp[j] = ((const f32x4*)p)[ic]; gg[j] = ((const f32x4*)g)[ic]; mm[j] = ((const f32x4*)m)[ic]; vv[j] = ((const f32x4*)v)[ic];
-    }
-#pragma unroll
-    for (int j = 0; j < ADAM_ITER; ++j) {
-        const size_t i = base + j * NT + threadIdx.x;
-        if (i >= end) continue;
-        f32x4 x = pp[j], gr = gg[j] * gscale + wd * pp[j];
-        const f32x4 mo = b1 * mm[j] + (1.f - b1) * gr;
-        const f32x4 vo = b2 * vv[j] + (1.f - b2) * gr * gr;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) x[q] -= lr_c * mo[q] / (sqrtf(vo[q]) * rsq_bc2 + eps);
-        ((f32x4*)p)[i] = x; ((f32x4*)m)[i] = mo; ((f32x4*)v)[i] = vo;
-        if (zero_grad) ((f32x4*)g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (S.dst) {
-            const size_t e = 4 * (i - S.off4);               // element index inside the [rows, cols] matrix; cols % 4 == 0
-            if (e < (size_t)S.rows * S.cols) {               // (the segment's 64-element alignment tail has no shadow)
-                size_t o = e;
-                if (S.cols != S.dst_ld) { const size_t r = e / (unsigned)S.cols; o = r * S.dst_ld + (e - r * S.cols); }
-                put4<CT>(S.dst, o, x);
-            }
-        }
-    }
-}
-
 extern "C" int bpm_adam_blocks(size_t n4) { return (int)((n4 + ADAM_CHUNK - 1) / ADAM_CHUNK); }
 
-extern "C" int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
-                                        float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                                        float weight_decay, int step, float grad_scale, const float* scale_dev, int zero_grad,
-                                        void* stream) {
-    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || step < 1) return BPM_ERR_ARG;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
-    if ((uintptr_t)scale_dev & 3) return BPM_ERR_ALIGN;
-    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    const float lr_c = (float)(lr / bc1), rsq_bc2 = (float)(1.0 / sqrt(bc2));
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, param, grad, exp_avg,
-                           exp_avg_sq, lr_c, beta1, beta2, eps, weight_decay, rsq_bc2, grad_scale, zero_grad, scale_dev);
-    };
-    if (dtype == BPM_BF16) scale_dev ? launch(adam_table_kernel<bf16_t, true>) : launch(adam_table_kernel<bf16_t, false>);
-    else scale_dev ? launch(adam_table_kernel<float, true>) : launch(adam_table_kernel<float, false>);
-    BPM_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int bpm_adam_step_table(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
-                                   float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                                   float weight_decay, int step, float grad_scale, int zero_grad, void* stream) {
-    return bpm_adam_step_table_clip(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
-                                    weight_decay, step, grad_scale, nullptr, zero_grad, stream);
-}
-
-// ---------------------------------------------------------------------------
-// The table-driven step with PARAMETER GROUPS (bpm_adam_step_groups): a segment carries the index of its group (or -1: not
-// stepped), the groups' constants ride in the kernel arguments, and group, skip decision and step number are uniform per
-// block.  Same shape as adam_table_kernel: one segment lookup per block, 4 x 4 clamped unconditional loads in flight
-// before the first use, the shadow stored from the updated value.
-//   L2 group        : g = grad * scale + wd * p                       (wd_l2 = wd, decay = 1: adam_table_kernel's arithmetic)
-//   decoupled group : p *= 1 - lr * wd, then the update on g = grad * scale       (wd_l2 = 0, decay = 1 - lr * wd)
-// One expression serves both, so a table whose segments all sit in one L2 group gives what adam_table_kernel gives.
-// A block that is not stepped (group -1, or *norm_dev not finite) loads nothing and stores nothing but zeros to its
-// gradients when zero_grad is set.  steps_dev: the bias corrections come from steps_dev[group] + 1, in double.
-// ---------------------------------------------------------------------------
 struct AdamGroupK { float lr, b1, b2, eps, wd_l2, decay, lr_c, rsq_bc2; };
 struct AdamGroupsK { AdamGroupK g[BPM_ADAM_MAX_GROUPS]; };
 
@@ -1104,7 +1037,8 @@ __global__ __launch_bounds__(NT) void adam_groups_kernel(const bpm_adam_seg* __r
     const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
     const size_t base = S.off4 + (size_t)(blockIdx.x - S.blk0) * ADAM_CHUNK;
     const size_t end = S.off4 + S.n4;
-    bool live = S.group >= 0 && S.group < ngroups;
+    const int grp = ngroups ? S.group : 0;              // block-uniform; ngroups == 0: whatever the word holds, group 0
+    bool live = grp >= 0 && grp < (ngroups ? ngroups : 1);
     if (live && norm_dev) live = adam_norm_finite(norm_dev);
     if (!live) {
         if (zero_grad) {
@@ -1124,11 +1058,11 @@ __global__ __launch_bounds__(NT) void adam_groups_kernel(const bpm_adam_seg* __r
         pp[j] = ((const f32x4*)p)[ic]; gg[j] = ((const f32x4*)g)[ic]; mm[j] = ((const f32x4*)m)[ic]; vv[j] = ((const f32x4*)v)[ic];
     }
     if (scale_dev) gscale *= *scale_dev;
-    const AdamGroupK H = G.g[S.group];
+    const AdamGroupK H = G.g[grp];
     const float b1 = H.b1, b2 = H.b2, eps = H.eps, wd = H.wd_l2, decay = H.decay;
     float lr_c = H.lr_c, rsq_bc2 = H.rsq_bc2;
     if (steps_dev) {
-        const int t = steps_dev[S.group] + 1;
+        const int t = steps_dev[grp] + 1;
         const double bc1 = 1.0 - adam_ipow((double)b1, t), bc2 = 1.0 - adam_ipow((double)b2, t);
         lr_c = (float)((double)H.lr / bc1);
         rsq_bc2 = (float)(1.0 / sqrt(bc2));
@@ -1166,14 +1100,10 @@ __global__ __launch_bounds__(64) void adam_counters_kernel(const float* norm_dev
     }
 }
 
-extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
-                                    float* grad, float* exp_avg, float* exp_avg_sq, const bpm_adam_group* groups, int ngroups,
-                                    float grad_scale, const float* scale_dev, const float* norm_dev, int* steps_dev,
-                                    int* skipped_dev, int zero_grad, void* stream) {
-    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || !groups) return BPM_ERR_ARG;
-    if (ngroups < 1 || ngroups > BPM_ADAM_MAX_GROUPS) return BPM_ERR_ARG;
-    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
-    if (((uintptr_t)scale_dev | (uintptr_t)norm_dev | (uintptr_t)steps_dev | (uintptr_t)skipped_dev) & 3) return BPM_ERR_ALIGN;
+// Fills the launch's copy of the groups and launches.  ngroups_k: what the kernel takes (0: ignore the group words).
+static int adam_launch(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
+                       float* exp_avg, float* exp_avg_sq, const bpm_adam_group* groups, int ngroups, int ngroups_k, float grad_scale,
+                       const float* scale_dev, const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad, void* stream) {
     AdamGroupsK G = {};
     for (int i = 0; i < ngroups; ++i) {
         const bpm_adam_group& h = groups[i];
@@ -1182,14 +1112,14 @@ extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, in
         k.lr = h.lr; k.b1 = h.beta1; k.b2 = h.beta2; k.eps = h.eps;
         k.wd_l2 = h.decoupled ? 0.f : h.weight_decay;
         k.decay = h.decoupled ? (float)(1.0 - (double)h.lr * (double)h.weight_decay) : 1.f;
-        if (!steps_dev) {                                  // as bpm_adam_step_table takes them
+        if (!steps_dev) {
             const double bc1 = 1.0 - pow((double)h.beta1, h.step), bc2 = 1.0 - pow((double)h.beta2, h.step);
             k.lr_c = (float)(h.lr / bc1); k.rsq_bc2 = (float)(1.0 / sqrt(bc2));
         }
     }
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, param, grad, exp_avg,
-                           exp_avg_sq, G, ngroups, grad_scale, zero_grad, scale_dev, norm_dev, (const int*)steps_dev);
+                           exp_avg_sq, G, ngroups_k, grad_scale, zero_grad, scale_dev, norm_dev, (const int*)steps_dev);
     };
     if (dtype == BPM_BF16) launch(adam_groups_kernel<bf16_t>);
     else launch(adam_groups_kernel<float>);
@@ -1199,6 +1129,38 @@ extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, in
         BPM_CHECK_LAUNCH();
     }
     return 0;
+}
+
+extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
+                                    float* grad, float* exp_avg, float* exp_avg_sq, const bpm_adam_group* groups, int ngroups,
+                                    float grad_scale, const float* scale_dev, const float* norm_dev, int* steps_dev,
+                                    int* skipped_dev, int zero_grad, void* stream) {
+    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || !groups) return BPM_ERR_ARG;
+    if (ngroups < 1 || ngroups > BPM_ADAM_MAX_GROUPS) return BPM_ERR_ARG;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
+    if (((uintptr_t)scale_dev | (uintptr_t)norm_dev | (uintptr_t)steps_dev | (uintptr_t)skipped_dev) & 3) return BPM_ERR_ALIGN;
+    return adam_launch(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, groups, ngroups, ngroups, grad_scale,
+                       scale_dev, norm_dev, steps_dev, skipped_dev, zero_grad, stream);
+}
+
+// The one-group entries: one L2 group at the host's `step`, no skip, no counters, the segments' group words ignored.
+extern "C" int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
+                                        float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                        float weight_decay, int step, float grad_scale, const float* scale_dev, int zero_grad,
+                                        void* stream) {
+    if (!table_dev || nseg < 1 || total_blocks < 1 || !param || !grad || !exp_avg || !exp_avg_sq || step < 1) return BPM_ERR_ARG;
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) return BPM_ERR_ALIGN;
+    if ((uintptr_t)scale_dev & 3) return BPM_ERR_ALIGN;
+    const bpm_adam_group one = {lr, beta1, beta2, eps, weight_decay, 0, step, 0};
+    return adam_launch(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, &one, 1, 0, grad_scale, scale_dev,
+                       nullptr, nullptr, nullptr, zero_grad, stream);
+}
+
+extern "C" int bpm_adam_step_table(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
+                                   float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, int step, float grad_scale, int zero_grad, void* stream) {
+    return bpm_adam_step_table_clip(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
+                                    weight_decay, step, grad_scale, nullptr, zero_grad, stream);
 }
 
 extern "C" int bpm_fold_bias(const bpm_fold_desc* table_dev, int ndesc, unsigned total_blocks, void* stream) {

@@ -93,6 +93,9 @@ class ParamStore:
     ALIGN = 64  # elements
 
     def __init__(self, named_params: Sequence[Tuple[str, torch.nn.Parameter]], dtype: int, x3: bool = False):
+        self._x3_range = None                           # (first: __del__ reads it even when the constructor raises)
+        self._dirty, self._dirty_rest, self._shadow_sig = True, False, None
+        self._zero_table = None                         # built by set_store_written()
         self.dtype = dtype
         self.x3 = bool(x3) and dtype != BPM_BF16      # bf16x3 mode: fp32 storage, large GEMMs as three split-bf16 products
         self.side_low = True                            # side-stream priority: set by the plan that launches over this store
@@ -130,10 +133,9 @@ class ParamStore:
         self._master_ptr = self.master.data_ptr()
 
     def __del__(self):
-        r = getattr(self, "_x3_range", None)
-        if r is not None:
+        if self._x3_range is not None:
             try:
-                ops.x3_drop_static(*r)
+                ops.x3_drop_static(*self._x3_range)
             except Exception:              # noqa: BLE001 -- interpreter shutdown
                 pass
 
@@ -192,7 +194,7 @@ class ParamStore:
         the gradients are unset, only the small tensors are cleared and True is returned -- the caller must then run the
         storing tables."""
         fresh = self._fresh()
-        if stores and fresh and getattr(self, "_zero_table", None) is not None:
+        if stores and fresh and self._zero_table is not None:
             ops.zero_segments(*self._zero_table)
             return True
         if fresh:
@@ -243,25 +245,11 @@ class ParamStore:
     def finalize_shadows(self) -> None:
         ct = ops.ct_torch(self.dtype)
         self.shadow_flat = torch.zeros(max(self._shadow_total, 32), device=self.device, dtype=ct)
-        esz = self.shadow_flat.element_size()
-        descs, blk = [], 0
-        for (name, rows, cols, ld, src_ld, dst_ld, src_off, off, colscale) in self._shadow_specs:
-            d = PackDesc()
-            d.src = self.params[name].data_ptr() + 4 * src_off
-            d.dst = self.shadow_flat.data_ptr() + esz * off
-            d.rows, d.cols, d.ld, d.src_ld, d.dst_ld, d.blk0 = rows, cols, ld, src_ld, dst_ld, blk
-            d.colscale = self.params[colscale].data_ptr() if colscale else None
-            blk += (rows * ld + 1023) // 1024
-            descs.append(d)
         if self.x3:                                    # the weight shadows are the static operands of the bf16x3 products
-            self._x3_range = (self.shadow_flat.data_ptr(), self.shadow_flat.data_ptr() + self.shadow_flat.numel() * esz)
+            a = self.shadow_flat.data_ptr()
+            self._x3_range = (a, a + self.shadow_flat.numel() * self.shadow_flat.element_size())
             ops.x3_register_static(*self._x3_range)
-        self._ndesc, self._nblk = len(descs), blk
-        if descs:
-            arr = (PackDesc * len(descs))(*descs)
-            raw = bytes(memoryview(arr))
-            self._table = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-            self._table = self._table if ops._DRY_RUN else self._table.to(self.device)
+        self._table = self._pack_table(self._shadow_specs)
         self._build_adam_table()
         self.fold_flat = torch.zeros(max(self._fold_total, 64), device=self.device, dtype=torch.float32)
         fd, blk = [], 0
@@ -279,8 +267,22 @@ class ParamStore:
         self._nfold, self._fold_blk = len(fd), blk
         self._fold_table = ops.device_table(fd) if fd else None
 
+    def _pack_table(self, specs):
+        """(device table, descriptors, blocks) of a pack_weights launch over a list of shadow specs; None for an empty one."""
+        esz = self.shadow_flat.element_size()
+        descs, blk = [], 0
+        for (name, rows, cols, ld, src_ld, dst_ld, src_off, off, colscale) in specs:
+            d = PackDesc()
+            d.src = self.params[name].data_ptr() + 4 * src_off
+            d.dst = self.shadow_flat.data_ptr() + esz * off
+            d.rows, d.cols, d.ld, d.src_ld, d.dst_ld, d.blk0 = rows, cols, ld, src_ld, dst_ld, blk
+            d.colscale = self.params[colscale].data_ptr() if colscale else None
+            blk += (rows * ld + 1023) // 1024
+            descs.append(d)
+        return (ops.device_table(descs), len(descs), blk) if descs else None
+
     def _build_adam_table(self) -> None:
-        """Segment table of the fused optimizer step (bpm_adam_step_table) and the pack table of what it leaves over.
+        """Segment table of the fused optimizer step (every segment in group 0) and the pack table of what it leaves over.
         A shadow is written BY THE OPTIMIZER KERNEL when it is the plain CT copy of a whole parameter matrix (the large
         encoder matrices, the projections, the GMU hidden maps, the time maps); shadows that mix two parameters (the K / V
         projection weights with their LayerNorm gain folded in) or re-arrange columns (the x_gate halves) stay with a second,
@@ -295,16 +297,7 @@ class ParamStore:
                 plain[name] = (rows, cols, dst_ld, off)
             else:
                 rest.append(spec)
-        descs, blk = [], 0
-        for (name, rows, cols, ld, src_ld, dst_ld, src_off, off, colscale) in rest:
-            d = PackDesc()
-            d.src = self.params[name].data_ptr() + 4 * src_off
-            d.dst = self.shadow_flat.data_ptr() + esz * off
-            d.rows, d.cols, d.ld, d.src_ld, d.dst_ld, d.blk0 = rows, cols, ld, src_ld, dst_ld, blk
-            d.colscale = self.params[colscale].data_ptr() if colscale else None
-            blk += (rows * ld + 1023) // 1024
-            descs.append(d)
-        self._rest_table = (ops.device_table(descs), len(descs), blk) if descs else None
+        self._rest_table = self._pack_table(rest)
         self._adam_plain = plain
         self._adam_table = self._adam_segments(None)
 
@@ -313,7 +306,7 @@ class ParamStore:
         runs of consecutive parameters without one.  group_of (bpm_adam_step_groups): {parameter name: group index, or -1
         for a parameter that is not stepped}; a run is then cut wherever the group changes, so that a segment belongs to
         exactly one group.  A parameter's alignment padding rides with it; offsets are 64-element aligned, so every cut
-        is 16-byte aligned.  None: every segment in group 0 (the tables of bpm_adam_step_table / _clip)."""
+        is 16-byte aligned.  None: every segment in group 0 (`_adam_table`)."""
         esz = 2 if self.dtype == BPM_BF16 else 4
         plain = self._adam_plain
         nblk = ops.adam_blocks
@@ -400,35 +393,31 @@ class ParamStore:
 
     def adam_step(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                   zero_grad: bool, scale_dev: Optional[torch.Tensor] = None) -> None:
-        """One launch: torch.optim.Adam's update of every trunk parameter (flat master / gradient / moments) AND the CT
-        shadows of the plain weight matrices, written from the updated values as they are stored.  What is left for the
-        next forward's refresh_shadows is the small rest (K / V weights with the LayerNorm gain folded in, folded biases).
-        scale_dev: one device float multiplied into grad_scale by the kernel (the clip coefficient of grad_sumsq)."""
-        tab, nseg, nblk = self._adam_table
-        if scale_dev is None:
-            ops.adam_step_table(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, lr, beta1, beta2, eps,
-                                weight_decay, step, grad_scale, zero_grad)
-        else:
-            ops.adam_step_table_clip(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, lr, beta1, beta2,
-                                     eps, weight_decay, step, grad_scale, scale_dev, zero_grad)
-        # every plain shadow now holds the CT image of its updated master (whatever was pending before the step); the rest
-        # (shadows that mix parameters, folded biases) is stale until the next refresh_shadows
-        self._dirty, self._dirty_rest, self._shadow_sig = False, True, self._versions()
+        """adam_step_groups over the whole trunk (`_adam_table`) as one L2 group at the host's step number."""
+        one = ops.adam_groups([dict(lr=lr, betas=(beta1, beta2), eps=eps, weight_decay=weight_decay, step=step)])
+        self.adam_step_groups(exp_avg, exp_avg_sq, self._adam_table, one, grad_scale, zero_grad, scale_dev=scale_dev)
 
     def adam_step_groups(self, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor, table, groups, grad_scale,
                          zero_grad: bool, scale_dev: Optional[torch.Tensor] = None, norm_dev: Optional[torch.Tensor] = None,
                          steps_dev: Optional[torch.Tensor] = None, skipped_dev: Optional[torch.Tensor] = None) -> None:
-        """adam_step with parameter groups (bpm_adam_step_groups): table = adam_group_table({parameter name: index into
-        `groups`}); groups = ops.adam_groups(...).  norm_dev: the step is skipped on the device when that norm is not
-        finite.  Still one launch that writes the plain shadows of what it steps."""
+        """One launch (bpm_adam_step_groups): torch.optim.Adam's update of the trunk parameters (flat master / gradient /
+        moments) AND the CT shadows of the plain weight matrices, written from the updated values as they are stored.  What
+        is left for the next forward's refresh_shadows is the small rest (K / V weights with the LayerNorm gain folded in,
+        folded biases).  table = adam_group_table({parameter name: index into `groups`}) or `_adam_table`; groups =
+        ops.adam_groups(...).  scale_dev: one device float multiplied into grad_scale by the kernel (the clip coefficient
+        of grad_sumsq).  norm_dev: the step is skipped on the device when that norm is not finite.
+        When a full refresh is pending (the masters were edited since the last one) it runs first, one extra pack_weights
+        launch: this launch need not rewrite every plain shadow (a parameter that is not stepped, a skipped step).  The
+        stored results are the same with or without it, and a training loop never pays it: its forward has refreshed."""
         tab, nseg, nblk = table
-        if getattr(self, "_dirty", True) or self._versions() != getattr(self, "_shadow_sig", None):
-            # a full refresh is pending (the masters were edited), and this launch need not rewrite every plain shadow (a
-            # parameter that is not stepped, a skipped step): derive them now, so that what is left below is the rest
+        sig = self._versions()                             # (the launches below go through raw pointers: no counter moves)
+        if self._dirty or sig != self._shadow_sig:
             self.refresh_shadows()
         ops.adam_step_groups(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, groups, grad_scale,
                              zero_grad, scale_dev, norm_dev, steps_dev, skipped_dev)
-        self._dirty, self._dirty_rest, self._shadow_sig = False, True, self._versions()
+        # every plain shadow now holds the CT image of its master; the rest (shadows that mix parameters, folded biases) is
+        # stale until the next refresh_shadows
+        self._dirty, self._dirty_rest, self._shadow_sig = False, True, sig
 
     def sptr(self, key: str, elem_off: int = 0) -> int:
         return self.shadow_flat.data_ptr() + self.shadow_flat.element_size() * (self._shadow_off[key] + elem_off)
@@ -456,13 +445,13 @@ class ParamStore:
         since the last refresh (an optimizer step, load_state_dict, any in-place edit: torch's per-tensor version
         counters, or mark_dirty() for raw-pointer writers).  In a training loop that is once per optimizer step."""
         sig = self._versions()
-        full = force or getattr(self, "_dirty", True) or sig != getattr(self, "_shadow_sig", None)
-        if not full and not getattr(self, "_dirty_rest", False):
+        full = force or self._dirty or sig != self._shadow_sig
+        if not full and not self._dirty_rest:
             return
         self._dirty, self._dirty_rest, self._shadow_sig = False, False, sig
         if full:
             if self._table is not None:
-                ops.pack_weights(self.dtype, self._table, self._ndesc, self._nblk)
+                ops.pack_weights(self.dtype, *self._table)
         elif self._rest_table is not None:         # after a fused optimizer step: it wrote the plain shadows itself
             ops.pack_weights(self.dtype, *self._rest_table)
         if self._fold_table is not None:

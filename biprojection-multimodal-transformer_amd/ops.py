@@ -368,30 +368,6 @@ def adam_blocks(n4: int) -> int:
     return int(_lib.lib().bpm_adam_blocks(n4)) if not _DRY_RUN else (n4 + 1023) // 1024
 
 
-def adam_step_table(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
-                    grad_scale, zero_grad) -> None:
-    for t in (master, grad, exp_avg, exp_avg_sq):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != master.numel():
-            raise ValueError("adam_step_table: flat contiguous float32 buffers of one size")
-    _lib.check(_lib.lib().bpm_adam_step_table(dtype, table_dev.data_ptr(), nseg, nblk, _p(master), _p(grad), _p(exp_avg), _p(exp_avg_sq),
-                                              lr, beta1, beta2, eps, weight_decay, step, grad_scale, int(bool(zero_grad)), _stream()),
-               "bpm_adam_step_table")
-
-
-def adam_step_table_clip(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step,
-                         grad_scale, scale_dev, zero_grad) -> None:
-    """adam_step_table with the gradient scale grad_scale * scale_dev[0] (a device float, e.g. grad_sumsq's coefficient)."""
-    for t in (master, grad, exp_avg, exp_avg_sq):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != master.numel():
-            raise ValueError("adam_step_table_clip: flat contiguous float32 buffers of one size")
-    if scale_dev is not None and (scale_dev.dtype != torch.float32 or scale_dev.numel() < 1):
-        raise ValueError("adam_step_table_clip: scale_dev is a float32 device tensor")
-    _lib.check(_lib.lib().bpm_adam_step_table_clip(dtype, table_dev.data_ptr(), nseg, nblk, _p(master), _p(grad), _p(exp_avg),
-                                                   _p(exp_avg_sq), lr, beta1, beta2, eps, weight_decay, step, grad_scale,
-                                                   _p(scale_dev), int(bool(zero_grad)), _stream()),
-               "bpm_adam_step_table_clip")
-
-
 def adam_groups(groups) -> "C.Array":
     """[{lr, betas, eps, weight_decay, decoupled_weight_decay, step}] -> the host array bpm_adam_step_groups takes."""
     if not 1 <= len(groups) <= _lib.ADAM_MAX_GROUPS:

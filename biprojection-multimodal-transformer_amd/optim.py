@@ -4,16 +4,16 @@ The reference trains with `torch.optim.Adam(model.parameters(), lr=...)` (train.
 `ReduceLROnPlateau` (train.py:128-136), steps it after the backward pass (train.py:396-398) and stores
 `optimizer.state_dict()` in its checkpoints (train.py:372-379).  Here every trunk parameter is a view into one flat fp32
 master buffer and its gradient a view into one flat gradient buffer (engine.ParamStore), so the optimizer step for ~all
-of the model is ONE streaming kernel (`bpm_adam_step`) instead of a foreach loop over ~1700 tensors; the few parameters
+of the model is ONE streaming kernel (`bpm_adam_step_groups`) instead of a foreach loop over ~1700 tensors; the few parameters
 outside the trunk (final GMU, head, front-ends) go through an ordinary torch.optim.Adam with the same hyper-parameters.
 
 `FusedAdam` IS a `torch.optim.Optimizer` (by default one param group holding every trainable model parameter), so LR
 schedulers and the reference's checkpoint code accept it; every group's hyper-parameters are read at every step.
 
 Parameter groups (per-group lr / betas / eps / weight decay, L2 or decoupled), parameters left out of every group, and a
-step that skips itself when the gradient norm is not finite all stay ONE launch over the flat buffers
-(`bpm_adam_step_groups`): the segment table carries each segment's group, the groups' constants ride in the kernel
-arguments, and the skip decision is a device float the norm reduction left behind.
+step that skips itself when the gradient norm is not finite all stay that ONE launch over the flat buffers: the segment
+table carries each segment's group, the groups' constants ride in the kernel arguments, and the skip decision is a device
+float the norm reduction left behind.  The default construction is the same launch with one group.
 
 Global-norm gradient clipping (`max_grad_norm`; upstream MulT calls `torch.nn.utils.clip_grad_norm_(model.parameters(), 0.8)`
 before `optimizer.step()`) is part of the step: one reduction over the flat gradient buffer (`bpm_grad_sumsq`) leaves the
@@ -51,8 +51,8 @@ class FusedAdam(torch.optim.Optimizer):
     their bits, and it does not count in the clip norm (its slice of the flat gradient buffer, which the backward
     launches still fill, is only cleared under `fused_zero_grad`).  `decoupled_weight_decay` (per group): p *= 1 - lr *
     wd first, then the Adam update on the undecayed gradient -- `torch.optim.AdamW`.  The trunk goes through ONE launch
-    whatever the groups are (`bpm_adam_step_groups`: a block looks up its segment's group); the default construction on
-    a model whose trunk is all trainable launches `bpm_adam_step_table` / `_clip` as it always has.
+    whatever the groups are (`bpm_adam_step_groups`: a block looks up its segment's group), the default construction's
+    single group included.
 
     `max_grad_norm=c` clips the global gradient norm to c inside the step, as `torch.nn.utils.clip_grad_norm_(
     params, c)` in front of it would: ONE norm over the parameters of all groups, coefficient min(1, c / (norm + 1e-6)),
@@ -194,15 +194,10 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("no parameter of the flat trunk buffers is in any parameter group: FusedAdam steps the trunk "
                              "(and the tail beside it); for tail parameters alone use torch.optim.Adam")
         self._group_of = group_of
-        self._group_table = None                           # bpm_adam_step_groups' segment table: built by the first step that needs it
+        self._group_table = None                           # bpm_adam_step_groups' segment table: built by the next step
         self._trunk_set = frozenset(group_of)
         self._all_trunk = len(group_of) == len(st.params)
         self._stale = False
-
-    def _grouped(self) -> bool:
-        """False: the one-group L2 step over an all-trainable trunk, which stays on bpm_adam_step_table / _clip."""
-        return (self.skip_nonfinite or len(self.param_groups) > 1 or not self._all_trunk
-                or self.param_groups[0]["decoupled_weight_decay"])
 
     def _applied_steps(self) -> List[int]:
         if self._counters is not None and self.skip_nonfinite:
@@ -232,33 +227,28 @@ class FusedAdam(torch.optim.Optimizer):
             raise RuntimeError("flat parameter buffer is not a multiple of 4 elements")
         clip = g.get("max_grad_norm")
         tail = [p for tg in self._tail_opt.param_groups for p in tg["params"]] if self._tail_opt is not None else []
-        grouped = self._grouped()
         coef = norm = None
         if clip is not None or self.skip_nonfinite:
-            # the trunk's share: one reduction over gflat; the tail's (PyTorch-owned parameters) through torch; one root.
-            # Norm and coefficient stay on the device: the Adam kernel and the tail read them there.
+            # the trunk's share: one reduction over gflat (the store's own table when every trunk parameter is stepped); the
+            # tail's (PyTorch-owned parameters) through torch; one root.  Norm and coefficient stay on the device: the Adam
+            # kernel and the tail read them there.
             _check_max_norm(clip)
             tail_grads = [p.grad for p in tail if p.grad is not None]
             res = st.grad_sumsq(grad_scale, float(clip) if clip is not None else 0.0, _sumsq(tail_grads),
-                                names=self._trunk_set if grouped else None)
+                                names=None if self._all_trunk else self._trunk_set)
             self.last_grad_norm = res[0].clone()
             coef = res[1:2] if clip is not None else None
             norm = res[0:1] if self.skip_nonfinite else None
         # one launch: the update of every trunk parameter AND the CT shadows of the plain weight matrices, written from
         # the updated masters as they are stored (no second pass over the flat master for the next forward's operands)
-        if not grouped:
-            self._group_steps[0] += 1
-            st.adam_step(self._m, self._v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self._group_steps[0],
-                         grad_scale, self.fused_zero_grad, scale_dev=coef)
-        else:
-            if norm is None:
-                self._group_steps = [s + 1 for s in self._group_steps]
-            hyper = ops.adam_groups([dict(pg, step=s) for pg, s in zip(self.param_groups, self._group_steps)])
-            if self._group_table is None:
-                self._group_table = st.adam_group_table(self._group_of)
-            st.adam_step_groups(self._m, self._v, self._group_table, hyper, grad_scale, self.fused_zero_grad, scale_dev=coef,
-                                norm_dev=norm, steps_dev=None if norm is None else self._counters,
-                                skipped_dev=None if norm is None else self._counters[_lib.ADAM_MAX_GROUPS:])
+        if norm is None:                                   # (under skip_nonfinite the counts live on the device)
+            self._group_steps = [s + 1 for s in self._group_steps]
+        hyper = ops.adam_groups([dict(pg, step=s) for pg, s in zip(self.param_groups, self._group_steps)])
+        if self._group_table is None:
+            self._group_table = st.adam_group_table(self._group_of)
+        st.adam_step_groups(self._m, self._v, self._group_table, hyper, grad_scale, self.fused_zero_grad, scale_dev=coef,
+                            norm_dev=norm, steps_dev=None if norm is None else self._counters,
+                            skipped_dev=None if norm is None else self._counters[_lib.ADAM_MAX_GROUPS:])
         if self._tail_opt is not None:
             for tg, gi in zip(self._tail_opt.param_groups, self._tail_gi):
                 for k in _HYPER:

@@ -418,7 +418,8 @@ int bpm_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, 
  * aligned), blk0 = first block (a segment takes bpm_adam_blocks(n4) blocks; entries sorted by blk0, covering the buffer).
  * dst != NULL: the segment starts with a whole [rows, cols] fp32 matrix (cols % 4 == 0) whose CT shadow is [rows, dst_ld];
  * shadow element (r, c) = CT(updated master (r, c)), pad columns are not touched.  dtype = the shadows' CT.
- * group: read by bpm_adam_step_groups only (below); the entries here ignore it, and their tables hold 0 there. */
+ * group: read by bpm_adam_step_groups only (below).  bpm_adam_step_table and bpm_adam_step_table_clip are entries into the
+ * same kernel with one L2 group at the host's `step`; they ignore the word, whatever a caller's table holds there. */
 typedef struct bpm_adam_seg {
     size_t off4;
     unsigned n4;
@@ -460,22 +461,23 @@ int bpm_grad_sumsq(const bpm_sumsq_seg* table_dev, int nseg, unsigned total_bloc
 
 /* bpm_adam_step_table with the gradient scale grad_scale * (*scale_dev): scale_dev is a device float written by an earlier
  * launch on the stream (out + 1 of bpm_grad_sumsq: the clip coefficient), read once per block.  scale_dev = NULL is
- * bpm_adam_step_table itself (the same kernel); *scale_dev == 1 gives bit-equal results. */
+ * bpm_adam_step_table itself; *scale_dev == 1 gives bit-equal results. */
 int bpm_adam_step_table_clip(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
                              float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay,
                              int step, float grad_scale, const float* scale_dev, int zero_grad, void* stream);
 
 /* The table-driven step with PARAMETER GROUPS, decoupled weight decay and a skip on a non-finite gradient norm: what
  * torch.optim.Adam(param_groups, decoupled_weight_decay=...) does for the trunk, and what torch.amp.GradScaler makes an
- * optimizer do when a gradient is inf / NaN.  Still one launch over the flat buffers that writes the CT shadows.
+ * optimizer do when a gradient is inf / NaN.  Still one launch over the flat buffers that writes the CT shadows: THE
+ * table-driven Adam kernel, which the two entries above launch as well.
  * Table: bpm_adam_seg as above, with seg.group = index into `groups` of the group the segment's parameters belong to (a
  * segment belongs to exactly one group), or -1: NOT STEPPED -- nothing of the segment is loaded and nothing stored (master,
  * moments and shadow keep their bits), except zeros to its gradients when zero_grad != 0 (a frozen parameter's slice is
  * still filled by the backward launches and must not grow for ever).  A group index >= ngroups is treated as -1.
  * groups: HOST array of ngroups (1 .. BPM_ADAM_MAX_GROUPS) entries, copied into the launch.  decoupled == 0: L2 decay,
- * g = grad * scale + weight_decay * p, the arithmetic of bpm_adam_step_table (one group 0 over the whole table gives
- * bit-equal results).  decoupled != 0: p *= 1 - lr * weight_decay first, then the Adam update on the undecayed gradient
- * (torch.optim.AdamW).  step: the group's 1-based step number for the bias corrections when steps_dev == NULL.
+ * g = grad * scale + weight_decay * p, the arithmetic of bpm_adam_step (one group 0 over the whole table is what
+ * bpm_adam_step_table / _clip launch).  decoupled != 0: p *= 1 - lr * weight_decay first, then the Adam update on the
+ * undecayed gradient (torch.optim.AdamW).  step: the group's 1-based step number for the bias corrections when steps_dev == NULL.
  * scale_dev: NULL or a device float multiplied into grad_scale (the clip coefficient, out + 1 of bpm_grad_sumsq).
  * norm_dev: NULL or a device float (out of bpm_grad_sumsq); when it is NaN or +-inf the step is SKIPPED: every block
  * stores nothing but the cleared gradients.  The decision is taken on the device; the host never waits.

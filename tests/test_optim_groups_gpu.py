@@ -1,19 +1,24 @@
-"""FusedAdam's parameter groups on the MI355X: bpm_adam_step_groups against bpm_adam_step_table (bit-equal for one L2 group)
-and against torch.optim.Adam with the same groups (L2 and decoupled decay, parameters in no group, a step left out for
-a non-finite norm, a group added later), and the Python surface end to end.
+"""FusedAdam's parameter groups on the MI355X: bpm_adam_step_groups against the recorded bits of the one-group table step
+(bpm_adam_step_table / _clip are now entries into the same kernel) and against torch.optim.Adam with the same groups
+(L2 and decoupled decay, parameters in no group, a step left out for a non-finite norm, a group added later), and the
+Python surface end to end.
 
 Kernel-level comparisons run on GIVEN gradients (one magnitude in 1e-6 .. 1 per parameter) and hold the project's kernel
 limit, max-abs 2e-6 against torch (test_fused_adam_kernel_exact): an fp32 restatement of both updates stays within 2.4e-7
 of torch.optim.Adam at learning rates <= 3e-3 over four steps, one of them left out."""
 import copy
+import ctypes as C
+import hashlib
+import json
 import math
+import os
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from bpmult_amd import ops  # noqa: E402
+from bpmult_amd import _lib, ops  # noqa: E402
 from bpmult_amd.models import get_model  # noqa: E402
 from bpmult_amd.optim import FusedAdam, decay_groups  # noqa: E402
 from test_model_gpu import args_for  # noqa: E402
@@ -98,11 +103,19 @@ def padded():
     return m, st, st.master.clone(), st.shadow_flat.clone(), grads
 
 
+def sha256(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
 def test_one_group_is_the_existing_step(padded):
-    """Every segment in group 0 with L2 decay: master, both moments and the shadows bit-equal to ParamStore.adam_step
-    (bpm_adam_step_table / _clip), with and without scale_dev.  With the step count on the device the bias corrections
-    are taken there (integer power by squaring instead of the host's pow): the kernel limit holds, and the counter
-    advances."""
+    """Every segment in group 0 with L2 decay, through ParamStore.adam_step_groups and through ParamStore.adam_step, with
+    and without scale_dev: master, both moments and the shadows carry the SHA-256 digests that the separate one-group
+    kernel of bpm_adam_step_table / _clip left for the same start values on the commit before it was folded into the
+    grouped kernel (tests/golden/adam_one_group_digests.json; there the two kernels gave equal bits).  The flat
+    bpm_adam_step is no stand-in for that record: its results were not bit-equal to the table kernel's on that commit.
+    Independently of the record, the plain shadows are bit-equal to a forced refresh_shadows of the stepped masters and
+    every other shadow element is untouched.  With the step count on the device the bias corrections are taken there
+    (integer power by squaring instead of the host's pow): the kernel limit holds, and the counter advances."""
     m, st, master0, shadow0, grads = padded
     n = st.total
     g = torch.Generator().manual_seed(4)
@@ -111,6 +124,10 @@ def test_one_group_is_the_existing_step(padded):
     hp = dict(lr=3e-3, beta1=0.9, beta2=0.98, eps=1e-8, weight_decay=0.01)
     one = [dict(lr=3e-3, betas=(0.9, 0.98), eps=1e-8, weight_decay=0.01, step=2)]
     everyone = {k: 0 for k in st.names}
+    plain = torch.zeros(st.shadow_flat.numel(), dtype=torch.bool, device=DEV)
+    for rows, cols, dst_ld, off in st._adam_plain.values():
+        plain[off: off + rows * dst_ld] = True
+    assert bool(plain.any()) and not bool(plain.all())
 
     def run(grouped, scale_dev, steps_dev=None):
         st.master.copy_(master0)
@@ -124,11 +141,23 @@ def test_one_group_is_the_existing_step(padded):
         return st.master.clone(), ma, va, st.shadow_flat.clone()
 
     assert st.adam_group_table(everyone)[1:] == st._adam_table[1:]
-    for scale in (None, torch.tensor([0.37], device=DEV)):
-        old, new = run(False, scale), run(True, scale)
-        for a, b, what in zip(old, new, ("master", "exp_avg", "exp_avg_sq", "shadows")):
-            assert torch.equal(a, b), (what, scale)
-        assert not torch.equal(old[0], master0) and not torch.equal(old[3], shadow0)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adam_one_group_digests.json")) as f:
+        want = json.load(f)
+    names = ("master", "exp_avg", "exp_avg_sq", "shadows")
+    cases = {"no_scale_dev": None, "scale_dev_0.37": torch.tensor([0.37], device=DEV)}
+    results = {(key, grouped): run(grouped, scale) for key, scale in cases.items() for grouped in (False, True)}
+    got = {"start_values": sha256(torch.cat([master0, shadow0.float(), grads[0], m0, v0]))}
+    for (key, grouped), res in results.items():
+        got[key + (" adam_step_groups" if grouped else " adam_step")] = dict(zip(names, map(sha256, res)))
+    print(json.dumps(got))
+    assert got["start_values"] == want["start_values"], "not the start values of the record: the digests cannot match"
+    for (key, grouped), res in results.items():
+        assert got[key + (" adam_step_groups" if grouped else " adam_step")] == want[key], (key, grouped)
+        st.master.copy_(res[0])
+        st.refresh_shadows(force=True)
+        assert torch.equal(st.shadow_flat[plain], res[3][plain]), ("shadows", key, grouped)
+        assert torch.equal(res[3][~plain], shadow0[~plain]), ("the other shadows", key, grouped)
+        assert not torch.equal(res[0], master0) and not torch.equal(res[3][plain], shadow0[plain])
     steps = torch.tensor([1, 7], device=DEV, dtype=torch.int32)
     host, dev = run(False, None), run(True, None, steps_dev=steps)
     for a, b, what in zip(host[:3], dev[:3], ("master", "exp_avg", "exp_avg_sq")):
@@ -136,6 +165,38 @@ def test_one_group_is_the_existing_step(padded):
         print("device step count,", what, "max-abs", d)
         assert d <= LIMIT, what
     assert steps.tolist() == [2, 7]
+    st.master.copy_(master0)
+    st.refresh_shadows(force=True)
+
+
+def test_table_entries_ignore_the_group_word(padded):
+    """bpm_adam_step_table on the store's table and on a copy whose segments carry 7 and -1 in their `group` words (a
+    caller's table from before the word had a meaning may hold anything there): master, moments and shadows bit-equal."""
+    m, st, master0, shadow0, grads = padded
+    tab, nseg, nblk = st._adam_table
+    words = C.sizeof(_lib.AdamSeg) // 4
+    host = tab.cpu().view(torch.int32).view(nseg, words).clone()
+    assert _lib.AdamSeg.group.offset == 4 * (words - 1) and nseg >= 2 and int(host[:, -1].abs().max()) == 0
+    host[0::2, -1], host[1::2, -1] = 7, -1
+    scribbled = host.view(-1).view(torch.uint8).to(DEV)
+    g = torch.Generator().manual_seed(5)
+    m0 = (torch.randn(st.total, generator=g) * 1e-2).to(DEV)
+    v0 = (torch.rand(st.total, generator=g) * 1e-4).to(DEV)
+
+    def run(table):
+        st.master.copy_(master0)
+        st.shadow_flat.copy_(shadow0)
+        st.gflat.copy_(grads[1])
+        ma, va = m0.clone(), v0.clone()
+        _lib.check(_lib.lib().bpm_adam_step_table(st.dtype, table.data_ptr(), nseg, nblk, st.master.data_ptr(), st.gflat.data_ptr(),
+                                                  ma.data_ptr(), va.data_ptr(), 3e-3, 0.9, 0.98, 1e-8, 0.01, 3, 0.5, 0,
+                                                  torch.cuda.current_stream().cuda_stream), "bpm_adam_step_table")
+        return st.master.clone(), ma, va, st.shadow_flat.clone()
+
+    want, got = run(tab), run(scribbled)
+    for a, b, what in zip(want, got, ("master", "exp_avg", "exp_avg_sq", "shadows")):
+        assert torch.equal(a, b), what
+    assert not torch.equal(want[0], master0) and not torch.equal(want[3], shadow0)
     st.master.copy_(master0)
     st.refresh_shadows(force=True)
 

@@ -4,7 +4,7 @@ same model and the same gradients, HIP events around each phase, the variants al
 
   a  FusedAdam.step()                                                      (no clipping)
   b  torch.nn.utils.clip_grad_norm_(model.parameters(), c); FusedAdam.step()
-  c  FusedAdam(max_grad_norm=c).step()                                      (bpm_grad_sumsq + bpm_adam_step_table_clip)
+  c  FusedAdam(max_grad_norm=c).step()                                      (bpm_grad_sumsq + bpm_adam_step_groups)
 
 and the reduction alone (ParamStore.grad_sumsq: both launches), with the HBM rate it reaches over the bytes it reads.
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Cost of parameter groups, decoupled decay and the non-finite skip in the optimizer phase of a bench.py configuration
 (one GPU), four ways on the same model and the same gradients, HIP events around each step, the variants alternating in
-one process after warm-up:
+one process after warm-up.  Every variant is the same launch, bpm_adam_step_groups, over a table of its own:
 
-  a  FusedAdam(model)                                               (bpm_adam_step_table on the ungrouped table)
-  b  FusedAdam(param_groups=decay_groups(decoupled_weight_decay))   (bpm_adam_step_groups, two groups)
+  a  FusedAdam(model)                                               (one L2 group over the whole trunk)
+  b  FusedAdam(param_groups=decay_groups(decoupled_weight_decay))   (two groups)
   c  b with skip_nonfinite=True                                     (+ bpm_grad_sumsq, device counters, fused torch Adam on the tail)
   d  b with one large matrix left out of every group                (a segment that is not stepped)
 
@@ -69,12 +69,10 @@ def main():
             e1.synchronize()
             ms[k].append(e0.elapsed_time(e1))
     med = {k: round(statistics.median(v), 4) for k, v in ms.items()}
-    tables = {k: o._group_table[1:] for k, o in opts.items() if k != "a_adam"}
     out = {"config": a.config, "precision": a.precision, "reps": a.reps, "median_ms": med,
            "min_ms": {k: round(min(v), 4) for k, v in ms.items()}, "max_ms": {k: round(max(v), 4) for k, v in ms.items()},
            "flat_buffer_bytes": 4 * st.total, "left_out_elements": big.numel(),
-           "segments_blocks": dict(tables, a_adam=st._adam_table[1:]),
-           "a_is_ungrouped": not opts["a_adam"]._grouped(), "skipped_steps": int(opts["c_groups_skip_nonfinite"].skipped_steps),
+           "segments_blocks": {k: o._group_table[1:] for k, o in opts.items()}, "skipped_steps": int(opts["c_groups_skip_nonfinite"].skipped_steps),
            "vs_a_ms": {k: round(med[k] - med["a_adam"], 4) for k in med if k != "a_adam"}}
     print(json.dumps(out))
 
