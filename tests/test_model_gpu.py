@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 from detgen import det, det_param  # noqa: E402
 
 import bpmult_amd  # noqa: E402
+from bpmult_amd._lib import GEMM_NN, GEMM_NT, GEMM_TN  # noqa: E402
 from bpmult_amd.models import get_model  # noqa: E402
 
 G = os.path.join(os.path.dirname(__file__), "golden")
@@ -97,9 +98,25 @@ def _record(tag, prec, rec):
 SCHEDULES = [pytest.param(True, id="pruned"), pytest.param(False, id="dense")]
 
 
-def run_model(g, model, pfx, inputs, call, prec, BF16_GRAD=BF16_GRAD_TOY, BF16_GNORM=1e-1, prune=False):
+def run_model(g, model, pfx, inputs, call, prec, BF16_GRAD=BF16_GRAD_TOY, BF16_GNORM=1e-1, prune=False, x3_split=()):
     """Both schedules are held to the SAME reference fixture and the same limits: `prune` = exact dead-row elimination
-    (the library's default), dense = the reference's own schedule."""
+    (the library's default), dense = the reference's own schedule.  x3_split: the operand arrangements
+    (GEMM_NT / GEMM_NN / GEMM_TN) of which at least one launch must have run as split-bf16 products in bf16x3 mode --
+    below 256 rows / columns / k a bf16x3 model runs exact fp32 products and would prove nothing about the split path."""
+    from bpmult_amd import ops
+    split_ran, plan_run = set(), ops._X3Plan.run
+
+    def counted_run(self, L, variant, seed, s):
+        assert self.ok
+        split_ran.add(variant)
+        return plan_run(self, L, variant, seed, s)
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(ops._X3Plan, "run", counted_run)
+        return _run_model(g, model, pfx, inputs, call, prec, BF16_GRAD, BF16_GNORM, prune, x3_split, split_ran)
+
+
+def _run_model(g, model, pfx, inputs, call, prec, BF16_GRAD, BF16_GNORM, prune, x3_split, split_ran):
     model.set_prune_unused_rows(prune)
     with torch.no_grad():
         for k, p in model.named_parameters():
@@ -111,6 +128,8 @@ def run_model(g, model, pfx, inputs, call, prec, BF16_GRAD=BF16_GRAD_TOY, BF16_G
     tgt = (T(det(pfx + "tgt", tuple(logits.shape))) > 0).float().cuda()
     loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, tgt)
     loss.backward()
+    if prec == "bf16x3":
+        assert set(x3_split) <= split_ran, f"split-bf16 launches ran for {sorted(split_ran)}, expected {sorted(x3_split)}"
     rec = {}
     for nm, t in (("logits", logits), ("z", z), ("loss", loss)):
         e, scale, rel = err(t, g[nm])
@@ -185,8 +204,10 @@ def test_f9_cfg1_shape(prec, prune):
     g = load("f9_cfg1")
     model = get_model(args_for("mmtrvat"))
     inputs = {"xl": T(det("f9.xl", (2, 20, 768))), "img": T(det("f9.img", (2, 500, 35))), "aud": T(det("f9.aud", (2, 400, 74)))}
+    # (bf16x3 at d = 300: the forward and data-gradient products split; no weight-gradient launch reaches the 96 tiles of
+    # 256 x 256 the split path asks of one -- F11 covers those)
     run_model(g, model, "f9.", inputs, lambda m, d: m(d["xl"], None, None, d["img"], d["aud"], output_gate=True), prec,
-              BF16_GRAD=BF16_GRAD, prune=prune)
+              BF16_GRAD=BF16_GRAD, prune=prune, x3_split=(GEMM_NT, GEMM_NN))
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(G, "f10_cfg3.npz")), reason="f10 fixture not generated")
@@ -229,7 +250,7 @@ def test_f11_headline(prec, prune):
     assert sorted(k for k, _ in model.named_parameters()) == sorted(g["param_names"].tolist())
     inputs = {"xl": T(det("f11.xl", (1, 20, 768))), "img": T(det("f11.img", (1, 500, 35))), "aud": T(det("f11.aud", (1, 400, 74)))}
     run_model(g, model, "f11.", inputs, lambda m, d: m(d["xl"], None, None, d["img"], d["aud"], output_gate=True), prec,
-              BF16_GRAD=BF16_GRAD, BF16_GNORM=BF16_GNORM_BIG, prune=prune)
+              BF16_GRAD=BF16_GRAD, BF16_GNORM=BF16_GNORM_BIG, prune=prune, x3_split=(GEMM_NT, GEMM_NN, GEMM_TN))
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(G, "f12_k768.npz")), reason="f12 fixture not generated")
@@ -352,7 +373,8 @@ def test_low_rank_key_side_equals_the_dk_dv_route(prec, B):
     """Level 2 of the pruned 3-modal model, TRAINING mode with every dropout on (attention dropout included: the folded
     value-bias gradient then carries rowsum(Pd) != 1): the low-rank key side (dS / Pd from the dQ pass, bpm_expand_heads,
     batched products; engine.EncoderGroupPlan._lowrank) against the dK / dV route on the same weights, inputs and seeds --
-    the same dropout masks, so the two may differ by rounding only.  Key lengths that are not whole 64-key tiles (96)."""
+    the same dropout masks, so the two may differ by rounding only.  Key lengths that are not whole 64-key tiles (96).
+    At hidden 48 the bf16x3 case runs exact fp32 products (ops._X3Plan._eligible needs M, N, K >= 256)."""
     import copy
     from bpmult_amd import engine
     torch.manual_seed(5)
