@@ -131,6 +131,15 @@ class AttnProblem(C.Structure):
                 ("dS", C.c_void_p), ("Pd", C.c_void_p), ("xs_b", C.c_int), ("xs_h", C.c_int), ("xs_q", C.c_int)]
 
 
+class AttnKMask(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("ldm", C.c_int)]
+
+
+class GeluProblem(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("ldu", C.c_int), ("u_is_ct", C.c_int), ("g", C.c_void_p), ("ldg", C.c_int),
+                ("dg", C.c_void_p), ("lddg", C.c_int), ("du", C.c_void_p), ("lddu", C.c_int), ("R", C.c_int), ("C", C.c_int)]
+
+
 class AttnMapProblem(C.Structure):
     _fields_ = [("Q", C.c_void_p), ("K", C.c_void_p), ("lse", C.c_void_p), ("W", C.c_void_p), ("ldw", C.c_int),
                 ("B", C.c_int), ("H", C.c_int), ("T", C.c_int), ("S", C.c_int), ("dh", C.c_int), ("dhp", C.c_int),
@@ -250,7 +259,12 @@ SIGNATURES = {
     "bpm_attn_bwd": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
     "bpm_attn_bwd_dq": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
     "bpm_attn_bwd_dkv": [_I, C.POINTER(AttnProblem), _I, _U64, _P],
+    "bpm_attn_fwd_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), _I, _U64, _P],
     "bpm_attn_maps": [_I, C.POINTER(AttnMapProblem), _I, _P],
+    "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
+    "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_pack_rows_fwd": [_I, C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_rows_bwd": [C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_weights": [_I, _P, _I, C.c_uint, _P],

@@ -100,6 +100,16 @@ struct AGroup {
     AProb p[BPM_MAX_GROUP];
 };
 
+// Per-key padding mask of the *_kmask entries (HF's attention_mask): bytes [B, ldm], key j of sample b is visible iff
+// mask[b * ldm + j] != 0, ANDed with the mask_off rule.  A second argument block beside AGroup, so the unmasked kernels
+// keep their argument layout (and their code: the block bodies below take the mask as a compile-time switch).
+struct AMask { const uint8_t* mask; int ldm; };
+struct AGroupK {
+    AGroup g;
+    AMask m[BPM_MAX_GROUP];
+};
+static_assert(sizeof(AGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
+
 template <typename CT, int DHP> struct Cfg {
     static constexpr int SZ = sizeof(CT);
     static constexpr int NKS = DHP / Tr<CT>::KSTEP;        // k-steps over head_dim
@@ -174,6 +184,15 @@ BPM_DEV const AProb& pick(const AGroup& grp, int& bid) {
     return grp.p[pi];
 }
 
+BPM_DEV int pick_index(const AGroup& grp, int& bid) {      // the *_kmask kernels: the problem's index also selects its mask
+    int pi = 0;
+#pragma unroll 1
+    for (int i = 1; i < grp.nprob; ++i)
+        if (bid >= grp.p[i].blk0) pi = i;
+    bid -= grp.p[pi].blk0;
+    return pi;
+}
+
 // ---------------------------------------------------------------------------
 // Row-contiguous store of one wave's 16 x dh result tile.  The MFMA leaves lane (c = lane & 15, g = lane >> 4) with
 // columns 16n + 4g + r of row c; written from there, every element is its own 2-byte request to L2 (64 lanes x 16
@@ -227,12 +246,17 @@ BPM_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_ex
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <typename CT, int DHP>
-BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb) {
+// KM: with a per-key mask (AMask).  The tile's KT mask bytes are fetched one tile ahead by the first KT threads (never at
+// j >= S: those keys are hidden without a load), pass through KT bytes of LDS behind the K / V images as 0 / 1, and every
+// lane reads the four words that cover its 16 keys.  A hidden key's score becomes -inf before the maximum, like a key
+// beyond the mask_off limit; a tile without any visible key is skipped.  Without KM none of this is compiled.
+template <typename CT, int DHP, bool KM>
+BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
     char* vimg = smem + KT * C::STRIDE;
+    uint8_t* smask = (uint8_t*)(smem + 2 * KT * C::STRIDE);    // KM only
 
     const int b = bh / P.H, h = bh % P.H;
     int tid_ = threadIdx.x;
@@ -264,14 +288,33 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
     const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
 
     RowStage<CT, DHP, KT> kst, vst;
-    if (ntile > 0) { kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid); }
+    uint32_t n_vis = 0;                                // KM, threads < KT: next tile's visibility of key kt * KT + tid
+    auto stage_mask = [&](int kt) {
+        const int jm = kt * KT + tid;
+        n_vis = 0;
+        if (tid < KT && jm < P.S) n_vis = km.mask[(size_t)b * km.ldm + jm] != 0;
+    };
+    if (ntile > 0) {
+        kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
+        if constexpr (KM) stage_mask(0);
+    }
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
         kst.store(kimg, tid);
         vst.store(vimg, tid);
+        if constexpr (KM) { if (tid < KT) smask[tid] = (uint8_t)n_vis; }
         __syncthreads();
-        if (kt + 1 < ntile) { kst.load(Kh, (kt + 1) * KT, P.S, tid); vst.load(Vh, (kt + 1) * KT, P.S, tid); }
+        if (kt + 1 < ntile) {
+            kst.load(Kh, (kt + 1) * KT, P.S, tid); vst.load(Vh, (kt + 1) * KT, P.S, tid);
+            if constexpr (KM) stage_mask(kt + 1);
+        }
+        bool k_all = true;                             // KM: every key of the tile is visible (wave-uniform)
+        if constexpr (KM) {
+            const uint32_t w = *(const uint32_t*)(smask + 4 * (lane & 15));
+            if (__builtin_amdgcn_ballot_w64(w != 0u) == 0) continue;      // no visible key (the same in every wave)
+            k_all = __builtin_amdgcn_ballot_w64(w != 0x01010101u) == 0;
+        }
 
         f32x4 st[4];
 #pragma unroll
@@ -289,6 +332,16 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
 #pragma unroll
                 for (int r = 0; r < 4; ++r) st[n][r] = (16 * n + r < rel) ? st[n][r] : -INFINITY;
         }
+        if constexpr (KM) {
+            if (!k_all) {
+#pragma unroll
+                for (int n = 0; n < 4; ++n) {
+                    const uint32_t w = *(const uint32_t*)(smask + 16 * n + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) st[n][r] = ((w >> (8 * r)) & 0xffu) ? st[n][r] : -INFINITY;
+                }
+            }
+        }
         // 3-input maxima (v_max3_f32): two chains of four instead of a tree of fifteen 2-input ones
         auto max3 = [](float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); };
         float mx = max3(max3(max3(max3(st[0][0], st[0][1], st[0][2]), st[0][3], st[1][0]), st[1][1], st[1][2]), st[1][3], st[2][0]);
@@ -296,9 +349,12 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
         mx = fmaxf(mx, my);
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        const float alpha = fast_exp2((m_run - m_new) * LOG2E);
-        const float mneg = -m_new * LOG2E;
+        float m_new = fmaxf(m_run, mx);
+        // KM: a query may have met no visible key yet (holes in front): keep the exponents finite, every p is exp2(-inf) = 0
+        float m_use = m_new;
+        if constexpr (KM) m_use = m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = fast_exp2((m_run - m_use) * LOG2E);
+        const float mneg = -m_use * LOG2E;
         m_run = m_new;
         // 4-wide float arithmetic compiles to packed-f32 VALU (v_pk_fma_f32 / v_pk_add_f32: two lanes of work per
         // instruction); only the exponentials stay scalar
@@ -378,7 +434,27 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         if (pass && second == first) break;
-        attn_fwd_block<CT, DHP>(P, drop, smem, bh, pass ? second : first);
+        attn_fwd_block<CT, DHP, false>(P, drop, smem, bh, pass ? second : first, AMask{nullptr, 0});
+    }
+}
+
+// the same schedule with a per-key mask (bpm_attn_fwd_kmask)
+template <typename CT, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves<CT>(0, DHP), attn_waves<CT>(0, DHP)))) void attn_fwd_kmask_kernel(const AGroupK gk) {
+    typedef Cfg<CT, DHP> C;
+    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE + KT];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(gk.g, bid);
+    const AProb& P = gk.g.p[pi];
+    const AMask km = gk.m[pi];
+    const DropCfg drop = bpm_resolve_drop(P.drop, gk.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2, first = P.pair ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        attn_fwd_block<CT, DHP, true>(P, drop, smem, bh, pass ? second : first, km);
     }
 }
 
@@ -389,12 +465,14 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 // dead-row elimination) continue from those instead of dK / dV: with two query rows dK and dV have rank two per head, and
 // every key / value-side product factors through [rows, S] matrices (engine.EncoderGroupPlan, "low-rank key side").
 // A separate instantiation: the stores would cost the T = S = 512 launches registers.
-template <typename CT, int DHP, bool XP>
-BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb) {
+// KM: per-key mask, staged as in the forward block (KTQ bytes of LDS behind the images).
+template <typename CT, int DHP, bool XP, bool KM>
+BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
     char* vimg = smem + C::KTQ * C::STRIDE;
+    uint8_t* smask = (uint8_t*)(smem + 2 * C::KTQ * C::STRIDE);    // KM only
 
     const int b = bh / P.H, h = bh % P.H;
     int tid_ = threadIdx.x;
@@ -450,14 +528,33 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
     const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
 
     RowStage<CT, DHP, C::KTQ> kst, vst;
-    if (ntile > 0) { kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid); }
+    uint32_t n_vis = 0;                                // KM, threads < KTQ: next tile's visibility of key kt * KTQ + tid
+    auto stage_mask = [&](int kt) {
+        const int jm = kt * C::KTQ + tid;
+        n_vis = 0;
+        if (tid < C::KTQ && jm < P.S) n_vis = km.mask[(size_t)b * km.ldm + jm] != 0;
+    };
+    if (ntile > 0) {
+        kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
+        if constexpr (KM) stage_mask(0);
+    }
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
         kst.store(kimg, tid);
         vst.store(vimg, tid);
+        if constexpr (KM) { if (tid < C::KTQ) smask[tid] = (uint8_t)n_vis; }
         __syncthreads();
-        if (kt + 1 < ntile) { kst.load(Kh, (kt + 1) * C::KTQ, P.S, tid); vst.load(Vh, (kt + 1) * C::KTQ, P.S, tid); }
+        if (kt + 1 < ntile) {
+            kst.load(Kh, (kt + 1) * C::KTQ, P.S, tid); vst.load(Vh, (kt + 1) * C::KTQ, P.S, tid);
+            if constexpr (KM) stage_mask(kt + 1);
+        }
+        bool k_all = true;                             // KM: every key of the tile is visible (wave-uniform)
+        if constexpr (KM) {
+            const uint32_t w = *(const uint32_t*)(smask + 4 * (lane & (C::KTQ / 4 - 1)));
+            if (__builtin_amdgcn_ballot_w64(w != 0u) == 0) continue;      // no visible key (the same in every wave)
+            k_all = __builtin_amdgcn_ballot_w64(w != 0x01010101u) == 0;
+        }
         const int jb = kt * C::KTQ + 4 * g;
         const bool edge = kt * C::KTQ + C::KTQ > lim_min;
         const int rel = lim - jb;
@@ -488,6 +585,13 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
                 if (edge) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) e4[r] = (16 * n + r < rel) ? e4[r] : -INFINITY;   // exp2(-inf) = 0: masked before the exponential
+                }
+                if constexpr (KM) {
+                    if (!k_all) {
+                        const uint32_t w = *(const uint32_t*)(smask + 16 * n + 4 * g);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) e4[r] = ((w >> (8 * r)) & 0xffu) ? e4[r] : -INFINITY;
+                    }
                 }
                 f32x4 p4;
 #pragma unroll
@@ -545,15 +649,38 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         if (pass && second == first) break;
-        attn_bwd_dq_block<CT, DHP, XP>(P, drop, smem, bh, pass ? second : first);
+        attn_bwd_dq_block<CT, DHP, XP, false>(P, drop, smem, bh, pass ? second : first, AMask{nullptr, 0});
+    }
+}
+
+// the same schedule with a per-key mask (bpm_attn_bwd_dq_kmask)
+template <typename CT, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves<CT>(1, DHP), attn_waves<CT>(1, DHP)))) void attn_bwd_dq_kmask_kernel(const AGroupK gk) {
+    typedef Cfg<CT, DHP> C;
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::KTQ * C::STRIDE + C::KTQ];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(gk.g, bid);
+    const AProb& P = gk.g.p[pi];
+    const AMask km = gk.m[pi];
+    const DropCfg drop = bpm_resolve_drop(P.drop, gk.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2, first = P.pair ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        attn_bwd_dq_block<CT, DHP, false, true>(P, drop, smem, bh, pass ? second : first, km);
     }
 }
 
 // ---------------------------------------------------------------------------
 // backward, dK and dV
 // ---------------------------------------------------------------------------
-template <typename CT, int DHP>
-BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int kb) {
+// KM: per-key mask.  A lane owns one key: its byte is read once (never at j >= S); a hidden key sees no query row
+// (ilo past every row), so its probabilities are exp2(-inf) = 0 and its dK / dV rows are exact zeros.  A block without
+// any visible key skips its query tiles.
+template <typename CT, int DHP, bool KM>
+BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int kb, const AMask km) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* qimg = smem;
@@ -586,11 +713,18 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     // query i sees key j iff i >= ilo = j - mask_off + 1 (and i < T, j < S)
     // in ROW indices: row i sits at time qpos0 + i*qstride, so "time >= tmin" is "i >= ceil((tmin - qpos0) / qstride)"
     auto first_row = [&](int tmin) { const int a = tmin - P.qpos0; return a <= 0 ? 0 : (a + P.qstride - 1) / P.qstride; };
-    const int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
-    const int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);   // wave-uniform: tiles at or above it need no test
+    int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
+    int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);         // wave-uniform: tiles at or above it need no test
     const int i_first = first_row(kb * 64 - P.mask_off + 1);                                   // first query row that sees any key of the block
     const int qt_lo = i_first / C::QTK;
-    const int qt_hi = (P.T + C::QTK - 1) / C::QTK;
+    int qt_hi = (P.T + C::QTK - 1) / C::QTK;
+    if constexpr (KM) {
+        bool kvis = false;
+        if (j < P.S) kvis = km.mask[(size_t)b * km.ldm + j] != 0;
+        if (!kvis) ilo = 1 << 30;
+        if (__builtin_amdgcn_ballot_w64(!kvis) != 0) ilo_max = 1 << 30;                        // a hidden key in the wave: every tile tests
+        if (!__syncthreads_or(kvis)) qt_hi = qt_lo;                                            // block-uniform: nothing to do but store zeros
+    }
     const bool dropping = drop.thresh != 0;
     const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
 
@@ -710,7 +844,27 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
         if (pass && second == first) break;
-        attn_bwd_dkv_block<CT, DHP>(P, drop, smem, bh, pass ? second : first);
+        attn_bwd_dkv_block<CT, DHP, false>(P, drop, smem, bh, pass ? second : first, AMask{nullptr, 0});
+    }
+}
+
+// the same schedule with a per-key mask (bpm_attn_bwd_dkv_kmask)
+template <typename CT, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves<CT>(2, DHP), attn_waves<CT>(2, DHP)))) void attn_bwd_dkv_kmask_kernel(const AGroupK gk) {
+    typedef Cfg<CT, DHP> C;
+    __shared__ __attribute__((aligned(16))) char smem[2 * C::QTK * C::STRIDE + 2 * C::QTK * 4];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(gk.g, bid);
+    const AProb& P = gk.g.p[pi];
+    const AMask km = gk.m[pi];
+    const DropCfg drop = bpm_resolve_drop(P.drop, gk.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2, first = P.pair ? bid % nb2 : bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        attn_bwd_dkv_block<CT, DHP, true>(P, drop, smem, bh, pass ? second : first, km);
     }
 }
 
@@ -945,6 +1099,60 @@ int dispatch(int which, int dhp, const AGroup& g, int total, hipStream_t s) {
     return 0;
 }
 
+// the per-key-mask kernels (which: 0 forward, 1 dQ, 2 dK / dV)
+template <typename CT>
+int dispatch_kmask(int which, int dhp, const AGroupK& g, int total, hipStream_t s) {
+    dim3 grid(total), block(NTHREADS);
+#define BPM_ATTN_KCASE(D)                                                                                       \
+    case D:                                                                                                     \
+        if (which == 0) hipLaunchKernelGGL((attn_fwd_kmask_kernel<CT, D>), grid, block, 0, s, g);               \
+        else if (which == 1) hipLaunchKernelGGL((attn_bwd_dq_kmask_kernel<CT, D>), grid, block, 0, s, g);       \
+        else hipLaunchKernelGGL((attn_bwd_dkv_kmask_kernel<CT, D>), grid, block, 0, s, g);                      \
+        break;
+    switch (dhp) {
+        BPM_ATTN_KCASE(32)
+        BPM_ATTN_KCASE(64)
+        BPM_ATTN_KCASE(128)
+        BPM_ATTN_KCASE(256)
+        default: return BPM_ERR_ARG;
+    }
+#undef BPM_ATTN_KCASE
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+// host checks + argument block of one *_kmask launch (which: 0 forward, 1 dQ, 2 dK / dV); nothing is launched on an error
+int fill_kmask(AGroupK& gk, int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* masks, int nprob, uint64_t seed, int* total,
+               int which) {
+    if (dtype != BPM_BF16 && dtype != BPM_F32) return BPM_ERR_ARG;
+    if (!masks) return BPM_ERR_ARG;
+    int rc = fill(gk.g, probs, nprob, which == 2, seed, total, which);
+    if (rc) return rc;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        if (!q.Q || !q.K || !q.V || !q.O || !q.lse) return BPM_ERR_ARG;
+        if (which != 0 && (!q.dO || !q.delta)) return BPM_ERR_ARG;
+        if (which == 1 && !q.dQ) return BPM_ERR_ARG;
+        if (which == 2 && (!q.dK || !q.dV)) return BPM_ERR_ARG;
+        if (q.dS || q.Pd) return BPM_ERR_ARG;                    // the score-gradient export has no masked instantiation
+        if (!masks[i].mask || masks[i].ldm < q.S) return BPM_ERR_ARG;
+        gk.m[i].mask = masks[i].mask; gk.m[i].ldm = masks[i].ldm;
+    }
+    for (int i = nprob; i < BPM_MAX_GROUP; ++i) { gk.m[i].mask = nullptr; gk.m[i].ldm = 0; }
+    return 0;
+}
+
+int attn_kmask(int which, int kind, int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* masks, int nprob, uint64_t seed,
+               void* stream) {
+    AGroupK gk;
+    int total = 0;
+    int rc = fill_kmask(gk, dtype, probs, masks, nprob, seed, &total, which);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    BpmProfScope prof(kind, s, 4.0 * useful_pair_flops(probs, nprob), attn_bytes(probs, nprob, dtype == BPM_BF16 ? 2 : 4, which));
+    return dtype == BPM_BF16 ? dispatch_kmask<bf16_t>(which, probs[0].dhp, gk, total, s) : dispatch_kmask<float>(which, probs[0].dhp, gk, total, s);
+}
+
 }  // namespace
 
 #ifdef BPM_LAB
@@ -1008,6 +1216,18 @@ extern "C" int bpm_attn_bwd_dq(int dtype, const bpm_attn_problem* probs, int npr
 }
 extern "C" int bpm_attn_bwd_dkv(int dtype, const bpm_attn_problem* probs, int nprob, uint64_t seed, void* stream) {
     return attn_bwd_parts(dtype, probs, nprob, seed, stream, 2);
+}
+
+// Attention with a per-key padding mask (HF's attention_mask): see bpm_attn_kmask in include/bpmult_hip.h.  The work
+// tallied for the launch profiler is that of the unmasked problem (the mask lives on the device).
+extern "C" int bpm_attn_fwd_kmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_kmask(0, BPM_K_ATTN_FWD, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dq_kmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_kmask(1, BPM_K_ATTN_BWD_DQ, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dkv_kmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_kmask(2, BPM_K_ATTN_BWD_DKV, dtype, probs, masks, nprob, seed, stream);
 }
 
 // Head-averaged attention probabilities of finished forward passes (see attn_maps_kernel).

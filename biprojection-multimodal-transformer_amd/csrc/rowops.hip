@@ -891,6 +891,61 @@ __global__ __launch_bounds__(NT) void split_rows_kernel(const Grp<SplitP> grp) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// exact (erf) GELU between the two FFN products of a BERT layer (HF BertIntermediate, hidden_act = "gelu")
+//   forward   g  = u Phi(u)                      Phi(u) = 0.5 (1 + erf(u / sqrt 2))
+//   backward  du = dg (Phi(u) + u phi(u))        phi(u) = exp(-u^2 / 2) / sqrt(2 pi)
+// Phi(u) is taken as 0.5 erfc(|u| / sqrt 2) for u < 0: 1 + erf cancels there (at u = -6 nothing of it is left in fp32).
+// One thread per 4-column chunk, grid-stride over the [R, ld / 4] chunks of the output (chunks at or past C are the zero
+// pad the next GEMM reads under BPM_GEMM_KPAD_ZERO).  Vector loads and stores only: every leading dimension is a multiple
+// of 4, so a row's last chunk may read up to 3 pad elements of its own row (ignored).
+// ---------------------------------------------------------------------------
+struct GeluP { const void* u; int ldu; int u_is_ct; void* g; int ldg; const float* dg; int lddg; void* du; int lddu; int R, C; };
+
+BPM_DEV float gelu_cdf(float u) {
+    const float a = fabsf(u) * 0.70710678118654752f;
+    return u < 0.f ? 0.5f * erfcf(a) : 0.5f + 0.5f * erff(a);
+}
+
+template <typename CT>
+BPM_DEV f32x4 gelu_load_u(const GeluP& P, int r, int c) {
+    if (P.u_is_ct && sizeof(CT) == 2) {
+        const bf16x4 t = *(const bf16x4*)((const bf16_t*)P.u + (size_t)r * P.ldu + c);
+        return f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+    }
+    return *(const f32x4*)((const float*)P.u + (size_t)r * P.ldu + c);
+}
+
+template <typename CT, bool BWD>
+__global__ __launch_bounds__(NT) void gelu_kernel(const Grp<GeluP> grp) {
+    unsigned bid = blockIdx.x, nblk;
+    const GeluP& P = pick(grp, bid, nblk);
+    const int ldo = BWD ? P.lddu : P.ldg;
+    void* out = BWD ? P.du : P.g;
+    const unsigned cpr = (unsigned)ldo >> 2;                   // chunks per output row
+    const size_t total = (size_t)P.R * cpr;
+    for (size_t i = (size_t)bid * NT + threadIdx.x; i < total; i += (size_t)nblk * NT) {
+        const int r = (int)(i / cpr), c = 4 * (int)(i - (size_t)r * cpr);
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c < P.C) {
+            const f32x4 u = gelu_load_u<CT>(P, r, c);
+            if constexpr (BWD) {
+                const f32x4 d = *(const f32x4*)(P.dg + (size_t)r * P.lddg + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = d[k] * (gelu_cdf(u[k]) + u[k] * (0.3989422804014327f * __expf(-0.5f * u[k] * u[k])));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = u[k] * gelu_cdf(u[k]);
+            }
+            if (c + 3 >= P.C) {                                // the row's last, partial chunk: what was read past C is pad
+#pragma unroll
+                for (int k = 1; k < 4; ++k) v[k] = c + k < P.C ? v[k] : 0.f;
+            }
+        }
+        put4<CT>(out, (size_t)r * ldo + c, v);
+    }
+}
+
 constexpr unsigned CAP = 2048;   // blocks per problem for grid-stride kernels
 
 template <typename P> inline bool grp_ok(int n) { return n >= 1 && n <= BPM_MAX_GROUP; }
@@ -1406,6 +1461,40 @@ extern "C" int bpm_rows_cast(int dtype, const bpm_cast_problem* q, int n, uint64
     BPM_CHECK_LAUNCH();
     return 0;
 }
+
+static int gelu_launch(int dtype, const bpm_gelu_problem* q, int n, bool bwd, void* stream) {
+    if (!q || n < 1 || n > BPM_MAX_GROUP || (dtype != BPM_BF16 && dtype != BPM_F32)) return BPM_ERR_ARG;
+    const size_t csz = dtype == BPM_BF16 ? 2 : 4;
+    Grp<GeluP> g;
+    g.n = n; g.blk0[0] = 0; g.seedp = nullptr;
+    for (int i = 0; i < n; ++i) {
+        const bpm_gelu_problem& s = q[i];
+        const int ldo = bwd ? s.lddu : s.ldg;
+        const void* out = bwd ? s.du : s.g;
+        if (!s.u || !out || (bwd && !s.dg) || s.R < 1 || s.C < 1 || s.ldu < s.C || ldo < s.C || (bwd && s.lddg < s.C)) return BPM_ERR_ARG;
+        if ((long)s.R * (ldo > s.ldu ? ldo : s.ldu) > (1l << 40)) return BPM_ERR_ARG;
+        const size_t usz = s.u_is_ct ? csz : 4;
+        // whole 4-element chunks: 16 bytes of fp32, 8 bytes of bf16
+        if ((s.ldu & 3) || (ldo & 3) || (bwd && (s.lddg & 3))) return BPM_ERR_ALIGN;
+        if (((uintptr_t)s.u % (4 * usz)) || ((uintptr_t)out % (4 * csz)) || (bwd && ((uintptr_t)s.dg & 15))) return BPM_ERR_ALIGN;
+        GeluP& p = g.p[i];
+        p.u = s.u; p.ldu = s.ldu; p.u_is_ct = s.u_is_ct; p.g = s.g; p.ldg = s.ldg; p.dg = s.dg; p.lddg = s.lddg; p.du = s.du; p.lddu = s.lddu;
+        p.R = s.R; p.C = s.C;
+        g.blk0[i + 1] = g.blk0[i] + blocks_for((size_t)s.R * (ldo >> 2), NT * 4, CAP);
+    }
+    if (bwd) {
+        if (dtype == BPM_BF16) hipLaunchKernelGGL((gelu_kernel<bf16_t, true>), dim3(g.blk0[n]), dim3(NT), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL((gelu_kernel<float, true>), dim3(g.blk0[n]), dim3(NT), 0, (hipStream_t)stream, g);
+    } else {
+        if (dtype == BPM_BF16) hipLaunchKernelGGL((gelu_kernel<bf16_t, false>), dim3(g.blk0[n]), dim3(NT), 0, (hipStream_t)stream, g);
+        else hipLaunchKernelGGL((gelu_kernel<float, false>), dim3(g.blk0[n]), dim3(NT), 0, (hipStream_t)stream, g);
+    }
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bpm_gelu_fwd(int dtype, const bpm_gelu_problem* q, int n, void* stream) { return gelu_launch(dtype, q, n, false, stream); }
+extern "C" int bpm_gelu_bwd(int dtype, const bpm_gelu_problem* q, int n, void* stream) { return gelu_launch(dtype, q, n, true, stream); }
 
 static int fill_gmu(Grp<GmuP>& g, const bpm_gmu_problem* q, int n, int d, bool bwd) {
     if (!q || n < 1 || n > BPM_MAX_GROUP || d < 1) return BPM_ERR_ARG;

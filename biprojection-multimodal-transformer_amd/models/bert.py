@@ -1,0 +1,363 @@
+"""The layer stack of an HF `BertModel` on the HIP path (reference mmtr.py:144-158: the text encoder upstream of the
+trunk; opt-in through `args.text_encoder = "hip"`, models/bpmult.py:BertEncoder).
+
+The module tree stays HF's: parameters, `state_dict` keys and optimizer groups are untouched.  `BertLayerStack` only
+reads `bert.encoder.layer[*]` and runs the post-LN layers as grouped launches behind ONE autograd node (`_StackFn`):
+embedding output [B, L, d] + attention mask [B, L] + the layers' parameters in, last hidden state [B, L, d] out; backward
+returns the gradient of the embedding output and of every layer parameter.  The embeddings (a gather + LayerNorm) stay on
+torch, the pooler is not evaluated (the reference discards its output).
+
+Schedule of one layer, rows time-major (row = t*B + b, what the head-major attention layout expects), x fp32 [R, d]:
+
+  xc            = CT(x)                                                      bpm_rows_cast
+  q, k, v       = heads(xc Wq^T + bq) dh^-0.5, heads(xc Wk^T + bk), ..       bpm_gemm_grouped NT, BPM_OUT_HEADS (one launch)
+  ctx, lse      = softmax(q k^T | key mask) v, dropout on the probabilities  bpm_attn_fwd_kmask
+  y1            = drop(ctx Wo^T + bo) + x                                    NT, bias -> dropout -> + resid epilogue
+  x1            = LN(y1), x1c = CT(x1)                                       bpm_ln_fwd (fp32 out), bpm_rows_cast
+  u             = x1c Wi^T + bi                                              NT, BPM_OUT_CT
+  g             = gelu(u)                                                    bpm_gelu_fwd
+  y2            = drop(g Wo2^T + bo2) + x1                                   NT, bias -> dropout -> + resid epilogue
+  x'            = LN(y2)                                                     bpm_ln_fwd
+
+Backward mirrors it: bpm_ln_bwd_ws (whose fused cast output is d(dense output) = dropmask(dy) as CT, with the dense bias
+gradient as its column sums), TN weight gradients (colsum_a for the q / k / v / intermediate biases), NN data gradients
+(the residual gradient rides in their `resid` epilogue), bpm_gelu_bwd, bpm_attn_bwd_dq_kmask / _dkv_kmask.
+
+Key mask: HF's `attention_mask` as bytes [B, L], built on the device ((mask != 0).to(uint8)); no length ever travels to
+the host.  Padded QUERY positions are computed like any other (HF does, and the trunk consumes them).  Every sample needs
+at least one visible key.
+
+Precision: "bf16" = bf16 MFMA operands (CT shadows of the weights, refreshed when a parameter's version changes), fp32
+accumulation, fp32 residual stream and LayerNorm; "f32" = exact fp32 products; "bf16x3" runs this stack's f32 path.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Tuple
+
+import torch
+
+from .. import config, ops
+from .._lib import F_KPAD, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_F32, OUT_HEADS, PackDesc
+from ..engine import dhp_for
+from ..ops import pad32
+
+# dropout sites of the text encoder: disjoint from engine.site() (enc_id < 12 -> below 1 << 16) and engine.SITE_TEXT (1 << 20)
+SITE_BERT = 1 << 21
+S_PROBS, S_ATT_OUT, S_FFN_OUT = range(3)
+
+# per layer, in this order (HF names below bert.encoder.layer[i])
+LAYER_PARAMS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight", "attention.self.key.bias",
+                "attention.self.value.weight", "attention.self.value.bias", "attention.output.dense.weight",
+                "attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
+                "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",
+                "output.LayerNorm.weight", "output.LayerNorm.bias")
+_WEIGHTS = ("attention.self.query.weight", "attention.self.key.weight", "attention.self.value.weight",
+            "attention.output.dense.weight", "intermediate.dense.weight", "output.dense.weight")
+
+
+def bert_site(layer: int, op: int) -> int:
+    return SITE_BERT | (layer << 4) | op
+
+
+def check_config(cfg) -> None:
+    """What the HIP layer stack implements; anything else is refused when the model is built."""
+    act = getattr(cfg, "hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"text_encoder='hip': hidden_act {act!r} is not supported (only the exact erf 'gelu')")
+    pet = getattr(cfg, "position_embedding_type", "absolute")
+    if pet != "absolute":
+        raise ValueError(f"text_encoder='hip': position_embedding_type {pet!r} is not supported (only 'absolute')")
+    if getattr(cfg, "is_decoder", False) or getattr(cfg, "add_cross_attention", False):
+        raise ValueError("text_encoder='hip': is_decoder / add_cross_attention are not supported (a bidirectional encoder only)")
+    if cfg.hidden_size % cfg.num_attention_heads:
+        raise ValueError("text_encoder='hip': hidden_size must be divisible by num_attention_heads")
+    dh = cfg.hidden_size // cfg.num_attention_heads
+    if dh > 256:
+        raise ValueError(f"text_encoder='hip': head_dim {dh} > 256 is not supported by the attention kernels")
+    if cfg.hidden_size % 32 or cfg.intermediate_size % 32:
+        raise ValueError("text_encoder='hip': hidden_size and intermediate_size must be multiples of 32 (rows without padding "
+                         f"columns; got {cfg.hidden_size} / {cfg.intermediate_size}): other sizes are not covered by a parity test yet")
+
+
+def layer_parameters(bert) -> List[torch.nn.Parameter]:
+    """The stack's parameters in the order _StackFn takes them and returns their gradients."""
+    out = []
+    for layer in bert.encoder.layer:
+        named = dict(layer.named_parameters())
+        out += [named[n] for n in LAYER_PARAMS]
+    return out
+
+
+class _Plan:
+    """Activation buffers of one (B, L) shape; kept from forward to backward."""
+
+    def __init__(self, st: "BertLayerStack", B: int, L: int):
+        d, I, H, nl, dev = st.d, st.I, st.H, st.n_layers, st.device
+        ct = ops.ct_torch(st.dtype)
+        R, ld, ldI, dhp = L * B, st.ld, st.ldI, st.dhp
+        self.B, self.L, self.R = B, L, R
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
+        self.x = [z(R, d) for _ in range(nl + 1)]             # layer inputs; x[nl] is the stack's output
+        self.xc = [z(R, ld, dt=ct) for _ in range(nl)]
+        self.q = [z(B, H, L, dhp, dt=ct) for _ in range(nl)]
+        self.k = [z(B, H, L, dhp, dt=ct) for _ in range(nl)]
+        self.v = [z(B, H, L, dhp, dt=ct) for _ in range(nl)]
+        self.ctx = [z(R, ld, dt=ct) for _ in range(nl)]
+        self.lse = [z(B, H, L) for _ in range(nl)]
+        self.y1 = [z(R, d) for _ in range(nl)]
+        self.x1 = [z(R, d) for _ in range(nl)]
+        self.x1c = [z(R, ld, dt=ct) for _ in range(nl)]
+        self.u = [z(R, ldI, dt=ct) for _ in range(nl)]
+        self.g = [z(R, ldI, dt=ct) for _ in range(nl)]
+        self.y2 = [z(R, d) for _ in range(nl)]
+        self.stats = [[z(R) for _ in range(4)] for _ in range(nl)]         # mean1, rstd1, mean2, rstd2
+        # backward scratch, shared by the layers
+        self.dx = [z(R, d), z(R, d)]                          # gradient of a layer's output / input (ping-pong)
+        self.dy2, self.dy1, self.dx1 = z(R, d), z(R, d), z(R, d)
+        self.dy2c, self.dy1c = z(R, ld, dt=ct), z(R, ld, dt=ct)
+        self.dg = z(R, I)
+        self.du = z(R, ldI, dt=ct)
+        self.dao = z(B, H, L, dhp, dt=ct)
+        self.delta = z(B, H, L)
+        self.dqkv = z(R, 3 * ld, dt=ct)
+        self.stamp = 0
+        self.mask: Optional[torch.Tensor] = None
+        self.seed, self.training = 0, False
+
+
+class BertLayerStack:
+    """Host driver of `bert.encoder.layer[*]` (see the module docstring).  Holds no parameters: it reads the HF
+    modules' and keeps CT shadows of the six weight matrices of every layer."""
+
+    def __init__(self, bert, precision: Optional[str] = None):
+        cfg = bert.config
+        check_config(cfg)
+        self.bert = bert
+        self.precision = precision
+        self.d, self.I, self.H, self.n_layers = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
+        self.dh = self.d // self.H
+        self.dhp = dhp_for(self.dh)
+        self.scale = self.dh ** -0.5
+        self.ld, self.ldI = pad32(self.d), pad32(self.I)
+        self.eps = float(cfg.layer_norm_eps)
+        self.p_hidden, self.p_probs = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
+        self.device: Optional[torch.device] = None
+        self.dtype = None
+        self._plans: Dict[Tuple[int, int], _Plan] = {}
+        self._versions = None
+
+    # -- parameters and their CT shadows -----------------------------------------
+    def _prepare(self, device: torch.device) -> None:
+        prec = self.precision or config.precision()
+        dtype = config.dtype_code(prec)                # bf16x3: the f32 path
+        params = getattr(self, "params", None) or layer_parameters(self.bert)
+        key = (str(device), dtype, tuple(p.data_ptr() for p in params))      # .to() / .cuda() move the storage
+        if getattr(self, "_key", None) == key:
+            return
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
+                raise RuntimeError("text_encoder='hip': BERT layer parameters must be contiguous float32 tensors on the input's device")
+        self._key, self.device, self.dtype = key, device, dtype
+        self._plans, self._versions = {}, None
+        self.params = params
+        ct = ops.ct_torch(dtype)
+        d, I, ld, ldI = self.d, self.I, self.ld, self.ldI
+        # shadows per layer: [Wq; Wk; Wv] as one [3d, ld] block (the data gradient reads it as one K = 3d operand),
+        # Wo [d, ld], Wi [I, ld], Wo2 [d, ldI]
+        per_layer = 3 * d * ld + d * ld + I * ld + d * ldI
+        self.shadow = torch.zeros(per_layer * self.n_layers, device=device, dtype=ct)
+        esz = self.shadow.element_size()
+        self._soff: List[Dict[str, int]] = []
+        descs, blk = [], 0
+        for i, layer in enumerate(self.bert.encoder.layer):
+            named = dict(layer.named_parameters())
+            base = i * per_layer
+            offs = {"qkv": base, "ao": base + 3 * d * ld, "fc1": base + 4 * d * ld, "fc2": base + 4 * d * ld + I * ld}
+            self._soff.append(offs)
+            for name, off, rows, cols in ((_WEIGHTS[0], offs["qkv"], d, d), (_WEIGHTS[1], offs["qkv"] + d * ld, d, d),
+                                          (_WEIGHTS[2], offs["qkv"] + 2 * d * ld, d, d), (_WEIGHTS[3], offs["ao"], d, d),
+                                          (_WEIGHTS[4], offs["fc1"], I, d), (_WEIGHTS[5], offs["fc2"], d, I)):
+                pd = PackDesc()
+                pd.src, pd.dst = named[name].data_ptr(), self.shadow.data_ptr() + esz * off
+                pd.rows, pd.cols, pd.ld, pd.src_ld, pd.dst_ld, pd.blk0 = rows, cols, pad32(cols), cols, pad32(cols), blk
+                pd.colscale = None
+                blk += (rows * pad32(cols) + 1023) // 1024
+                descs.append(pd)
+        self._pack = (ops.device_table(descs), len(descs), blk)
+
+    def _sptr(self, layer: int, key: str, elem_off: int = 0) -> int:
+        return self.shadow.data_ptr() + self.shadow.element_size() * (self._soff[layer][key] + elem_off)
+
+    def refresh_shadows(self) -> None:
+        """Re-pack the CT weight shadows when a parameter changed.  A change is seen through autograd's version counters:
+        an optimizer step, `load_state_dict`, `copy_` and any other in-place op on the parameter move them.  A write
+        through `p.data` does NOT (EMA swaps, clamping, some checkpoint loaders): call invalidate_shadows() after one, or
+        the products keep reading the old weights."""
+        sig = tuple(p._version for p in self.params)
+        if sig != self._versions:
+            ops.pack_weights(self.dtype, *self._pack)
+            self._versions = sig
+
+    def invalidate_shadows(self) -> None:
+        """The next forward re-packs the weight shadows whatever the version counters say."""
+        self._versions = None
+
+    def _plan(self, B: int, L: int) -> _Plan:
+        pl = self._plans.get((B, L))
+        if pl is None:
+            if len(self._plans) >= 2:                         # activation sets are large: keep the two most recent shapes
+                self._plans.pop(next(iter(self._plans)))
+            pl = self._plans[(B, L)] = _Plan(self, B, L)
+        return pl
+
+    def _P(self, layer: int, name: str) -> torch.Tensor:
+        return self.params[layer * len(LAYER_PARAMS) + LAYER_PARAMS.index(name)]
+
+    # -- forward ---------------------------------------------------------------------
+    def forward(self, emb: torch.Tensor, mask_u8: torch.Tensor, seed: int, training: bool) -> Tuple[torch.Tensor, _Plan]:
+        """emb fp32 [B, L, d] (the embeddings module's output), mask_u8 uint8 [B, L] -> last hidden state [B, L, d]."""
+        B, L, d = emb.shape
+        self._prepare(emb.device)
+        self.refresh_shadows()
+        pl = self._plan(B, L)
+        pl.stamp += 1
+        pl.mask, pl.seed, pl.training = mask_u8, seed, training
+        dt, R, ld, ldI, I, H = self.dtype, pl.R, self.ld, self.ldI, self.I, self.H
+        heads = (B, H, L, self.dh, self.dhp)
+        ph = self.p_hidden if training else 0.0
+        pp = self.p_probs if training else 0.0
+        km = ops.attn_kmasks([(mask_u8, L)])
+        pl.x[0].view(L, B, d).copy_(emb.transpose(0, 1))     # time-major rows
+        for i in range(self.n_layers):
+            P = lambda n, i=i: self._P(i, n)
+            x, xc = pl.x[i], pl.xc[i]
+            ops.rows_cast(dt, [ops.cast_problem(x, d, R, d, dst_ct=xc, ldd=ld)], 0)
+            qkv = [ops.gemm_problem(xc, self._sptr(i, "qkv", w * d * ld), out, R, d, d, ld, ld, 0, bias_n=P(f"attention.self.{nm}.bias"),
+                                    alpha=self.scale if w == 0 else 1.0, out_kind=OUT_HEADS, heads=heads, flags=F_KPAD)
+                   for w, (nm, out) in enumerate((("query", pl.q[i]), ("key", pl.k[i]), ("value", pl.v[i])))]
+            ops.gemm_grouped(dt, GEMM_NT, qkv, seed)
+            ops.attn_fwd_kmask(dt, [ops.attn_problem(pl.q[i], pl.k[i], pl.v[i], pl.ctx[i], ld, pl.lse[i], B, H, L, L, self.dh, self.dhp,
+                                                     0, drop_p=pp, drop_site=bert_site(i, S_PROBS))], km, seed)
+            ops.gemm_grouped(dt, GEMM_NT, [ops.gemm_problem(pl.ctx[i], self._sptr(i, "ao"), pl.y1[i], R, d, d, ld, ld, d,
+                                                            bias_n=P("attention.output.dense.bias"), resid=x, ldr=d, drop_p=ph,
+                                                            drop_site=bert_site(i, S_ATT_OUT), flags=F_KPAD)], seed)
+            m1, r1, m2, r2 = pl.stats[i]
+            ops.ln_fwd(dt, [ops.ln_problem(pl.y1[i], P("attention.output.LayerNorm.weight"), P("attention.output.LayerNorm.bias"),
+                                           m1, r1, R, out=pl.x1[i], ldo=d, out_f32=True)], d, self.eps)
+            ops.rows_cast(dt, [ops.cast_problem(pl.x1[i], d, R, d, dst_ct=pl.x1c[i], ldd=ld)], 0)
+            ops.gemm_grouped(dt, GEMM_NT, [ops.gemm_problem(pl.x1c[i], self._sptr(i, "fc1"), pl.u[i], R, I, d, ld, ld, ldI,
+                                                            bias_n=P("intermediate.dense.bias"), out_kind=OUT_CT, flags=F_KPAD)], seed)
+            ops.gelu_fwd(dt, [ops.gelu_problem(pl.u[i], ldI, R, I, u_is_ct=True, g=pl.g[i], ldg=ldI)])
+            ops.gemm_grouped(dt, GEMM_NT, [ops.gemm_problem(pl.g[i], self._sptr(i, "fc2"), pl.y2[i], R, d, I, ldI, ldI, d,
+                                                            bias_n=P("output.dense.bias"), resid=pl.x1[i], ldr=d, drop_p=ph,
+                                                            drop_site=bert_site(i, S_FFN_OUT), flags=F_KPAD)], seed)
+            ops.ln_fwd(dt, [ops.ln_problem(pl.y2[i], P("output.LayerNorm.weight"), P("output.LayerNorm.bias"), m2, r2, R,
+                                           out=pl.x[i + 1], ldo=d, out_f32=True)], d, self.eps)
+        return pl.x[self.n_layers].view(L, B, d).transpose(0, 1).contiguous(), pl
+
+    # -- backward ----------------------------------------------------------------------
+    def backward(self, pl: _Plan, dout: torch.Tensor, need_demb: bool) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+        """dout fp32 [B, L, d] -> (d(emb) [B, L, d] or None, the gradients of layer_parameters() in order).  Fresh tensors
+        every call (autograd may keep them as .grad)."""
+        B, L, R = pl.B, pl.L, pl.R
+        d, I, H, ld, ldI, dt, seed = self.d, self.I, self.H, self.ld, self.ldI, self.dtype, pl.seed
+        heads = (B, H, L, self.dh, self.dhp)
+        ph = self.p_hidden if pl.training else 0.0
+        pp = self.p_probs if pl.training else 0.0
+        km = ops.attn_kmasks([(pl.mask, L)])
+        # weight gradients are WRITTEN by their launch; the vectors (biases, LayerNorm affines) are accumulated into: zeroed
+        wsize = self.n_layers * (4 * d * d + 2 * d * I)
+        vsize = self.n_layers * (9 * d + I)
+        gw = torch.empty(wsize, device=self.device, dtype=torch.float32)
+        gv = torch.zeros(vsize, device=self.device, dtype=torch.float32)
+        grads: List[torch.Tensor] = []
+        ow = ov = 0
+        for p in self.params:
+            n = p.numel()
+            if p.dim() == 2:
+                grads.append(gw[ow:ow + n].view_as(p))
+                ow += n
+            else:
+                grads.append(gv[ov:ov + n].view_as(p))
+                ov += n
+        G = lambda i, n: grads[i * len(LAYER_PARAMS) + LAYER_PARAMS.index(n)]
+        cur = 0
+        pl.dx[cur].view(L, B, d).copy_(dout.transpose(0, 1))
+        for i in reversed(range(self.n_layers)):
+            P = lambda n, i=i: self._P(i, n)
+            dxo, dxi = pl.dx[cur], pl.dx[cur ^ 1]
+            m1, r1, m2, r2 = pl.stats[i]
+            # output LayerNorm; its cast output is d(output.dense result) = dropmask(dy2) as CT, column sums = the dense bias gradient
+            ops.ln_bwd([ops.ln_problem(pl.y2[i], P("output.LayerNorm.weight"), None, m2, r2, R, dy=dxo, ldy=d, dx=pl.dy2,
+                                       dgamma=G(i, "output.LayerNorm.weight"), dbeta=G(i, "output.LayerNorm.bias"), cast=pl.dy2c, ldc=ld,
+                                       cast_colsum=G(i, "output.dense.bias"), drop_p=ph, drop_site=bert_site(i, S_FFN_OUT))], d, dt, seed)
+            ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy2c, pl.g[i], G(i, "output.dense.weight"), d, I, R, ld, ldI, I,
+                                                            flags=F_KPAD)], seed)
+            ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy2c, self._sptr(i, "fc2"), pl.dg, R, I, d, ld, ldI, I, out_kind=OUT_F32,
+                                                            flags=F_KPAD)], seed)
+            ops.gelu_bwd(dt, [ops.gelu_problem(pl.u[i], ldI, R, I, u_is_ct=True, dg=pl.dg, lddg=I, du=pl.du, lddu=ldI)])
+            ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.du, pl.x1c[i], G(i, "intermediate.dense.weight"), I, d, R, ldI, ld, d,
+                                                            colsum_a=G(i, "intermediate.dense.bias"), flags=F_KPAD)], seed)
+            # d(x1) = du Wi + dy2 (the residual branch rides in the epilogue)
+            ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.du, self._sptr(i, "fc1"), pl.dx1, R, d, I, ldI, ld, d, resid=pl.dy2, ldr=d,
+                                                            flags=F_KPAD)], seed)
+            ops.ln_bwd([ops.ln_problem(pl.y1[i], P("attention.output.LayerNorm.weight"), None, m1, r1, R, dy=pl.dx1, ldy=d, dx=pl.dy1,
+                                       dgamma=G(i, "attention.output.LayerNorm.weight"), dbeta=G(i, "attention.output.LayerNorm.bias"),
+                                       cast=pl.dy1c, ldc=ld, cast_colsum=G(i, "attention.output.dense.bias"), drop_p=ph,
+                                       drop_site=bert_site(i, S_ATT_OUT))], d, dt, seed)
+            ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy1c, pl.ctx[i], G(i, "attention.output.dense.weight"), d, d, R, ld, ld, d,
+                                                            flags=F_KPAD)], seed)
+            ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy1c, self._sptr(i, "ao"), pl.dao, R, d, d, ld, ld, 0, out_kind=OUT_HEADS,
+                                                            heads=heads, flags=F_KPAD)], seed)
+            dq, dk, dv = pl.dqkv[:, :ld], pl.dqkv[:, ld:2 * ld], pl.dqkv[:, 2 * ld:]
+            ap = [ops.attn_problem(pl.q[i], pl.k[i], pl.v[i], pl.ctx[i], ld, pl.lse[i], B, H, L, L, self.dh, self.dhp, 0, dO=pl.dao,
+                                   delta=pl.delta, dQ=dq, lddq=3 * ld, dK=dk, lddk=3 * ld, dV=dv, lddv=3 * ld, dq_scale=self.scale,
+                                   drop_p=pp, drop_site=bert_site(i, S_PROBS))]
+            ops.attn_bwd_dq_kmask(dt, ap, km, seed)
+            ops.attn_bwd_dkv_kmask(dt, ap, km, seed)
+            ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(src, pl.xc[i], G(i, f"attention.self.{nm}.weight"), d, d, R, 3 * ld, ld, d,
+                                                            colsum_a=G(i, f"attention.self.{nm}.bias"), flags=F_KPAD)
+                                           for nm, src in (("query", dq), ("key", dk), ("value", dv))], seed)
+            # d(x) = dq Wq + dk Wk + dv Wv + dy1
+            # (one K = 3d product: check_config admits only d % 32 == 0, so ld == d and [dq | dk | dv] has no pad columns)
+            ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dqkv, self._sptr(i, "qkv"), dxi, R, d, 3 * d, 3 * ld, ld, d,
+                                                            resid=pl.dy1, ldr=d, flags=F_KPAD)], seed)
+            cur ^= 1
+        demb = pl.dx[cur].view(L, B, d).transpose(0, 1).contiguous() if need_demb else None
+        return demb, grads
+
+
+class _StackFn(torch.autograd.Function):
+    """The BERT layer stack as one autograd node: (embedding output, byte mask, layer parameters) -> last hidden state."""
+
+    @staticmethod
+    def forward(ctx, emb, mask_u8, stack, seed, training, *params):
+        out, plan = stack.forward(emb.detach().contiguous().float(), mask_u8, seed, training)
+        ctx.stack, ctx.plan, ctx.stamp = stack, plan, plan.stamp
+        ctx.need_emb = emb.requires_grad
+        ctx.need_params = [p.requires_grad for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.stamp != ctx.plan.stamp:
+            raise RuntimeError("text encoder (HIP path): backward() of a forward pass that a later forward pass of the same shape "
+                               "has overwritten; run forward -> backward one step at a time")
+        demb, grads = ctx.stack.backward(ctx.plan, dout.contiguous().float(), ctx.need_emb)
+        return (demb, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.need_params))
+
+
+def run_layers(stack: BertLayerStack, emb: torch.Tensor, mask: Optional[torch.Tensor], seed: int, training: bool) -> torch.Tensor:
+    """emb [B, L, d] (output of bert.embeddings), mask [B, L] (HF attention_mask: non-zero = a real token; None = all) ->
+    last hidden state [B, L, d] through the HIP layer stack."""
+    if not emb.is_cuda:
+        raise RuntimeError("text encoder: the HIP layer stack needs CUDA (HIP) tensors; there is no CPU path")
+    B, L = emb.shape[0], emb.shape[1]
+    if mask is None:
+        mask_u8 = torch.ones(B, L, device=emb.device, dtype=torch.uint8)
+    else:
+        if mask.shape != (B, L):
+            raise ValueError(f"text encoder: attention mask of shape {tuple(mask.shape)} for inputs of shape {(B, L)}")
+        mask_u8 = (mask.to(emb.device) != 0).to(torch.uint8).contiguous()        # on the device: no length reaches the host
+    stack._prepare(emb.device)
+    return _StackFn.apply(emb, mask_u8, stack, seed, training, *stack.params)

@@ -94,22 +94,69 @@ class AudioEncoder(nn.Module):
         return audio_encoder_forward(x, (self.conv_layers[0], self.conv_layers[1]), int(pool), precision)
 
 
+TEXT_ENCODERS = ("torch", "hip")
+
+
+def step_seed(step: int) -> int:
+    """Dropout seed of forward pass number `step`: (process seed, data-parallel rank, step).  Ranks that seed alike must
+    still draw independent masks on their shards, as the reference's DataParallel replicas do.  The one formula of the
+    trunk (_BPMulTBase._next_seed) and of the HIP text encoder (BertEncoder._next_seed)."""
+    rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+    return (torch.initial_seed() * 1000003 + rank * 0x9E3779B97F4A7C15 + int(step)) & 0x7FFFFFFFFFFFFFFF   # 63 bits: bit 63 marks an indirect seed
+
+
 class BertEncoder(nn.Module):
     """Text encoder plug point (mmtr.py:144-158).  `args.bert_model` may be a local
     HF directory; with `args.text_features=True` (synthetic benchmarks, parity
-    tests) the `txt` argument already holds [B,L,orig_d_l] features."""
+    tests) the `txt` argument already holds [B,L,orig_d_l] features.
+
+    `args.text_encoder`: "torch" (the default: HF `BertModel` as it is) or "hip": `self.bert` is the same HF module (same
+    parameters, same state_dict keys), its embeddings still run on torch, and its `encoder.layer[*]` stack runs on the HIP
+    path behind one autograd node (models/bert.py); the pooler, whose output the reference discards, is not evaluated."""
 
     def __init__(self, args):
         super().__init__()
         self.features_in = bool(getattr(args, "text_features", False))
+        self.text_encoder = getattr(args, "text_encoder", "torch")
+        if self.text_encoder not in TEXT_ENCODERS:
+            raise ValueError(f"text_encoder must be one of {TEXT_ENCODERS}, got {self.text_encoder!r}")
+        self.precision: Optional[str] = getattr(args, "precision", None)
         self.bert = None
+        self._stack = None
+        self.dropout_step = 0           # host-side step counter of the HIP stack's dropout stream (the model sets it per step)
         if not self.features_in:
             from transformers import BertModel  # local directory only: there is no network
             self.bert = BertModel.from_pretrained(args.bert_model)
+            if self.text_encoder == "hip":
+                from .bert import check_config
+                check_config(self.bert.config)
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)
+        self._stack = None              # shadows and activation buffers live on the old device
+        return r
+
+    def _next_seed(self) -> int:
+        self.dropout_step += 1
+        return step_seed(self.dropout_step)
+
+    def invalidate_shadows(self) -> None:
+        """Call after writing BERT layer weights in a way autograd's version counters do not see (through `p.data`: EMA
+        swaps, clamping, some checkpoint loaders): the HIP stack re-packs its CT weight shadows on the next forward.
+        Optimizer steps, `load_state_dict`, `copy_` and other in-place ops on the parameters are noticed without it."""
+        if self._stack is not None:
+            self._stack.invalidate_shadows()
 
     def forward(self, txt, mask, segment):
         if self.features_in:
             return txt
+        if self.text_encoder == "hip":
+            from .bert import BertLayerStack, run_layers
+            emb = self.bert.embeddings(input_ids=txt, token_type_ids=segment)
+            if self._stack is None:
+                self._stack = BertLayerStack(self.bert, self.precision)
+            self._stack.precision = self.precision
+            return run_layers(self._stack, emb, mask, self._next_seed(), self.training)
         return self.bert(input_ids=txt, token_type_ids=segment, attention_mask=mask, return_dict=False)[0]
 
 
@@ -857,8 +904,7 @@ class _BPMulTBase(nn.Module):
         counter is saved with the optimizer state (FusedAdam.state_dict) so a resumed run does not
         replay the mask sequence from step 1."""
         self.dropout_step += 1
-        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
-        return (torch.initial_seed() * 1000003 + rank * 0x9E3779B97F4A7C15 + int(self.dropout_step)) & 0x7FFFFFFFFFFFFFFF   # 63 bits: bit 63 marks an indirect seed
+        return step_seed(self.dropout_step)
 
     def _graphs_on(self) -> bool:
         """Captured-graph replay of the step (_Trunk.graph_forward, graphs.GraphCache): on unless switched off (`use_graphs`,
@@ -869,6 +915,13 @@ class _BPMulTBase(nn.Module):
             return False
         from .. import _lib
         return not _lib.prof_enabled()
+
+    def _encode_text(self, txt, mask, segment):
+        """self.enc(...); a HIP text encoder runs at the model's precision and draws its dropout masks from the step the
+        trunk is about to take (the counter FusedAdam.state_dict carries)."""
+        self.enc.precision = self.precision
+        self.enc.dropout_step = self.dropout_step
+        return self.enc(txt, mask, segment)
 
     def tail_parameters(self):
         """The [B,d] tail's parameters in the order bpm_tail_bwd's gradients are returned."""
@@ -903,7 +956,7 @@ class MultiprojectionMMTransformer3DGMUClf(_BPMulTBase):
         self._init_time_maps()            # present in the state_dict, unused by the 3-modal graph (mmtr.py:794-795)
 
     def forward(self, txt, mask, segment, img, audio, output_gate=False):
-        x_l = self.enc(txt, mask, segment)                     # [B,L,orig_d_l]
+        x_l = self._encode_text(txt, mask, segment)            # [B,L,orig_d_l]
         logits, z = self._run(x_l, img, audio, None)
         return (logits, z) if output_gate else logits
 
@@ -928,7 +981,7 @@ class MultiprojectionMMTransformerGMUClf(_BPMulTBase):
     def forward(self, txt, mask, segment, img, audio, poster, output_gate=False):
         from ..frontend import skinny_linear
         prec = self.precision or config.precision()
-        x_l = self.enc(txt, mask, segment)
+        x_l = self._encode_text(txt, mask, segment)
         x_a = self.audio_enc.encode(audio, prec)               # [B,96,T_a] -> [B,A,96] (mmtr.py:449)
         logits, z = self._run(x_l, img, x_a, skinny_linear(poster, self.proj_poster.weight, prec))
         return (logits, z) if output_gate else logits

@@ -311,6 +311,44 @@ def attn_bwd_dkv(dtype: int, probs, seed: int = 0) -> None:
         _lib.check(L.bpm_attn_bwd_dkv(dtype, sub, k, _seed(seed), s), "bpm_attn_bwd_dkv")
 
 
+def attn_kmasks(masks) -> "C.Array":
+    """[(uint8 device tensor [B, ldm], ldm)] -> the host array of bpm_attn_kmask the *_kmask entries take beside the
+    problems: key j of sample b is visible iff mask[b, j] != 0 (AND the problem's mask_off rule).  Every sample needs at
+    least one visible key (not checked: the mask never travels to the host)."""
+    arr = (_lib.AttnKMask * len(masks))()
+    for a, (m, ldm) in zip(arr, masks):
+        if not isinstance(m, int) and m.dtype != torch.uint8:
+            raise ValueError(f"attention key mask: expected uint8, got {m.dtype}")
+        a.mask, a.ldm = _p(m), ldm
+    return arr
+
+
+def _attn_kmask(name: str, dtype: int, probs, masks, seed: int) -> None:
+    arr = _as_array(AttnProblem, probs)
+    if len(masks) != len(arr):
+        raise ValueError(f"{name}: one key mask per problem ({len(arr)} problems, {len(masks)} masks)")
+    L, s = _lib.lib(), _stream()
+    fn = getattr(L, name)
+    for i in range(0, len(arr), MAX_GROUP):
+        k = min(MAX_GROUP, len(arr) - i)
+        sub = C.cast(C.byref(arr, i * C.sizeof(AttnProblem)), C.POINTER(AttnProblem))
+        msub = C.cast(C.byref(masks, i * C.sizeof(_lib.AttnKMask)), C.POINTER(_lib.AttnKMask))
+        _lib.check(fn(dtype, sub, msub, k, _seed(seed), s), name)
+
+
+def attn_fwd_kmask(dtype: int, probs, masks, seed: int = 0) -> None:
+    """bpm_attn_fwd with a per-key padding mask: `masks` from attn_kmasks(), one per problem."""
+    _attn_kmask("bpm_attn_fwd_kmask", dtype, probs, masks, seed)
+
+
+def attn_bwd_dq_kmask(dtype: int, probs, masks, seed: int = 0) -> None:
+    _attn_kmask("bpm_attn_bwd_dq_kmask", dtype, probs, masks, seed)
+
+
+def attn_bwd_dkv_kmask(dtype: int, probs, masks, seed: int = 0) -> None:
+    _attn_kmask("bpm_attn_bwd_dkv_kmask", dtype, probs, masks, seed)
+
+
 def attn_map_problem(Q, K, lse, W, ldw, B, H, T, S, dh, dhp, mask_off, *, q_pos0=0, q_stride=1) -> AttnMapProblem:
     """One head-averaged attention map (bpm_attn_maps): Q / K / lse as attn_problem's after its forward, W fp32 [B, T, ldw]
     receives (1/H) sum_h softmax probabilities (before dropout; exactly 0 where the mask hides the key)."""
@@ -562,6 +600,28 @@ def rows_cast(dtype, probs, seed=0) -> None:
     arr = _as_array(CastProblem, probs)
     for sub, k in _chunks(arr, CastProblem, None):
         _lib.check(_lib.lib().bpm_rows_cast(dtype, sub, k, _seed(seed), _stream()), "bpm_rows_cast")
+
+
+def gelu_problem(u, ldu, R, Cn, *, u_is_ct=False, g=None, ldg=0, dg=None, lddg=0, du=None, lddu=0) -> "_lib.GeluProblem":
+    """Exact (erf) GELU rows: forward g (CT [R, ldg], pad zeroed) = gelu(u); backward du (CT [R, lddu]) = dg * gelu'(u),
+    dg fp32 [R, lddg].  u is fp32 or (u_is_ct) CT [R, ldu]."""
+    p = _lib.GeluProblem()
+    p.u, p.ldu, p.u_is_ct = _p(u), ldu, int(u_is_ct)
+    p.g, p.ldg, p.dg, p.lddg, p.du, p.lddu = _p(g), ldg, _f32(dg, "gelu.dg"), lddg, _p(du), lddu
+    p.R, p.C = R, Cn
+    return p
+
+
+def gelu_fwd(dtype: int, probs) -> None:
+    arr = _as_array(_lib.GeluProblem, probs)
+    for sub, k in _chunks(arr, _lib.GeluProblem, None):
+        _lib.check(_lib.lib().bpm_gelu_fwd(dtype, sub, k, _stream()), "bpm_gelu_fwd")
+
+
+def gelu_bwd(dtype: int, probs) -> None:
+    arr = _as_array(_lib.GeluProblem, probs)
+    for sub, k in _chunks(arr, _lib.GeluProblem, None):
+        _lib.check(_lib.lib().bpm_gelu_bwd(dtype, sub, k, _stream()), "bpm_gelu_bwd")
 
 
 def addn_problem(out, ins) -> "_lib.AddnProblem":

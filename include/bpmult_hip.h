@@ -158,6 +158,25 @@ int bpm_attn_bwd(int dtype, const bpm_attn_problem* probs /* host */, int nprob,
 int bpm_attn_bwd_dq(int dtype, const bpm_attn_problem* probs /* host */, int nprob, uint64_t seed, void* stream);
 int bpm_attn_bwd_dkv(int dtype, const bpm_attn_problem* probs /* host */, int nprob, uint64_t seed, void* stream);
 
+/* The same three kernels with a PER-KEY PADDING MASK (HF BertSelfAttention's attention_mask, mmtr.py:144-158): one
+ * bpm_attn_kmask per problem, a parallel host array.  mask: device bytes [B, ldm], ldm >= S; key j of sample b is visible
+ * iff mask[b*ldm + j] != 0, AND visible under the problem's mask_off rule.  A hidden key gets probability exactly 0, adds
+ * nothing to lse and receives exactly zero dK / dV rows; query rows are never masked (outputs at padded positions are
+ * computed, as HF does).  The kernels never read `mask` at j >= S (tile padding is hidden without a load), so a tight
+ * [B, S] tensor is legal.  EVERY SAMPLE MUST HAVE AT LEAST ONE VISIBLE KEY for each of its query rows -- not checked (it
+ * would take a host sync); a row without one yields NaN.  A NULL mask or ldm < S is BPM_ERR_ARG; dS / Pd are not
+ * supported here.  With an all-ones mask the results are bit-equal to the unmasked entries'. */
+typedef struct bpm_attn_kmask {
+    const uint8_t* mask;
+    int ldm;
+} bpm_attn_kmask;
+int bpm_attn_fwd_kmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* masks /* host */, int nprob,
+                       uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_kmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* masks /* host */, int nprob,
+                          uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_kmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* masks /* host */, int nprob,
+                           uint64_t seed, void* stream);
+
 /* Head-averaged attention maps of a finished forward pass: the reference's second return value
  * (multihead_attention.py:132-135, attn_weights.sum(dim=1) / num_heads), which the fused kernels never materialise.
  * Recomputed from the Q / K images and the lse that bpm_attn_fwd left:
@@ -307,6 +326,22 @@ typedef struct bpm_cast_problem {
     float drop_p; uint32_t drop_site;
 } bpm_cast_problem;
 int bpm_rows_cast(int dtype, const bpm_cast_problem* probs, int n, uint64_t seed, void* stream);
+
+/* Exact (erf) GELU, HF's hidden_act = "gelu" between intermediate.dense and output.dense (BertIntermediate):
+ *   forward   g = 0.5 u (1 + erf(u / sqrt 2)),  u fp32 or (u_is_ct) CT [R, ldu];  g written as CT [R, ldg] with the pad
+ *             columns [C, ldg) zeroed (the next GEMM's A operand under BPM_GEMM_KPAD_ZERO)
+ *   backward  du = dg (Phi(u) + u phi(u)),  dg fp32 [R, lddg];  du written as CT [R, lddu], pad columns zeroed
+ * All arithmetic in fp32, whole 4-element chunks: every leading dimension % 4 == 0 and >= C (a row's last chunk reads up to
+ * 3 pad elements of its own input row), 4-element aligned pointers; C itself is arbitrary. */
+typedef struct bpm_gelu_problem {
+    const void* u; int ldu; int u_is_ct;
+    void* g; int ldg;                       /* forward */
+    const float* dg; int lddg;              /* backward */
+    void* du; int lddu;
+    int R, C;
+} bpm_gelu_problem;
+int bpm_gelu_fwd(int dtype, const bpm_gelu_problem* probs, int n, void* stream);
+int bpm_gelu_bwd(int dtype, const bpm_gelu_problem* probs, int n, void* stream);
 
 /* fp32 [R, C] (row stride ld) -> split bf16 [R, 2 ldp] for the BPM_BF16X3 products: columns [0, ldp) = hi = bf16(x),
  * columns [ldp, 2 ldp) = lo = bf16(x - hi), pad columns [C, ldp) of both planes zero (ldp % 4 == 0; the LDS-DMA GEMM

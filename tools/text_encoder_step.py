@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Forward + backward of the text encoder ALONE at the bert-base shape (12 layers, d = 768, 12 heads, intermediate 3072,
+L = 512, B = 8, HF dropout defaults 0.1, train mode, randomly initialised weights -- nothing is downloaded), four ways:
+
+  hf_f32     HF BertModel in fp32, no autocast       (the reference's setting, mmtr.py:144-158)
+  hf_bf16    HF BertModel under torch.autocast(bf16)
+  hip_f32    text_encoder="hip", precision f32       (embeddings on torch, the layer stack on the HIP path)
+  hip_bf16   text_encoder="hip", precision bf16
+
+  python tools/text_encoder_step.py [--steps 40 --warmup 5 --repeats 3 --out profiles/text_encoder_step.json]
+
+Every mode runs in a child process of its own under `timeout` (a hung or faulted mode ends the whole measurement: nothing
+more is started on the device).  In the child: `--warmup` untimed steps, then `--repeats` windows of `--steps` steps, each
+between two device synchronisations and timed with events on the current stream; the median window and the spread
+(max - min) / median are reported.  A step is embeddings + layers forward, a loss that weights every position, and the
+backward down to the word embeddings.  No optimizer runs, so the HIP modes re-pack their weight shadows explicitly in every
+step (what an optimizer step would make them do; HF's autocast casts its weights inside every step too).  The default
+windows are 40 steps (0.4 - 1.2 s each).  All positions are real tokens (full-length mask: the most work a batch can be).
+Algorithmic flops per step (forward + backward = 3x forward; per layer 8 L d^2 for q / k / v / out, 4 L^2 d for the two
+attention products, 4 L d I for the FFN): printed as TFLOP/s next to each time -- a whole-step rate, not a kernel's."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPE = dict(layers=12, d=768, heads=12, inter=3072, L=512, B=8, vocab=30522)
+MODES = ("hf_f32", "hf_bf16", "hip_f32", "hip_bf16")
+
+
+def flops():
+    s = SHAPE
+    per_layer = 8 * s["L"] * s["d"] ** 2 + 4 * s["L"] ** 2 * s["d"] + 4 * s["L"] * s["d"] * s["inter"]
+    return 3 * s["B"] * s["layers"] * per_layer
+
+
+def one(mode, steps, warmup, repeats):
+    import torch
+    from transformers import BertConfig, BertModel
+
+    import bpmult_amd  # noqa: F401
+    from bpmult_amd.models.bert import BertLayerStack, run_layers
+    if not torch.cuda.is_available():
+        raise SystemExit("text_encoder_step: needs a GPU (no CPU timing is meaningful)")
+    s = SHAPE
+    torch.manual_seed(1234)
+    bert = BertModel(BertConfig(vocab_size=s["vocab"], hidden_size=s["d"], num_hidden_layers=s["layers"], num_attention_heads=s["heads"],
+                                intermediate_size=s["inter"], max_position_embeddings=s["L"])).cuda().train()
+    g = torch.Generator().manual_seed(5)
+    ids = torch.randint(1, s["vocab"], (s["B"], s["L"]), generator=g).cuda()
+    mask, seg = torch.ones_like(ids), torch.zeros_like(ids)
+    w = torch.randn(s["B"], s["L"], s["d"], generator=g).cuda()
+    hip = mode.startswith("hip")
+    stack = BertLayerStack(bert, "bf16" if mode == "hip_bf16" else "f32") if hip else None
+    seed = [0]
+
+    def step():
+        for p in bert.parameters():
+            p.grad = None
+        if hip:
+            seed[0] += 1
+            stack.invalidate_shadows()          # a training step moves every weight: the bf16 / f32 shadows are re-packed per step
+            emb = bert.embeddings(input_ids=ids, token_type_ids=seg)
+            out = run_layers(stack, emb, mask, seed[0], True)
+        else:
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=mode == "hf_bf16"):
+                out = bert(input_ids=ids, attention_mask=mask, token_type_ids=seg, return_dict=False)[0]
+        (out.float() * w).sum().backward()
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    windows = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        windows.append(e0.elapsed_time(e1) / steps)
+    windows.sort()
+    med = windows[len(windows) // 2]
+    print(json.dumps({"mode": mode, "ms_per_step": round(med, 3), "windows_ms": [round(x, 3) for x in windows],
+                      "spread": round((windows[-1] - windows[0]) / med, 4), "tflops": round(flops() / (med * 1e-3) / 1e12, 1)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per mode (child process)")
+    ap.add_argument("--out", default=None, help="also write the result as JSON here")
+    ap.add_argument("--one", default=None, choices=MODES, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.one:
+        return one(a.one, a.steps, a.warmup, a.repeats)
+    res = dict(SHAPE, steps=a.steps, warmup=a.warmup, repeats=a.repeats, dropout=0.1, gflop_per_step=round(flops() / 1e9, 1), modes={})
+    for mode in MODES:
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--one", mode, "--steps", str(a.steps),
+               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:              # a time limit, a fault, an abort: nothing more is started on the device
+            print(f"text_encoder_step: mode {mode} ended with status {r.returncode}; stopping", file=sys.stderr)
+            return r.returncode
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
+        m = json.loads(line)
+        res["modes"][m.pop("mode")] = m
+    md = res["modes"]
+    res["hip_bf16_over_hf_bf16"] = round(md["hf_bf16"]["ms_per_step"] / md["hip_bf16"]["ms_per_step"], 3)      # > 1: the HIP path is faster
+    res["hip_f32_over_hf_f32"] = round(md["hf_f32"]["ms_per_step"] / md["hip_f32"]["ms_per_step"], 3)
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
