@@ -17,7 +17,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BPMULT_LIB", os.path.join(_HERE, "libbpmult_hip.so"))   # override: kernel-variant experiments
-SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "tail.hip", "frontend.hip", "prof.hip")
+SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "bert_embed.hip", "tail.hip", "frontend.hip", "prof.hip")
 HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
@@ -138,6 +138,21 @@ class AttnKMask(C.Structure):
 class GeluProblem(C.Structure):
     _fields_ = [("u", C.c_void_p), ("ldu", C.c_int), ("u_is_ct", C.c_int), ("g", C.c_void_p), ("ldg", C.c_int),
                 ("dg", C.c_void_p), ("lddg", C.c_int), ("du", C.c_void_p), ("lddu", C.c_int), ("R", C.c_int), ("C", C.c_int)]
+
+
+class BertEmbedProblem(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("seg", C.c_void_p), ("word", C.c_void_p), ("pos", C.c_void_p), ("type", C.c_void_p),
+                ("V", C.c_int), ("P", C.c_int), ("Tt", C.c_int), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("B", C.c_int), ("L", C.c_int), ("x", C.c_void_p), ("xc", C.c_void_p), ("ldc", C.c_int),
+                ("s", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("bad", C.c_void_p),
+                ("drop_p", C.c_float), ("drop_site", C.c_uint32)]
+
+
+class BertScatterProblem(C.Structure):
+    _fields_ = [("ds", C.c_void_p), ("sorted_ids", C.c_void_p), ("perm", C.c_void_p), ("seg", C.c_void_p),
+                ("dword", C.c_void_p), ("dpos", C.c_void_p), ("dtype", C.c_void_p),
+                ("V", C.c_int), ("Tt", C.c_int), ("B", C.c_int), ("L", C.c_int), ("padding_idx", C.c_int64),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
 class AttnMapProblem(C.Structure):
@@ -265,6 +280,9 @@ SIGNATURES = {
     "bpm_attn_maps": [_I, C.POINTER(AttnMapProblem), _I, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
+    "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],
+    "bpm_bert_embed_scatter_ws_bytes": [_I, _I, _I],
+    "bpm_bert_embed_scatter": [C.POINTER(BertScatterProblem), _I, _P],
     "bpm_pack_rows_fwd": [_I, C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_rows_bwd": [C.POINTER(PackProblem), _I, _U64, _P],
     "bpm_pack_weights": [_I, _P, _I, C.c_uint, _P],

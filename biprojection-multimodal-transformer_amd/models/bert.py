@@ -4,8 +4,10 @@ trunk; opt-in through `args.text_encoder = "hip"`, models/bpmult.py:BertEncoder)
 The module tree stays HF's: parameters, `state_dict` keys and optimizer groups are untouched.  `BertLayerStack` only
 reads `bert.encoder.layer[*]` and runs the post-LN layers as grouped launches behind ONE autograd node (`_StackFn`):
 embedding output [B, L, d] + attention mask [B, L] + the layers' parameters in, last hidden state [B, L, d] out; backward
-returns the gradient of the embedding output and of every layer parameter.  The embeddings (a gather + LayerNorm) stay on
-torch, the pooler is not evaluated (the reference discards its output).
+returns the gradient of the embedding output and of every layer parameter.  The embeddings (a gather + LayerNorm) run on
+torch by default; with `args.text_embeddings = "hip"` they are HIP kernels too (`BertEmbeddingsHip` below) and the node
+becomes `_EncoderFn`: (ids, type ids, byte mask, embedding parameters, layer parameters) -> last hidden state.  The pooler
+is not evaluated (the reference discards its output).
 
 Schedule of one layer, rows time-major (row = t*B + b, what the head-major attention layout expects), x fp32 [R, d]:
 
@@ -27,6 +29,20 @@ Key mask: HF's `attention_mask` as bytes [B, L], built on the device ((mask != 0
 the host.  Padded QUERY positions are computed like any other (HF does, and the trunk consumes them).  Every sample needs
 at least one visible key.
 
+Embeddings on the HIP path (HF `BertEmbeddings`, absolute positions):
+
+  x, xc, s, mean, rstd = drop(LN((word[id] + type[seg]) + pos[t]))          bpm_bert_embed_fwd: writes the plan's x[0] and
+                                                                             xc[0] in time-major rows straight from the
+                                                                             batch-major int64 ids (no cast, no transpose)
+  backward, from the stack's dx buffer (time-major, consumed where it lies):
+  g             = dy * dropmask                                              bpm_rows_cast (training with p > 0 only)
+  ds, dgamma, dbeta = dLN(g | s, mean, rstd)                                 bpm_ln_bwd_ws (the deterministic workspace route)
+  dword, dpos, dtype                                                         bpm_bert_embed_scatter (two launches, no float
+                                                                             atomics: bit-reproducible), after a stable
+                                                                             torch.sort of the ids on the device
+  The existing rows_cast + ln_bwd_ws pair was preferred to one fused new kernel: it costs one launch more in training and
+  none in eval, and reuses the workspace reduction that is already tested.  fp32 tensors in every precision mode (the forward carries a row's LayerNorm in fp64 registers and rounds once).
+
 Precision: "bf16" = bf16 MFMA operands (CT shadows of the weights, refreshed when a parameter's version changes), fp32
 accumulation, fp32 residual stream and LayerNorm; "f32" = exact fp32 products; "bf16x3" runs this stack's f32 path.
 """
@@ -44,6 +60,8 @@ from ..ops import pad32
 # dropout sites of the text encoder: disjoint from engine.site() (enc_id < 12 -> below 1 << 16) and engine.SITE_TEXT (1 << 20)
 SITE_BERT = 1 << 21
 S_PROBS, S_ATT_OUT, S_FFN_OUT = range(3)
+S_EMBED = 3                      # bert_site(0, S_EMBED): the embedding output's dropout, element (t*B + b)*d + c
+MAX_EMBED_HIDDEN = 1024          # reach of the 16-byte row kernels (one wave per row, four chunks per lane)
 
 # per layer, in this order (HF names below bert.encoder.layer[i])
 LAYER_PARAMS = ("attention.self.query.weight", "attention.self.query.bias", "attention.self.key.weight", "attention.self.key.bias",
@@ -122,7 +140,15 @@ class _Plan:
         self.dqkv = z(R, 3 * ld, dt=ct)
         self.stamp = 0
         self.mask: Optional[torch.Tensor] = None
-        self.seed, self.training = 0, False
+        self.seed, self.training, self.emb_p = 0, False, 0.0
+        # embeddings on the HIP path (embed_buffers): pre-LayerNorm sum, its row statistics, its gradient, scatter workspace
+        self.s = self.ds = self.emean = self.erstd = self.ews = None
+
+    def embed_buffers(self, st: "BertLayerStack", type_rows: int) -> None:
+        if self.s is None:
+            z = lambda *s: torch.zeros(*s, device=st.device, dtype=torch.float32)
+            self.s, self.ds, self.emean, self.erstd = z(self.R, st.d), z(self.R, st.d), z(self.R), z(self.R)
+            self.ews = z(max(1, ops.bert_embed_scatter_ws_bytes(self.R, st.d, type_rows) // 4))
 
 
 class BertLayerStack:
@@ -214,10 +240,16 @@ class BertLayerStack:
         return self.params[layer * len(LAYER_PARAMS) + LAYER_PARAMS.index(name)]
 
     # -- forward ---------------------------------------------------------------------
-    def forward(self, emb: torch.Tensor, mask_u8: torch.Tensor, seed: int, training: bool) -> Tuple[torch.Tensor, _Plan]:
-        """emb fp32 [B, L, d] (the embeddings module's output), mask_u8 uint8 [B, L] -> last hidden state [B, L, d]."""
-        B, L, d = emb.shape
-        self._prepare(emb.device)
+    def forward(self, emb: Optional[torch.Tensor], mask_u8: torch.Tensor, seed: int, training: bool,
+                embed=None) -> Tuple[torch.Tensor, _Plan]:
+        """emb fp32 [B, L, d] (the embeddings module's output), mask_u8 uint8 [B, L] -> last hidden state [B, L, d].
+        `embed` (with emb None): a callable(plan) that fills the plan's x[0] and xc[0] itself (the HIP embeddings): the
+        transposing copy of emb and the first cast launch are then not made."""
+        if embed is None:
+            B, L, d = emb.shape
+        else:
+            (B, L), d = mask_u8.shape, self.d
+        self._prepare(mask_u8.device if embed is not None else emb.device)
         self.refresh_shadows()
         pl = self._plan(B, L)
         pl.stamp += 1
@@ -227,11 +259,15 @@ class BertLayerStack:
         ph = self.p_hidden if training else 0.0
         pp = self.p_probs if training else 0.0
         km = ops.attn_kmasks([(mask_u8, L)])
-        pl.x[0].view(L, B, d).copy_(emb.transpose(0, 1))     # time-major rows
+        if embed is None:
+            pl.x[0].view(L, B, d).copy_(emb.transpose(0, 1))     # time-major rows
+        else:
+            embed(pl)
         for i in range(self.n_layers):
             P = lambda n, i=i: self._P(i, n)
             x, xc = pl.x[i], pl.xc[i]
-            ops.rows_cast(dt, [ops.cast_problem(x, d, R, d, dst_ct=xc, ldd=ld)], 0)
+            if i or embed is None:
+                ops.rows_cast(dt, [ops.cast_problem(x, d, R, d, dst_ct=xc, ldd=ld)], 0)
             qkv = [ops.gemm_problem(xc, self._sptr(i, "qkv", w * d * ld), out, R, d, d, ld, ld, 0, bias_n=P(f"attention.self.{nm}.bias"),
                                     alpha=self.scale if w == 0 else 1.0, out_kind=OUT_HEADS, heads=heads, flags=F_KPAD)
                    for w, (nm, out) in enumerate((("query", pl.q[i]), ("key", pl.k[i]), ("value", pl.v[i])))]
@@ -256,9 +292,10 @@ class BertLayerStack:
         return pl.x[self.n_layers].view(L, B, d).transpose(0, 1).contiguous(), pl
 
     # -- backward ----------------------------------------------------------------------
-    def backward(self, pl: _Plan, dout: torch.Tensor, need_demb: bool) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
+    def backward(self, pl: _Plan, dout: torch.Tensor, need_demb: bool, raw: bool = False) -> Tuple[Optional[torch.Tensor], List[torch.Tensor]]:
         """dout fp32 [B, L, d] -> (d(emb) [B, L, d] or None, the gradients of layer_parameters() in order).  Fresh tensors
-        every call (autograd may keep them as .grad)."""
+        every call (autograd may keep them as .grad).  raw: d(emb) is handed back as the plan's own time-major buffer
+        [L*B, d] (pl.dx[0] or pl.dx[1]; the other one is free scratch) instead of a batch-major copy."""
         B, L, R = pl.B, pl.L, pl.R
         d, I, H, ld, ldI, dt, seed = self.d, self.I, self.H, self.ld, self.ldI, self.dtype, pl.seed
         heads = (B, H, L, self.dh, self.dhp)
@@ -323,6 +360,8 @@ class BertLayerStack:
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dqkv, self._sptr(i, "qkv"), dxi, R, d, 3 * d, 3 * ld, ld, d,
                                                             resid=pl.dy1, ldr=d, flags=F_KPAD)], seed)
             cur ^= 1
+        if raw:
+            return (pl.dx[cur] if need_demb else None), grads
         demb = pl.dx[cur].view(L, B, d).transpose(0, 1).contiguous() if need_demb else None
         return demb, grads
 
@@ -361,3 +400,137 @@ def run_layers(stack: BertLayerStack, emb: torch.Tensor, mask: Optional[torch.Te
         mask_u8 = (mask.to(emb.device) != 0).to(torch.uint8).contiguous()        # on the device: no length reaches the host
     stack._prepare(emb.device)
     return _StackFn.apply(emb, mask_u8, stack, seed, training, *stack.params)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# embeddings on the HIP path (args.text_embeddings = "hip")
+# ---------------------------------------------------------------------------------------------------------------------
+EMBED_PARAMS = ("word_embeddings.weight", "position_embeddings.weight", "token_type_embeddings.weight", "LayerNorm.weight",
+                "LayerNorm.bias")
+
+
+def check_embed_config(cfg) -> None:
+    """What the HIP embeddings implement beyond check_config()."""
+    if cfg.hidden_size > MAX_EMBED_HIDDEN:
+        raise ValueError(f"text_embeddings='hip': hidden_size {cfg.hidden_size} > {MAX_EMBED_HIDDEN} is beyond the reach of the "
+                         "16-byte row kernels")
+
+
+def check_positions(L: int, cfg) -> None:
+    if L > cfg.max_position_embeddings:
+        raise ValueError(f"text encoder: {L} tokens per sample, but the model has max_position_embeddings = "
+                         f"{cfg.max_position_embeddings}")
+
+
+def embed_parameters(bert) -> List[torch.nn.Parameter]:
+    named = dict(bert.embeddings.named_parameters())
+    return [named[n] for n in EMBED_PARAMS]
+
+
+class BertEmbeddingsHip:
+    """Host driver of `bert.embeddings` on the HIP path.  Holds no parameters: it reads the HF module's tables and
+    LayerNorm affine where they lie.  `bad` is the int32 device counter of ids outside their table (cumulative)."""
+
+    def __init__(self, bert, bad: torch.Tensor):
+        check_embed_config(bert.config)
+        self.bert, self.bad = bert, bad
+        self.eps = float(bert.config.layer_norm_eps)
+        self.padding_idx = bert.embeddings.word_embeddings.padding_idx
+
+    def parameters(self) -> List[torch.nn.Parameter]:
+        params = embed_parameters(self.bert)
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != self.bad.device:
+                raise RuntimeError("text_embeddings='hip': BERT embedding parameters must be contiguous float32 tensors on the input's device")
+        return params
+
+    def drop_p(self, training: bool) -> float:
+        return float(self.bert.embeddings.dropout.p) if training else 0.0
+
+    def forward(self, st: BertLayerStack, pl: _Plan, ids: torch.Tensor, seg: Optional[torch.Tensor], seed: int, training: bool) -> None:
+        word, pos, typ, gamma, beta = self.parameters()
+        pl.embed_buffers(st, typ.shape[0])
+        pl.emb_p = self.drop_p(training)
+        prob = ops.bert_embed_problem(ids, seg, word, pos, typ, gamma, beta, x=pl.x[0], xc=pl.xc[0], ldc=st.ld, s=pl.s, mean=pl.emean,
+                                      rstd=pl.erstd, bad=self.bad, drop_p=pl.emb_p, drop_site=bert_site(0, S_EMBED))
+        ops.bert_embed_fwd(st.dtype, prob, st.d, self.eps, seed)
+
+    def backward(self, st: BertLayerStack, pl: _Plan, dy: torch.Tensor, ids: torch.Tensor, seg: Optional[torch.Tensor],
+                 need: List[bool]) -> List[Optional[torch.Tensor]]:
+        """dy: the stack's time-major d(x[0]) buffer (pl.dx[0] or pl.dx[1]) -> gradients of EMBED_PARAMS (None where not
+        needed).  Launches nothing when nothing is needed."""
+        if not any(need):
+            return [None] * 5
+        word, pos, typ, gamma, beta = self.parameters()
+        d, R, dev = st.d, pl.R, st.device
+        if pl.emb_p > 0.0:                                # regenerate the forward's mask into the free ping-pong buffer
+            g = pl.dx[1] if dy is pl.dx[0] else pl.dx[0]
+            ops.rows_cast(st.dtype, [ops.cast_problem(dy, d, R, d, dst_f32=g, ldf=d, drop_p=pl.emb_p, drop_site=bert_site(0, S_EMBED))],
+                          pl.seed)
+            dy = g
+        affine = need[3] or need[4]
+        gv = torch.zeros(2, d, device=dev, dtype=torch.float32) if affine else None
+        ops.ln_bwd([ops.ln_problem(pl.s, gamma, None, pl.emean, pl.erstd, R, dy=dy, ldy=d, dx=pl.ds,
+                                   dgamma=gv[0] if affine else None, dbeta=gv[1] if affine else None)], d, st.dtype, pl.seed)
+        out: List[Optional[torch.Tensor]] = [None, None, None, gv[0] if need[3] else None, gv[1] if need[4] else None]
+        if any(need[:3]):
+            kw = {}
+            if need[0]:
+                sid, perm = torch.sort(ids.view(-1), stable=True)         # integer plumbing on the device, no sync
+                out[0] = torch.zeros_like(word)
+                kw.update(sorted_ids=sid, perm=perm, dword=out[0], padding_idx=self.padding_idx)
+            if need[1]:
+                out[1] = torch.zeros_like(pos)
+                kw.update(dpos=out[1])
+            if need[2]:
+                out[2] = torch.zeros_like(typ)
+                kw.update(dtype_=out[2])
+            ops.bert_embed_scatter(ops.bert_scatter_problem(pl.ds, pl.B, pl.L, pl.ews, seg=seg, **kw), d)
+        return out
+
+
+class _EncoderFn(torch.autograd.Function):
+    """Embeddings + layer stack as ONE autograd node: (ids, type ids, byte mask, the five embedding parameters, the layer
+    parameters) -> last hidden state."""
+
+    @staticmethod
+    def forward(ctx, ids, seg, mask_u8, stack, embd, seed, training, *params):
+        out, plan = stack.forward(None, mask_u8, seed, training, embed=lambda pl: embd.forward(stack, pl, ids, seg, seed, training))
+        ctx.stack, ctx.embd, ctx.plan, ctx.stamp, ctx.ids, ctx.seg = stack, embd, plan, plan.stamp, ids, seg
+        ctx.need = [p.requires_grad for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if ctx.stamp != ctx.plan.stamp:
+            raise RuntimeError("text encoder (HIP path): backward() of a forward pass that a later forward pass of the same shape "
+                               "has overwritten; run forward -> backward one step at a time")
+        need_e, need_l = ctx.need[:5], ctx.need[5:]
+        dx, grads = ctx.stack.backward(ctx.plan, dout.contiguous().float(), any(need_e), raw=True)
+        egrads = ctx.embd.backward(ctx.stack, ctx.plan, dx, ctx.ids, ctx.seg, need_e)
+        return (None,) * 7 + tuple(egrads) + tuple(g if n else None for g, n in zip(grads, need_l))
+
+
+def run_encoder(stack: BertLayerStack, embd: BertEmbeddingsHip, ids: torch.Tensor, mask: Optional[torch.Tensor],
+                seg: Optional[torch.Tensor], seed: int, training: bool) -> torch.Tensor:
+    """ids [B, L] (token ids), mask [B, L] (HF attention_mask; None = all), seg [B, L] (token type ids; None = zeros) ->
+    last hidden state [B, L, d]: HIP embeddings and HIP layer stack behind one autograd node."""
+    if ids.dim() != 2:
+        raise ValueError(f"text encoder: token ids of shape {tuple(ids.shape)}, expected [B, L]")
+    B, L = ids.shape
+    check_positions(L, stack.bert.config)                 # from the shapes, on the host, before the device check
+    if not ids.is_cuda:
+        raise RuntimeError("text encoder: the HIP layer stack needs CUDA (HIP) tensors; there is no CPU path")
+    dev = ids.device
+    if seg is not None and seg.shape != (B, L):
+        raise ValueError(f"text encoder: token type ids of shape {tuple(seg.shape)} for inputs of shape {(B, L)}")
+    if mask is None:
+        mask_u8 = torch.ones(B, L, device=dev, dtype=torch.uint8)
+    else:
+        if mask.shape != (B, L):
+            raise ValueError(f"text encoder: attention mask of shape {tuple(mask.shape)} for inputs of shape {(B, L)}")
+        mask_u8 = (mask.to(dev) != 0).to(torch.uint8).contiguous()
+    ids = ids.long().contiguous()                         # HF passes int64: no launch then
+    seg = seg.to(dev).long().contiguous() if seg is not None else None
+    stack._prepare(dev)
+    return _EncoderFn.apply(ids, seg, mask_u8, stack, embd, seed, training, *embd.parameters(), *stack.params)

@@ -95,6 +95,7 @@ class AudioEncoder(nn.Module):
 
 
 TEXT_ENCODERS = ("torch", "hip")
+TEXT_EMBEDDINGS = ("torch", "hip")
 
 
 def step_seed(step: int) -> int:
@@ -111,8 +112,13 @@ class BertEncoder(nn.Module):
     tests) the `txt` argument already holds [B,L,orig_d_l] features.
 
     `args.text_encoder`: "torch" (the default: HF `BertModel` as it is) or "hip": `self.bert` is the same HF module (same
-    parameters, same state_dict keys), its embeddings still run on torch, and its `encoder.layer[*]` stack runs on the HIP
-    path behind one autograd node (models/bert.py); the pooler, whose output the reference discards, is not evaluated."""
+    parameters, same state_dict keys), its embeddings run on torch (by default), and its `encoder.layer[*]` stack runs on the HIP
+    path behind one autograd node (models/bert.py); the pooler, whose output the reference discards, is not evaluated.
+
+    `args.text_embeddings`: "torch" (the default) or "hip" (needs text_encoder = "hip" and hidden_size <= 1024): the
+    embeddings (three gathers, LayerNorm, dropout from the library's keyed hash) are HIP kernels too, and ids -> last
+    hidden state is ONE autograd node with bit-reproducible embedding gradients.  `bad_token_ids`: an int32 device counter
+    of token / type ids outside their table met so far (each contributes a zero row; reading it is the caller's sync)."""
 
     def __init__(self, args):
         super().__init__()
@@ -120,9 +126,16 @@ class BertEncoder(nn.Module):
         self.text_encoder = getattr(args, "text_encoder", "torch")
         if self.text_encoder not in TEXT_ENCODERS:
             raise ValueError(f"text_encoder must be one of {TEXT_ENCODERS}, got {self.text_encoder!r}")
+        self.text_embeddings = getattr(args, "text_embeddings", "torch")
+        if self.text_embeddings not in TEXT_EMBEDDINGS:
+            raise ValueError(f"text_embeddings must be one of {TEXT_EMBEDDINGS}, got {self.text_embeddings!r}")
+        if self.text_embeddings == "hip" and self.text_encoder != "hip":
+            raise ValueError("text_embeddings='hip' needs text_encoder='hip' (the embeddings feed the HIP layer stack's buffers)")
         self.precision: Optional[str] = getattr(args, "precision", None)
         self.bert = None
         self._stack = None
+        self._embd = None
+        self.bad_token_ids: Optional[torch.Tensor] = None       # device counter, created by the first HIP-embeddings forward
         self.dropout_step = 0           # host-side step counter of the HIP stack's dropout stream (the model sets it per step)
         if not self.features_in:
             from transformers import BertModel  # local directory only: there is no network
@@ -130,10 +143,15 @@ class BertEncoder(nn.Module):
             if self.text_encoder == "hip":
                 from .bert import check_config
                 check_config(self.bert.config)
+                if self.text_embeddings == "hip":
+                    from .bert import check_embed_config
+                    check_embed_config(self.bert.config)
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
         self._stack = None              # shadows and activation buffers live on the old device
+        self._embd = None
+        self.bad_token_ids = None
         return r
 
     def _next_seed(self) -> int:
@@ -151,11 +169,21 @@ class BertEncoder(nn.Module):
         if self.features_in:
             return txt
         if self.text_encoder == "hip":
-            from .bert import BertLayerStack, run_layers
-            emb = self.bert.embeddings(input_ids=txt, token_type_ids=segment)
+            from .bert import BertEmbeddingsHip, BertLayerStack, check_positions, run_encoder, run_layers
+            if self.text_embeddings == "hip":
+                check_positions(txt.shape[-1], self.bert.config)
+                if not txt.is_cuda:
+                    raise RuntimeError("text encoder: the HIP layer stack needs CUDA (HIP) tensors; there is no CPU path")
+            else:
+                emb = self.bert.embeddings(input_ids=txt, token_type_ids=segment)
             if self._stack is None:
                 self._stack = BertLayerStack(self.bert, self.precision)
             self._stack.precision = self.precision
+            if self.text_embeddings == "hip":
+                if self._embd is None:
+                    self.bad_token_ids = torch.zeros(1, device=txt.device, dtype=torch.int32)
+                    self._embd = BertEmbeddingsHip(self.bert, self.bad_token_ids)
+                return run_encoder(self._stack, self._embd, txt, mask, segment, self._next_seed(), self.training)
             return run_layers(self._stack, emb, mask, self._next_seed(), self.training)
         return self.bert(input_ids=txt, token_type_ids=segment, attention_mask=mask, return_dict=False)[0]
 

@@ -624,6 +624,71 @@ def gelu_bwd(dtype: int, probs) -> None:
         _lib.check(_lib.lib().bpm_gelu_bwd(dtype, sub, k, _stream()), "bpm_gelu_bwd")
 
 
+def _table(t, what: str, d: int):
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d or t.stride(1) != 1 or t.stride(0) != d:
+        raise ValueError(f"{what}: a float32 [rows, {d}] table with contiguous rows")
+    return _p(t)
+
+
+def _ids(t, what: str, B: int, L: int):
+    if t is None:
+        return None
+    if t.dtype != torch.int64 or tuple(t.shape) != (B, L) or not t.is_contiguous():
+        raise ValueError(f"{what}: a contiguous int64 [B, L] tensor")
+    return _p(t)
+
+
+def bert_embed_problem(ids, seg, word, pos, typ, gamma, beta, *, x, s, mean, rstd, bad, xc=None, ldc: int = 0, drop_p: float = 0.0,
+                       drop_site: int = 0) -> "_lib.BertEmbedProblem":
+    """bpm_bert_embed_fwd: ids / seg int64 [B, L] (seg None = all zeros), the three fp32 tables [rows, d] (views with
+    contiguous rows are fine), outputs in time-major rows (t*B + b); bad: the int32 device counter of ids outside a table."""
+    B, L = ids.shape
+    d = word.shape[1]
+    p = _lib.BertEmbedProblem()
+    p.ids, p.seg = _ids(ids, "bert_embed.ids", B, L), _ids(seg, "bert_embed.seg", B, L)
+    p.word, p.pos, p.type = _table(word, "bert_embed.word", d), _table(pos, "bert_embed.pos", d), _table(typ, "bert_embed.type", d)
+    p.V, p.P, p.Tt = word.shape[0], pos.shape[0], typ.shape[0]
+    p.gamma, p.beta, p.B, p.L = _f32(gamma, "bert_embed.gamma"), _f32(beta, "bert_embed.beta"), B, L
+    p.x, p.xc, p.ldc = _f32(x, "bert_embed.x"), _p(xc), ldc
+    p.s, p.mean, p.rstd = _f32(s, "bert_embed.s"), _f32(mean, "bert_embed.mean"), _f32(rstd, "bert_embed.rstd")
+    if bad.dtype != torch.int32 or bad.numel() < 1:
+        raise ValueError("bert_embed.bad: an int32 device counter")
+    p.bad, p.drop_p, p.drop_site = _p(bad), drop_p, drop_site
+    return p
+
+
+def bert_embed_fwd(dtype: int, prob, d: int, eps: float, seed: int = 0) -> None:
+    _lib.check(_lib.lib().bpm_bert_embed_fwd(dtype, C.byref(prob), d, eps, _seed(seed), _stream()), "bpm_bert_embed_fwd")
+
+
+def bert_embed_scatter_ws_bytes(rows: int, d: int, type_rows: int) -> int:
+    return int(_lib.lib().bpm_bert_embed_scatter_ws_bytes(rows, d, type_rows))
+
+
+def bert_scatter_problem(ds, B: int, L: int, ws, *, sorted_ids=None, perm=None, seg=None, dword=None, padding_idx=None, dpos=None,
+                         dtype_=None) -> "_lib.BertScatterProblem":
+    """bpm_bert_embed_scatter: ds fp32 [L*B, d] time-major; dword (zeroed by the caller) needs sorted_ids / perm = the stable
+    sort of ids.view(-1); a gradient left None is not computed."""
+    p = _lib.BertScatterProblem()
+    p.ds, p.B, p.L = _f32(ds, "bert_scatter.ds"), B, L
+    for t, what in ((sorted_ids, "sorted_ids"), (perm, "perm")):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != B * L or not t.is_contiguous()):
+            raise ValueError(f"bert_scatter.{what}: a contiguous int64 tensor of B*L elements")
+    p.sorted_ids, p.perm, p.seg = _p(sorted_ids), _p(perm), _ids(seg, "bert_scatter.seg", B, L)
+    p.dword, p.dpos, p.dtype = _f32(dword, "bert_scatter.dword"), _f32(dpos, "bert_scatter.dpos"), _f32(dtype_, "bert_scatter.dtype")
+    p.V = dword.shape[0] if dword is not None else 0
+    p.Tt = dtype_.shape[0] if dtype_ is not None else 0
+    if dpos is not None and dpos.shape[0] < L:
+        raise ValueError("bert_scatter.dpos: fewer rows than time steps")
+    p.padding_idx = -1 if padding_idx is None else int(padding_idx)
+    p.ws, p.ws_bytes = _f32(ws, "bert_scatter.ws"), (ws.numel() * 4 if ws is not None else 0)
+    return p
+
+
+def bert_embed_scatter(prob, d: int) -> None:
+    _lib.check(_lib.lib().bpm_bert_embed_scatter(C.byref(prob), d, _stream()), "bpm_bert_embed_scatter")
+
+
 def addn_problem(out, ins) -> "_lib.AddnProblem":
     """out = sum(ins): contiguous fp32 tensors of one size (16-byte aligned); out may be one of them."""
     p = _lib.AddnProblem()

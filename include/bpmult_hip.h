@@ -343,6 +343,55 @@ typedef struct bpm_gelu_problem {
 int bpm_gelu_fwd(int dtype, const bpm_gelu_problem* probs, int n, void* stream);
 int bpm_gelu_bwd(int dtype, const bpm_gelu_problem* probs, int n, void* stream);
 
+/* HF BertEmbeddings (absolute positions) in front of the text encoder's layer stack (mmtr.py:144-158), one problem per
+ * launch.  ids / seg: int64 [B, L], batch-major as HF passes them (seg NULL = all zeros); word [V,d], pos [P,d] (L <= P),
+ * type [Tt,d]: fp32 tables with contiguous rows.  Per time-major row r = t*B + b:
+ *   s = (word[ids[b,t]] + type[seg[b,t]]) + pos[t]          (HF's summation order)
+ *   x = (LN(s) * gamma + beta) * dropout_mult(r*d + c)      (eps inside the sqrt, biased variance)
+ * Outputs: x fp32 [R,d]; optionally xc, the CT copy [R, ldc] of x with zero pad columns (bit-equal to what bpm_rows_cast
+ * makes of x); s fp32 [R,d] and mean / rstd [R] of s for the backward.  The sum s is HF's two fp32 adds; the LayerNorm of a row is carried in fp64 registers and rounded once
+ * to fp32 (x is the correctly rounded LayerNorm of s); nothing is bf16 whatever `dtype`, which
+ * only names CT (BPM_F32 or BPM_BF16).  The kernel never reads outside a table: an id outside [0, V) or a type id outside
+ * [0, Tt) contributes a ZERO row and adds one to the device counter *bad (one vector atomic; no host sync, no device
+ * assert).  d % 32 == 0, 32 <= d <= 1024; tables, gamma, beta, x, s 16-byte aligned; B*L*d < 2^32.
+ * BPM_ERR_ARG / BPM_ERR_ALIGN before anything is launched. */
+typedef struct bpm_bert_embed_problem {
+    const int64_t* ids; const int64_t* seg;
+    const float* word; const float* pos; const float* type;
+    int V, P, Tt;
+    const float* gamma; const float* beta;
+    int B, L;
+    float* x;
+    void* xc; int ldc;                      /* optional */
+    float* s; float* mean; float* rstd;
+    unsigned* bad;
+    float drop_p; uint32_t drop_site;       /* element index (t*B + b)*d + c */
+} bpm_bert_embed_problem;
+int bpm_bert_embed_fwd(int dtype, const bpm_bert_embed_problem* prob /* host */, int d, float eps, uint64_t seed, void* stream);
+
+/* Backward of the three gathers: ds fp32 [R,d] (time-major; the dx of bpm_ln_bwd_ws on (s, mean, rstd, gamma) with
+ * dy = the layer stack's input gradient times the forward's dropout mask) -> the table gradients, each optional (NULL =
+ * that table is frozen).  NO float atomics: every destination row is written by one owner that adds its rows in one
+ * fixed order, so the result is bitwise reproducible.
+ *   dword [V,d], ZEROED by the caller: sorted_ids / perm = the stable ascending sort of ids.view(-1) and its permutation
+ *     (int64 [R], perm indexes the batch-major [B, L] ids).  Rows of one id are added in sorted order, runs longer than
+ *     32 in 32-row pieces combined in order; ids outside [0, V) and row padding_idx (-1 = none) are skipped: those rows
+ *     stay as the caller left them.
+ *   dpos [P,d]: row t < L = sum_b ds[t*B + b]; rows >= L are not written.
+ *   dtype [Tt,d]: every row written (two stages: per-block partial rows, then one owner per column); seg as in the forward.
+ * ws: at least bpm_bert_embed_scatter_ws_bytes(B*L, d, Tt) bytes, 16-byte aligned, private to the stream for the call;
+ * its contents do not matter.  Two launches.  Same limits on d as the forward. */
+typedef struct bpm_bert_scatter_problem {
+    const float* ds;
+    const int64_t* sorted_ids; const int64_t* perm; const int64_t* seg;
+    float* dword; float* dpos; float* dtype;
+    int V, Tt, B, L;
+    int64_t padding_idx;
+    float* ws; size_t ws_bytes;
+} bpm_bert_scatter_problem;
+size_t bpm_bert_embed_scatter_ws_bytes(int rows, int d, int type_rows);
+int bpm_bert_embed_scatter(const bpm_bert_scatter_problem* prob /* host */, int d, void* stream);
+
 /* fp32 [R, C] (row stride ld) -> split bf16 [R, 2 ldp] for the BPM_BF16X3 products: columns [0, ldp) = hi = bf16(x),
  * columns [ldp, 2 ldp) = lo = bf16(x - hi), pad columns [C, ldp) of both planes zero (ldp % 4 == 0; the LDS-DMA GEMM
  * wants ldp % 128 == 0).  The parity-grade mode of the linear layers (multihead_attention.py:152-158,

@@ -7,7 +7,12 @@ L = 512, B = 8, HF dropout defaults 0.1, train mode, randomly initialised weight
   hip_f32    text_encoder="hip", precision f32       (embeddings on torch, the layer stack on the HIP path)
   hip_bf16   text_encoder="hip", precision bf16
 
+`--embeddings hip` runs the two hip modes with text_embeddings="hip" (ids -> hidden state -> backward as one autograd node,
+models/bert.py:run_encoder) and records them as hip_f32_hip_embeddings / hip_bf16_hip_embeddings; `--modes` selects a subset.
+With `--out`, modes that were not run keep the figures the file already holds.
+
   python tools/text_encoder_step.py [--steps 40 --warmup 5 --repeats 3 --out profiles/text_encoder_step.json]
+  python tools/text_encoder_step.py --modes hip_bf16 --embeddings hip --out profiles/text_encoder_step.json
 
 Every mode runs in a child process of its own under `timeout` (a hung or faulted mode ends the whole measurement: nothing
 more is started on the device).  In the child: `--warmup` untimed steps, then `--repeats` windows of `--steps` steps, each
@@ -37,12 +42,12 @@ def flops():
     return 3 * s["B"] * s["layers"] * per_layer
 
 
-def one(mode, steps, warmup, repeats):
+def one(mode, steps, warmup, repeats, embeddings="torch"):
     import torch
     from transformers import BertConfig, BertModel
 
     import bpmult_amd  # noqa: F401
-    from bpmult_amd.models.bert import BertLayerStack, run_layers
+    from bpmult_amd.models.bert import BertEmbeddingsHip, BertLayerStack, run_encoder, run_layers
     if not torch.cuda.is_available():
         raise SystemExit("text_encoder_step: needs a GPU (no CPU timing is meaningful)")
     s = SHAPE
@@ -55,6 +60,8 @@ def one(mode, steps, warmup, repeats):
     w = torch.randn(s["B"], s["L"], s["d"], generator=g).cuda()
     hip = mode.startswith("hip")
     stack = BertLayerStack(bert, "bf16" if mode == "hip_bf16" else "f32") if hip else None
+    hip_emb = hip and embeddings == "hip"
+    embd = BertEmbeddingsHip(bert, torch.zeros(1, device="cuda", dtype=torch.int32)) if hip_emb else None
     seed = [0]
 
     def step():
@@ -63,8 +70,11 @@ def one(mode, steps, warmup, repeats):
         if hip:
             seed[0] += 1
             stack.invalidate_shadows()          # a training step moves every weight: the bf16 / f32 shadows are re-packed per step
-            emb = bert.embeddings(input_ids=ids, token_type_ids=seg)
-            out = run_layers(stack, emb, mask, seed[0], True)
+            if hip_emb:
+                out = run_encoder(stack, embd, ids, mask, seg, seed[0], True)
+            else:
+                emb = bert.embeddings(input_ids=ids, token_type_ids=seg)
+                out = run_layers(stack, emb, mask, seed[0], True)
         else:
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=mode == "hf_bf16"):
                 out = bert(input_ids=ids, attention_mask=mask, token_type_ids=seg, return_dict=False)[0]
@@ -84,6 +94,9 @@ def one(mode, steps, warmup, repeats):
         windows.append(e0.elapsed_time(e1) / steps)
     windows.sort()
     med = windows[len(windows) // 2]
+    if hip_emb:
+        assert int(embd.bad) == 0
+        mode += "_hip_embeddings"
     print(json.dumps({"mode": mode, "ms_per_step": round(med, 3), "windows_ms": [round(x, 3) for x in windows],
                       "spread": round((windows[-1] - windows[0]) / med, 4), "tflops": round(flops() / (med * 1e-3) / 1e12, 1)}), flush=True)
 
@@ -95,14 +108,21 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=240, help="seconds per mode (child process)")
     ap.add_argument("--out", default=None, help="also write the result as JSON here")
+    ap.add_argument("--embeddings", default="torch", choices=("torch", "hip"), help="embeddings of the hip_* modes")
+    ap.add_argument("--modes", default=",".join(MODES), help="comma-separated subset of " + ",".join(MODES))
     ap.add_argument("--one", default=None, choices=MODES, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
-        return one(a.one, a.steps, a.warmup, a.repeats)
+        return one(a.one, a.steps, a.warmup, a.repeats, a.embeddings)
+    modes = [m for m in a.modes.split(",") if m]
+    if any(m not in MODES for m in modes):
+        ap.error(f"--modes: a subset of {MODES}")
     res = dict(SHAPE, steps=a.steps, warmup=a.warmup, repeats=a.repeats, dropout=0.1, gflop_per_step=round(flops() / 1e9, 1), modes={})
-    for mode in MODES:
+    if a.out and os.path.exists(a.out):    # modes that are not run now keep their recorded figures
+        res["modes"] = json.load(open(a.out)).get("modes", {})
+    for mode in modes:
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--one", mode, "--steps", str(a.steps),
-               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+               "--warmup", str(a.warmup), "--repeats", str(a.repeats), "--embeddings", a.embeddings]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         if r.returncode != 0:              # a time limit, a fault, an abort: nothing more is started on the device
             print(f"text_encoder_step: mode {mode} ended with status {r.returncode}; stopping", file=sys.stderr)
@@ -111,8 +131,10 @@ def main():
         m = json.loads(line)
         res["modes"][m.pop("mode")] = m
     md = res["modes"]
-    res["hip_bf16_over_hf_bf16"] = round(md["hf_bf16"]["ms_per_step"] / md["hip_bf16"]["ms_per_step"], 3)      # > 1: the HIP path is faster
-    res["hip_f32_over_hf_f32"] = round(md["hf_f32"]["ms_per_step"] / md["hip_f32"]["ms_per_step"], 3)
+    ratio = lambda a_, b_: round(md[a_]["ms_per_step"] / md[b_]["ms_per_step"], 3) if a_ in md and b_ in md else None
+    res["hip_bf16_over_hf_bf16"] = ratio("hf_bf16", "hip_bf16")      # > 1: the HIP path is faster
+    res["hip_f32_over_hf_f32"] = ratio("hf_f32", "hip_f32")
+    res["hip_embeddings_over_torch_embeddings_bf16"] = ratio("hip_bf16", "hip_bf16_hip_embeddings")   # > 1: HIP embeddings are faster
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
