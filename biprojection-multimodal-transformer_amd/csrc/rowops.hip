@@ -167,20 +167,100 @@ __global__ __launch_bounds__(NT) void fold_bias_kernel(const bpm_fold_desc* __re
 // (Measured in round 3 and not kept: per-block partial rows through a workspace + last-block sum instead of the float
 // atomics on dgamma / dbeta -- 72 us against 42 stand-alone at hidden 768: the 4-byte write-through stores cost more
 // than the contended atomics.)
+//
+// A block owns 16 rows.  Wide path (cols and ldw multiples of 4, every matrix and vector 16-byte aligned): a thread owns
+// four consecutive columns and walks its rows in batches of UNF_BATCH, the 16-byte loads of dWf, W and (when it is
+// accumulated into) dW of a whole batch issued before the first use -- the one-column loop below keeps a single 4-byte
+// load per operand in flight, because the store into dW may alias the next row's loads.  The per-column sums run over
+// r ascending with the expressions of the one-column loop, so both paths give the same dW, dbias and partial sums.  The
+// sums of a pass go through LDS to be added as the one-column loop adds them: consecutive lanes on consecutive columns
+// (one 256-byte atomic instruction per wave, not 64 dwords 16 bytes apart).
 constexpr int UNF_ROWS = 16;
+constexpr int UNF_BATCH = 8;
+
+// the descriptor's pointers come out of a device table, which makes them generic (flat_*) to the compiler: the wide path
+// says that they are global memory, so its loads take a uniform row base and count their own waits
+typedef f32x4 __attribute__((address_space(1))) g_f32x4;
+BPM_DEV f32x4 gload4(const float* p) { return *(const g_f32x4*)p; }
+BPM_DEV void gstore4(float* p, f32x4 v) { *(g_f32x4*)p = v; }
+BPM_DEV float gload1(const float* p) { return *(const float __attribute__((address_space(1)))*)p; }
+
+// one element of dW's update, written once so that both paths round it alike: two rounded products, then their sum (left
+// to the compiler, the wide path fused db * bt into the sum and the one-column loop neither); the column sums are fused
+BPM_DEV float unf_dw(float f, float g, float db, float bt) {
+#pragma clang fp contract(off)
+    return f * g + db * bt;
+}
+
+BPM_DEV bool unf_wide(const bpm_unfold_desc& d) {
+    const uintptr_t a = (uintptr_t)d.dWf | (uintptr_t)d.W | (uintptr_t)d.dW | (uintptr_t)d.gamma | (uintptr_t)d.beta |
+                        (uintptr_t)d.dgamma | (uintptr_t)d.dbeta;
+    return ((d.cols | d.ldw) & 3) == 0 && (a & 15) == 0;
+}
+
+template <bool STORE>
+BPM_DEV void unfold_wide(const bpm_unfold_desc& d, int r0, int r1, float* sums) {
+    const int tid = threadIdx.x;
+    for (int c0 = 0; c0 < d.cols; c0 += 4 * NT) {         // (block-uniform trip count: the barriers below)
+        const int c = c0 + 4 * tid;
+        f32x4 ag = f32x4{0.f, 0.f, 0.f, 0.f}, ab = ag;
+        if (c < d.cols) {
+            const f32x4 g = gload4(d.gamma + c), bt = gload4(d.beta + c);
+            for (int rb = r0; rb < r1; rb += UNF_BATCH) {
+                f32x4 f[UNF_BATCH], w[UNF_BATCH], o[UNF_BATCH];
+                float db[UNF_BATCH];
+#pragma unroll
+                for (int j = 0; j < UNF_BATCH; ++j) {
+                    const int r = min(rb + j, r1 - 1);    // a dead row of the last batch re-reads the last live one
+                    f[j] = gload4(d.dWf + (size_t)r * d.cols + c);
+                    w[j] = gload4(d.W + (size_t)r * d.ldw + c);
+                    if (!STORE) o[j] = gload4(d.dW + (size_t)r * d.ldw + c);
+                    db[j] = gload1(d.dbf + r);
+                }
+                __builtin_amdgcn_sched_barrier(0);        // the whole batch is issued before the first row is used
+#pragma unroll
+                for (int j = 0; j < UNF_BATCH; ++j) {
+                    if (rb + j >= r1) break;
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        v[e] = unf_dw(f[j][e], g[e], db[j], bt[e]);
+                        if (!STORE) v[e] = o[j][e] + v[e];
+                        ag[e] = fmaf(f[j][e], w[j][e], ag[e]);
+                        ab[e] = fmaf(db[j], w[j][e], ab[e]);
+                    }
+                    gstore4(d.dW + (size_t)(rb + j) * d.ldw + c, v);
+                }
+            }
+        }
+        *(f32x4*)(sums + 4 * tid) = ag;
+        *(f32x4*)(sums + 4 * NT + 4 * tid) = ab;
+        __syncthreads();
+        for (int k = tid; k < 4 * NT && c0 + k < d.cols; k += NT) {
+            atomicAdd(d.dgamma + c0 + k, sums[k]);
+            atomicAdd(d.dbeta + c0 + k, sums[4 * NT + k]);
+        }
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(NT) void unfold_grads_kernel(const bpm_unfold_desc* __restrict__ tab, int ndesc, int store_dw) {
     const bpm_unfold_desc d = find_desc(tab, ndesc, blockIdx.x);
     const int r0 = (int)(blockIdx.x - d.blk0) * UNF_ROWS, r1 = min(d.rows, r0 + UNF_ROWS);
-    for (int c = threadIdx.x; c < d.cols; c += NT) {
+    __shared__ __attribute__((aligned(16))) float sums[2 * 4 * NT];
+    if (unf_wide(d)) {
+        if (store_dw) unfold_wide<true>(d, r0, r1, sums);
+        else unfold_wide<false>(d, r0, r1, sums);
+    } else for (int c = threadIdx.x; c < d.cols; c += NT) {
         const float g = d.gamma[c], bt = d.beta[c];
         float ag = 0.f, ab = 0.f;
         for (int r = r0; r < r1; ++r) {
             const float f = d.dWf[(size_t)r * d.cols + c], w = d.W[(size_t)r * d.ldw + c], db = d.dbf[r];
-            const float v = f * g + db * bt;
+            const float v = unf_dw(f, g, db, bt);
             float* o = d.dW + (size_t)r * d.ldw + c;
             *o = store_dw ? v : *o + v;                   // store_dw: this launch is the first writer of dW this step
-            ag += f * w;
-            ab += db * w;
+            ag = fmaf(f, w, ag);
+            ab = fmaf(db, w, ab);
         }
         atomicAdd(d.dgamma + c, ag);
         atomicAdd(d.dbeta + c, ab);

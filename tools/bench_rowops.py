@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the row kernels (LayerNorm fwd/bwd, rows_cast) at the model's shapes (MI355X only)."""
+"""Micro-benchmark of the row kernels (LayerNorm fwd/bwd, rows_cast) at the model's shapes (MI355X only).
+
+--streaming: the pure streaming kernels at the headline step's shapes (hidden 768) against ln_fwd in the same run --
+unfold_grads over six descriptors of 1536 x 768, embed_pos forward / backward and ln_fwd over six problems of 4096 x 768;
+--json PATH writes {case: {"us", "GBps"}} (BPMULT_LIB selects the library, so two builds can alternate on one box)."""
 import argparse
+import json
 import os
 import sys
 
@@ -16,6 +21,8 @@ def main():
     ap.add_argument("--R", type=int, default=4096)
     ap.add_argument("--G", type=int, default=6)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--streaming", action="store_true", help="only the streaming cases at hidden 768")
+    ap.add_argument("--json", default=None, help="write the results to this file")
     a = ap.parse_args()
     import bpmult_amd  # noqa: F401
     from bpmult_amd import ops
@@ -41,8 +48,16 @@ def main():
         ts.sort()
         med = ts[len(ts) // 2]
         print(f"{name:44s} {med * 1e3:8.1f} us  {nbytes / med / 1e6:8.1f} GB/s", flush=True)
+        results[name] = {"us": round(med * 1e3, 2), "GBps": round(nbytes / med / 1e6, 1)}
 
+    results = {}
     keep = []
+    if a.streaming:
+        streaming_cases(ops, timeit, a.G)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(results, f, indent=1)
+        return
 
     def ln_probs(n, gam=True, cast=False, add=True):
         ps = []
@@ -95,6 +110,52 @@ def main():
         ps.append(ops.cast_problem(src, d, R, d, dst_ct=dst, ldd=ld, colsum=cs, drop_p=0.1, drop_site=4))
     arr4 = ops.array(ops.CastProblem, ps)
     timeit(f"rows_cast f32->CT drop colsum x{G}", lambda: ops.rows_cast(BPM_BF16, arr4, 5), G * (R * d * 4 + R * ld * 2))
+
+
+def streaming_cases(ops, timeit, G, R=4096, d=768):
+    """Bytes are algorithmic: every matrix once per direction it moves in; the [d] vectors and the cached position
+    table are left out."""
+    from bpmult_amd import _lib
+    from bpmult_amd.ops import BPM_BF16, pad32
+    dev = "cuda"
+    rn = lambda *s: torch.randn(*s, device=dev)
+    keep = []
+
+    # unfold_grads: in_proj rows [d, 3d) of one layer of six encoders
+    rows, descs = 2 * d, []
+    for k in range(G):
+        t = [rn(rows, d), rn(rows), rn(rows, d), rn(d), rn(d), rn(rows, d), rn(rows), rn(d), rn(d)]
+        keep.append(t)
+        ud = _lib.UnfoldDesc()
+        (ud.dWf, ud.dbf, ud.W, ud.gamma, ud.beta, ud.dW, ud.dbias, ud.dgamma, ud.dbeta) = (x.data_ptr() for x in t)
+        ud.rows, ud.cols, ud.ldw, ud.blk0 = rows, d, d, k * ((rows + 15) // 16)
+        descs.append(ud)
+    tab, nblk = ops.device_table(descs), G * ((rows + 15) // 16)
+    for store in (0, 1):
+        timeit(f"unfold_grads x{G} {rows}x{d} store_dw={store}", lambda: ops.unfold_grads(tab, G, nblk, store_dw=bool(store)),
+               G * rows * d * 4 * (3 if store else 4))
+
+    # embed_pos: T*B = R rows
+    T, B = R // 8, 8
+    table = rn(T + 2, d)
+    x, out = [rn(T, B, d) for _ in range(G)], [rn(T, B, d) for _ in range(G)]
+    for p in (0.0, 0.25):
+        fw = ops.array(ops.EmbedProblem, [ops.embed_problem(x[k], out[k], T, B, drop_p=p, drop_site=k) for k in range(G)])
+        timeit(f"embed_pos_fwd x{G} {R}x{d} drop={p}", lambda: ops.embed_pos_fwd(fw, table, d, d ** 0.5, seed=1), G * R * d * 4 * 2)
+        for acc in (0, 1):
+            bw = ops.array(ops.EmbedProblem, [ops.embed_problem(x[k], out[k], T, B, accumulate=bool(acc), drop_p=p, drop_site=k)
+                                              for k in range(G)])
+            timeit(f"embed_pos_bwd x{G} {R}x{d} drop={p} accumulate={acc}", lambda: ops.embed_pos_bwd(bw, d, d ** 0.5, seed=1),
+                   G * R * d * 4 * (3 if acc else 2))
+
+    # ln_fwd: the rate the same file reaches on the same rows
+    ld, ps = pad32(d), []
+    for _ in range(G):
+        t = [rn(R, d), rn(d), rn(d), rn(R), rn(R), torch.zeros(R, ld, device=dev, dtype=torch.bfloat16)]
+        keep.append(t)
+        ps.append(ops.ln_problem(t[0], t[1], t[2], t[3], t[4], R, out=t[5], ldo=ld))
+    arr = ops.array(ops.LnProblem, ps)
+    timeit(f"ln_fwd x{G} {R}x{d}", lambda: ops.ln_fwd(BPM_BF16, arr, d), G * (R * d * 4 + R * ld * 2))
 
 
 if __name__ == "__main__":
