@@ -17,7 +17,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BPMULT_LIB", os.path.join(_HERE, "libbpmult_hip.so"))   # override: kernel-variant experiments
-SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "bert_embed.hip", "tail.hip", "frontend.hip", "prof.hip")
+SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "bert_embed.hip", "loss.hip", "tail.hip", "frontend.hip", "prof.hip")
 HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
@@ -39,6 +39,8 @@ MAX_GROUP = 18
 SEED_INDIRECT = 1 << 63          # seed = SEED_INDIRECT | device address of a uint64 (include/bpmult_hip.h)
 GEMM_MAX_GROUP = 24
 ADAM_MAX_GROUPS = 16             # == BPM_ADAM_MAX_GROUPS
+LOSS_BCE, LOSS_CE, LOSS_L1 = 0, 1, 2              # BPM_LOSS_* kinds
+LOSS_MEAN, LOSS_SUM, LOSS_NONE = 0, 1, 2          # BPM_LOSS_* reductions
 
 
 def build(force: bool = False, verbose: bool = False, out: str | None = None, flags: tuple = (), objdir: str | None = None) -> str:
@@ -202,6 +204,13 @@ class SumsqSeg(C.Structure):
     _fields_ = [("p", C.c_void_p), ("n", C.c_size_t), ("blk0", C.c_uint), ("pad_", C.c_uint)]
 
 
+class LossDesc(C.Structure):
+    _fields_ = [("kind", C.c_int), ("reduction", C.c_int), ("B", C.c_int), ("C", C.c_int),
+                ("logits", C.c_void_p), ("ld", C.c_int), ("target", C.c_void_p), ("ldt", C.c_int), ("weight", C.c_void_p),
+                ("ignore_index", C.c_int64), ("loss", C.c_void_p), ("dlogits_unit", C.c_void_p), ("ldd", C.c_int),
+                ("bad", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class SplitProblem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("R", C.c_int), ("C", C.c_int), ("ld", C.c_int), ("ldp", C.c_int)]
 
@@ -316,6 +325,9 @@ SIGNATURES = {
     "bpm_grad_sumsq_blocks": [_P, C.c_size_t],
     "bpm_grad_sumsq_ws_bytes": [C.c_uint],
     "bpm_grad_sumsq": [_P, _I, C.c_uint, _F, _F, _P, _P, C.c_size_t, _P, _P],
+    "bpm_loss_ws_bytes": [_I, _I, _I, _I],
+    "bpm_loss_fwd": [C.POINTER(LossDesc), _P],
+    "bpm_loss_bwd": [C.POINTER(LossDesc), _P, _I, _P, _I, _P],
     "bpm_stream_create": [_I, C.POINTER(C.c_void_p)],
     "bpm_stream_priority_range": [C.POINTER(_I), C.POINTER(_I)],
     "bpm_prof_enable": [C.c_uint],

@@ -689,6 +689,45 @@ def bert_embed_scatter(prob, d: int) -> None:
     _lib.check(_lib.lib().bpm_bert_embed_scatter(C.byref(prob), d, _stream()), "bpm_bert_embed_scatter")
 
 
+def loss_ws_bytes(kind: int, reduction: int, B: int, Cn: int) -> int:
+    return int(_lib.lib().bpm_loss_ws_bytes(kind, reduction, B, Cn))
+
+
+def loss_problem(kind: int, reduction: int, logits, target, loss, B: int, Cn: int, *, ld: Optional[int] = None, ldt: Optional[int] = None,
+                 weight=None, ignore_index: int = -100, dlogits_unit=None, ldd: Optional[int] = None, bad=None, ws=None) -> "_lib.LossDesc":
+    """bpm_loss_fwd / bpm_loss_bwd: logits fp32 [B, ld], target fp32 [B, ldt] (LOSS_BCE, LOSS_L1) or int64 [B] (LOSS_CE),
+    weight fp32 [C] (pos_weight / class weight), loss fp32 (one value, or the elements / rows for LOSS_NONE), dlogits_unit
+    fp32 [B, ldd] or None (no derivative wanted), bad: the int32 device counter of class indices outside [0, C), ws: any
+    tensor of at least loss_ws_bytes(...) bytes.  Leading dimensions default to C."""
+    p = _lib.LossDesc()
+    p.kind, p.reduction, p.B, p.C = kind, reduction, B, Cn
+    p.logits, p.ld = _f32(logits, "loss.logits"), Cn if ld is None else ld
+    if kind == _lib.LOSS_CE:
+        if target is not None and not isinstance(target, int) and target.dtype != torch.int64:
+            raise ValueError(f"loss.target: cross-entropy takes int64 class indices, got {target.dtype}")
+        p.target, p.ldt = _p(target), 0
+    else:
+        p.target, p.ldt = _f32(target, "loss.target"), Cn if ldt is None else ldt
+    p.weight, p.ignore_index, p.loss = _f32(weight, "loss.weight"), ignore_index, _f32(loss, "loss.loss")
+    p.dlogits_unit, p.ldd = _f32(dlogits_unit, "loss.dlogits_unit"), Cn if ldd is None else ldd
+    if bad is not None and not isinstance(bad, int) and (bad.dtype != torch.int32 or bad.numel() < 1):
+        raise ValueError("loss.bad: an int32 device counter")
+    p.bad = _p(bad)
+    p.ws, p.ws_bytes = _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+    return p
+
+
+def loss_fwd(prob) -> None:
+    _lib.check(_lib.lib().bpm_loss_fwd(C.byref(prob), _stream()), "bpm_loss_fwd")
+
+
+def loss_bwd(prob, g, dlogits, *, ldg: Optional[int] = None, lddl: Optional[int] = None) -> None:
+    """dlogits = prob.dlogits_unit * g; g: one fp32 device value (mean / sum) or the elements / rows (LOSS_NONE), read by
+    the kernel when it runs."""
+    _lib.check(_lib.lib().bpm_loss_bwd(C.byref(prob), _f32(g, "loss.g"), prob.C if ldg is None else ldg, _f32(dlogits, "loss.dlogits"),
+                                       prob.C if lddl is None else lddl, _stream()), "bpm_loss_bwd")
+
+
 def addn_problem(out, ins) -> "_lib.AddnProblem":
     """out = sum(ins): contiguous fp32 tensors of one size (16-byte aligned); out may be one of them."""
     p = _lib.AddnProblem()

@@ -14,6 +14,8 @@ Reference behaviour reproduced (file:line in /root/reference/bpmult):
   metric is minimised, train.py:411-414); a checkpoint is written on improvement only; stop when
   `n_no_improve >= patience` (train.py:432-439).
 * the five-seed outer loop `for i in range(from_seed, 6)` with `inverse_seed` (train.py:490-503).
+* the criterion: `get_criterion(args)` (train.py:99-120), torch's modules or, with `args.criterion = "hip"`, their
+  subclasses in losses.py.
 """
 from __future__ import annotations
 
@@ -58,6 +60,31 @@ def save_checkpoint(state: dict, is_best: bool, checkpoint_path: str, filename: 
 def get_scheduler(optimizer, lr_patience: int = 2, lr_factor: float = 0.5, mode: str = "max"):
     """train.py:128-136."""
     return torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode, patience=lr_patience, factor=lr_factor)
+
+
+def get_criterion(args):
+    """train.py:99-120: BCE-with-logits for multilabel tasks, cross-entropy otherwise, both weighted by the inverse label
+    frequencies `(freqs / train_data_len) ** -1` under `args.weight_classes` -- except for cmu-mosi, which is never
+    weighted and trains its non-multilabel form on L1.  `args.criterion`: "torch" (default) returns torch's own modules,
+    "hip" the HIP-path subclasses of losses.py.  The weights are a buffer of the module: move it with `.to(device)` (the
+    reference's `.cuda()` at construction is not reproduced)."""
+    backend = getattr(args, "criterion", "torch")
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"args.criterion: expected 'torch' or 'hip', got {backend!r}")
+    if backend == "hip":
+        from . import losses as L
+    else:
+        L = torch.nn
+    weighted = bool(args.weight_classes) and args.task != "cmu-mosi"
+    label_weights = None
+    if weighted:
+        freqs = [args.label_freqs[l] for l in args.labels]
+        label_weights = (torch.FloatTensor(freqs) / args.train_data_len) ** -1
+    if args.task_type == "multilabel":
+        return L.BCEWithLogitsLoss(pos_weight=label_weights) if weighted else L.BCEWithLogitsLoss()
+    if weighted:
+        return L.CrossEntropyLoss(weight=label_weights)
+    return L.L1Loss() if args.task == "cmu-mosi" else L.CrossEntropyLoss()
 
 
 def fit(model, optimizer, scheduler, train_batches: Callable[[], Iterable], forward_loss: Callable, evaluate: Callable,

@@ -583,6 +583,54 @@ int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, uns
                          const float* scale_dev, const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad,
                          void* stream);
 
+/* ------------------------------------------------------------------------
+ * Training criterion.  Replaces nn.BCEWithLogitsLoss(pos_weight) / nn.CrossEntropyLoss(weight) / nn.L1Loss of
+ * get_criterion (train.py:99-120) as called at train.py:333, and their autograd backward: the last torch compute ops of
+ * the step BERT -> trunk -> loss -> Adam.  x = logits fp32 [B, ld >= C]; every element is carried in fp64 and rounded to
+ * fp32 once, every sum is fp64 in one fixed order (no float atomics: loss and gradient are bitwise reproducible).
+ *   BPM_LOSS_BCE  y fp32 [B, ldt >= C] (soft targets in [0, 1] are legal), weight = pos_weight [C] or NULL (= 1):
+ *                 w = 1 + (pos_weight_c - 1) y;   l = (1 - y) x + w (max(-x, 0) + log1p(exp(-|x|)))
+ *                 dl/dx = (1 - y) - w sigmoid(-x), sigmoid(-x) = (x >= 0 ? e : 1) / (1 + e), e = exp(-|x|);   mean: / (B C)
+ *   BPM_LOSS_CE   t int64 [B], weight = class weight [C] or NULL (= 1).  Row i is KEPT when t_i != ignore_index and
+ *                 0 <= t_i < C; every other row has loss 0, an all-zero gradient row and no part in the denominator.
+ *                 m = max_c x_ic, S = sum_c exp(x_ic - m):   l_i = w[t_i] ((m - x_i[t_i]) + log S)
+ *                 mean: / W, W = sum of w[t_i] over the kept rows (NaN when W = 0, as torch; sum is then 0)
+ *                 dl/dx_ic = (exp(x_ic - m) / S - [c == t_i]) w[t_i] (/ W for mean).  C = 1: loss 0, gradient 0.
+ *                 t_i is compared with [0, C) BEFORE any use as an index; an index that is neither ignore_index nor in
+ *                 range adds one to *bad (int32 device counter, vector atomic add; NULL = not counted) and is treated
+ *                 exactly like an ignored row: no device assert, no sync.
+ *   BPM_LOSS_L1   y fp32 [B, ldt >= C]; l = |x - y|; dl/dx = sign(x - y) (exactly 0 where x == y); mean: / (B C); no weight.
+ * loss: one fp32 for BPM_LOSS_MEAN / _SUM; dense [B, C] (BCE, L1) or [B] (CE) for BPM_LOSS_NONE.
+ * dlogits_unit (optional, [B, ldd >= C]): the derivative of the REDUCED loss for an upstream gradient of 1 (so 1 / (B C)
+ * or 1 / W is already in it); for BPM_LOSS_NONE the derivative of each element's / row's own loss.
+ * Pad columns [C, ld) of logits / target are never read, those of dlogits_unit / dlogits never written.
+ * ws: bpm_loss_ws_bytes(kind, reduction, B, C) bytes (0: may be NULL), 8-byte aligned, private to the stream for the
+ * call; its contents do not matter before or after.  At most two launches.
+ * BPM_ERR_ARG (nothing launched): NULL desc / logits / target / loss, B < 1, C < 1, unknown kind / reduction, ld < C,
+ * ldt < C (BCE, L1), ldd < C with dlogits_unit, a weight for BPM_LOSS_L1, a workspace that is NULL or too small;
+ * BPM_ERR_ALIGN: pointers not 4-byte (int64 target, ws: 8-byte) aligned.
+ *
+ * bpm_loss_bwd: dlogits[b, c] = dlogits_unit[b, c] * g, one launch; g is READ ON THE DEVICE when the kernel runs (what
+ * (loss / gradient_accumulation_steps).backward() hands to the node, train.py:387-394): one fp32 for mean / sum (ldg
+ * ignored), [B, ldg >= C] for none of BCE / L1, [B] for none of CE.  dlogits [B, lddl >= C] may alias dlogits_unit. */
+enum { BPM_LOSS_BCE = 0, BPM_LOSS_CE = 1, BPM_LOSS_L1 = 2 };
+enum { BPM_LOSS_MEAN = 0, BPM_LOSS_SUM = 1, BPM_LOSS_NONE = 2 };
+typedef struct bpm_loss_desc {
+    int kind, reduction;    /* BPM_LOSS_* */
+    int B, C;
+    const float* logits; int ld;
+    const void* target; int ldt;
+    const float* weight;
+    int64_t ignore_index;   /* CE only */
+    float* loss;
+    float* dlogits_unit; int ldd;
+    int* bad;               /* CE only, optional */
+    void* ws; size_t ws_bytes;
+} bpm_loss_desc;
+size_t bpm_loss_ws_bytes(int kind, int reduction, int B, int C);
+int bpm_loss_fwd(const bpm_loss_desc* d, void* stream);
+int bpm_loss_bwd(const bpm_loss_desc* d, const float* g, int ldg, float* dlogits, int lddl, void* stream);
+
 /* Engine plumbing (no reference counterpart): a non-blocking HIP stream at the device's lowest priority
  * (low_priority != 0) or at the default priority.  The host engine puts weight-gradient GEMMs and the
  * key/value-side chain there so that the dispatcher serves the critical-path stream first. */
