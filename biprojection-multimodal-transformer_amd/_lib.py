@@ -39,6 +39,7 @@ MAX_GROUP = 18
 SEED_INDIRECT = 1 << 63          # seed = SEED_INDIRECT | device address of a uint64 (include/bpmult_hip.h)
 GEMM_MAX_GROUP = 24
 ADAM_MAX_GROUPS = 16             # == BPM_ADAM_MAX_GROUPS
+ADAM_MAX_SETS, ADAM_SET_SHIFT = 4, 8         # == BPM_ADAM_MAX_SETS, BPM_ADAM_SET_SHIFT
 LOSS_BCE, LOSS_CE, LOSS_L1 = 0, 1, 2              # BPM_LOSS_* kinds
 LOSS_MEAN, LOSS_SUM, LOSS_NONE = 0, 1, 2          # BPM_LOSS_* reductions
 
@@ -200,6 +201,16 @@ class AdamGroup(C.Structure):
                 ("decoupled", C.c_int), ("step", C.c_int), ("pad_", C.c_int)]
 
 
+class AdamSet(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_size_t)]
+
+
+def adam_set_group(set_index: int, group: int) -> int:
+    """BPM_ADAM_SET_GROUP: the `group` word of a bpm_adam_step_sets segment (a signed 32-bit value, as AdamSeg.group takes it)."""
+    w = (set_index << ADAM_SET_SHIFT) | (group & 0xff)
+    return w - (1 << 32) if w >= 1 << 31 else w
+
+
 class SumsqSeg(C.Structure):
     _fields_ = [("p", C.c_void_p), ("n", C.c_size_t), ("blk0", C.c_uint), ("pad_", C.c_uint)]
 
@@ -322,6 +333,8 @@ SIGNATURES = {
     "bpm_adam_step_table": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _I, _P],
     "bpm_adam_step_table_clip": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P],
     "bpm_adam_step_groups": [_I, _P, _I, C.c_uint, _P, _P, _P, _P, C.POINTER(AdamGroup), _I, _F, _P, _P, _P, _P, _I, _P],
+    "bpm_adam_step_sets": [_I, _P, C.POINTER(AdamSeg), _I, C.c_uint, _P, C.POINTER(AdamSet), _I, C.POINTER(AdamGroup), _I, _F, _P, _P, _P,
+                           _P, _I, _P],
     "bpm_grad_sumsq_blocks": [_P, C.c_size_t],
     "bpm_grad_sumsq_ws_bytes": [C.c_uint],
     "bpm_grad_sumsq": [_P, _I, C.c_uint, _F, _F, _P, _P, C.c_size_t, _P, _P],

@@ -1163,16 +1163,13 @@ BPM_DEV double adam_ipow(double b, int e) {              // b^e, e >= 1, by squa
 
 BPM_DEV bool adam_norm_finite(const float* norm_dev) { return fabsf(*norm_dev) <= 3.402823466e+38f; }   // NaN, +-inf: false
 
+// One block's work: segment S of the buffers p / g / m / v, group grp (block-uniform).  Shared by the two kernels below.
 template <typename CT>
-__global__ __launch_bounds__(NT) void adam_groups_kernel(const bpm_adam_seg* __restrict__ tab, int nseg, float* __restrict__ p,
-                                                        float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                        const AdamGroupsK G, int ngroups, float gscale, int zero_grad,
-                                                        const float* __restrict__ scale_dev, const float* __restrict__ norm_dev,
-                                                        const int* __restrict__ steps_dev) {
-    const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
+BPM_DEV void adam_block(const bpm_adam_seg& S, const int grp, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                        float* __restrict__ v, const AdamGroupsK& G, int ngroups, float gscale, int zero_grad,
+                        const float* __restrict__ scale_dev, const float* __restrict__ norm_dev, const int* __restrict__ steps_dev) {
     const size_t base = S.off4 + (size_t)(blockIdx.x - S.blk0) * ADAM_CHUNK;
     const size_t end = S.off4 + S.n4;
-    const int grp = ngroups ? S.group : 0;              // block-uniform; ngroups == 0: whatever the word holds, group 0
     bool live = grp >= 0 && grp < (ngroups ? ngroups : 1);
     if (live && norm_dev) live = adam_norm_finite(norm_dev);
     if (!live) {
@@ -1224,6 +1221,33 @@ __global__ __launch_bounds__(NT) void adam_groups_kernel(const bpm_adam_seg* __r
     }
 }
 
+template <typename CT>
+__global__ __launch_bounds__(NT) void adam_groups_kernel(const bpm_adam_seg* __restrict__ tab, int nseg, float* __restrict__ p,
+                                                        float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        const AdamGroupsK G, int ngroups, float gscale, int zero_grad,
+                                                        const float* __restrict__ scale_dev, const float* __restrict__ norm_dev,
+                                                        const int* __restrict__ steps_dev) {
+    const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
+    // block-uniform; ngroups == 0: whatever the word holds, group 0
+    adam_block<CT>(S, ngroups ? S.group : 0, p, g, m, v, G, ngroups, gscale, zero_grad, scale_dev, norm_dev, steps_dev);
+}
+
+// The same block over SEVERAL buffer sets (bpm_adam_step_sets): the segment's group word names its set (BPM_ADAM_SET_SHIFT)
+// beside its group (the low byte, signed), and off4 is relative to that set.  The sets are a device-resident array: one
+// block-uniform 32-byte load after find_desc -- a by-value argument indexed by a loaded value would be copied to scratch.
+template <typename CT>
+__global__ __launch_bounds__(NT) void adam_sets_kernel(const bpm_adam_seg* __restrict__ tab, int nseg,
+                                                      const bpm_adam_set* __restrict__ sets, int nsets, const AdamGroupsK G,
+                                                      int ngroups, float gscale, int zero_grad, const float* __restrict__ scale_dev,
+                                                      const float* __restrict__ norm_dev, const int* __restrict__ steps_dev) {
+    const bpm_adam_seg S = find_desc(tab, nseg, blockIdx.x);
+    const unsigned set = (unsigned)S.group >> BPM_ADAM_SET_SHIFT;
+    if (set >= (unsigned)nsets) return;                  // (the entry has checked the host copy of the table: never taken)
+    const bpm_adam_set B = sets[set];
+    adam_block<CT>(S, (int)(signed char)(S.group & 0xff), B.param, B.grad, B.exp_avg, B.exp_avg_sq, G, ngroups, gscale, zero_grad,
+                   scale_dev, norm_dev, steps_dev);
+}
+
 // After the step, one tiny launch: every group's counter of applied steps goes up by one, or, when the step was skipped,
 // the skip counter does.  Plain stores from one wave; the stream orders it behind the kernel that read the counters.
 __global__ __launch_bounds__(64) void adam_counters_kernel(const float* norm_dev, int* steps_dev, int ngroups, int* skipped_dev) {
@@ -1235,23 +1259,37 @@ __global__ __launch_bounds__(64) void adam_counters_kernel(const float* norm_dev
     }
 }
 
+// Fills the launch's copy of the groups.
+static int adam_fill_groups(AdamGroupsK& G, const bpm_adam_group* groups, int ngroups, bool host_steps) {
+    for (int i = 0; i < ngroups; ++i) {
+        const bpm_adam_group& h = groups[i];
+        if (host_steps && h.step < 1) return BPM_ERR_ARG;
+        AdamGroupK& k = G.g[i];
+        k.lr = h.lr; k.b1 = h.beta1; k.b2 = h.beta2; k.eps = h.eps;
+        k.wd_l2 = h.decoupled ? 0.f : h.weight_decay;
+        k.decay = h.decoupled ? (float)(1.0 - (double)h.lr * (double)h.weight_decay) : 1.f;
+        if (host_steps) {
+            const double bc1 = 1.0 - pow((double)h.beta1, h.step), bc2 = 1.0 - pow((double)h.beta2, h.step);
+            k.lr_c = (float)(h.lr / bc1); k.rsq_bc2 = (float)(1.0 / sqrt(bc2));
+        }
+    }
+    return 0;
+}
+
+static int adam_count(int ngroups, const float* norm_dev, int* steps_dev, int* skipped_dev, void* stream) {
+    if (steps_dev || (skipped_dev && norm_dev)) {
+        hipLaunchKernelGGL(adam_counters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, norm_dev, steps_dev, ngroups, skipped_dev);
+        BPM_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
 // Fills the launch's copy of the groups and launches.  ngroups_k: what the kernel takes (0: ignore the group words).
 static int adam_launch(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param, float* grad,
                        float* exp_avg, float* exp_avg_sq, const bpm_adam_group* groups, int ngroups, int ngroups_k, float grad_scale,
                        const float* scale_dev, const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad, void* stream) {
     AdamGroupsK G = {};
-    for (int i = 0; i < ngroups; ++i) {
-        const bpm_adam_group& h = groups[i];
-        if (!steps_dev && h.step < 1) return BPM_ERR_ARG;
-        AdamGroupK& k = G.g[i];
-        k.lr = h.lr; k.b1 = h.beta1; k.b2 = h.beta2; k.eps = h.eps;
-        k.wd_l2 = h.decoupled ? 0.f : h.weight_decay;
-        k.decay = h.decoupled ? (float)(1.0 - (double)h.lr * (double)h.weight_decay) : 1.f;
-        if (!steps_dev) {
-            const double bc1 = 1.0 - pow((double)h.beta1, h.step), bc2 = 1.0 - pow((double)h.beta2, h.step);
-            k.lr_c = (float)(h.lr / bc1); k.rsq_bc2 = (float)(1.0 / sqrt(bc2));
-        }
-    }
+    if (const int rc = adam_fill_groups(G, groups, ngroups, !steps_dev)) return rc;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, param, grad, exp_avg,
                            exp_avg_sq, G, ngroups_k, grad_scale, zero_grad, scale_dev, norm_dev, (const int*)steps_dev);
@@ -1259,11 +1297,7 @@ static int adam_launch(int dtype, const bpm_adam_seg* table_dev, int nseg, unsig
     if (dtype == BPM_BF16) launch(adam_groups_kernel<bf16_t>);
     else launch(adam_groups_kernel<float>);
     BPM_CHECK_LAUNCH();
-    if (steps_dev || (skipped_dev && norm_dev)) {
-        hipLaunchKernelGGL(adam_counters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, norm_dev, steps_dev, ngroups, skipped_dev);
-        BPM_CHECK_LAUNCH();
-    }
-    return 0;
+    return adam_count(ngroups, norm_dev, steps_dev, skipped_dev, stream);
 }
 
 extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, unsigned total_blocks, float* param,
@@ -1276,6 +1310,44 @@ extern "C" int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, in
     if (((uintptr_t)scale_dev | (uintptr_t)norm_dev | (uintptr_t)steps_dev | (uintptr_t)skipped_dev) & 3) return BPM_ERR_ALIGN;
     return adam_launch(dtype, table_dev, nseg, total_blocks, param, grad, exp_avg, exp_avg_sq, groups, ngroups, ngroups, grad_scale,
                        scale_dev, norm_dev, steps_dev, skipped_dev, zero_grad, stream);
+}
+
+// Several buffer sets, one launch and one counter launch.  Every check reads the HOST copies of the table and the sets (the
+// arrays the device ones were uploaded from); nothing is launched unless the whole table is sound: sorted and gap-free in
+// blocks, every segment inside its set.
+extern "C" int bpm_adam_step_sets(int dtype, const bpm_adam_seg* table_dev, const bpm_adam_seg* table_host, int nseg,
+                                  unsigned total_blocks, const bpm_adam_set* sets_dev, const bpm_adam_set* sets_host, int nsets,
+                                  const bpm_adam_group* groups, int ngroups, float grad_scale, const float* scale_dev,
+                                  const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad, void* stream) {
+    if (!table_dev || !table_host || nseg < 1 || total_blocks < 1 || !sets_dev || !sets_host || !groups) return BPM_ERR_ARG;
+    if (nsets < 1 || nsets > BPM_ADAM_MAX_SETS || ngroups < 1 || ngroups > BPM_ADAM_MAX_GROUPS) return BPM_ERR_ARG;
+    for (int i = 0; i < nsets; ++i) {
+        const bpm_adam_set& b = sets_host[i];
+        if (!b.param || !b.grad || !b.exp_avg || !b.exp_avg_sq || b.n == 0 || (b.n & 3)) return BPM_ERR_ARG;
+        if (((uintptr_t)b.param | (uintptr_t)b.grad | (uintptr_t)b.exp_avg | (uintptr_t)b.exp_avg_sq) & 15) return BPM_ERR_ALIGN;
+    }
+    if (((uintptr_t)scale_dev | (uintptr_t)norm_dev | (uintptr_t)steps_dev | (uintptr_t)skipped_dev) & 3) return BPM_ERR_ALIGN;
+    unsigned blk = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const bpm_adam_seg& s = table_host[i];
+        const unsigned set = (unsigned)s.group >> BPM_ADAM_SET_SHIFT;
+        if (set >= (unsigned)nsets || s.n4 == 0 || s.blk0 != blk) return BPM_ERR_ARG;
+        if (s.off4 > sets_host[set].n / 4 || s.n4 > sets_host[set].n / 4 - s.off4) return BPM_ERR_ARG;
+        if (s.dst && (s.rows < 1 || s.cols < 4 || (s.cols & 3) || s.dst_ld < s.cols || (size_t)s.rows * s.cols > 4 * (size_t)s.n4))
+            return BPM_ERR_ARG;
+        blk += (unsigned)bpm_adam_blocks(s.n4);
+    }
+    if (blk != total_blocks) return BPM_ERR_ARG;
+    AdamGroupsK G = {};
+    if (const int rc = adam_fill_groups(G, groups, ngroups, !steps_dev)) return rc;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(total_blocks), dim3(NT), 0, (hipStream_t)stream, table_dev, nseg, sets_dev, nsets, G, ngroups,
+                           grad_scale, zero_grad, scale_dev, norm_dev, (const int*)steps_dev);
+    };
+    if (dtype == BPM_BF16) launch(adam_sets_kernel<bf16_t>);
+    else launch(adam_sets_kernel<float>);
+    BPM_CHECK_LAUNCH();
+    return adam_count(ngroups, norm_dev, steps_dev, skipped_dev, stream);
 }
 
 // The one-group entries: one L2 group at the host's `step`, no skip, no counters, the segments' group words ignored.

@@ -16,6 +16,14 @@ a communication stream as soon as backward has finished it, overlapping with
 the rest of backward.  The [B,d]-sized tail's parameters (a few hundred KB) are
 reduced as one flattened message at the end.
 
+With `args.text_params = "flat"` the text encoder's gradients live in a second
+flat buffer (layer n-1 first, down to layer 0, then the embeddings): the text
+backward, the last thing that runs, reports every layer's slice and then the
+embeddings' as it finishes them, and they are exchanged in place like the
+trunk's -- never flatten-copied with the tail.  "auto" resolves on the bytes of
+both buffers together.  (No box here has two GPUs: this path is rehearsed on
+gloo with host tensors, tests/test_text_params_cpu.py; its time is not measured.)
+
 * 1/world is NOT a separate pass over the gradient buffer when a FusedAdam is
   attached (`GradSync(model, optimizer=opt)`): finish() leaves the SUM in the
   flat buffer and hands 1/world to the optimizer, whose kernel multiplies the
@@ -74,9 +82,16 @@ class GradSync:
         self._steps = 0
         model._grad_ready_hook = self._on_ready
 
+    def _stores(self) -> list:
+        """The model's flat stores: model._flat_stores() (the trunk's; with text_params = "flat" the text encoder's behind
+        it), or the one store of a model that has no such method."""
+        flat = getattr(self.model, "_flat_stores", None)
+        return flat() if flat is not None else [self.model._store]
+
     def _resolve(self, flat: torch.Tensor) -> None:
-        if self.compress is None:
-            self.compress = "bf16" if flat.numel() * 4 > AUTO_BF16_BYTES else "none"
+        if self.compress is None:                          # "auto": on the bytes of every flat gradient buffer together
+            total = sum(s.gflat.numel() for s in self._stores())
+            self.compress = "bf16" if total * 4 > AUTO_BF16_BYTES else "none"
 
     def _exchange(self, flat: torch.Tensor, lo: int, hi: int) -> None:
         self._resolve(flat)
@@ -119,8 +134,10 @@ class GradSync:
         """After loss.backward(): reduce the tail, wait for everything, apply (or hand on) 1/world."""
         if self.world == 1 or not self.active:
             return
-        st = self.model._store
-        tail = [p.grad for n, p in self.model.named_parameters() if p.grad is not None and n not in st.params]
+        stores = self._stores()
+        st = stores[0]
+        # what lies in no flat store; the stores' gradients were exchanged in place, section by section
+        tail = [p.grad for n, p in self.model.named_parameters() if p.grad is not None and not any(n in s.params for s in stores)]
         cuda = st.gflat.is_cuda
         if cuda:
             main = torch.cuda.current_stream()
@@ -163,7 +180,8 @@ class GradSync:
         if self.optimizer is not None:
             self.optimizer.pending_grad_scale = inv      # consumed (and reset) by the next FusedAdam.step()
         else:
-            st.gflat.mul_(inv)
+            for s in stores:
+                s.gflat.mul_(inv)
 
     # -- measurement aid for bench.py ---------------------------------------------
     def reset_stats(self) -> None:

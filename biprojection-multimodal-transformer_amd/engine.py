@@ -33,7 +33,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from ._lib import (BPM_BF16, AdamSeg, AddnProblem, ExpandProblem, F_CT_NARROW, F_ACCUM, F_BACKGROUND, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_HEADS,
+from ._lib import (BPM_BF16, AdamSeg, adam_set_group, AddnProblem, ExpandProblem, F_CT_NARROW, F_ACCUM, F_BACKGROUND, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_HEADS,
                    AttnProblem, CastProblem, FoldDesc, GemmProblem, LnProblem, PackDesc,
                    UnfoldDesc)
 from .ops import pad32
@@ -301,12 +301,12 @@ class ParamStore:
         self._adam_plain = plain
         self._adam_table = self._adam_segments(None)
 
-    def _adam_segments(self, group_of: Optional[Dict[str, int]]):
+    def _adam_segments(self, group_of: Optional[Dict[str, int]], raw: bool = False):
         """(device table, segments, blocks) over [0, total) in flat order: one segment per parameter with a plain shadow,
         runs of consecutive parameters without one.  group_of (bpm_adam_step_groups): {parameter name: group index, or -1
         for a parameter that is not stepped}; a run is then cut wherever the group changes, so that a segment belongs to
         exactly one group.  A parameter's alignment padding rides with it; offsets are 64-element aligned, so every cut
-        is 16-byte aligned.  None: every segment in group 0 (`_adam_table`)."""
+        is 16-byte aligned.  None: every segment in group 0 (`_adam_table`).  raw: the AdamSeg list itself (adam_sets_table)."""
         esz = 2 if self.dtype == BPM_BF16 else 4
         plain = self._adam_plain
         nblk = ops.adam_blocks
@@ -338,7 +338,7 @@ class ParamStore:
                 sg.dst, sg.rows, sg.cols, sg.dst_ld = self.shadow_flat.data_ptr() + esz * off, rows, cols, dst_ld
             blk += nblk((b - a) // 4)
             out.append(sg)
-        return ops.device_table(out), len(out), blk
+        return (ops.device_table(out), len(out), blk) if not raw else out
 
     def adam_group_table(self, group_of: Dict[str, int]):
         """The grouped segment table (device table, segments, blocks) for {parameter name: group index or -1}; a name the
@@ -354,6 +354,21 @@ class ParamStore:
         list the same way -- so a store that never clips or reads the norm allocates nothing."""
         self._norm_table, self._norm_ws = self._norm_segments(lambda n: self.params[n].requires_grad)
         self._norm_out = torch.zeros(2, device=self.device, dtype=torch.float32)
+
+    def norm_ranges(self, counts) -> List[Tuple[int, int]]:
+        """[(device address, elements)] of the gradient slices of the parameters `counts(name)` admits, merged where one
+        ends where the next begins (bpm_grad_sumsq takes absolute addresses: one table may span several stores)."""
+        segs: List[List[int]] = []
+        for n in self.names:
+            if not counts(n):
+                continue
+            a, b = self.off[n], self.off[n] + self.params[n].numel()
+            if segs and segs[-1][1] == a:
+                segs[-1][1] = b
+            else:
+                segs.append([a, b])
+        base = self.gflat.data_ptr()
+        return [(base + 4 * a, b - a) for a, b in segs]
 
     def _norm_segments(self, counts):
         segs: List[List[int]] = []
@@ -410,13 +425,22 @@ class ParamStore:
         launch: this launch need not rewrite every plain shadow (a parameter that is not stepped, a skipped step).  The
         stored results are the same with or without it, and a training loop never pays it: its forward has refreshed."""
         tab, nseg, nblk = table
-        sig = self._versions()                             # (the launches below go through raw pointers: no counter moves)
-        if self._dirty or sig != self._shadow_sig:
-            self.refresh_shadows()
+        sig = self.begin_adam_step()
         ops.adam_step_groups(self.dtype, tab, nseg, nblk, self.master, self.gflat, exp_avg, exp_avg_sq, groups, grad_scale,
                              zero_grad, scale_dev, norm_dev, steps_dev, skipped_dev)
-        # every plain shadow now holds the CT image of its master; the rest (shadows that mix parameters, folded biases) is
-        # stale until the next refresh_shadows
+        self.end_adam_step(sig)
+
+    def begin_adam_step(self) -> int:
+        """Before a fused optimizer launch over this store: the pending full shadow refresh, if any (see adam_step_groups).
+        Returns the version signature end_adam_step() takes."""
+        sig = self._versions()                             # (the launches go through raw pointers: no counter moves)
+        if self._dirty or sig != self._shadow_sig:
+            self.refresh_shadows()
+        return sig
+
+    def end_adam_step(self, sig: int) -> None:
+        """After it: every plain shadow holds the CT image of its master; the rest (shadows that mix parameters, folded
+        biases) is stale until the next refresh_shadows."""
         self._dirty, self._dirty_rest, self._shadow_sig = False, True, sig
 
     def sptr(self, key: str, elem_off: int = 0) -> int:
@@ -458,6 +482,32 @@ class ParamStore:
             ops.fold_bias(self._fold_table, self._nfold, self._fold_blk)
         if self.x3:
             ops.x3_refresh_static()                # split images of the shadows that just changed (outside any graph)
+
+
+def adam_sets_table(stores: Sequence[ParamStore], group_ofs: Sequence[Dict[str, int]]):
+    """One segment table over SEVERAL stores for adam_step_sets (bpm_adam_step_sets): store i is buffer set i, its segments
+    are those of its own adam_group_table(group_ofs[i]) -- {parameter name: group index}, a name left out is not stepped --
+    with offsets relative to that store, in store order, blocks numbered through.  All stores share one CT."""
+    if len({st.dtype for st in stores}) != 1:
+        raise ValueError("adam_sets_table: the stores of one launch share one CT (the kernel writes every shadow in it)")
+    segs = []
+    for si, (st, group_of) in enumerate(zip(stores, group_ofs)):
+        for sg in st._adam_segments({n: group_of.get(n, -1) for n in st.names}, raw=True):
+            sg.group = adam_set_group(si, sg.group)
+            segs.append(sg)
+    return ops.adam_sets_table(segs)
+
+
+def adam_step_sets(stores: Sequence[ParamStore], table, sets, groups, grad_scale, zero_grad: bool,
+                   scale_dev: Optional[torch.Tensor] = None, norm_dev: Optional[torch.Tensor] = None,
+                   steps_dev: Optional[torch.Tensor] = None, skipped_dev: Optional[torch.Tensor] = None) -> None:
+    """ParamStore.adam_step_groups over several stores in ONE launch: table = adam_sets_table(stores, ...), sets =
+    ops.adam_sets([(st.master, st.gflat, exp_avg, exp_avg_sq) for st in stores]).  The device step counts and the skip
+    decision are read once for all stores, and the counters advance once."""
+    sigs = [st.begin_adam_step() for st in stores]
+    ops.adam_step_sets(stores[0].dtype, table, sets, groups, grad_scale, zero_grad, scale_dev, norm_dev, steps_dev, skipped_dev)
+    for st, sig in zip(stores, sigs):
+        st.end_adam_step(sig)
 
 
 # ----------------------------------------------------------------------------

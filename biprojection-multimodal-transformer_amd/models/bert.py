@@ -43,6 +43,14 @@ Embeddings on the HIP path (HF `BertEmbeddings`, absolute positions):
   The existing rows_cast + ln_bwd_ws pair was preferred to one fused new kernel: it costs one launch more in training and
   none in eval, and reuses the workspace reduction that is already tested.  fp32 tensors in every precision mode (the forward carries a row's LayerNorm in fp64 registers and rounds once).
 
+Parameters (`args.text_params`): "torch" (the default) leaves them PyTorch's -- backward returns fresh gradient tensors
+to autograd, an optimizer steps them one by one and the next forward re-packs the CT shadows.  "flat" (build_text_store):
+the layer parameters (and the HIP embeddings') are views into an engine.ParamStore; the backward launches write the
+store's gradient buffer under the trunk's rules (unset gradients: the weight-gradient GEMMs store and one
+bpm_zero_segments launch clears the rest; otherwise F_ACCUM, and the embedding tables through a scratch copy + bpm_add_n),
+the nodes return None for the stored parameters, every finished section (layer n-1 ... 0, then the embeddings) is
+reported to `grad_ready`, and the shadows belong to the store, where FusedAdam's kernel writes them.
+
 Precision: "bf16" = bf16 MFMA operands (CT shadows of the weights, refreshed when a parameter's version changes), fp32
 accumulation, fp32 residual stream and LayerNorm; "f32" = exact fp32 products; "bf16x3" runs this stack's f32 path.
 """
@@ -53,8 +61,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from .. import config, ops
-from .._lib import F_KPAD, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_F32, OUT_HEADS, PackDesc
-from ..engine import dhp_for
+from .._lib import F_ACCUM, F_KPAD, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_F32, OUT_HEADS, PackDesc
+from ..engine import ParamStore, dhp_for
 from ..ops import pad32
 
 # dropout sites of the text encoder: disjoint from engine.site() (enc_id < 12 -> below 1 << 16) and engine.SITE_TEXT (1 << 20)
@@ -106,6 +114,48 @@ def layer_parameters(bert) -> List[torch.nn.Parameter]:
     return out
 
 
+def build_text_store(bert, dtype: int, embeddings: bool, prefix: str = "") -> ParamStore:
+    """The flat store of the text parameters whose gradients the HIP path produces (`args.text_params = "flat"`): the 16
+    LAYER_PARAMS of every layer and, with `embeddings`, the five EMBED_PARAMS, re-pointed into one fp32 master with one
+    gradient buffer beside it (engine.ParamStore, as the trunk's).  Names are `prefix` + the name below `bert`'s owner
+    ("bert.encoder.layer.0...."): what the model's named_parameters() calls them.  Laid out in reverse execution order --
+    layer n-1 first, down to layer 0, then the embeddings -- so that a finished slice can be exchanged while backward
+    continues; `sections` = {"layer{i}": (lo, hi), "embeddings": (lo, hi)} in elements.  The weight shadows keep the
+    stack's layout ([Wq; Wk; Wv] as one [3d, ld] block, Wo, Wi, Wo2; keys "layer{i}.qkv" / ".ao" / ".fc1" / ".fc2") and are
+    all plain images of whole matrices: the fused optimizer kernel writes them, and nothing is left for a second pack."""
+    cfg = bert.config
+    d, I, nl = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+    named, bounds = [], []
+    for i in reversed(range(nl)):
+        lp = dict(bert.encoder.layer[i].named_parameters())
+        bounds.append((f"layer{i}", len(named)))
+        named += [(f"{prefix}bert.encoder.layer.{i}.{n}", lp[n]) for n in LAYER_PARAMS]
+    if embeddings:
+        ep = dict(bert.embeddings.named_parameters())
+        bounds.append(("embeddings", len(named)))
+        named += [(f"{prefix}bert.embeddings.{n}", ep[n]) for n in EMBED_PARAMS]
+    for n, p in named:
+        if p.dtype != torch.float32:
+            raise RuntimeError(f"text_params='flat': {n} is {p.dtype}; the flat store holds float32 parameters")
+    st = ParamStore(named, dtype)
+    st.prefix = prefix
+    st.sections = {}
+    for k, (sname, a) in enumerate(bounds):
+        st.sections[sname] = (st.off[named[a][0]], st.off[named[bounds[k + 1][1]][0]] if k + 1 < len(bounds) else st.total)
+    ld = pad32(d)
+    for i in range(nl):
+        P = f"{prefix}bert.encoder.layer.{i}."
+        st.add_blank_shadow(f"layer{i}.qkv", 3 * d, ld)
+        for w in range(3):
+            st.add_shadow(f"layer{i}.qkv#{w}", P + _WEIGHTS[w], d, d, base_key=f"layer{i}.qkv", dst_row0=w * d)
+        st.add_shadow(f"layer{i}.ao", P + _WEIGHTS[3], d, d)
+        st.add_shadow(f"layer{i}.fc1", P + _WEIGHTS[4], I, d)
+        st.add_shadow(f"layer{i}.fc2", P + _WEIGHTS[5], d, I)
+    st.finalize_shadows()
+    st.set_store_written([f"{prefix}bert.encoder.layer.{i}.{w}" for i in range(nl) for w in _WEIGHTS])
+    return st
+
+
 class _Plan:
     """Activation buffers of one (B, L) shape; kept from forward to backward."""
 
@@ -155,11 +205,15 @@ class BertLayerStack:
     """Host driver of `bert.encoder.layer[*]` (see the module docstring).  Holds no parameters: it reads the HF
     modules' and keeps CT shadows of the six weight matrices of every layer."""
 
-    def __init__(self, bert, precision: Optional[str] = None):
+    def __init__(self, bert, precision: Optional[str] = None, store: Optional[ParamStore] = None):
         cfg = bert.config
         check_config(cfg)
         self.bert = bert
         self.precision = precision
+        # text_params = "flat": the layer parameters are views into this store, which owns the CT shadows (written by the
+        # fused optimizer kernel) and the flat gradient buffer the backward launches write into
+        self.store = store
+        self.grad_ready = None                         # callable(gflat, lo, hi) or None: a finished section (GradSync)
         self.d, self.I, self.H, self.n_layers = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_hidden_layers
         self.dh = self.d // self.H
         self.dhp = dhp_for(self.dh)
@@ -186,6 +240,13 @@ class BertLayerStack:
         self._key, self.device, self.dtype = key, device, dtype
         self._plans, self._versions = {}, None
         self.params = params
+        if self.store is not None:
+            if self.store.dtype != dtype or not self.store.still_flat():
+                raise RuntimeError("text_params='flat': the flat text store is stale (another precision, or a parameter was "
+                                   "re-pointed); BertEncoder rebuilds it before the forward")
+            pre = self.store.prefix
+            self._names = [f"{pre}bert.encoder.layer.{i}.{n}" for i in range(self.n_layers) for n in LAYER_PARAMS]
+            return
         ct = ops.ct_torch(dtype)
         d, I, ld, ldI = self.d, self.I, self.ld, self.ldI
         # shadows per layer: [Wq; Wk; Wv] as one [3d, ld] block (the data gradient reads it as one K = 3d operand),
@@ -212,13 +273,19 @@ class BertLayerStack:
         self._pack = (ops.device_table(descs), len(descs), blk)
 
     def _sptr(self, layer: int, key: str, elem_off: int = 0) -> int:
+        if self.store is not None:
+            return self.store.sptr(f"layer{layer}.{key}", elem_off)
         return self.shadow.data_ptr() + self.shadow.element_size() * (self._soff[layer][key] + elem_off)
 
     def refresh_shadows(self) -> None:
         """Re-pack the CT weight shadows when a parameter changed.  A change is seen through autograd's version counters:
         an optimizer step, `load_state_dict`, `copy_` and any other in-place op on the parameter move them.  A write
         through `p.data` does NOT (EMA swaps, clamping, some checkpoint loaders): call invalidate_shadows() after one, or
-        the products keep reading the old weights."""
+        the products keep reading the old weights.  With a flat store the store keeps the shadows (the same rule; after a
+        FusedAdam step they are already current and nothing is launched)."""
+        if self.store is not None:
+            self.store.refresh_shadows()
+            return
         sig = tuple(p._version for p in self.params)
         if sig != self._versions:
             ops.pack_weights(self.dtype, *self._pack)
@@ -227,6 +294,8 @@ class BertLayerStack:
     def invalidate_shadows(self) -> None:
         """The next forward re-packs the weight shadows whatever the version counters say."""
         self._versions = None
+        if self.store is not None:
+            self.store.mark_dirty()
 
     def _plan(self, B: int, L: int) -> _Plan:
         pl = self._plans.get((B, L))
@@ -303,20 +372,29 @@ class BertLayerStack:
         pp = self.p_probs if pl.training else 0.0
         km = ops.attn_kmasks([(pl.mask, L)])
         # weight gradients are WRITTEN by their launch; the vectors (biases, LayerNorm affines) are accumulated into: zeroed
-        wsize = self.n_layers * (4 * d * d + 2 * d * I)
-        vsize = self.n_layers * (9 * d + I)
-        gw = torch.empty(wsize, device=self.device, dtype=torch.float32)
-        gv = torch.zeros(vsize, device=self.device, dtype=torch.float32)
-        grads: List[torch.Tensor] = []
-        ow = ov = 0
-        for p in self.params:
-            n = p.numel()
-            if p.dim() == 2:
-                grads.append(gw[ow:ow + n].view_as(p))
-                ow += n
-            else:
-                grads.append(gv[ov:ov + n].view_as(p))
-                ov += n
+        wacc = 0
+        if self.store is not None:
+            # the store's gradient views, under the trunk's rules: unset gradients -> the weight-gradient launches store
+            # and one launch clears everything else; otherwise (an accumulation micro-step) every launch adds
+            self._fresh_bwd = self.store.begin_backward(stores=True)
+            if not self._fresh_bwd:
+                wacc = F_ACCUM
+            grads = [self.store.g(n) for n in self._names]
+        else:
+            wsize = self.n_layers * (4 * d * d + 2 * d * I)
+            vsize = self.n_layers * (9 * d + I)
+            gw = torch.empty(wsize, device=self.device, dtype=torch.float32)
+            gv = torch.zeros(vsize, device=self.device, dtype=torch.float32)
+            grads: List[torch.Tensor] = []
+            ow = ov = 0
+            for p in self.params:
+                n = p.numel()
+                if p.dim() == 2:
+                    grads.append(gw[ow:ow + n].view_as(p))
+                    ow += n
+                else:
+                    grads.append(gv[ov:ov + n].view_as(p))
+                    ov += n
         G = lambda i, n: grads[i * len(LAYER_PARAMS) + LAYER_PARAMS.index(n)]
         cur = 0
         pl.dx[cur].view(L, B, d).copy_(dout.transpose(0, 1))
@@ -329,12 +407,12 @@ class BertLayerStack:
                                        dgamma=G(i, "output.LayerNorm.weight"), dbeta=G(i, "output.LayerNorm.bias"), cast=pl.dy2c, ldc=ld,
                                        cast_colsum=G(i, "output.dense.bias"), drop_p=ph, drop_site=bert_site(i, S_FFN_OUT))], d, dt, seed)
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy2c, pl.g[i], G(i, "output.dense.weight"), d, I, R, ld, ldI, I,
-                                                            flags=F_KPAD)], seed)
+                                                            flags=F_KPAD | wacc)], seed)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy2c, self._sptr(i, "fc2"), pl.dg, R, I, d, ld, ldI, I, out_kind=OUT_F32,
                                                             flags=F_KPAD)], seed)
             ops.gelu_bwd(dt, [ops.gelu_problem(pl.u[i], ldI, R, I, u_is_ct=True, dg=pl.dg, lddg=I, du=pl.du, lddu=ldI)])
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.du, pl.x1c[i], G(i, "intermediate.dense.weight"), I, d, R, ldI, ld, d,
-                                                            colsum_a=G(i, "intermediate.dense.bias"), flags=F_KPAD)], seed)
+                                                            colsum_a=G(i, "intermediate.dense.bias"), flags=F_KPAD | wacc)], seed)
             # d(x1) = du Wi + dy2 (the residual branch rides in the epilogue)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.du, self._sptr(i, "fc1"), pl.dx1, R, d, I, ldI, ld, d, resid=pl.dy2, ldr=d,
                                                             flags=F_KPAD)], seed)
@@ -343,7 +421,7 @@ class BertLayerStack:
                                        cast=pl.dy1c, ldc=ld, cast_colsum=G(i, "attention.output.dense.bias"), drop_p=ph,
                                        drop_site=bert_site(i, S_ATT_OUT))], d, dt, seed)
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy1c, pl.ctx[i], G(i, "attention.output.dense.weight"), d, d, R, ld, ld, d,
-                                                            flags=F_KPAD)], seed)
+                                                            flags=F_KPAD | wacc)], seed)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy1c, self._sptr(i, "ao"), pl.dao, R, d, d, ld, ld, 0, out_kind=OUT_HEADS,
                                                             heads=heads, flags=F_KPAD)], seed)
             dq, dk, dv = pl.dqkv[:, :ld], pl.dqkv[:, ld:2 * ld], pl.dqkv[:, 2 * ld:]
@@ -353,17 +431,26 @@ class BertLayerStack:
             ops.attn_bwd_dq_kmask(dt, ap, km, seed)
             ops.attn_bwd_dkv_kmask(dt, ap, km, seed)
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(src, pl.xc[i], G(i, f"attention.self.{nm}.weight"), d, d, R, 3 * ld, ld, d,
-                                                            colsum_a=G(i, f"attention.self.{nm}.bias"), flags=F_KPAD)
+                                                            colsum_a=G(i, f"attention.self.{nm}.bias"), flags=F_KPAD | wacc)
                                            for nm, src in (("query", dq), ("key", dk), ("value", dv))], seed)
             # d(x) = dq Wq + dk Wk + dv Wv + dy1
             # (one K = 3d product: check_config admits only d % 32 == 0, so ld == d and [dq | dk | dv] has no pad columns)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dqkv, self._sptr(i, "qkv"), dxi, R, d, 3 * d, 3 * ld, ld, d,
                                                             resid=pl.dy1, ldr=d, flags=F_KPAD)], seed)
             cur ^= 1
+            if self.store is not None and self.grad_ready is not None:
+                self.grad_ready(self.store.gflat, *self.store.sections[f"layer{i}"])
         if raw:
             return (pl.dx[cur] if need_demb else None), grads
         demb = pl.dx[cur].view(L, B, d).transpose(0, 1).contiguous() if need_demb else None
         return demb, grads
+
+
+    def finish_backward(self) -> None:
+        """Flat store: `.grad` of every stored parameter becomes its view of the store's gradient buffer (after the last
+        launch that writes it: the embeddings' when they are HIP kernels)."""
+        if self.store is not None:
+            self.store.end_backward()
 
 
 class _StackFn(torch.autograd.Function):
@@ -383,6 +470,9 @@ class _StackFn(torch.autograd.Function):
             raise RuntimeError("text encoder (HIP path): backward() of a forward pass that a later forward pass of the same shape "
                                "has overwritten; run forward -> backward one step at a time")
         demb, grads = ctx.stack.backward(ctx.plan, dout.contiguous().float(), ctx.need_emb)
+        if ctx.stack.store is not None:                    # the launches wrote the store's gradient buffer: nothing to hand back
+            ctx.stack.finish_backward()
+            return (demb, None, None, None, None) + (None,) * len(grads)
         return (demb, None, None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.need_params))
 
 
@@ -431,9 +521,11 @@ class BertEmbeddingsHip:
     """Host driver of `bert.embeddings` on the HIP path.  Holds no parameters: it reads the HF module's tables and
     LayerNorm affine where they lie.  `bad` is the int32 device counter of ids outside their table (cumulative)."""
 
-    def __init__(self, bert, bad: torch.Tensor):
+    def __init__(self, bert, bad: torch.Tensor, store: Optional[ParamStore] = None):
         check_embed_config(bert.config)
         self.bert, self.bad = bert, bad
+        self.store = store                                 # text_params = "flat": the five parameters live in this store
+        self._scratch: Optional[torch.Tensor] = None      # table gradients of an accumulation micro-step (allocated once)
         self.eps = float(bert.config.layer_norm_eps)
         self.padding_idx = bert.embeddings.word_embeddings.padding_idx
 
@@ -469,6 +561,8 @@ class BertEmbeddingsHip:
                           pl.seed)
             dy = g
         affine = need[3] or need[4]
+        if self.store is not None:
+            return self._backward_flat(st, pl, dy, ids, seg, need, (word, pos, typ, gamma, beta))
         gv = torch.zeros(2, d, device=dev, dtype=torch.float32) if affine else None
         ops.ln_bwd([ops.ln_problem(pl.s, gamma, None, pl.emean, pl.erstd, R, dy=dy, ldy=d, dx=pl.ds,
                                    dgamma=gv[0] if affine else None, dbeta=gv[1] if affine else None)], d, st.dtype, pl.seed)
@@ -487,6 +581,43 @@ class BertEmbeddingsHip:
                 kw.update(dtype_=out[2])
             ops.bert_embed_scatter(ops.bert_scatter_problem(pl.ds, pl.B, pl.L, pl.ews, seg=seg, **kw), d)
         return out
+
+
+    def _backward_flat(self, st: BertLayerStack, pl: _Plan, dy, ids, seg, need, params) -> List[None]:
+        """The same launches writing the store's gradient views.  The LayerNorm affine gradients are accumulated into
+        (cleared with the other vectors when the gradients were unset).  bpm_bert_embed_scatter STORES its rows: on a fresh
+        step it writes the cleared table slices themselves; on an accumulation micro-step it writes a scratch copy of the
+        three tables' slice (kept, cleared here), which one bpm_add_n then adds in -- one fp32 add per element, the bits of
+        autograd's `+=`."""
+        store, d = self.store, st.d
+        names = [f"{store.prefix}bert.embeddings.{n}" for n in EMBED_PARAMS]
+        g = [store.g(n) for n in names]
+        ops.ln_bwd([ops.ln_problem(pl.s, params[3], None, pl.emean, pl.erstd, pl.R, dy=dy, ldy=d, dx=pl.ds,
+                                   dgamma=g[3] if need[3] or need[4] else None, dbeta=g[4] if need[3] or need[4] else None)],
+                   d, st.dtype, pl.seed)
+        if any(need[:3]):
+            lo = store.off[names[0]]
+            hi = store.off[names[2]] + (params[2].numel() + store.ALIGN - 1) // store.ALIGN * store.ALIGN
+            if st._fresh_bwd:
+                dst = g[:3]
+            else:
+                if self._scratch is None or self._scratch.numel() != hi - lo:
+                    self._scratch = torch.zeros(hi - lo, device=store.device, dtype=torch.float32)
+                else:
+                    self._scratch.zero_()
+                dst = [self._scratch[store.off[n] - lo: store.off[n] - lo + p.numel()].view(p.shape) for n, p in zip(names, params[:3])]
+            kw = {}
+            if need[0]:
+                sid, perm = torch.sort(ids.view(-1), stable=True)         # integer plumbing on the device, no sync
+                kw.update(sorted_ids=sid, perm=perm, dword=dst[0], padding_idx=self.padding_idx)
+            if need[1]:
+                kw.update(dpos=dst[1])
+            if need[2]:
+                kw.update(dtype_=dst[2])
+            ops.bert_embed_scatter(ops.bert_scatter_problem(pl.ds, pl.B, pl.L, pl.ews, seg=seg, **kw), d)
+            if not st._fresh_bwd:
+                ops.add_n([ops.addn_problem(store.gflat[lo:hi], [store.gflat[lo:hi], self._scratch])])
+        return [None] * 5
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -508,6 +639,12 @@ class _EncoderFn(torch.autograd.Function):
         need_e, need_l = ctx.need[:5], ctx.need[5:]
         dx, grads = ctx.stack.backward(ctx.plan, dout.contiguous().float(), any(need_e), raw=True)
         egrads = ctx.embd.backward(ctx.stack, ctx.plan, dx, ctx.ids, ctx.seg, need_e)
+        store = ctx.stack.store
+        if store is not None:
+            if ctx.stack.grad_ready is not None:
+                ctx.stack.grad_ready(store.gflat, *store.sections["embeddings"])
+            ctx.stack.finish_backward()
+            return (None,) * (7 + len(ctx.need))
         return (None,) * 7 + tuple(egrads) + tuple(g if n else None for g, n in zip(grads, need_l))
 
 

@@ -96,6 +96,7 @@ class AudioEncoder(nn.Module):
 
 TEXT_ENCODERS = ("torch", "hip")
 TEXT_EMBEDDINGS = ("torch", "hip")
+TEXT_PARAMS = ("torch", "flat")
 
 
 def step_seed(step: int) -> int:
@@ -118,7 +119,11 @@ class BertEncoder(nn.Module):
     `args.text_embeddings`: "torch" (the default) or "hip" (needs text_encoder = "hip" and hidden_size <= 1024): the
     embeddings (three gathers, LayerNorm, dropout from the library's keyed hash) are HIP kernels too, and ids -> last
     hidden state is ONE autograd node with bit-reproducible embedding gradients.  `bad_token_ids`: an int32 device counter
-    of token / type ids outside their table met so far (each contributes a zero row; reading it is the caller's sync)."""
+    of token / type ids outside their table met so far (each contributes a zero row; reading it is the caller's sync).
+
+    `args.text_params`: "torch" (the default: the BERT parameters are PyTorch's, "tail" parameters of FusedAdam) or "flat"
+    (needs text_encoder = "hip"): the parameters whose gradients the HIP path produces live in a flat store of their own
+    (`flat_store()`), the backward writes their gradients there and FusedAdam steps them in the trunk's launch."""
 
     def __init__(self, args):
         super().__init__()
@@ -131,8 +136,17 @@ class BertEncoder(nn.Module):
             raise ValueError(f"text_embeddings must be one of {TEXT_EMBEDDINGS}, got {self.text_embeddings!r}")
         if self.text_embeddings == "hip" and self.text_encoder != "hip":
             raise ValueError("text_embeddings='hip' needs text_encoder='hip' (the embeddings feed the HIP layer stack's buffers)")
+        self.text_params = getattr(args, "text_params", "torch")
+        if self.text_params not in TEXT_PARAMS:
+            raise ValueError(f"text_params must be one of {TEXT_PARAMS}, got {self.text_params!r}")
+        if self.text_params == "flat" and self.text_encoder != "hip":
+            raise ValueError("text_params='flat' needs text_encoder='hip' (the flat store holds the parameters whose gradients "
+                             "the HIP layer stack writes)")
         self.precision: Optional[str] = getattr(args, "precision", None)
         self.bert = None
+        self.store_prefix = ""          # this module's name in the model ("enc."): the flat store uses the model's parameter names
+        self._text_store = None
+        self._grad_ready = None         # set by the model: callable(gflat, lo, hi) for a finished section of the text store
         self._stack = None
         self._embd = None
         self.bad_token_ids: Optional[torch.Tensor] = None       # device counter, created by the first HIP-embeddings forward
@@ -151,8 +165,26 @@ class BertEncoder(nn.Module):
         r = super()._apply(fn, *a, **k)
         self._stack = None              # shadows and activation buffers live on the old device
         self._embd = None
+        self._text_store = None
         self.bad_token_ids = None
         return r
+
+    def flat_store(self):
+        """`text_params = "flat"`: the engine.ParamStore of the text parameters whose gradients the HIP path produces --
+        the 16 parameters of every `bert.encoder.layer[i]` and, with `text_embeddings = "hip"`, the five embedding
+        parameters; the pooler (and the embeddings on torch) stay PyTorch's.  The module tree, named_parameters() and the
+        state_dict keys are unchanged: the parameters become views into the store's master.  Built at the first use and
+        again after anything re-pointed a parameter (.to() / .cuda(), `p.data = ...`) or changed the precision; None with
+        `text_params = "torch"` or text features.  The parameters must be on the GPU."""
+        if self.text_params != "flat" or self.bert is None:
+            return None
+        dt = config.dtype_code(self.precision or config.precision())
+        st = self._text_store
+        if st is None or st.dtype != dt or st.prefix != self.store_prefix or not st.still_flat():
+            from .bert import build_text_store
+            self._text_store = st = build_text_store(self.bert, dt, self.text_embeddings == "hip", self.store_prefix)
+            self._stack = self._embd = None
+        return st
 
     def _next_seed(self) -> int:
         self.dropout_step += 1
@@ -164,6 +196,8 @@ class BertEncoder(nn.Module):
         Optimizer steps, `load_state_dict`, `copy_` and other in-place ops on the parameters are noticed without it."""
         if self._stack is not None:
             self._stack.invalidate_shadows()
+        if self._text_store is not None:
+            self._text_store.mark_dirty()
 
     def forward(self, txt, mask, segment):
         if self.features_in:
@@ -176,13 +210,15 @@ class BertEncoder(nn.Module):
                     raise RuntimeError("text encoder: the HIP layer stack needs CUDA (HIP) tensors; there is no CPU path")
             else:
                 emb = self.bert.embeddings(input_ids=txt, token_type_ids=segment)
+            store = self.flat_store()       # (drops a stack built over an older store)
             if self._stack is None:
-                self._stack = BertLayerStack(self.bert, self.precision)
+                self._stack = BertLayerStack(self.bert, self.precision, store=store)
             self._stack.precision = self.precision
+            self._stack.grad_ready = self._grad_ready
             if self.text_embeddings == "hip":
                 if self._embd is None:
                     self.bad_token_ids = torch.zeros(1, device=txt.device, dtype=torch.int32)
-                    self._embd = BertEmbeddingsHip(self.bert, self.bad_token_ids)
+                    self._embd = BertEmbeddingsHip(self.bert, self.bad_token_ids, store=store)
                 return run_encoder(self._stack, self._embd, txt, mask, segment, self._next_seed(), self.training)
             return run_layers(self._stack, emb, mask, self._next_seed(), self.training)
         return self.bert(input_ids=txt, token_type_ids=segment, attention_mask=mask, return_dict=False)[0]
@@ -765,6 +801,7 @@ class _BPMulTBase(nn.Module):
         self.prune_unused_rows = (os.environ.get("BPMULT_PRUNE", "1") != "0") if flag is None else bool(flag)
         d = self.d
         self.enc = BertEncoder(args)
+        self.enc.store_prefix = "enc."
         for t in ("l", "v", "a"):
             setattr(self, f"gmu_{t}_m", GatedMultimodalLayerFeatures(d, d, d))
         for t in ("l", "v", "a"):
@@ -907,6 +944,16 @@ class _BPMulTBase(nn.Module):
             self._anchor = torch.zeros(1, device=st.device, requires_grad=True)
         return self._store
 
+    def _flat_stores(self) -> List[ParamStore]:
+        """Every flat parameter store of the model: [trunk store], and behind it the text encoder's with
+        `args.text_params = "flat"`.  What FusedAdam steps in one launch and GradSync exchanges in place."""
+        stores = [self._ensure_store()]
+        self.enc.precision = self.precision
+        text = self.enc.flat_store()
+        if text is not None:
+            stores.append(text)
+        return stores
+
     MAX_TRUNKS = 2          # activation buffer sets kept (one per batch size, multi-GB each): most recently used
 
     def _trunk_for(self, B: int) -> _Trunk:
@@ -949,6 +996,9 @@ class _BPMulTBase(nn.Module):
         trunk is about to take (the counter FusedAdam.state_dict carries)."""
         self.enc.precision = self.precision
         self.enc.dropout_step = self.dropout_step
+        hook = getattr(self, "_grad_ready_hook", None)
+        # all text work is on the current stream: a section is final once everything launched so far has run (events None)
+        self.enc._grad_ready = (lambda flat, lo, hi: hook(flat, lo, hi, None)) if hook is not None else None
         return self.enc(txt, mask, segment)
 
     def tail_parameters(self):

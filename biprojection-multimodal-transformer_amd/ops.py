@@ -437,6 +437,51 @@ def adam_step_groups(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_av
                "bpm_adam_step_groups")
 
 
+def adam_sets(buffers):
+    """[(master, grad, exp_avg, exp_avg_sq)] flat float32 buffers, one tuple per set -> (device array, host array, the
+    tensors) for adam_step_sets: the kernel reads the device array, the entry's checks the host one."""
+    if not 1 <= len(buffers) <= _lib.ADAM_MAX_SETS:
+        raise ValueError(f"adam_sets: 1 .. {_lib.ADAM_MAX_SETS} buffer sets, got {len(buffers)}")
+    arr = (_lib.AdamSet * len(buffers))()
+    for a, bufs in zip(arr, buffers):
+        for t in bufs:
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != bufs[0].numel():
+                raise ValueError("adam_sets: every set is four flat contiguous float32 buffers of one size")
+        a.param, a.grad, a.exp_avg, a.exp_avg_sq = (_p(t) for t in bufs)
+        a.n = bufs[0].numel()
+    return device_table(list(arr)), arr, [tuple(b) for b in buffers]
+
+
+def adam_sets_table(segments):
+    """[AdamSeg] with group words from _lib.adam_set_group(), blk0 filled in here -> (device table, host array, segments,
+    blocks) for adam_step_sets."""
+    arr = (_lib.AdamSeg * len(segments))(*segments)
+    blk = 0
+    for sg in arr:
+        sg.blk0 = blk
+        blk += adam_blocks(sg.n4)
+    return device_table(list(arr)), arr, len(arr), blk
+
+
+def adam_step_sets(dtype, table, sets, groups, grad_scale, zero_grad, scale_dev=None, norm_dev=None, steps_dev=None,
+                   skipped_dev=None) -> None:
+    """bpm_adam_step_sets: adam_step_groups over several buffer sets in one launch.  table = adam_sets_table(...), sets =
+    adam_sets(...), everything else as adam_step_groups."""
+    table_dev, table_host, nseg, nblk = table
+    sets_dev, sets_host, _ = sets
+    for t, what in ((scale_dev, "scale_dev"), (norm_dev, "norm_dev")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
+            raise ValueError(f"adam_step_sets: {what} is a float32 device tensor")
+    if steps_dev is not None and (steps_dev.dtype != torch.int32 or steps_dev.numel() < len(groups) or not steps_dev.is_contiguous()):
+        raise ValueError("adam_step_sets: steps_dev is a contiguous int32 device tensor with one counter per group")
+    if skipped_dev is not None and (skipped_dev.dtype != torch.int32 or skipped_dev.numel() < 1):
+        raise ValueError("adam_step_sets: skipped_dev is an int32 device tensor")
+    _lib.check(_lib.lib().bpm_adam_step_sets(dtype, table_dev.data_ptr(), table_host, nseg, nblk, sets_dev.data_ptr(), sets_host,
+                                             len(sets_host), groups, len(groups), grad_scale, _p(scale_dev), _p(norm_dev),
+                                             _p(steps_dev), _p(skipped_dev), int(bool(zero_grad)), _stream()),
+               "bpm_adam_step_sets")
+
+
 def grad_sumsq_blocks(ptr: int, n: int) -> int:
     return int(_lib.lib().bpm_grad_sumsq_blocks(ptr, n)) if not _DRY_RUN else ((ptr >> 2 & 3) + n + 4095) // 4096
 

@@ -4,8 +4,14 @@ The reference trains with `torch.optim.Adam(model.parameters(), lr=...)` (train.
 `ReduceLROnPlateau` (train.py:128-136), steps it after the backward pass (train.py:396-398) and stores
 `optimizer.state_dict()` in its checkpoints (train.py:372-379).  Here every trunk parameter is a view into one flat fp32
 master buffer and its gradient a view into one flat gradient buffer (engine.ParamStore), so the optimizer step for ~all
-of the model is ONE streaming kernel (`bpm_adam_step_groups`) instead of a foreach loop over ~1700 tensors; the few parameters
-outside the trunk (final GMU, head, front-ends) go through an ordinary torch.optim.Adam with the same hyper-parameters.
+of the model is ONE streaming kernel (`bpm_adam_step_groups`) instead of a foreach loop over ~1700 tensors; the parameters
+in no flat store -- the "tail": final GMU, head, front-ends, the BERT pooler, and by default all of `enc.*` -- go through an
+ordinary torch.optim.Adam with the same hyper-parameters.  That tail is a few hundred KB with text features; with a real
+text encoder it is ~109 M parameters in ~200 tensors unless `args.text_params = "flat"` puts the text parameters whose
+gradients the HIP path produces into a flat store of their own (models/bert.py:build_text_store).  The optimizer steps EVERY
+flat store of the model (`model._flat_stores()`) in one launch, `bpm_adam_step_sets`: one pair of moment buffers per
+store, one segment table over all of them, one global gradient norm, one set of device step counters.  With one store the
+launch is `bpm_adam_step_groups` as before.
 
 `FusedAdam` IS a `torch.optim.Optimizer` (by default one param group holding every trainable model parameter), so LR
 schedulers and the reference's checkpoint code accept it; every group's hyper-parameters are read at every step.
@@ -27,7 +33,7 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, engine, ops
 
 
 _HYPER = ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay")
@@ -40,7 +46,10 @@ class FusedAdam(torch.optim.Optimizer):
     Differences from torch.optim.Adam, all deliberate: trunk parameters that never receive a gradient keep a zero
     gradient instead of `None` (their update is exactly zero unless weight_decay > 0); `zero_grad()` clears the flat
     gradient buffer in place (fused into the step when `fused_zero_grad=True`); the moments are two flat buffers
-    (`state_dict()["flat"]`), not per-parameter tensors.
+    (`state_dict()["flat"]`; with a flat text store also `state_dict()["flat_text"]`: its moments and the names and offsets
+    that say what lies where), not per-parameter tensors.  A checkpoint written with text_params = "torch" loads into an
+    optimizer over a "flat" model: the per-parameter moments of its tail state are copied into the flat text moments by
+    parameter name.  The reverse raises ValueError.
 
     `param_groups`: None (one group of every parameter that is trainable at construction), or torch-style dicts
     `{"params": [...], "lr": ..., "betas": ..., "eps": ..., "weight_decay": ..., "decoupled_weight_decay": ...}`; keys a
@@ -97,9 +106,17 @@ class FusedAdam(torch.optim.Optimizer):
         # int32[16 + 1] on the device: under skip_nonfinite THE counts of applied steps (started from _group_steps, which
         # is not advanced from then on), and in its last word the skips
         self._counters: Optional[torch.Tensor] = None
-        self._m: Optional[torch.Tensor] = None
+        self._m: Optional[torch.Tensor] = None              # the trunk store's moments
         self._v: Optional[torch.Tensor] = None
         self._store_id = None
+        # every flat store of the model (model._flat_stores(): the trunk's, then the text encoder's under text_params =
+        # "flat"), one pair of moment buffers per store ([0] is _m / _v) and what the one launch over all of them takes
+        self._stores: list = []
+        self._ms: List[torch.Tensor] = []
+        self._vs: List[torch.Tensor] = []
+        self._store_ids: tuple = ()
+        self._sets = None
+        self._norm_multi = None
         self._tail_opt = None
         self._tail_gi: List[int] = []                        # tail group -> index of the group it mirrors
 
@@ -156,12 +173,23 @@ class FusedAdam(torch.optim.Optimizer):
 
     # -- plumbing ---------------------------------------------------------------
     def _store(self):
-        st = self.model._ensure_store()
-        if self._store_id != id(st):                       # (re)built after .to()/.cuda(): restart the moments
-            self._m = torch.zeros_like(st.master)
-            self._v = torch.zeros_like(st.master)
-            self._store_id = id(st)
+        flat = getattr(self.model, "_flat_stores", None)
+        stores = flat() if flat is not None else [self.model._ensure_store()]
+        ids = tuple(id(st) for st in stores)
+        if ids != self._store_ids:                         # (re)built after .to()/.cuda(): restart that store's moments
+            ms, vs = [], []
+            for i, st in enumerate(stores):
+                if i < len(self._store_ids) and self._store_ids[i] == ids[i]:
+                    ms.append(self._ms[i])
+                    vs.append(self._vs[i])
+                else:
+                    ms.append(torch.zeros_like(st.master))
+                    vs.append(torch.zeros_like(st.master))
+            self._stores, self._ms, self._vs, self._store_ids = stores, ms, vs, ids
+            self._m, self._v, self._store_id = ms[0], vs[0], ids[0]
+            self._sets = self._norm_multi = None
             self._tail_opt, self._tail_gi, self._stale = None, [], True
+        st = stores[0]
         if self._stale:
             self._regroup(st)
         if self.skip_nonfinite and self._counters is None:
@@ -170,16 +198,18 @@ class FusedAdam(torch.optim.Optimizer):
         return st
 
     def _regroup(self, st) -> None:
-        """Trunk: {name: group} for the grouped launch table and the norm's parameter set.  Tail: one torch.optim.Adam
-        whose groups mirror the caller's (same membership order); a group added later is added there too, so the state
-        of the earlier ones stays."""
-        group_of = {}
+        """Flat stores: {name: group} per store for the grouped launch table and the norm's parameter set.  Tail (what is
+        in no store): one torch.optim.Adam whose groups mirror the caller's (same membership order); a group added later
+        is added there too, so the state of the earlier ones stays."""
+        group_ofs = [{} for _ in self._stores]
         for gi, g in enumerate(self.param_groups):
             tail = []
             for p in g["params"]:
                 n = self._name_of[id(p)]
-                if n in st.params:
-                    group_of[n] = gi
+                for group_of, store in zip(group_ofs, self._stores):
+                    if n in store.params:
+                        group_of[n] = gi
+                        break
                 else:
                     tail.append(p)
             if not tail or gi in self._tail_gi:
@@ -190,14 +220,27 @@ class FusedAdam(torch.optim.Optimizer):
             else:
                 self._tail_opt.add_param_group(tg)
             self._tail_gi.append(gi)
-        if not group_of:
+        if not any(group_ofs):
             raise ValueError("no parameter of the flat trunk buffers is in any parameter group: FusedAdam steps the trunk "
                              "(and the tail beside it); for tail parameters alone use torch.optim.Adam")
-        self._group_of = group_of
-        self._group_table = None                           # bpm_adam_step_groups' segment table: built by the next step
-        self._trunk_set = frozenset(group_of)
-        self._all_trunk = len(group_of) == len(st.params)
+        self._group_ofs = group_ofs
+        self._group_of = group_ofs[0]
+        self._group_table = None                           # the segment table of the launch: built by the next step
+        self._norm_multi = None
+        self._trunk_set = frozenset(group_ofs[0])
+        self._all_trunk = len(group_ofs[0]) == len(st.params)
         self._stale = False
+
+    def _grad_sumsq(self, grad_scale: float, max_norm: float, extra: Optional[torch.Tensor]) -> torch.Tensor:
+        """[total_norm, coef] on the device (ParamStore.grad_sumsq).  Several stores: ONE reduction whose table spans every
+        store's gradient buffer (bpm_grad_sumsq takes absolute addresses), over the parameters this optimizer steps."""
+        if len(self._stores) == 1:
+            return self._stores[0].grad_sumsq(grad_scale, max_norm, extra, names=None if self._all_trunk else self._trunk_set)
+        if self._norm_multi is None:
+            self._norm_multi = _norm_over(self._stores, [lambda n, g=g: n in g for g in self._group_ofs])
+        table, ws, out = self._norm_multi
+        ops.grad_sumsq(*table, ws, out, grad_scale, max_norm, extra)
+        return out
 
     def _applied_steps(self) -> List[int]:
         if self._counters is not None and self.skip_nonfinite:
@@ -205,8 +248,9 @@ class FusedAdam(torch.optim.Optimizer):
         return list(self._group_steps)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
-        st = self._store()
-        st.gflat.zero_()
+        self._store()
+        for st in self._stores:
+            st.gflat.zero_()
         if self._tail_opt is not None:
             self._tail_opt.zero_grad(set_to_none=set_to_none)
 
@@ -222,8 +266,7 @@ class FusedAdam(torch.optim.Optimizer):
             grad_scale = self.pending_grad_scale if self.pending_grad_scale is not None else 1.0
         self.pending_grad_scale = None
         self.step_count += 1
-        n = st.master.numel()
-        if n % 4:
+        if any(s.master.numel() % 4 for s in self._stores):
             raise RuntimeError("flat parameter buffer is not a multiple of 4 elements")
         clip = g.get("max_grad_norm")
         tail = [p for tg in self._tail_opt.param_groups for p in tg["params"]] if self._tail_opt is not None else []
@@ -234,8 +277,7 @@ class FusedAdam(torch.optim.Optimizer):
             # kernel and the tail read them there.
             _check_max_norm(clip)
             tail_grads = [p.grad for p in tail if p.grad is not None]
-            res = st.grad_sumsq(grad_scale, float(clip) if clip is not None else 0.0, _sumsq(tail_grads),
-                                names=None if self._all_trunk else self._trunk_set)
+            res = self._grad_sumsq(grad_scale, float(clip) if clip is not None else 0.0, _sumsq(tail_grads))
             self.last_grad_norm = res[0].clone()
             coef = res[1:2] if clip is not None else None
             norm = res[0:1] if self.skip_nonfinite else None
@@ -244,11 +286,18 @@ class FusedAdam(torch.optim.Optimizer):
         if norm is None:                                   # (under skip_nonfinite the counts live on the device)
             self._group_steps = [s + 1 for s in self._group_steps]
         hyper = ops.adam_groups([dict(pg, step=s) for pg, s in zip(self.param_groups, self._group_steps)])
-        if self._group_table is None:
-            self._group_table = st.adam_group_table(self._group_of)
-        st.adam_step_groups(self._m, self._v, self._group_table, hyper, grad_scale, self.fused_zero_grad, scale_dev=coef,
-                            norm_dev=norm, steps_dev=None if norm is None else self._counters,
-                            skipped_dev=None if norm is None else self._counters[_lib.ADAM_MAX_GROUPS:])
+        dev = dict(scale_dev=coef, norm_dev=norm, steps_dev=None if norm is None else self._counters,
+                   skipped_dev=None if norm is None else self._counters[_lib.ADAM_MAX_GROUPS:])
+        if len(self._stores) == 1:
+            if self._group_table is None:
+                self._group_table = st.adam_group_table(self._group_of)
+            st.adam_step_groups(self._m, self._v, self._group_table, hyper, grad_scale, self.fused_zero_grad, **dev)
+        else:                                              # every store in the same launch: bpm_adam_step_sets
+            if self._group_table is None:
+                self._group_table = engine.adam_sets_table(self._stores, self._group_ofs)
+            if self._sets is None:
+                self._sets = ops.adam_sets([(s.master, s.gflat, m, v) for s, m, v in zip(self._stores, self._ms, self._vs)])
+            engine.adam_step_sets(self._stores, self._group_table, self._sets, hyper, grad_scale, self.fused_zero_grad, **dev)
         if self._tail_opt is not None:
             for tg, gi in zip(self._tail_opt.param_groups, self._tail_gi):
                 for k in _HYPER:
@@ -281,10 +330,68 @@ class FusedAdam(torch.optim.Optimizer):
         skipped = int(self._counters[_lib.ADAM_MAX_GROUPS]) if self._counters is not None else 0
         return {"step": steps[0], "group_steps": steps, "skipped": skipped, "step_calls": self.step_count,
                 "flat": {"exp_avg": self._m, "exp_avg_sq": self._v},
+                **self._flat_text_state(),
                 "tail": self._tail_opt.state_dict() if self._tail_opt is not None else None,
                 "dropout_step": int(getattr(self.model, "dropout_step", 0)),
                 "param_groups": [dict({k: v for k, v in g.items() if k != "params"}, param_names=self._group_names(gi))
                                  for gi, g in enumerate(self.param_groups)]}
+
+    def _flat_text_state(self) -> dict:
+        """`flat_text`: the moments of the text encoder's flat store (text_params = "flat") with the names and offsets that
+        say what lies where; absent without such a store."""
+        if len(self._stores) < 2:
+            return {}
+        st = self._stores[1]
+        return {"flat_text": {"exp_avg": self._ms[1], "exp_avg_sq": self._vs[1], "names": list(st.names),
+                              "offsets": [st.off[n] for n in st.names]}}
+
+    def _load_flat_text(self, sd) -> Optional[dict]:
+        """Restores the text store's moments; returns the tail state to load (the checkpoint's, or what is left of it).
+        A checkpoint written with text_params = "torch" holds them per parameter in its tail state: they are copied into
+        the flat moments by parameter name and taken out of the tail state, so a run may turn the switch on at a resume."""
+        tail_sd, ft = sd.get("tail"), sd.get("flat_text")
+        if len(self._stores) < 2:
+            if ft is not None:
+                raise ValueError("the checkpoint was written with text_params='flat' (it holds 'flat_text' moments), this model "
+                                 "runs text_params='torch': loading in that direction is not supported -- build the model with "
+                                 "text_params='flat'")
+            return tail_sd
+        st, m, v = self._stores[1], self._ms[1], self._vs[1]
+        if ft is not None:
+            if list(ft["names"]) != list(st.names) or list(ft["offsets"]) != [st.off[n] for n in st.names]:
+                raise ValueError("flat_text: the checkpoint's text parameters or their offsets differ from this model's text store")
+            m.copy_(ft["exp_avg"])
+            v.copy_(ft["exp_avg_sq"])
+            return tail_sd
+        m.zero_()
+        v.zero_()
+        if tail_sd is None:
+            return None
+        groups = sd["param_groups"]
+        if any("param_names" not in g for g in groups):
+            raise ValueError("the checkpoint names no parameters: its tail state cannot be moved into the flat text moments")
+        trunk = self._stores[0].params
+        saved = [[n for n in g["param_names"] if n not in trunk] for g in groups]          # the saving optimizer's tail groups
+        saved = [names for names in saved if names]
+        if len(saved) != len(tail_sd["param_groups"]) or any(len(a) != len(b["params"]) for a, b in zip(saved, tail_sd["param_groups"])):
+            raise ValueError("the checkpoint's tail state does not match its parameter names")
+        state, new_groups, new_state, k = tail_sd["state"], [], {}, 0
+        for names, tg in zip(saved, tail_sd["param_groups"]):
+            keep = []
+            for n, idx in zip(names, tg["params"]):
+                if n in st.params:
+                    if idx in state:
+                        a, cnt = st.off[n], st.params[n].numel()
+                        m[a:a + cnt].copy_(state[idx]["exp_avg"].reshape(-1))
+                        v[a:a + cnt].copy_(state[idx]["exp_avg_sq"].reshape(-1))
+                else:
+                    if idx in state:
+                        new_state[k] = state[idx]
+                    keep.append(k)
+                    k += 1
+            if keep:
+                new_groups.append(dict(tg, params=keep))
+        return {"state": new_state, "param_groups": new_groups} if new_groups else None
 
     def load_state_dict(self, sd) -> None:
         """Restores what state_dict() wrote.  A checkpoint written before parameter groups existed (no `param_names`, no
@@ -310,8 +417,9 @@ class FusedAdam(torch.optim.Optimizer):
             self._counters[_lib.ADAM_MAX_GROUPS] = int(sd.get("skipped", 0))
         self._m.copy_(sd["flat"]["exp_avg"])
         self._v.copy_(sd["flat"]["exp_avg_sq"])
-        if self._tail_opt is not None and sd.get("tail") is not None:
-            self._load_tail(sd["tail"])
+        tail_sd = self._load_flat_text(sd)
+        if self._tail_opt is not None and tail_sd is not None:
+            self._load_tail(tail_sd)
         if hasattr(self.model, "dropout_step"):
             self.model.dropout_step = int(sd.get("dropout_step", 0))
         for mine, theirs in zip(self.param_groups, groups):
@@ -362,8 +470,31 @@ def grad_norm(model, grad_scale: float = 1.0) -> torch.Tensor:
     `torch.nn.utils.clip_grad_norm_(model.parameters(), inf)` would return, without its per-tensor loop over the trunk
     (one reduction over the flat gradient buffer; the few tail parameters through torch) and without a host sync.
     Modifies nothing: for logging in loops that keep their own optimizer.  RuntimeError before the first backward."""
-    st = model._ensure_store()
-    tail = [p.grad for n, p in model.named_parameters() if n not in st.params and p.requires_grad and p.grad is not None]
+    flat = getattr(model, "_flat_stores", None)
+    stores = flat() if flat is not None else [model._ensure_store()]
+    st = stores[0]
+    tail = [p.grad for n, p in model.named_parameters()
+            if not any(n in s.params for s in stores) and p.requires_grad and p.grad is not None]
     if st._fresh():                                        # the flat gradient buffer holds nothing current
         raise RuntimeError("grad_norm: no gradients yet (call backward first)")
-    return st.grad_sumsq(float(grad_scale), 0.0, _sumsq(tail))[0].clone()
+    if len(stores) == 1:
+        return st.grad_sumsq(float(grad_scale), 0.0, _sumsq(tail))[0].clone()
+    cached = getattr(model, "_grad_norm_tables", None)
+    if cached is None or len(cached[0]) != len(stores) or any(a is not b for a, b in zip(cached[0], stores)):
+        # one table over every store, built once per set of stores (which it keeps alive: the table holds their addresses)
+        cached = model._grad_norm_tables = (stores, _norm_over(stores, [lambda n, s=s: s.params[n].requires_grad for s in stores]))
+    table, ws, out = cached[1]
+    ops.grad_sumsq(*table, ws, out, float(grad_scale), 0.0, _sumsq(tail))
+    return out[0].clone()
+
+
+def _norm_over(stores, counts):
+    """(table, workspace, result) of one bpm_grad_sumsq launch over the gradient buffers of several stores: the slices of
+    the parameters counts[i](name) admits in store i, in store order."""
+    ranges = [r for s, c in zip(stores, counts) for r in s.norm_ranges(c)]
+    if not ranges:
+        raise RuntimeError("gradient norm: no trainable parameter in the flat buffers")
+    table = ops.sumsq_table(ranges)
+    dev = stores[0].device
+    return (table, torch.empty(ops.grad_sumsq_ws_bytes(table[2]) // 4, device=dev, dtype=torch.float32),
+            torch.zeros(2, device=dev, dtype=torch.float32))

@@ -583,6 +583,40 @@ int bpm_adam_step_groups(int dtype, const bpm_adam_seg* table_dev, int nseg, uns
                          const float* scale_dev, const float* norm_dev, int* steps_dev, int* skipped_dev, int zero_grad,
                          void* stream);
 
+/* bpm_adam_step_groups over SEVERAL BUFFER SETS in one launch: a model whose parameters live in more than one flat store
+ * (the trunk's and the text encoder's) is stepped by ONE kernel launch and ONE counter launch, so that every block of the
+ * step reads the same steps_dev / norm_dev and the step counts advance once.  (Two bpm_adam_step_groups calls cannot
+ * express this under steps_dev: the counts would advance between them.)
+ * sets: 1 .. BPM_ADAM_MAX_SETS entries {param, grad, exp_avg, exp_avg_sq, n}: four flat fp32 buffers of n elements each
+ * (n % 4 == 0, 16-byte aligned).  Table: bpm_adam_seg as above, except that
+ *   seg.group = BPM_ADAM_SET_GROUP(set, group): the set the segment lies in (off4 / n4 are relative to that set's
+ *               buffers) and its group, -1 (not stepped) included; only this entry reads the word that way;
+ *   the segments need not cover a set, but their blocks are consecutive: seg[0].blk0 = 0, seg[i + 1].blk0 = seg[i].blk0 +
+ *   bpm_adam_blocks(seg[i].n4), and total_blocks is their sum.
+ * table_dev / sets_dev: the device-resident arrays the kernel reads (built once).  table_host / sets_host: the host arrays
+ * they were uploaded from, with the same contents; EVERY check below reads these, so nothing waits for the device.
+ * groups, grad_scale, scale_dev, norm_dev, steps_dev, skipped_dev, zero_grad and the shadow write: as bpm_adam_step_groups.
+ * With one set whose table holds the same segments the results are bit-equal to bpm_adam_step_groups.
+ * BPM_ERR_ARG: a NULL table / sets / groups (device or host copy), nsets outside 1..BPM_ADAM_MAX_SETS, a set with a NULL
+ * buffer or n == 0 or n % 4 != 0, a segment whose set index is >= nsets, that reaches beyond its set, that is empty or
+ * whose blk0 breaks the rule above, a shadow with cols % 4 != 0 or larger than its segment, ngroups outside 1..16, a host
+ * step < 1 when steps_dev == NULL.  BPM_ERR_ALIGN: a buffer of a set not 16-byte, a device scalar not 4-byte aligned.
+ * Nothing is launched on an error. */
+#define BPM_ADAM_MAX_SETS 4
+#define BPM_ADAM_SET_SHIFT 8
+#define BPM_ADAM_SET_GROUP(set, group) ((int)(((unsigned)(set) << BPM_ADAM_SET_SHIFT) | ((unsigned)(group) & 0xffu)))
+typedef struct bpm_adam_set {
+    float* param;
+    float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    size_t n;
+} bpm_adam_set;
+int bpm_adam_step_sets(int dtype, const bpm_adam_seg* table_dev, const bpm_adam_seg* table_host, int nseg, unsigned total_blocks,
+                       const bpm_adam_set* sets_dev, const bpm_adam_set* sets_host, int nsets, const bpm_adam_group* groups,
+                       int ngroups, float grad_scale, const float* scale_dev, const float* norm_dev, int* steps_dev,
+                       int* skipped_dev, int zero_grad, void* stream);
+
 /* ------------------------------------------------------------------------
  * Training criterion.  Replaces nn.BCEWithLogitsLoss(pos_weight) / nn.CrossEntropyLoss(weight) / nn.L1Loss of
  * get_criterion (train.py:99-120) as called at train.py:333, and their autograd backward: the last torch compute ops of

@@ -21,6 +21,15 @@ between two device synchronisations and timed with events on the current stream;
 backward down to the word embeddings.  No optimizer runs, so the HIP modes re-pack their weight shadows explicitly in every
 step (what an optimizer step would make them do; HF's autocast casts its weights inside every step too).  The default
 windows are 40 steps (0.4 - 1.2 s each).  All positions are real tokens (full-length mask: the most work a batch can be).
+`--optimizer` measures the whole training step instead: forward + backward + `FusedAdam.step()` of a model with this text
+encoder (hip_bf16, HIP embeddings) in front of a toy trunk (hidden 24, one layer), `args.text_params = "torch"` against
+`"flat"`, alternated `--rounds` times in one call, one child process per run.  Per run: the median window and spread as
+above, the bytes the caching allocator handed out per step (`torch.cuda.memory_stats`, allocated_bytes.all.allocated), and
+the device kernels of ONE optimizer step counted with torch.profiler after the timing.  Written to `--out`
+(profiles/text_params_step.json):
+
+  python tools/text_encoder_step.py --optimizer [--rounds 2] --out profiles/text_params_step.json
+
 Algorithmic flops per step (forward + backward = 3x forward; per layer 8 L d^2 for q / k / v / out, 4 L^2 d for the two
 attention products, 4 L d I for the FFN): printed as TFLOP/s next to each time -- a whole-step rate, not a kernel's."""
 import argparse
@@ -101,6 +110,105 @@ def one(mode, steps, warmup, repeats, embeddings="torch"):
                       "spread": round((windows[-1] - windows[0]) / med, 4), "tflops": round(flops() / (med * 1e-3) / 1e12, 1)}), flush=True)
 
 
+def one_optimizer(text_params, steps, warmup, repeats):
+    """forward + backward + FusedAdam.step() with the text parameters on the torch tail optimizer or in the flat store"""
+    from types import SimpleNamespace
+
+    import torch
+    from transformers import BertConfig, BertModel
+
+    import bpmult_amd  # noqa: F401
+    from bpmult_amd.models import get_model
+    from bpmult_amd.optim import FusedAdam
+    if not torch.cuda.is_available():
+        raise SystemExit("text_encoder_step: needs a GPU (no CPU timing is meaningful)")
+    s = SHAPE
+    torch.manual_seed(1234)
+    a = SimpleNamespace(model="mmtrvat", orig_d_l=s["d"], orig_d_v=35, orig_d_a=74, orig_d_p=64, hidden_sz=24, vonly=True, lonly=True,
+                        aonly=True, num_heads=4, layers=1, attn_dropout=0., attn_dropout_v=0., attn_dropout_a=0., relu_dropout=0.,
+                        res_dropout=0., out_dropout=0., embed_dropout=0., attn_mask=True, hybrid=False, n_classes=6, bert_model="unused",
+                        text_features=True, num_vectors_l=s["L"], num_vectors_a=48, num_vectors_v=48, precision="bf16",
+                        text_encoder="hip", text_embeddings="hip", text_params=text_params)
+    model = get_model(a)
+    # a randomly initialised bert-base in place of BertModel.from_pretrained(directory): nothing is read or downloaded
+    model.enc.bert = BertModel(BertConfig(vocab_size=s["vocab"], hidden_size=s["d"], num_hidden_layers=s["layers"],
+                                          num_attention_heads=s["heads"], intermediate_size=s["inter"], max_position_embeddings=s["L"]))
+    model.enc.features_in = False
+    model = model.cuda().train()
+    g = torch.Generator().manual_seed(5)
+    ids = torch.randint(1, s["vocab"], (s["B"], s["L"]), generator=g).cuda()
+    mask, seg = torch.ones_like(ids), torch.zeros_like(ids)
+    img, aud = torch.randn(s["B"], 40, 35, generator=g).cuda(), torch.randn(s["B"], 31, 74, generator=g).cuda()
+    tgt = (torch.randn(s["B"], 6, generator=g) > 0).float().cuda()
+    opt = FusedAdam(model, lr=1e-4, fused_zero_grad=True)
+
+    def fwd_bwd():
+        torch.nn.functional.binary_cross_entropy_with_logits(model(ids, mask, seg, img, aud), tgt).backward()
+
+    def step():
+        fwd_bwd()
+        opt.step()
+        if opt._tail_opt is not None:                # (the flat buffers are cleared by the fused step)
+            opt._tail_opt.zero_grad(set_to_none=False)
+
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    windows, alloc = [], []
+    for _ in range(repeats):
+        b0 = torch.cuda.memory_stats()["allocated_bytes.all.allocated"]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        windows.append(e0.elapsed_time(e1) / steps)
+        alloc.append((torch.cuda.memory_stats()["allocated_bytes.all.allocated"] - b0) // steps)
+    windows.sort()
+    med = windows[len(windows) // 2]
+    stores = model._flat_stores()
+    tail = [p for tg in opt._tail_opt.param_groups for p in tg["params"]] if opt._tail_opt is not None else []
+    res = {"mode": text_params, "ms_per_step": round(med, 3), "windows_ms": [round(x, 3) for x in windows],
+           "spread": round((windows[-1] - windows[0]) / med, 4), "allocated_bytes_per_step": sorted(alloc)[len(alloc) // 2],
+           "flat_stores": len(stores), "flat_elements": [st.total for st in stores], "tail_tensors": len(tail),
+           "tail_elements": sum(p.numel() for p in tail), "bad_token_ids": int(model.enc.bad_token_ids)}
+    fwd_bwd()
+    torch.cuda.synchronize()
+    try:                                             # device kernels of one optimizer step
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            opt.step()
+            torch.cuda.synchronize()
+        res["optimizer_step_kernels"] = sum(1 for e in prof.events() if "cuda" in str(e.device_type).lower())
+    except Exception as e:                           # noqa: BLE001 -- the timing above stands without the count
+        res["optimizer_step_kernels"] = None
+        res["optimizer_step_kernels_error"] = f"{type(e).__name__}: {e}"[:200]
+    print(json.dumps(res), flush=True)
+
+
+def main_optimizer(a):
+    res = dict(SHAPE, steps=a.steps, warmup=a.warmup, repeats=a.repeats, dropout=0.1, precision="bf16", text_embeddings="hip",
+               trunk="mmtrvat hidden 24, 1 layer", step="forward + backward + FusedAdam.step(fused_zero_grad)", runs=[])
+    for mode in ("torch", "flat") * a.rounds:
+        cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--one-optimizer", mode, "--steps", str(a.steps),
+               "--warmup", str(a.warmup), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:              # a time limit, a fault, an abort: nothing more is started on the device
+            print(f"text_encoder_step: text_params {mode} ended with status {r.returncode}; stopping", file=sys.stderr)
+            return r.returncode
+        res["runs"].append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    med = lambda mode: sorted(x["ms_per_step"] for x in res["runs"] if x["mode"] == mode)[(a.rounds - 1) // 2]
+    res["ms_per_step"] = {"torch": med("torch"), "flat": med("flat")}
+    res["torch_over_flat"] = round(med("torch") / med("flat"), 3)      # > 1: the flat store is faster
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -111,9 +219,16 @@ def main():
     ap.add_argument("--embeddings", default="torch", choices=("torch", "hip"), help="embeddings of the hip_* modes")
     ap.add_argument("--modes", default=",".join(MODES), help="comma-separated subset of " + ",".join(MODES))
     ap.add_argument("--one", default=None, choices=MODES, help=argparse.SUPPRESS)
+    ap.add_argument("--optimizer", action="store_true", help="the whole step with FusedAdam: text_params torch against flat")
+    ap.add_argument("--rounds", type=int, default=2, help="--optimizer: how often the two settings alternate")
+    ap.add_argument("--one-optimizer", default=None, choices=("torch", "flat"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         return one(a.one, a.steps, a.warmup, a.repeats, a.embeddings)
+    if a.one_optimizer:
+        return one_optimizer(a.one_optimizer, a.steps, a.warmup, a.repeats)
+    if a.optimizer:
+        return main_optimizer(a)
     modes = [m for m in a.modes.split(",") if m]
     if any(m not in MODES for m in modes):
         ap.error(f"--modes: a subset of {MODES}")
