@@ -231,6 +231,14 @@ class EmbedProblem(C.Structure):
                 ("drop_p", C.c_float), ("drop_site", C.c_uint32), ("pos0", C.c_int), ("pos_stride", C.c_int)]
 
 
+class KvSourceProblem(C.Structure):
+    _fields_ = [("xk", C.c_void_p), ("xv", C.c_void_p), ("T", C.c_int), ("B", C.c_int), ("pos0", C.c_int), ("pos_stride", C.c_int),
+                ("drop_p_k", C.c_float), ("drop_site_k", C.c_uint32), ("drop_p_v", C.c_float), ("drop_site_v", C.c_uint32),
+                ("khat", C.c_void_p), ("vhat", C.c_void_p), ("ld", C.c_int),
+                ("mean_k", C.c_void_p), ("rstd_k", C.c_void_p), ("mean_v", C.c_void_p), ("rstd_v", C.c_void_p),
+                ("gk", C.c_void_p), ("gv", C.c_void_p), ("dxk", C.c_void_p), ("dxv", C.c_void_p)]
+
+
 class LnProblem(C.Structure):
     _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
                 ("out", C.c_void_p), ("ldo", C.c_int), ("out_f32", C.c_int),
@@ -312,6 +320,8 @@ SIGNATURES = {
     "bpm_zero_segments": [C.c_void_p, _I, C.c_uint, _P],
     "bpm_embed_pos_fwd": [C.POINTER(EmbedProblem), _I, _P, _I, _I, _F, _U64, _P],
     "bpm_embed_pos_bwd": [C.POINTER(EmbedProblem), _I, _I, _F, _U64, _P],
+    "bpm_kv_source_fwd": [_I, C.POINTER(KvSourceProblem), _I, _P, _I, _I, _F, _F, _U64, _P],
+    "bpm_kv_source_bwd": [C.POINTER(KvSourceProblem), _I, _P, _I, _I, _F, _U64, _P],
     "bpm_ln_fwd": [_I, C.POINTER(LnProblem), _I, _I, _F, _P],
     "bpm_ln_bwd": [_I, C.POINTER(LnProblem), _I, _I, _U64, _P],
     "bpm_ln_bwd_ws": [_I, C.POINTER(LnProblem), _I, _I, _U64, _P, C.c_size_t, _P],

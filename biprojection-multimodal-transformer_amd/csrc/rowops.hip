@@ -786,6 +786,218 @@ __global__ __launch_bounds__(NT) void ln_bwd_vec_kernel(const Grp<LnP> grp, int 
 }
 
 // ---------------------------------------------------------------------------
+// Key / value source of a crossmodal encoder in ONE pass per direction: embed_pos_fwd -> affine-free ln_fwd, and
+// ln_bwd -> embed_pos_bwd (-> the dxk + dxv sum), without the fp32 [S B, d] tensors ke / ve / dke / dve in between.
+// The source is the same tensor for K and V at every call site of the model: it is read once, embedded with the two
+// sites' dropout masks, and both rows are normalised from registers; the backward recomputes the embedded rows from
+// the source (the dropout hash per quad is the one the embedding backward draws anyway).
+// One wave per row, a lane owns the 4-column chunks lane + 64 e as in the vector LayerNorm kernels.  Every value that
+// the two-kernel route rounds to fp32 in memory is kept from being contracted into a neighbouring operation here
+// (kv_opaque), and the expressions are those of embed_pos_*_kernel / ln_*_vec_kernel: the results are the same bits.
+// ---------------------------------------------------------------------------
+struct KvP {
+    const float* xk; const float* xv; int T, B, pos0, pstride; DropCfg dk, dv;
+    void* khat; void* vhat; int ld; float* mk; float* rk; float* mv; float* rv;
+    const float* gk; const float* gv; float* dxk; float* dxv;
+};
+
+BPM_DEV f32x4 kv_opaque(f32x4 v) {
+    asm("" : "+v"(v));
+    return v;
+}
+
+BPM_DEV float kv_opaque1(float v) {
+    asm("" : "+v"(v));
+    return v;
+}
+BPM_DEV f32x4 kv_fma4(f32x4 a, f32x4 b, f32x4 c) {
+    return f32x4{__builtin_fmaf(a[0], b[0], c[0]), __builtin_fmaf(a[1], b[1], c[1]), __builtin_fmaf(a[2], b[2], c[2]), __builtin_fmaf(a[3], b[3], c[3])};
+}
+
+// dropout(scale * x + table[pos]) of the quad at element index i0 (embed_pos_fwd_kernel, wide path); mult: its dropout factors
+BPM_DEV f32x4 kv_embed4(f32x4 x, f32x4 tab, float scale, const DropCfg& drop, uint32_t i0, f32x4& mult) {
+    f32x4 v = scale * x + tab;
+    mult = f32x4{1.f, 1.f, 1.f, 1.f};
+    if (drop.thresh != 0) {
+        float d0, d1, d2, d3;
+        bpm_drop_mult4(drop, i0, d0, d1, d2, d3);
+        mult = f32x4{d0, d1, d2, d3};
+        v *= mult;
+    }
+    return kv_opaque(v);
+}
+
+// ln_fwd_vec_kernel's row body with gamma = 1, beta = 0
+template <typename CT, int NV>
+BPM_DEV void kv_norm_store(f32x4 (&v)[NV], int lane, int nch, float inv_d, float eps, int row, void* out, int ld, float* mean, float* rstd) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) s += sum4(v[e]);
+    const float mu = wave_sum(s) * inv_d;
+    float qq = 0.f;
+#pragma unroll
+    for (int e = 0; e < NV; ++e) {
+        const int q = lane + 64 * e;
+        f32x4 t = v[e] - mu;
+        if (q >= nch) t = f32x4{0.f, 0.f, 0.f, 0.f};
+        v[e] = t;
+        qq += sum4(t * t);
+    }
+    const float rs = rsqrtf(wave_sum(qq) * inv_d + eps);
+    if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
+#pragma unroll
+    for (int e = 0; e < NV; ++e) {
+        const int q = lane + 64 * e;
+        if (q < nch) put4<CT>(out, (size_t)row * ld + 4 * q, v[e] * rs + 0.f);
+        else if (4 * q < ld) put4<CT>(out, (size_t)row * ld + 4 * q, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+}
+
+template <typename CT, int NV>
+__global__ __launch_bounds__(NT) void kv_source_fwd_kernel(const Grp<KvP> grp, const float* __restrict__ table, int d, float scale, float eps) {
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    unsigned bid = blockIdx.x, nblk;
+    const KvP& P = pick(grp, bid, nblk);
+    const DropCfg dk = bpm_resolve_drop(P.dk, grp.seedp), dv = bpm_resolve_drop(P.dv, grp.seedp);
+    const int lane = threadIdx.x & 63;
+    const int wpb = NT / 64;
+    const int nch = d >> 2, R = P.T * P.B;
+    const bool same = P.xk == P.xv;                  // uniform per block
+    const float inv_d = 1.f / d;
+    for (int row = bid * wpb + (threadIdx.x >> 6); row < R; row += nblk * wpb) {
+        const int t = row / P.B;
+        const uint32_t r0 = (uint32_t)row * (uint32_t)d;
+        const float* xkr = P.xk + r0;
+        const float* xvr = P.xv + r0;
+        const int posk = xkr[0] != 0.f ? P.pos0 + t * P.pstride + 1 : 0;
+        const int posv = same ? posk : xvr[0] != 0.f ? P.pos0 + t * P.pstride + 1 : 0;
+        const float* tk = table + (size_t)posk * d;
+        const float* tv = table + (size_t)posv * d;
+        f32x4 ek[NV], ev[NV];
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            const int q = lane + 64 * e;
+            const int qc = q < nch ? q : 0;
+            const f32x4 xk4 = *(const f32x4*)(xkr + 4 * qc), tk4 = *(const f32x4*)(tk + 4 * qc);
+            f32x4 xv4 = xk4, tv4 = tk4, m;
+            if (!same) { xv4 = *(const f32x4*)(xvr + 4 * qc); tv4 = *(const f32x4*)(tv + 4 * qc); }
+            const f32x4 a = kv_embed4(xk4, tk4, scale, dk, r0 + 4u * (uint32_t)qc, m);
+            const f32x4 b = kv_embed4(xv4, tv4, scale, dv, r0 + 4u * (uint32_t)qc, m);
+            ek[e] = q < nch ? a : f32x4{0.f, 0.f, 0.f, 0.f};
+            ev[e] = q < nch ? b : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        kv_norm_store<CT, NV>(ek, lane, nch, inv_d, eps, row, P.khat, P.ld, P.mk, P.rk);
+        kv_norm_store<CT, NV>(ev, lane, nch, inv_d, eps, row, P.vhat, P.ld, P.mv, P.rv);
+    }
+}
+
+// dx = scale * drop * rstd * (g - mean(g) - xhat * mean(g * xhat)) for the K and the V side of each row (ln_bwd_vec_kernel
+// without affine, add or column sums, then embed_pos_bwd_kernel); merged: their fp32 sum goes to dxk.  SAME: every problem
+// of the launch has xk == xv -- one source row serves both sides and two rows are in flight per wave; otherwise the two
+// rows in flight are the K and the V source row.
+template <int NV, bool SAME>
+__global__ __launch_bounds__(NT) void kv_source_bwd_kernel(const Grp<KvP> grp, const float* __restrict__ table, int d, float scale) {
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    constexpr int U = SAME ? 2 : 1;                  // rows in flight per wave
+    constexpr int NS = SAME ? 1 : 2;                 // source rows loaded per row
+    unsigned bid = blockIdx.x, nblk;
+    const KvP& P = pick(grp, bid, nblk);
+    const DropCfg dk = bpm_resolve_drop(P.dk, grp.seedp), dv = bpm_resolve_drop(P.dv, grp.seedp);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wpb = NT / 64;
+    const int nch = d >> 2, R = P.T * P.B;
+    const bool merge = P.dxv == nullptr || P.dxv == P.dxk;       // uniform per block
+    const float inv_d = 1.f / d;
+    for (int row0 = (bid * wpb + wv) * U; row0 < R; row0 += nblk * wpb * U) {
+        f32x4 xs[U][NS][NV], tb[U][NS][NV], g[U][2][NV];
+        float mu[U][2], rs[U][2];
+        // phase 1: every load of the rows in flight (clamped rows / chunks, zeroed by selects)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int row = row0 + u;
+            const int rc = row < R ? row : row0;
+            const int t = rc / P.B;
+            const uint32_t r0 = (uint32_t)rc * (uint32_t)d;
+            mu[u][0] = P.mk[rc]; rs[u][0] = P.rk[rc];
+            mu[u][1] = P.mv[rc]; rs[u][1] = P.rv[rc];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const float* xr = (s ? P.xv : P.xk) + r0;
+                const int pos = xr[0] != 0.f ? P.pos0 + t * P.pstride + 1 : 0;
+                const float* tr = table + (size_t)pos * d;
+#pragma unroll
+                for (int e = 0; e < NV; ++e) {
+                    const int q = lane + 64 * e;
+                    const int qc = q < nch ? q : 0;
+                    xs[u][s][e] = *(const f32x4*)(xr + 4 * qc);
+                    tb[u][s][e] = *(const f32x4*)(tr + 4 * qc);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < NV; ++e) {
+                const int q = lane + 64 * e;
+                const int qc = q < nch ? q : 0;
+                g[u][0][e] = *(const f32x4*)(P.gk + r0 + 4 * qc);
+                g[u][1][e] = *(const f32x4*)(P.gv + r0 + 4 * qc);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int row = row0 + u;
+            const bool rok = row < R;
+            const uint32_t r0 = (uint32_t)(rok ? row : row0) * (uint32_t)d;
+#pragma unroll
+            for (int side = 0; side < 2; ++side) {
+                const int s = SAME ? 0 : side;
+                const DropCfg& drop = side ? dv : dk;
+                f32x4 xh[NV], mult[NV];
+                float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                for (int e = 0; e < NV; ++e) {
+                    const int q = lane + 64 * e;
+                    const bool ok = rok && q < nch;
+                    const f32x4 emb = kv_embed4(xs[u][s][e], tb[u][s][e], scale, drop, r0 + 4u * (uint32_t)(q < nch ? q : 0), mult[e]);
+                    const f32x4 dyv = ok ? g[u][side][e] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    xh[e] = ok ? (emb - mu[u][side]) * rs[u][side] : f32x4{0.f, 0.f, 0.f, 0.f};
+                    s1 += sum4(dyv);
+                    s2 += sum4(dyv * xh[e]);
+                    g[u][side][e] = dyv;
+                }
+                // The roundings of g - mean(g) - xhat * mean(g xhat) are spelled out as ln_bwd_vec_kernel<., NV> is compiled:
+                // xhat * mean(g xhat) and the product with rstd are fused everywhere; mean(g) = sum / d is rounded before it
+                // is subtracted, except at NV == 1, where the division is fused into the subtraction.
+                s1 = wave_sum(s1);
+                if constexpr (NV != 1) s1 = kv_opaque1(s1 * inv_d);
+                s2 = kv_opaque1(wave_sum(s2) * inv_d);
+#pragma unroll
+                for (int e = 0; e < NV; ++e) {
+                    f32x4 t = NV == 1 ? kv_fma4(f32x4{-inv_d, -inv_d, -inv_d, -inv_d}, f32x4{s1, s1, s1, s1}, g[u][side][e]) : g[u][side][e] - s1;
+                    t = kv_fma4(-xh[e], f32x4{s2, s2, s2, s2}, kv_opaque(t));
+                    const f32x4 rs4 = f32x4{rs[u][side], rs[u][side], rs[u][side], rs[u][side]};
+                    const f32x4 dl = kv_opaque(kv_fma4(rs4, t, f32x4{0.f, 0.f, 0.f, 0.f}));                  // = dke / dve
+                    f32x4 v = scale * dl;
+                    if (drop.thresh != 0) v *= mult[e];
+                    g[u][side][e] = kv_opaque(v);
+                }
+            }
+            if (!rok) continue;                      // wave-uniform
+#pragma unroll
+            for (int e = 0; e < NV; ++e) {
+                const int q = lane + 64 * e;
+                if (q < nch) {
+                    if (merge) {
+                        *(f32x4*)(P.dxk + r0 + 4 * q) = g[u][0][e] + g[u][1][e];
+                    } else {
+                        *(f32x4*)(P.dxk + r0 + 4 * q) = g[u][0][e];
+                        *(f32x4*)(P.dxv + r0 + 4 * q) = g[u][1][e];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // rows_cast: y = (a [+ b]) * drop_mult ; a is fp32 or CT; written as CT
 // (padded) and/or fp32; optional column sums (bias gradient) by atomics.
 // Block = 32 rows x 256 columns.
@@ -1573,6 +1785,85 @@ extern "C" int bpm_ln_bwd_ws(int dtype, const bpm_ln_problem* q, int n, int d, u
 
 extern "C" int bpm_ln_bwd(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* stream) {
     return bpm_ln_bwd_ws(dtype, q, n, d, seed, nullptr, 0, stream);
+}
+
+// Domain of the fused key / value source kernels (the wide paths of the kernels they replace): d % 4 == 0, d <= 1024,
+// 16-byte aligned fp32 tensors, fewer than 2^32 elements per tensor.  *all_same: xk == xv in every problem.
+static int fill_kv(Grp<KvP>& g, const bpm_kv_source_problem* q, int n, const float* table, int table_rows, int d, uint64_t seed,
+                   bool bwd, int ct_size, int rows_per_wave, int* span, bool* all_same) {
+    if (!q || n < 1 || n > BPM_MAX_GROUP || !table || d < 4 || d % 4 || d > 4 * 64 * 4 || ((uintptr_t)table & 15)) return BPM_ERR_ARG;
+    g.n = n; g.blk0[0] = 0; g.seedp = bpm_seed_ptr(seed);
+    *span = d; *all_same = true;
+    for (int i = 0; i < n; ++i) {
+        const bpm_kv_source_problem& s = q[i];
+        if (!s.xk || !s.xv || s.T < 1 || s.B < 1 || s.pos0 < 0 || s.pos_stride < 0) return BPM_ERR_ARG;
+        if (!s.mean_k || !s.rstd_k || !s.mean_v || !s.rstd_v) return BPM_ERR_ARG;
+        const int pstride = s.pos_stride > 0 ? s.pos_stride : 1;
+        if ((long long)table_rows < (long long)s.pos0 + (long long)(s.T - 1) * pstride + 2) return BPM_ERR_ARG;
+        if ((unsigned long long)s.T * (unsigned long long)s.B * (unsigned long long)d >= (1ull << 32)) return BPM_ERR_ARG;
+        uintptr_t a = (uintptr_t)s.xk | (uintptr_t)s.xv;
+        if (bwd) {
+            if (!s.gk || !s.gv || !s.dxk) return BPM_ERR_ARG;
+            a |= (uintptr_t)s.gk | (uintptr_t)s.gv | (uintptr_t)s.dxk | (uintptr_t)s.dxv;
+        } else {
+            if (!s.khat || !s.vhat || s.ld < d || s.ld % 4 || s.ld > 4 * 64 * 4) return BPM_ERR_ARG;
+            if (((uintptr_t)s.khat | (uintptr_t)s.vhat) % (4 * ct_size)) return BPM_ERR_ARG;
+            if (s.ld > *span) *span = s.ld;
+        }
+        if (a & 15) return BPM_ERR_ARG;
+        if (s.xk != s.xv) *all_same = false;
+        KvP& p = g.p[i];
+        p.xk = s.xk; p.xv = s.xv; p.T = s.T; p.B = s.B; p.pos0 = s.pos0; p.pstride = pstride;
+        p.dk = make_drop(s.drop_p_k, seed, s.drop_site_k);
+        p.dv = make_drop(s.drop_p_v, seed, s.drop_site_v);
+        p.khat = s.khat; p.vhat = s.vhat; p.ld = s.ld;
+        p.mk = s.mean_k; p.rk = s.rstd_k; p.mv = s.mean_v; p.rv = s.rstd_v;
+        p.gk = s.gk; p.gv = s.gv; p.dxk = s.dxk; p.dxv = s.dxv;
+        g.blk0[i + 1] = g.blk0[i] + blocks_for(((size_t)s.T * s.B + rows_per_wave - 1) / rows_per_wave, 4, 4096);
+    }
+    return 0;
+}
+
+extern "C" int bpm_kv_source_fwd(int dtype, const bpm_kv_source_problem* q, int n, const float* table, int table_rows, int d,
+                                 float scale, float eps, uint64_t seed, void* stream) {
+    if (dtype != BPM_F32 && dtype != BPM_BF16) return BPM_ERR_ARG;
+    Grp<KvP> g;
+    int span;
+    bool same;
+    int rc = fill_kv(g, q, n, table, table_rows, d, seed, false, dtype == BPM_BF16 ? 2 : 4, 1, &span, &same);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+#define BPM_KV_FWD(NV)                                                                                         \
+    if (span <= 256 * NV) {                                                                                    \
+        if (dtype == BPM_BF16) hipLaunchKernelGGL((kv_source_fwd_kernel<bf16_t, NV>), dim3(g.blk0[n]), dim3(NT), 0, s, g, table, d, scale, eps); \
+        else hipLaunchKernelGGL((kv_source_fwd_kernel<float, NV>), dim3(g.blk0[n]), dim3(NT), 0, s, g, table, d, scale, eps);                   \
+        BPM_CHECK_LAUNCH();                                                                                    \
+        return 0;                                                                                              \
+    }
+    BPM_KV_FWD(1) BPM_KV_FWD(2) BPM_KV_FWD(3) BPM_KV_FWD(4)
+#undef BPM_KV_FWD
+    return BPM_ERR_ARG;
+}
+
+extern "C" int bpm_kv_source_bwd(const bpm_kv_source_problem* q, int n, const float* table, int table_rows, int d, float scale,
+                                 uint64_t seed, void* stream) {
+    Grp<KvP> g;
+    int span;
+    bool same = q != nullptr;
+    for (int i = 0; same && i < n && i < BPM_MAX_GROUP; ++i) same = q[i].xk == q[i].xv;
+    int rc = fill_kv(g, q, n, table, table_rows, d, seed, true, 4, same ? 2 : 1, &span, &same);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+#define BPM_KV_BWD(NV)                                                                                         \
+    if (d <= 256 * NV) {                                                                                       \
+        if (same) hipLaunchKernelGGL((kv_source_bwd_kernel<NV, true>), dim3(g.blk0[n]), dim3(NT), 0, s, g, table, d, scale);  \
+        else hipLaunchKernelGGL((kv_source_bwd_kernel<NV, false>), dim3(g.blk0[n]), dim3(NT), 0, s, g, table, d, scale);     \
+        BPM_CHECK_LAUNCH();                                                                                    \
+        return 0;                                                                                              \
+    }
+    BPM_KV_BWD(1) BPM_KV_BWD(2) BPM_KV_BWD(3) BPM_KV_BWD(4)
+#undef BPM_KV_BWD
+    return BPM_ERR_ARG;
 }
 
 extern "C" int bpm_rows_cast(int dtype, const bpm_cast_problem* q, int n, uint64_t seed, void* stream) {

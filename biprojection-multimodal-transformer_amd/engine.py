@@ -34,7 +34,7 @@ import torch
 
 from . import ops
 from ._lib import (BPM_BF16, AdamSeg, adam_set_group, AddnProblem, ExpandProblem, F_CT_NARROW, F_ACCUM, F_BACKGROUND, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, OUT_CT, OUT_HEADS,
-                   AttnProblem, CastProblem, FoldDesc, GemmProblem, LnProblem, PackDesc,
+                   AttnProblem, CastProblem, FoldDesc, GemmProblem, KvSourceProblem, LnProblem, PackDesc,
                    UnfoldDesc)
 from .ops import pad32
 
@@ -646,6 +646,14 @@ class EncoderGroupPlan:
                          and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs) and self.dh <= 256)
         self.ld, self.ld4 = pad32(d), pad32(4 * d)
         self.scale = self.dh ** -0.5
+        # KEY / VALUE SOURCES IN ONE PASS (bpm_kv_source_fwd / _bwd): embedding + affine-free LayerNorm of every key / value
+        # source as one side-stream launch per direction, read from the caller's xk / xv -- no embedded copies (ke / ve) and
+        # no LayerNorm-input gradients (dke / dve).  Same bits as the embed_pos / ln launches it replaces; BPMULT_KV_FUSED=0
+        # (read when the plan is built) keeps those, as does a shape outside the kernels' domain.
+        self._kv_fused = (self._kv and os.environ.get("BPMULT_KV_FUSED", "1") != "0"
+                          and all(ops.kv_source_ok(d, e.S, B) for e in self.encs))
+        self._kv_dst: List[Optional[torch.Tensor]] = [None] * len(self.encs)     # merge_kv_grads: where d(xk) + d(xv) goes
+        self._kv_keep = None                                                     # the last forward's xk / xv (read again by backward)
         # FFN LayerNorm: layer_norms.2 in the biprojection kind (its layer_norms.1 normalises the key / value source, or is
         # the identity of maybe_layer_norm(1, after=True) in the self-attention-only stack: no gradient)
         self._lnF = 2 if cfg.biprojection else 1
@@ -660,6 +668,17 @@ class EncoderGroupPlan:
             raise ValueError("a gathered query subset is only exact for crossmodal (non-biprojection) encoders")
         self.table = sinusoid_table(max(max(e.T_full or e.T, e.S) for e in self.encs) + 2, d, dev)
         self._ones, self._zeros = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+        # fused key / value sources: one problem per encoder, shared by the forward and the backward tables of a mode; the
+        # source pointers are set by forward(), the gradient destinations by merge_kv_grads()
+        self._kvsrc = {}
+        if self._kv_fused:
+            for training in (True, False):
+                p = cfg.embed_dropout if training else 0.0
+                self._kvsrc[training] = ops.array(KvSourceProblem, [
+                    ops.kv_source_problem(None, None, e.S, B, khat=b["khat"], vhat=b["vhat"], ld=self.ld, stats_k=b["stk"],
+                                          stats_v=b["stv"], gk=b["Gk"], gv=b["Gv"], dxk=b["dxk"], dxv=b["dxv"], drop_p=p,
+                                          drop_site_k=site(e.enc_id, 0, S_EMB_K), drop_site_v=site(e.enc_id, 0, S_EMB_V))
+                    for e, b in zip(self.encs, self.buf)])
         # table of the launch that turns folded K/V gradients into in_proj / LayerNorm parameter gradients
         lnK = 1 if cfg.biprojection else 0
         self._unfold = []                                  # one table per layer: its gradients are final with it
@@ -715,7 +734,8 @@ class EncoderGroupPlan:
         b["out"] = z(Tl[-1], B, d)
         b["stf"] = (z(Rl[-1]), z(Rl[-1]))
         if self._kv:
-            b["ke"], b["ve"] = z(Rk, d), z(Rk, d)
+            if not self._kv_fused:
+                b["ke"], b["ve"] = z(Rk, d), z(Rk, d)
             # key / value source, normalised ONCE without affine (the per-layer LayerNorm gain and bias are folded
             # into the K / V projection weights, see register_encoder_shadows)
             b["khat"], b["vhat"] = z(Rk, ld, dt=ct), z(Rk, ld, dt=ct)
@@ -792,7 +812,8 @@ class EncoderGroupPlan:
             k = _BIP_SELF_KEYS if self._kv else _SELF_KEYS
             b[k["dao"]], b[k["delta"]] = z(B, H, e.T, dhp, dt=ct), z(B, H, e.T)
         if self._kv:
-            b["dke"], b["dve"] = z(Rk, d), z(Rk, d)
+            if not self._kv_fused:
+                b["dke"], b["dve"] = z(Rk, d), z(Rk, d)
             b["dxk"], b["dxv"] = z(e.S, B, d), z(e.S, B, d)
         b["dxq"] = z(e.T, B, d)
         return b
@@ -1048,7 +1069,9 @@ class EncoderGroupPlan:
         nt = lambda probs: self._gemm(GEMM_NT, probs)
         attn = lambda probs: (ops.attn_fwd, self.dtype, A(AttnProblem, probs))
         steps, kv_steps = [], []
-        if self._kv:
+        if self._kv_fused:
+            kv_steps = [(SIDE, (ops.kv_source_fwd, self.dtype, self._kvsrc[training], self.table, d, math.sqrt(d))), (MARK, "hat")]
+        elif self._kv:
             hat = []
             for b in self.buf:
                 hat += [ops.ln_problem(b["ke"], self._ones, self._zeros, b["stk"][0], b["stk"][1], b["Rk"], out=b["khat"], ldo=self.ld),
@@ -1106,6 +1129,10 @@ class EncoderGroupPlan:
             fn(s[1], s[2], s[3], s[4])
         elif fn is ops.add_n:
             fn(s[1])
+        elif fn is ops.kv_source_fwd:
+            fn(s[1], s[2], s[3], s[4], s[5], seed)
+        elif fn is ops.kv_source_bwd:
+            fn(s[1], s[2], s[3], s[4], seed)
         else:
             raise RuntimeError("unknown step")
 
@@ -1178,7 +1205,9 @@ class EncoderGroupPlan:
     def forward(self, xq: Sequence[torch.Tensor], xk: Sequence[torch.Tensor], xv: Sequence[torch.Tensor], seed: int,
                 training: bool) -> List[torch.Tensor]:
         """xq[e]: fp32 [T_e,B,d]; xk[e], xv[e]: fp32 [S_e,B,d] key / value sources (the same tensor at every
-        reference call site, mmtr.py:779-791; they still get independent embedding dropout, transformer.py:73-79)."""
+        reference call site, mmtr.py:779-791; they still get independent embedding dropout, transformer.py:73-79).
+        With fused key / value sources (the default) the plan keeps references to xk / xv until its next forward and
+        backward() reads them again: like any tensor saved for a backward pass they must not be modified in between."""
         c, B, d = self.cfg, self.B, self.cfg.d
         p = c.embed_dropout if training else 0.0
         emb = []
@@ -1190,9 +1219,18 @@ class EncoderGroupPlan:
                     raise ValueError(f"encoder {e.prefix}: expected contiguous fp32 [{n},{B},{d}], got {tuple(t.shape)} {t.dtype}")
             emb.append(ops.embed_problem(q, b["x"][0], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q), pos0=e.q_pos0,
                                          pos_stride=e.q_stride))
-            if self._kv:
+            if self._kv and not self._kv_fused:
                 emb += [ops.embed_problem(k, b["ke"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)),
                         ops.embed_problem(v, b["ve"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V))]
+        if self._kv_fused:
+            # 16-byte accesses: a source that starts off such a boundary (a view into a larger tensor) is copied first
+            al = lambda t: t if t.data_ptr() % 16 == 0 else t.clone()
+            ks = [al(k) for k in xk]
+            vs = [kk if v is k else al(v) for k, kk, v in zip(xk, ks, xv)]
+            self._kv_keep = (ks, vs)
+            for arr in self._kvsrc.values():
+                for i, (k, v) in enumerate(zip(ks, vs)):
+                    ops.set_kv_source(arr[i], k, v)
         self._maps_ok = False
         ops.embed_pos_fwd(emb, self.table, d, math.sqrt(d), seed)
         self._last = (seed, training)
@@ -1372,9 +1410,12 @@ class EncoderGroupPlan:
                 for all_, stack, G_ in ((b["dkall"], KSTACK, b["Gk"]), (b["dvall"], VSTACK, b["Gv"])):
                     dg_kv.append(ops.gemm_problem(all_, st.sptr(e.prefix + stack), G_, b["Rk"], d, c.layers * self.ld, c.layers * self.ld,
                                                   self.ld, d))
-            hat += [ops.ln_problem(b["ke"], self._ones, None, b["stk"][0], b["stk"][1], b["Rk"], dy=b["Gk"], ldy=d, dx=b["dke"]),
-                    ops.ln_problem(b["ve"], self._ones, None, b["stv"][0], b["stv"][1], b["Rk"], dy=b["Gv"], ldy=d, dx=b["dve"])]
-        return steps + [(SIDE, self._gemm(GEMM_TN if lr else GEMM_NN, dg_kv)), (SIDE, ln(hat)), JOIN]
+            if not self._kv_fused:
+                hat += [ops.ln_problem(b["ke"], self._ones, None, b["stk"][0], b["stk"][1], b["Rk"], dy=b["Gk"], ldy=d, dx=b["dke"]),
+                        ops.ln_problem(b["ve"], self._ones, None, b["stv"][0], b["stv"][1], b["Rk"], dy=b["Gv"], ldy=d, dx=b["dve"])]
+        # fused: LayerNorm backward + embedding backward (+ the sum of the two gradients) of every source in one launch
+        last = (ops.kv_source_bwd, self._kvsrc[training], self.table, d, math.sqrt(d)) if self._kv_fused else ln(hat)
+        return steps + [(SIDE, self._gemm(GEMM_TN if lr else GEMM_NN, dg_kv)), (SIDE, last), JOIN]
 
     @staticmethod
     def store_written(prefix: str, layers: int):
@@ -1416,16 +1457,39 @@ class EncoderGroupPlan:
         emb = []
         for e, b in zip(self.encs, self.buf):
             emb.append(ops.embed_problem(b["dx"], b["dxq"], e.T, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_Q)))
-            if self._kv:
+            if self._kv and not self._kv_fused:
                 emb.append(ops.embed_problem(b["dke"], b["dxk"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_K)))
                 emb.append(ops.embed_problem(b["dve"], b["dxv"], e.S, B, drop_p=p, drop_site=site(e.enc_id, 0, S_EMB_V)))
         ops.embed_pos_bwd(emb, d, math.sqrt(d), seed)
         return self.input_grads()
 
+    def merge_kv_grads(self, dests: Optional[Sequence[Optional[torch.Tensor]]] = None) -> bool:
+        """Opt in: backward() writes ONE gradient per key / value source, d(xk) + d(xv) summed in fp32 -- what a caller that
+        passes the same tensor as xk and xv adds up anyway.  dests[e] (contiguous fp32 [S_e, B, d], 16-byte aligned; None:
+        the plan's own buffer) receives encoder e's sum; input_grads() then returns it in the key list and None in the value
+        list.  Only the fused key / value source launch can do this: returns False, and changes nothing, without it."""
+        if not self._kv_fused:
+            return False
+        for i, (e, b) in enumerate(zip(self.encs, self.buf)):
+            dst = dests[i] if dests is not None and dests[i] is not None else b["dxk"]
+            if (tuple(dst.shape) != (e.S, self.B, self.cfg.d) or dst.dtype != torch.float32 or not dst.is_contiguous()
+                    or dst.data_ptr() % 16):
+                raise ValueError(f"encoder {e.prefix}: merged key / value gradient must be contiguous, 16-byte aligned fp32 "
+                                 f"[{e.S},{self.B},{self.cfg.d}], got {tuple(dst.shape)} {dst.dtype}")
+            self._kv_dst[i] = dst
+            for arr in self._kvsrc.values():
+                arr[i].dxk, arr[i].dxv = dst.data_ptr(), None
+        return True
+
     def input_grads(self):
-        """The plan-owned buffers backward() leaves the query, key and value source gradients in (three lists)."""
+        """The plan-owned buffers backward() leaves the query, key and value source gradients in (three lists); after
+        merge_kv_grads(): the merged gradient's tensor in the key list, None in the value list."""
         kv = lambda n: [b[n] if self._kv else None for b in self.buf]       # no key / value source: None in its place
-        return [b["dxq"] for b in self.buf], kv("dxk"), kv("dxv")
+        dk, dv = kv("dxk"), kv("dxv")
+        for i, dst in enumerate(self._kv_dst):
+            if dst is not None:
+                dk[i], dv[i] = dst, None
+        return [b["dxq"] for b in self.buf], dk, dv
 
 
 KVF = "self_attn.in_proj_weight#kvf"      # key suffix of the folded key/value shadow and bias

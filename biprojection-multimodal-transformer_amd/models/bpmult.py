@@ -591,17 +591,24 @@ class _Trunk(GraphCache):
                     whole[name], rows[name] = (terms, []) if self.Ng[tgt] == self.N[LEVEL1[name][0]] else ([], terms)
         self._d2 = [d2[n] for n in LEVEL2]
         self._d1 = [self.d1buf[n] for n in LEVEL1]
+        # Every encoder gets the same tensor as key and value source: both plans write ONE gradient per source, the fp32
+        # sum of the two (EncoderGroupPlan.merge_kv_grads; without the fused key / value source launch they keep two).
+        # Level 2's goes straight into d(level-1 output) where no other whole-tensor term joins it there (the pruned
+        # 3-modal schedule: the GMU terms are two rows each, added on top afterwards) -- no bpm_add_n for that tensor.
+        self.plan2.merge_kv_grads([self.d1buf[src] if not whole[src] else None for (q, src, _) in LEVEL2.values()])
+        self.plan1.merge_kv_grads()
         dq2, dk2, dv2 = self.plan2.input_grads()
         sums, rows2 = [], []
         for (n, (q, src, _)), gk, gv in zip(LEVEL2.items(), dk2, dv2):
             d1 = self.d1buf[src]
             rows2 += [(d1, t) for t in rows[src]]
-            sums.append(ops.addn_problem(d1, whole[src] + [gk, gv]))
+            if gk is not d1:
+                sums.append(ops.addn_problem(d1, whole[src] + [g for g in (gk, gv) if g is not None]))
         dq1, dk1, dv1 = self.plan1.input_grads()
         acc: Dict[str, List[torch.Tensor]] = {"l": [], "a": [], "v": []}
         for (n, (q, kv, _)), gq, gk, gv in zip(LEVEL1.items(), dq1, dk1, dv1):
             acc[q].append(gq)
-            acc[kv] += [gk, gv]
+            acc[kv] += [g for g in (gk, gv) if g is not None]
         small: Dict[str, List[torch.Tensor]] = {"l": [], "a": [], "v": []}
         for (n, (q, src, _)), e, gq in zip(LEVEL2.items(), self.plan2.encs, dq2):     # (3-modal pruned schedule: level 2 has
             (small if e.T != self.N[q] else acc)[q].append(gq)                          # two query rows)

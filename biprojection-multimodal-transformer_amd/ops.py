@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import (BPM_BF16, BPM_BF16X3, BPM_F32, F_ACCUM, F_ATOMIC, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, GEMM_MAX_GROUP, MAX_GROUP, OUT_CT,
                    OUT_F32, OUT_HEADS, AttnMapProblem, AttnProblem, CastProblem, EmbedProblem, GemmProblem, GmuProblem,
-                   LnProblem, PackProblem)
+                   KvSourceProblem, LnProblem, PackProblem)
 
 
 def pad32(n: int) -> int:
@@ -560,6 +560,50 @@ def embed_pos_bwd(probs, d, scale, seed=0) -> None:
     arr = _as_array(EmbedProblem, probs)
     for sub, k in _chunks(arr, EmbedProblem, None):
         _lib.check(_lib.lib().bpm_embed_pos_bwd(sub, k, d, scale, _seed(seed), _stream()), "bpm_embed_pos_bwd")
+
+
+def kv_source_ok(d: int, T: int, B: int) -> bool:
+    """Shape domain of bpm_kv_source_fwd / _bwd (the pointers' 16-byte alignment is checked by the library)."""
+    return d % 4 == 0 and 4 <= d <= 1024 and T * B * d < 1 << 32
+
+
+def kv_source_problem(xk, xv, T, B, *, khat=None, vhat=None, ld=0, stats_k=(None, None), stats_v=(None, None), gk=None, gv=None,
+                      dxk=None, dxv=None, drop_p=0.0, drop_site_k=0, drop_site_v=0, pos0=0, pos_stride=1) -> KvSourceProblem:
+    """One key / value source of bpm_kv_source_fwd / _bwd (both directions read the same struct).  xk / xv may be None while
+    a table is built and set before the launch (set_kv_source); dxv None (or dxk): the backward writes dxk = d(xk) + d(xv)."""
+    p = KvSourceProblem()
+    p.xk, p.xv, p.T, p.B, p.pos0, p.pos_stride = _f32(xk, "kv_source.xk"), _f32(xv, "kv_source.xv"), T, B, pos0, pos_stride
+    p.drop_p_k, p.drop_site_k, p.drop_p_v, p.drop_site_v = drop_p, drop_site_k, drop_p, drop_site_v
+    p.khat, p.vhat, p.ld = _p(khat), _p(vhat), ld
+    p.mean_k, p.rstd_k = _f32(stats_k[0], "kv_source.mean_k"), _f32(stats_k[1], "kv_source.rstd_k")
+    p.mean_v, p.rstd_v = _f32(stats_v[0], "kv_source.mean_v"), _f32(stats_v[1], "kv_source.rstd_v")
+    p.gk, p.gv = _f32(gk, "kv_source.gk"), _f32(gv, "kv_source.gv")
+    p.dxk, p.dxv = _f32(dxk, "kv_source.dxk"), _f32(dxv, "kv_source.dxv")
+    return p
+
+
+def set_kv_source(p: KvSourceProblem, xk, xv) -> None:
+    p.xk, p.xv = _f32(xk, "kv_source.xk"), _f32(xv, "kv_source.xv")
+
+
+def _kv_table(table, d):
+    if table.dtype != torch.float32 or table.shape[1] != d or not table.is_contiguous():
+        raise ValueError("kv_source: table must be contiguous fp32 [rows, d]")
+    return table.data_ptr(), table.shape[0]
+
+
+def kv_source_fwd(dtype, probs, table, d, scale, seed=0, eps=1e-5) -> None:
+    arr = _as_array(KvSourceProblem, probs)
+    tp, rows = _kv_table(table, d)
+    for sub, k in _chunks(arr, KvSourceProblem, None):
+        _lib.check(_lib.lib().bpm_kv_source_fwd(dtype, sub, k, tp, rows, d, scale, eps, _seed(seed), _stream()), "bpm_kv_source_fwd")
+
+
+def kv_source_bwd(probs, table, d, scale, seed=0) -> None:
+    arr = _as_array(KvSourceProblem, probs)
+    tp, rows = _kv_table(table, d)
+    for sub, k in _chunks(arr, KvSourceProblem, None):
+        _lib.check(_lib.lib().bpm_kv_source_bwd(sub, k, tp, rows, d, scale, _seed(seed), _stream()), "bpm_kv_source_bwd")
 
 
 def ln_problem(x, gamma, beta, mean, rstd, R, *, out=None, ldo=0, out_f32=False, dy=None, ldy=0, add=None, dx=None,

@@ -281,6 +281,35 @@ int bpm_embed_pos_fwd(const bpm_embed_problem* probs, int n, const float* table,
                       float scale, uint64_t seed, void* stream);
 int bpm_embed_pos_bwd(const bpm_embed_problem* probs, int n, int d, float scale, uint64_t seed, void* stream);
 
+/* Key / value source of a crossmodal encoder, embedded and normalised in one pass (transformer.py:73-79 and the
+ * affine-free half of the LayerNorm at transformer.py:167-172; the gain and bias are folded into the projections):
+ *   forward   khat = LNhat(dropout_k(scale*xk + table[pos])), vhat likewise from xv with its own dropout site; CT
+ *             [T*B, ld] with zero pad columns; mean / rstd [T*B] of both.  xk == xv (every call site of the model)
+ *             is read once.  pos follows bpm_embed_pos_fwd.
+ *   backward  dxk = scale * drop_k * dLNhat(gk), dxv likewise (gk / gv fp32 [T*B, d]; the embedded rows are recomputed
+ *             from xk / xv, which must still hold the forward's values, with the forward's seed).  dxv == NULL or
+ *             dxv == dxk: dxk receives the fp32 sum of the two instead.
+ * Same bits as bpm_embed_pos_fwd -> bpm_ln_fwd (gamma 1, beta 0) and bpm_ln_bwd -> bpm_embed_pos_bwd on the same
+ * inputs, without the four fp32 [T*B, d] tensors in between.
+ * Domain (BPM_ERR_ARG outside it, nothing launched): d % 4 == 0, 4 <= d <= 1024, d <= ld <= 1024, ld % 4 == 0,
+ * T*B*d < 2^32, table and every fp32 tensor 16-byte aligned, khat / vhat aligned to four CT elements,
+ * table_rows >= pos0 + (T-1)*pos_stride + 2. */
+typedef struct bpm_kv_source_problem {
+    const float* xk; const float* xv;
+    int T, B;
+    int pos0, pos_stride;                   /* as in bpm_embed_problem */
+    float drop_p_k; uint32_t drop_site_k;   /* element index (t*B + b)*d + c */
+    float drop_p_v; uint32_t drop_site_v;
+    void* khat; void* vhat; int ld;         /* forward outputs */
+    float* mean_k; float* rstd_k; float* mean_v; float* rstd_v;   /* written by the forward, read by the backward */
+    const float* gk; const float* gv;       /* backward inputs */
+    float* dxk; float* dxv;                 /* backward outputs */
+} bpm_kv_source_problem;
+int bpm_kv_source_fwd(int dtype, const bpm_kv_source_problem* probs, int n, const float* table, int table_rows, int d,
+                      float scale, float eps, uint64_t seed, void* stream);
+int bpm_kv_source_bwd(const bpm_kv_source_problem* probs, int n, const float* table, int table_rows, int d, float scale,
+                      uint64_t seed, void* stream);
+
 /* LayerNorm (nn.LayerNorm(d), eps inside sqrt; transformer.py:91,153,167-172,
  * 183-185,227-229).  x fp32 [R,d].  Forward writes CT [R, ldo] with zero pad
  * columns, or plain fp32 [R, ldo] when out_f32; saves mean / rstd [R].

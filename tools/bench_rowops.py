@@ -3,6 +3,9 @@
 
 --streaming: the pure streaming kernels at the headline step's shapes (hidden 768) against ln_fwd in the same run --
 unfold_grads over six descriptors of 1536 x 768, embed_pos forward / backward and ln_fwd over six problems of 4096 x 768;
+--kv-source: the key / value sources of the six encoders of a level at the headline step's shape (twelve K / V problems
+of 4096 x 768, bf16): the four launches embed_pos_fwd -> ln_fwd (hat) and ln_bwd (hat) -> embed_pos_bwd (+ add_n of the
+two gradients) against bpm_kv_source_fwd / _bwd, with ln_fwd over the same twelve problems as the yardstick;
 --json PATH writes {case: {"us", "GBps"}} (BPMULT_LIB selects the library, so two builds can alternate on one box)."""
 import argparse
 import json
@@ -22,6 +25,7 @@ def main():
     ap.add_argument("--G", type=int, default=6)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--streaming", action="store_true", help="only the streaming cases at hidden 768")
+    ap.add_argument("--kv-source", action="store_true", help="only the key / value source cases at hidden 768")
     ap.add_argument("--json", default=None, help="write the results to this file")
     a = ap.parse_args()
     import bpmult_amd  # noqa: F401
@@ -52,8 +56,8 @@ def main():
 
     results = {}
     keep = []
-    if a.streaming:
-        streaming_cases(ops, timeit, a.G)
+    if a.streaming or a.kv_source:
+        (kv_source_cases if a.kv_source else streaming_cases)(ops, timeit, a.G)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(results, f, indent=1)
@@ -156,6 +160,58 @@ def streaming_cases(ops, timeit, G, R=4096, d=768):
         ps.append(ops.ln_problem(t[0], t[1], t[2], t[3], t[4], R, out=t[5], ldo=ld))
     arr = ops.array(ops.LnProblem, ps)
     timeit(f"ln_fwd x{G} {R}x{d}", lambda: ops.ln_fwd(BPM_BF16, arr, d), G * (R * d * 4 + R * ld * 2))
+
+
+def kv_source_cases(ops, timeit, G, S=512, B=8, d=768):
+    """Bytes are algorithmic, in units of one fp32 [S B, d] tensor (Rb): the two-kernel route moves 7 Rb forward (source
+    twice, ke / ve written and read, khat / vhat as bf16) and 10 Rb backward (+ 2 Rb read and 1 Rb written by add_n); the
+    fused launches 2 Rb forward and 4 Rb backward (source, Gk, Gv, one summed gradient; 5 Rb with separate gradients)."""
+    from bpmult_amd.ops import BPM_BF16, pad32
+    dev = "cuda"
+    rn = lambda *s: torch.randn(*s, device=dev)
+    R, ld, scale, p = S * B, pad32(d), d ** 0.5, 0.25
+    Rb = R * d * 4
+    table = rn(S + 2, d)
+    ones, zeros = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
+    keep, emb, hat, hat_b, emb_b, add, kv, kvm, yard = [], [], [], [], [], [], [], [], []
+    for k in range(G):
+        x, gk, gv = rn(S, B, d), rn(R, d), rn(R, d)
+        t = dict(ke=z(R, d), ve=z(R, d), dke=z(R, d), dve=z(R, d), khat=z(R, ld, dt=torch.bfloat16), vhat=z(R, ld, dt=torch.bfloat16),
+                 dxk=z(S, B, d), dxv=z(S, B, d), dx=z(S, B, d), st=[z(R) for _ in range(4)])
+        keep += [x, gk, gv, t]
+        st = t["st"]
+        emb += [ops.embed_problem(x, t["ke"], S, B, drop_p=p, drop_site=2 * k), ops.embed_problem(x, t["ve"], S, B, drop_p=p, drop_site=2 * k + 1)]
+        hat += [ops.ln_problem(t["ke"], ones, zeros, st[0], st[1], R, out=t["khat"], ldo=ld),
+                ops.ln_problem(t["ve"], ones, zeros, st[2], st[3], R, out=t["vhat"], ldo=ld)]
+        hat_b += [ops.ln_problem(t["ke"], ones, None, st[0], st[1], R, dy=gk, ldy=d, dx=t["dke"]),
+                  ops.ln_problem(t["ve"], ones, None, st[2], st[3], R, dy=gv, ldy=d, dx=t["dve"])]
+        emb_b += [ops.embed_problem(t["dke"], t["dxk"], S, B, drop_p=p, drop_site=2 * k),
+                  ops.embed_problem(t["dve"], t["dxv"], S, B, drop_p=p, drop_site=2 * k + 1)]
+        add.append(ops.addn_problem(t["dx"], [t["dxk"], t["dxv"]]))
+        kw = dict(khat=t["khat"], vhat=t["vhat"], ld=ld, stats_k=(st[0], st[1]), stats_v=(st[2], st[3]), gk=gk, gv=gv, drop_p=p,
+                  drop_site_k=2 * k, drop_site_v=2 * k + 1)
+        kv.append(ops.kv_source_problem(x, x, S, B, dxk=t["dxk"], dxv=t["dxv"], **kw))
+        kvm.append(ops.kv_source_problem(x, x, S, B, dxk=t["dx"], dxv=None, **kw))
+    emb, emb_b = ops.array(ops.EmbedProblem, emb), ops.array(ops.EmbedProblem, emb_b)
+    hat, hat_b = ops.array(ops.LnProblem, hat), ops.array(ops.LnProblem, hat_b)
+    add = ops.array(ops._lib.AddnProblem, add)
+    kv, kvm = ops.array(ops.KvSourceProblem, kv), ops.array(ops.KvSourceProblem, kvm)
+    n = 2 * G
+    timeit(f"embed_pos_fwd x{n} {R}x{d}", lambda: ops.embed_pos_fwd(emb, table, d, scale, seed=1), G * 4 * Rb)
+    timeit(f"ln_fwd (hat) x{n}", lambda: ops.ln_fwd(BPM_BF16, hat, d), G * 3 * Rb)
+    timeit(f"ln_bwd (hat) x{n}", lambda: ops.ln_bwd(hat_b, d, BPM_BF16, 1), G * 6 * Rb)
+    timeit(f"embed_pos_bwd x{n}", lambda: ops.embed_pos_bwd(emb_b, d, scale, seed=1), G * 4 * Rb)
+    timeit(f"add_n x{G} (dxk + dxv)", lambda: ops.add_n(add), G * 3 * Rb)
+    timeit(f"kv_source_fwd x{G}", lambda: ops.kv_source_fwd(BPM_BF16, kv, table, d, scale, seed=1), G * 2 * Rb)
+    timeit(f"kv_source_bwd x{G} separate", lambda: ops.kv_source_bwd(kv, table, d, scale, seed=1), G * 5 * Rb)
+    timeit(f"kv_source_bwd x{G} merged", lambda: ops.kv_source_bwd(kvm, table, d, scale, seed=1), G * 4 * Rb)
+    for _ in range(n):
+        t = [rn(R, d), rn(d), rn(d), rn(R), rn(R), torch.zeros(R, ld, device=dev, dtype=torch.bfloat16)]
+        keep.append(t)
+        yard.append(ops.ln_problem(t[0], t[1], t[2], t[3], t[4], R, out=t[5], ldo=ld))
+    yard = ops.array(ops.LnProblem, yard)
+    timeit(f"ln_fwd x{n} {R}x{d} (yardstick)", lambda: ops.ln_fwd(BPM_BF16, yard, d), n * (Rb + R * ld * 2))
 
 
 if __name__ == "__main__":
