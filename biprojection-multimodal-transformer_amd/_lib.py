@@ -17,7 +17,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BPMULT_LIB", os.path.join(_HERE, "libbpmult_hip.so"))   # override: kernel-variant experiments
-SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "bert_embed.hip", "loss.hip", "tail.hip", "frontend.hip", "prof.hip")
+SOURCES = ("gemm.hip", "attention.hip", "rowops.hip", "bert_embed.hip", "loss.hip", "eval.hip", "tail.hip", "frontend.hip", "prof.hip")
 HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
@@ -42,6 +42,7 @@ ADAM_MAX_GROUPS = 16             # == BPM_ADAM_MAX_GROUPS
 ADAM_MAX_SETS, ADAM_SET_SHIFT = 4, 8         # == BPM_ADAM_MAX_SETS, BPM_ADAM_SET_SHIFT
 LOSS_BCE, LOSS_CE, LOSS_L1 = 0, 1, 2              # BPM_LOSS_* kinds
 LOSS_MEAN, LOSS_SUM, LOSS_NONE = 0, 1, 2          # BPM_LOSS_* reductions
+EVAL_MULTILABEL, EVAL_REGRESSION, EVAL_CLASSES = 0, 1, 2      # BPM_EVAL_* kinds
 
 
 def build(force: bool = False, verbose: bool = False, out: str | None = None, flags: tuple = (), objdir: str | None = None) -> str:
@@ -222,6 +223,16 @@ class LossDesc(C.Structure):
                 ("bad", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
 
 
+class EvalDesc(C.Structure):
+    _fields_ = [("kind", C.c_int), ("C", C.c_int), ("capacity", C.c_int), ("max_batches", C.c_int),
+                ("score", C.c_void_p), ("predict", C.c_void_p), ("raw", C.c_void_p), ("target", C.c_void_p),
+                ("pred", C.c_void_p), ("label", C.c_void_p), ("losses", C.c_void_p), ("bad", C.c_void_p),
+                ("logits", C.c_void_p), ("ld", C.c_int), ("targets", C.c_void_p), ("ldt", C.c_int), ("loss", C.c_void_p),
+                ("B", C.c_int), ("n0", C.c_int), ("batch_index", C.c_int),
+                ("N", C.c_int), ("nbatches", C.c_int), ("result", C.c_void_p), ("counts", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 class SplitProblem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("R", C.c_int), ("C", C.c_int), ("ld", C.c_int), ("ldp", C.c_int)]
 
@@ -351,6 +362,9 @@ SIGNATURES = {
     "bpm_loss_ws_bytes": [_I, _I, _I, _I],
     "bpm_loss_fwd": [C.POINTER(LossDesc), _P],
     "bpm_loss_bwd": [C.POINTER(LossDesc), _P, _I, _P, _I, _P],
+    "bpm_eval_ws_bytes": [_I, _I, _I],
+    "bpm_eval_update": [C.POINTER(EvalDesc), _P],
+    "bpm_eval_finalize": [C.POINTER(EvalDesc), _P],
     "bpm_stream_create": [_I, C.POINTER(C.c_void_p)],
     "bpm_stream_priority_range": [C.POINTER(_I), C.POINTER(_I)],
     "bpm_prof_enable": [C.c_uint],

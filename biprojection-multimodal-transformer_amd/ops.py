@@ -817,6 +817,58 @@ def loss_bwd(prob, g, dlogits, *, ldg: Optional[int] = None, lddl: Optional[int]
                                        prob.C if lddl is None else lddl, _stream()), "bpm_loss_bwd")
 
 
+def eval_ws_bytes(kind: int, capacity: int, Cn: int) -> int:
+    return int(_lib.lib().bpm_eval_ws_bytes(kind, capacity, Cn))
+
+
+def _bytes(t, what):
+    if t is not None and not isinstance(t, int) and t.dtype != torch.uint8:
+        raise ValueError(f"{what}: expected uint8, got {t.dtype}")
+    return _p(t)
+
+
+def eval_desc(kind: int, Cn: int, capacity: int, *, max_batches: int = 0, score=None, predict=None, raw=None, target=None,
+              pred=None, label=None, losses=None, bad=None, result=None, counts=None, ws=None) -> "_lib.EvalDesc":
+    """The store and outputs of bpm_eval_update / bpm_eval_finalize (include/bpmult_hip.h): fp32 score / predict / raw /
+    target, uint8 pred / label, fp32 losses [max_batches], the int32 counter `bad`, fp64 result, int64 counts, ws: any
+    tensor of at least eval_ws_bytes(...) bytes.  The per-call fields are set by eval_update / eval_finalize."""
+    p = _lib.EvalDesc()
+    p.kind, p.C, p.capacity, p.max_batches = kind, Cn, capacity, max_batches
+    p.score, p.predict, p.raw = _f32(score, "eval.score"), _f32(predict, "eval.predict"), _f32(raw, "eval.raw")
+    p.target, p.losses = _f32(target, "eval.target"), _f32(losses, "eval.losses")
+    p.pred, p.label = _bytes(pred, "eval.pred"), _bytes(label, "eval.label")
+    if bad is not None and not isinstance(bad, int) and (bad.dtype != torch.int32 or bad.numel() < 1):
+        raise ValueError("eval.bad: an int32 device counter")
+    p.bad = _p(bad)
+    if result is not None and not isinstance(result, int) and result.dtype != torch.float64:
+        raise ValueError(f"eval.result: expected float64, got {result.dtype}")
+    if counts is not None and not isinstance(counts, int) and counts.dtype != torch.int64:
+        raise ValueError(f"eval.counts: expected int64, got {counts.dtype}")
+    p.result, p.counts = _p(result), _p(counts)
+    p.ws, p.ws_bytes = _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
+    return p
+
+
+def eval_update(desc, logits, targets, B: int, n0: int, *, ld: Optional[int] = None, ldt: Optional[int] = None, loss=None,
+                batch_index: int = 0) -> None:
+    """Append rows [n0, n0 + B): logits fp32 [B, ld], targets fp32 [B, ldt] (multilabel), fp32 [B] (regression) or int64 [B]
+    (classes); loss: a device fp32 scalar copied to losses[batch_index].  One launch, no host read."""
+    desc.logits, desc.ld = _f32(logits, "eval.logits"), desc.C if ld is None else ld
+    if desc.kind == _lib.EVAL_CLASSES:
+        if targets is not None and not isinstance(targets, int) and targets.dtype != torch.int64:
+            raise ValueError(f"eval.targets: class indices are int64, got {targets.dtype}")
+        desc.targets, desc.ldt = _p(targets), 0
+    else:
+        desc.targets, desc.ldt = _f32(targets, "eval.targets"), desc.C if ldt is None else ldt
+    desc.loss, desc.B, desc.n0, desc.batch_index = _f32(loss, "eval.loss"), B, n0, batch_index
+    _lib.check(_lib.lib().bpm_eval_update(C.byref(desc), _stream()), "bpm_eval_update")
+
+
+def eval_finalize(desc, N: int, nbatches: int) -> None:
+    desc.N, desc.nbatches = N, nbatches
+    _lib.check(_lib.lib().bpm_eval_finalize(C.byref(desc), _stream()), "bpm_eval_finalize")
+
+
 def addn_problem(out, ins) -> "_lib.AddnProblem":
     """out = sum(ins): contiguous fp32 tensors of one size (16-byte aligned); out may be one of them."""
     p = _lib.AddnProblem()

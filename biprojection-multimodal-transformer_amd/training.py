@@ -1,6 +1,7 @@
 """Training-loop plumbing around the hot path, mirroring the reference's train.py so that a run can swap the model in
-unchanged.  Data loading and metrics stay the caller's (out of scope): the loop takes an iterable
-of batches, a `forward_loss(model, batch)` callable and an `evaluate(model)` callable that returns the tuning metric.
+unchanged.  Data loading stays the caller's (out of scope): the loop takes an iterable
+of batches, a `forward_loss(model, batch)` callable and an `evaluate(model)` callable that returns the tuning metric
+(`make_evaluate` builds one over `model_eval`, the reference's evaluation on the HIP path).
 
 Reference behaviour reproduced (file:line in /root/reference/bpmult):
 * checkpoints: `save_checkpoint(state, is_best, path)` writes `checkpoint.pt` and copies it to `model_best.pt`
@@ -16,6 +17,7 @@ Reference behaviour reproduced (file:line in /root/reference/bpmult):
 * the five-seed outer loop `for i in range(from_seed, 6)` with `inverse_seed` (train.py:490-503).
 * the criterion: `get_criterion(args)` (train.py:99-120), torch's modules or, with `args.criterion = "hip"`, their
   subclasses in losses.py.
+* evaluation: `model_eval` (train.py:165-280) with the reference's dict per task, over metrics.Evaluator.
 """
 from __future__ import annotations
 
@@ -199,3 +201,106 @@ def model_forward(model, criterion, batch, model_name: str, gmu_gate: bool = Fal
     tgt = tgt.to(dev)
     loss = criterion(out, tgt)
     return (loss, out, tgt, gates) if gmu_gate else (loss, out, tgt)
+
+
+# ----------------------------------------------------------------------------
+# evaluation (train.py:165-280) over metrics.Evaluator: one host read per evaluation
+# ----------------------------------------------------------------------------
+def eval_kind(args) -> str:
+    """The metrics.Evaluator kind of a task: BCE tasks are "multilabel", cmu-mosi is "regression", the other
+    cross-entropy tasks are "classes"."""
+    if args.task_type == "multilabel":
+        if args.task == "cmu-mosi":
+            raise ValueError("task: cmu-mosi with task_type 'multilabel' is not evaluated here (the reference builds its targets "
+                             "with a tensordot over 101 bins, train.py:324-326, which this library does not)")
+        return "multilabel"
+    return "regression" if args.task == "cmu-mosi" else "classes"
+
+
+def arrange_metrics(args, m: dict) -> dict:
+    """Evaluator.compute()'s primitives -> the reference's dict, with the reference's keys per task, mislabelled ones
+    included: under mmimdb `micro_f1` holds the micro average precision and `auc_pr_macro` the weighted F1
+    (train.py:206-211); under cmu-mosei `wacc_emos` holds the micro average precision and `auc_pr_micro` the mean weighted
+    accuracy (train.py:254-255); in the else-branch `weight_f1` is the mean absolute error (train.py:270).
+
+    Departures: a multilabel task for which the reference has no branch (iemocap: its model_eval returns the loss alone
+    and train() then fails on the missing tuning metric) gets the cmu-mosei form over its C classes; the cross-entropy
+    tasks also get `acc` (argmax == target); the argmax is taken over the logits, not over their fp32 softmax."""
+    out = {"loss": m["loss"]}
+    if args.task_type == "multilabel":
+        eval_kind(args)
+        f1, ap = m["f1"], m["ap"]
+        if args.task == "moviescope":
+            out.update(macro_f1=f1["macro"], micro_f1=f1["micro"], auc_pr_macro=ap["macro"], auc_pr_micro=ap["micro"],
+                       auc_pr_samples=ap["samples"])
+        elif args.task == "mmimdb":
+            out.update(macro_f1=f1["macro"], micro_f1=ap["micro"], auc_pr_macro=f1["weighted"], auc_pr_micro=f1["micro"],
+                       auc_pr_samples=f1["samples"])
+        elif args.task == "counseling":
+            if len(m["wf1"]) != 2:
+                raise ValueError(f"n_classes: counseling is evaluated over exactly 2 classes, got {len(m['wf1'])}")
+            out.update(f1_low=float(m["wf1"][1]), f1_high=float(m["wf1"][0]), acc=m["subset_accuracy"], auc_pr_micro=ap["micro"])
+        else:
+            n = len(m["wf1"])
+            if args.task == "cmu-mosei" and n != 6:
+                raise ValueError(f"n_classes: cmu-mosei is evaluated over exactly 6 classes, got {n}")
+            for i in range(n):
+                out[f"f1_emo{i + 1}"] = float(m["wf1"][i])
+            for i in range(n):
+                out[f"wacc_emo{i + 1}"] = float(m["wacc"][i])
+            out["f1_emos"] = float(sum(m["wf1"]) / n)
+            out["wacc_emos"] = ap["micro"]
+            out["auc_pr_micro"] = float(sum(m["wacc"]) / n)
+        return out
+    out.update(mae=m["mae"], corr=m["corr"], accuracy_7=m["accuracy_7"], weighted_f1=m["weighted_f1"], weight_f1=m["mae"])
+    if args.task != "cmu-mosi":
+        out["acc"] = m["acc"]
+    return out
+
+
+def model_eval(model, criterion, batches, args, evaluator=None, output_gates: bool = False) -> dict:
+    """The reference's model_eval (train.py:165-280) over model_forward and metrics.Evaluator: every batch is appended on
+    the device (no loss.item(), no .cpu()), the metrics are computed there, and one buffer is read at the end.  Returns
+    arrange_metrics' dict.  args: task, task_type, model, n_classes.  evaluator: a metrics.Evaluator to reuse (it is
+    reset); without one, a store for exactly these batches is made.  With output_gates the GMU gates are kept in the
+    evaluator (Evaluator.predictions()).  cmu-mosi: the logits [B, 1] are squeezed before the criterion, as
+    train.py:330 does."""
+    from .metrics import Evaluator
+    kind = eval_kind(args)
+    crit = criterion if kind != "regression" else (lambda out, tgt: criterion(out.squeeze(1) if out.dim() == 2 else out, tgt))
+    if evaluator is None:
+        batches = list(batches)
+        rows = sum(int(b[0].shape[0]) for b in batches)
+        dev = next(model.parameters()).device
+        evaluator = Evaluator(kind, 1 if kind == "regression" else int(args.n_classes), max(rows, 1), max(len(batches), 1), device=dev)
+    else:
+        evaluator.reset()
+    with torch.no_grad():
+        for batch in batches:
+            r = model_forward(model, crit, batch, args.model, gmu_gate=output_gates)
+            loss, out, tgt = r[0], r[1], r[2]
+            evaluator.update(out, tgt, loss, r[3] if output_gates else None)
+    return arrange_metrics(args, evaluator.compute())
+
+
+def make_evaluate(criterion, batches_fn: Callable[[], Iterable], args, key: str) -> Callable:
+    """The `evaluate` callable of fit(): evaluate(model) runs model_eval over batches_fn() and returns metrics[key]
+    (the reference tunes on "auc_pr_micro" for multilabel tasks and "weight_f1" otherwise, train.py:405-407).  One
+    Evaluator is made at the first call, sized by that epoch's batches, and reused; `evaluate.metrics` keeps the last
+    dict."""
+    state = {"evaluator": None}
+
+    def evaluate(model):
+        from .metrics import Evaluator
+        batches = batches_fn()
+        if state["evaluator"] is None:
+            batches = list(batches)
+            kind = eval_kind(args)
+            rows = sum(int(b[0].shape[0]) for b in batches)
+            state["evaluator"] = Evaluator(kind, 1 if kind == "regression" else int(args.n_classes), max(rows, 1),
+                                           max(len(batches), 1), device=next(model.parameters()).device)
+        evaluate.metrics = model_eval(model, criterion, batches, args, evaluator=state["evaluator"])
+        return evaluate.metrics[key]
+
+    evaluate.metrics = None
+    return evaluate

@@ -694,6 +694,80 @@ size_t bpm_loss_ws_bytes(int kind, int reduction, int B, int C);
 int bpm_loss_fwd(const bpm_loss_desc* d, void* stream);
 int bpm_loss_bwd(const bpm_loss_desc* d, const float* g, int ldg, float* dlogits, int lddl, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Evaluation of an epoch.  Replaces model_eval and weighted_acc (train.py:138-280): torch.sigmoid / softmax().argmax, the
+ * loss.item() and three .cpu() copies of every batch, and scikit-learn's f1_score / accuracy_score /
+ * average_precision_score at the end.  bpm_eval_update appends one batch to a store that the caller owns, in ONE launch
+ * with no reduction and no host read; bpm_eval_finalize reduces the N stored rows to int64 counts and fp64 sums (five
+ * launches and a memset for BPM_EVAL_MULTILABEL, two otherwise); the caller reads `result` and `counts` once.  Elements
+ * are carried in fp64 and rounded once, floating-point sums are fp64 through one fixed tree, everything else is combined
+ * in integers: no float atomics, two runs give identical bits.
+ *
+ * The store (rows [0, capacity), all allocated by the caller; only what the kind uses need be non-NULL):
+ *   BPM_EVAL_MULTILABEL  logits fp32 [B, ld >= C], targets fp32 [B, ldt >= C].  score [cap, C] = (float) sigmoid((double) x);
+ *                        pred [cap, C] bytes = score > 0.5f, compared ON THE FP32 SCORE as torch.sigmoid(out) > 0.5 is
+ *                        (x = 0 and x = 1e-9 predict 0, x = 1e-6 predicts 1); label [cap, C] bytes = target == 1.  A target
+ *                        that is neither 0 nor 1 is stored as label 0 and adds one to *bad.
+ *   BPM_EVAL_REGRESSION  (cmu-mosi) C = 1: logits [B, ld >= 1], targets fp32 [B].  score [cap] = (float) sigmoid(x),
+ *                        predict [cap] = score * 6 - 3 in two separately rounded fp32 operations (what numpy does to a
+ *                        float32 array at train.py:261), raw [cap] = x, target [cap].
+ *   BPM_EVAL_CLASSES     logits [B, ld >= C], targets int64 [B].  predict [cap] = argmax_c x[b, c] as fp32, the FIRST index
+ *                        on ties; target [cap] as fp32; label [cap] bytes = 1 when the row takes part.  A class index
+ *                        outside [0, C) is compared BEFORE any use, adds one to *bad, and its row is excluded from every
+ *                        count and sum.  (The reference takes the argmax of the fp32 softmax, which can tie where the
+ *                        logits do not: a departure.)
+ * bad: int32 device counter (one vector atomic add per block; NULL = not counted), no device assert, no sync.
+ * bpm_eval_update: rows [n0, n0 + B) are written (n0 is known to the host from shapes); when `loss` (device pointer to
+ * one fp32, the batch's criterion) is given, it is copied to losses[batch_index].
+ *
+ * bpm_eval_finalize over rows [0, N) and losses [0, nbatches):   result[0] = mean of the batch losses (NaN for none).
+ *   BPM_EVAL_MULTILABEL  result (C + 4 doubles): [1 + c] average precision of class c, [1 + C] micro (all N C elements as
+ *                        one list), [2 + C] samples (mean over the rows of the row's own list), [3 + C] mean over the rows
+ *                        of F1 = 2 |y & p| / (|y| + |p|) (0 when both are empty).
+ *                        counts (4 C + 1 int64): [4 c + 0..3] tp, fp, fn, tn of class c; [4 C] rows with every class right.
+ *                        AP = (1 / P) sum_{i : y_i = 1} TP>=(s_i) / N>=(s_i), N>=(s) the elements of the list with score
+ *                        >= s and TP>=(s) the positives among them: scikit-learn's -sum dR P over distinct thresholds,
+ *                        ties included (the k positives tied at a threshold each add that threshold's precision).  A
+ *                        list without a positive gives 0.  Cost O(n^2) integer compares per list of n, no sort.
+ *   other kinds          result (7 doubles): [1] sum |p - t|, [2] sum p, [3] sum t, [4] sum p p, [5] sum t t, [6] sum p t,
+ *                        p = predict (BPM_EVAL_CLASSES: argmax * 6 - 3, exact), t = target.
+ *                        counts (8 int64): [0] rintf(p) == rintf(t) (round-half-even, as np.round); over the rows with
+ *                        t != 0 the 2 x 2 of p > 0 against t > 0: [1] both, [2] p only, [3] t only, [4] neither;
+ *                        [5] argmax == t (BPM_EVAL_CLASSES) / predict == t; [6] rows that take part; [7] rows with t != 0.
+ * ws: bpm_eval_ws_bytes(kind, capacity, C) bytes (0 for arguments it does not accept), 8-byte aligned, private to the
+ * stream for the call; its contents do not matter before or after.
+ * BPM_ERR_ARG (nothing launched): NULL desc or a NULL pointer that the kind uses, B < 1, C < 1 (C != 1 for
+ * BPM_EVAL_REGRESSION), capacity < 1, n0 < 0, n0 + B > capacity, ld < C, ldt < C (BPM_EVAL_MULTILABEL), a loss with
+ * batch_index outside [0, max_batches), an unknown kind, capacity * C >= 2^31 (BPM_EVAL_MULTILABEL); finalize: N outside
+ * [1, capacity], nbatches outside [0, max_batches], NULL result / counts, a workspace that is NULL or too small.
+ * BPM_ERR_ALIGN: pointers not 4-byte (int64 targets, result, counts, ws: 8-byte) aligned. */
+enum { BPM_EVAL_MULTILABEL = 0, BPM_EVAL_REGRESSION = 1, BPM_EVAL_CLASSES = 2 };
+typedef struct bpm_eval_desc {
+    int kind;               /* BPM_EVAL_* */
+    int C, capacity, max_batches;
+    float* score;
+    float* predict;
+    float* raw;
+    float* target;
+    unsigned char* pred;
+    unsigned char* label;
+    float* losses;          /* [max_batches], optional */
+    int* bad;               /* optional */
+    /* bpm_eval_update */
+    const float* logits; int ld;
+    const void* targets; int ldt;
+    const float* loss;      /* optional */
+    int B, n0, batch_index;
+    /* bpm_eval_finalize */
+    int N, nbatches;
+    double* result;
+    int64_t* counts;
+    void* ws; size_t ws_bytes;
+} bpm_eval_desc;
+size_t bpm_eval_ws_bytes(int kind, int capacity, int C);
+int bpm_eval_update(const bpm_eval_desc* d, void* stream);
+int bpm_eval_finalize(const bpm_eval_desc* d, void* stream);
+
 /* Engine plumbing (no reference counterpart): a non-blocking HIP stream at the device's lowest priority
  * (low_priority != 0) or at the default priority.  The host engine puts weight-gradient GEMMs and the
  * key/value-side chain there so that the dispatcher serves the critical-path stream first. */
