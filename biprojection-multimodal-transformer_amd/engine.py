@@ -93,7 +93,6 @@ class ParamStore:
     ALIGN = 64  # elements
 
     def __init__(self, named_params: Sequence[Tuple[str, torch.nn.Parameter]], dtype: int, x3: bool = False):
-        self._x3_range = None                           # (first: __del__ reads it even when the constructor raises)
         self._dirty, self._dirty_rest, self._shadow_sig = True, False, None
         self._zero_table = None                         # built by set_store_written()
         self.dtype = dtype
@@ -105,6 +104,7 @@ class ParamStore:
         if dev.type != "cuda" and not ops._DRY_RUN:
             raise RuntimeError("BPMulT hot path: parameters must live on a CUDA (HIP) device; there is no CPU path")
         self.device = dev
+        self.x3_cache = ops.X3Cache(dev) if self.x3 else None       # split images of the weight shadows: they go with the store
         self.off: Dict[str, int] = {}
         total = 0
         for n, p in named_params:
@@ -131,13 +131,6 @@ class ParamStore:
         self._norm_table = None                         # built by the first grad_sumsq()
         self._norm_set = None                           # (names, table, workspace, result) of the first grad_sumsq(names=...)
         self._master_ptr = self.master.data_ptr()
-
-    def __del__(self):
-        if self._x3_range is not None:
-            try:
-                ops.x3_drop_static(*self._x3_range)
-            except Exception:              # noqa: BLE001 -- interpreter shutdown
-                pass
 
     # -- masters / grads ------------------------------------------------------
     def p(self, name: str) -> torch.Tensor:
@@ -247,8 +240,7 @@ class ParamStore:
         self.shadow_flat = torch.zeros(max(self._shadow_total, 32), device=self.device, dtype=ct)
         if self.x3:                                    # the weight shadows are the static operands of the bf16x3 products
             a = self.shadow_flat.data_ptr()
-            self._x3_range = (a, a + self.shadow_flat.numel() * self.shadow_flat.element_size())
-            ops.x3_register_static(*self._x3_range)
+            self.x3_cache.add_static(a, a + self.shadow_flat.numel() * self.shadow_flat.element_size())
         self._table = self._pack_table(self._shadow_specs)
         self._build_adam_table()
         self.fold_flat = torch.zeros(max(self._fold_total, 64), device=self.device, dtype=torch.float32)
@@ -481,7 +473,7 @@ class ParamStore:
         if self._fold_table is not None:
             ops.fold_bias(self._fold_table, self._nfold, self._fold_blk)
         if self.x3:
-            ops.x3_refresh_static()                # split images of the shadows that just changed (outside any graph)
+            self.x3_cache.refresh_static()         # split images of the shadows that just changed (outside any graph)
 
 
 def adam_sets_table(stores: Sequence[ParamStore], group_ofs: Sequence[Dict[str, int]]):
@@ -621,8 +613,11 @@ class EncoderGroupPlan:
     The per-block builders below (_ln0_* / _self_attn_* / _cross_attn_* / _ffn_*) append one encoder's problems of one
     layer to that layer's launch lists; _build_fwd / _build_bwd wire their operands and order the launches per kind."""
 
-    def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int):
+    def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int, x3: "Optional[ops.X3Cache]" = None):
         self.store, self.cfg, self.encs, self.B = store, cfg, list(encs), B
+        # bf16x3 mode: the owner of the activations' split images -- the caller's (a trunk shares one between its plans), or
+        # this plan's own (a stand-alone encoder); the weight shadows' images stay with the store
+        self.x3 = x3 if x3 is not None or not store.x3 else ops.X3Cache(store.device, weights=store.x3_cache)
         self.dtype = store.dtype
         d, H = cfg.d, cfg.H
         if d % H:
@@ -833,7 +828,7 @@ class EncoderGroupPlan:
         for p in probs:
             p.flags |= F_KPAD | (F_BACKGROUND if background else 0)
         arr = ops.array(GemmProblem, probs)
-        arr.x3 = self.store.x3                       # bf16x3 mode: ops.gemm_grouped splits the operands of eligible launches
+        arr.x3 = self.x3                             # bf16x3 mode: ops.gemm_grouped splits the operands of eligible launches
         # ... except operands whose split image an earlier launch of the same step has left: the forward activations a
         # weight gradient reads again, and gradients the main stream's data-gradient product of this layer has just split
         arr.x3_presplit = frozenset(t.data_ptr() for t in presplit)

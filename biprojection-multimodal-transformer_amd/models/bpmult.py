@@ -268,8 +268,10 @@ class _Trunk(GraphCache):
         else:
             e2 = [EncoderDesc(n + ".", ENC_ORDER.index(n), self.N[q], self.N[LEVEL1[src][0]], adrop[key])
                   for n, (q, src, key) in LEVEL2.items()]
-        self.plan1 = EncoderGroupPlan(st, cfg1, e1, B)
-        self.plan2 = EncoderGroupPlan(st, cfg2, e2, B)
+        # bf16x3 mode: the split images of this trunk's activations live and go with it (the weight shadows' with the store)
+        self.x3 = ops.X3Cache(dev, weights=st.x3_cache) if st.x3 else None
+        self.plan1 = EncoderGroupPlan(st, cfg1, e1, B, x3=self.x3)
+        self.plan2 = EncoderGroupPlan(st, cfg2, e2, B, x3=self.x3)
         self.out1 = {n: b["out"] for n, b in zip(LEVEL1, self.plan1.buf)}
         self.out2 = {n: b["out"] for n, b in zip(LEVEL2, self.plan2.buf)}
         self.d1buf = {n: z(self.N[q], B, d) for n, (q, _, _) in LEVEL1.items()}   # d(level-1 outputs)
@@ -351,7 +353,7 @@ class _Trunk(GraphCache):
             ops.pack_rows_fwd(BPM_F32, packs_f32, seed)
         if packs_ct:
             ops.pack_rows_fwd(self.dtype, packs_ct, seed)
-            ops.gemm_grouped(self.dtype, GEMM_NT, gemms, seed, x3=st.x3)
+            ops.gemm_grouped(self.dtype, GEMM_NT, gemms, seed, x3=self.x3)
 
     def conv_backward(self, seed: int, need_dx: Dict[str, bool]) -> Dict[str, Optional[torch.Tensor]]:
         """Consumes dpx[m]; accumulates proj_m.weight gradients; returns d(feats[m]) where requested."""
@@ -376,9 +378,9 @@ class _Trunk(GraphCache):
                 unpack.append(ops.pack_problem(B, T, od, 0, g=c["dpk"], ldg=od, dsrc=res[k], drop_p=c["p"], drop_site=SITE_TEXT))
         if casts:
             ops.rows_cast(self.dtype, casts, seed)
-            ops.gemm_grouped(self.dtype, GEMM_TN, wg, seed, x3=st.x3)
+            ops.gemm_grouped(self.dtype, GEMM_TN, wg, seed, x3=self.x3)
         if dg:
-            ops.gemm_grouped(self.dtype, GEMM_NN, dg, seed, x3=st.x3)
+            ops.gemm_grouped(self.dtype, GEMM_NN, dg, seed, x3=self.x3)
         if unpack:
             ops.pack_rows_bwd(unpack, seed)
         return res
@@ -473,7 +475,7 @@ class _Trunk(GraphCache):
         self._gmu_fwd = (A(CastProblem, casts), A(GemmProblem, gemms), A(GmuProblem, gates))
         self._gmu_bwd = (A(GmuProblem, bw_gate), A(GemmProblem, bw_wg), A(GemmProblem, bw_dg), A(GemmProblem, bw_dg2))
         for arr in (self._gmu_fwd[1],) + self._gmu_bwd[1:]:
-            arr.x3 = st.x3                       # bf16x3 mode: eligible launches run as three split-bf16 products
+            arr.x3 = self.x3                     # bf16x3 mode: eligible launches run as three split-bf16 products
 
     def gmu_forward(self) -> None:
         casts, gemms, gates = self._gmu_fwd
@@ -492,8 +494,8 @@ class _Trunk(GraphCache):
     def forward(self, feats: Dict[str, torch.Tensor], seed: int, training: bool) -> List[torch.Tensor]:
         """The caller has refreshed the weight shadows (ParamStore.refresh_shadows: a host-side decision, so it stays
         outside a captured graph)."""
-        if self.st.x3:
-            ops.x3_new_step()                        # bf16x3: split images of earlier passes are stale from here on
+        if self.x3 is not None:
+            self.x3.new_step()                       # bf16x3: split images of earlier passes are stale from here on
         self.conv_forward(feats, seed, training)
         px = self.px
         q1 = [px[q] for (q, kv, _) in LEVEL1.values()]

@@ -64,9 +64,8 @@ class _EncoderFn(torch.autograd.Function):
         """x_k / x_v None: the self-attention stack (the encoder's self-only plan; its only input is x_q)."""
         plan = enc._plan_for(x_q, x_k)
         enc._store.refresh_shadows()
-        if enc._store.x3:
-            from .. import ops
-            ops.x3_new_step()
+        if plan.x3 is not None:
+            plan.x3.new_step()
         kv = ([None], [None]) if x_k is None else ([x_k.detach().contiguous()], [x_v.detach().contiguous()])
         out = plan.forward([x_q.detach().contiguous()], *kv, enc._next_seed(), enc.training)[0]
         ctx.enc, ctx.plan = enc, plan

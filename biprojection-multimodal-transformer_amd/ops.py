@@ -114,16 +114,19 @@ def gemm_problem(A, B, Cc, M: int, N: int, K: int, lda: int, ldb: int, ldc: int,
     return p
 
 
-def gemm_grouped(dtype: int, variant: int, probs, seed: int = 0, n: Optional[int] = None, x3: bool = False) -> None:
-    """x3 (or an array tagged `.x3 = True` where the launch tables are built): the parity-grade fast mode -- fp32 operands,
-    each product as three bf16 MFMA products of split operands (see _X3Plan); launches the LDS-DMA kernel cannot take
-    run as exact fp32 products."""
+def gemm_grouped(dtype: int, variant: int, probs, seed: int = 0, n: Optional[int] = None, x3: "Optional[X3Cache]" = None) -> None:
+    """x3 (or an array tagged `.x3 = <X3Cache>` where the launch tables are built): the parity-grade fast mode -- fp32
+    operands, each product as three bf16 MFMA products of split operands (see _X3Plan), their split images held by that
+    cache; launches the LDS-DMA kernel cannot take run as exact fp32 products.  None or False: the mode is off."""
     arr = _as_array(GemmProblem, probs)
+    cache = x3 or getattr(arr, "x3", None) or None
+    if cache is not None and not isinstance(cache, X3Cache):
+        raise TypeError(f"x3: an ops.X3Cache (the owner of the split images) or None, got {type(cache).__name__}")
     L, s = _lib.lib(), _stream()
-    if (x3 or getattr(arr, "x3", False)) and dtype == BPM_F32 and variant in _X3_VARIANTS:
+    if cache is not None and dtype == BPM_F32 and variant in _X3_VARIANTS:
         plan = getattr(arr, "_x3_plan", None)
-        if plan is None or plan.n != n:
-            plan = _X3Plan(arr, variant, n)
+        if plan is None or plan.n != n or plan.cache is not cache:
+            plan = _X3Plan(arr, variant, n, cache)
             arr._x3_plan = plan              # tables are replayed every step; lists were turned into a fresh array above
         if plan.ok:
             plan.run(L, variant, _seed(seed), s)
@@ -138,26 +141,10 @@ def gemm_grouped(dtype: int, variant: int, probs, seed: int = 0, n: Optional[int
 # x = hi + lo (hi = bf16(x), lo = bf16(x - hi)); x y ~ hi hi + hi lo + lo hi with f32 accumulation: ~2^-16 relative per
 # product (the lo lo term and the rounding of lo), against 2^-9 for plain bf16 operands.  Every operand of an eligible
 # launch is split by bpm_split_rows into a [rows, hi plane | lo plane] bf16 image (cached per operand view: the buffers
-# of the hot path are static) right before the launch; weight shadows -- operands inside a registered static range -- are
-# split again only after the shadows were refreshed.
+# of the hot path are static) right before the launch; weight shadows -- operands inside a static range of the cache that
+# owns the weights -- are split again only after the shadows were refreshed.
 # lab knob: BPMULT_X3_ONLY=nt,nn restricts the split path to those operand arrangements (bisecting a parity failure)
 _X3_VARIANTS = {{"nt": GEMM_NT, "nn": GEMM_NN, "tn": GEMM_TN}[v] for v in __import__("os").environ.get("BPMULT_X3_ONLY", "nt,nn,tn").split(",") if v}
-_X3_BUFFERS = {}                # (ptr, rows, cols, ld) -> split image
-_X3_STATIC = []                 # [lo, hi) address ranges of operands that only change at a refresh (weight shadows)
-_X3_STATIC_SPLITS = {}          # (ptr, rows, cols, ld) -> SplitProblem of every static operand seen so far
-
-
-def x3_drop_static(lo: int, hi: int) -> None:
-    """A parameter store is gone (its model was moved or deleted): forget its static operands -- their addresses are."""
-    if (lo, hi) in _X3_STATIC:
-        _X3_STATIC.remove((lo, hi))
-    for k in [k for k in _X3_STATIC_SPLITS if lo <= k[0] < hi]:
-        del _X3_STATIC_SPLITS[k]
-
-
-def x3_register_static(lo: int, hi: int) -> None:
-    if (lo, hi) not in _X3_STATIC:
-        _X3_STATIC.append((lo, hi))
 
 
 def _split(L, probs, s) -> None:
@@ -166,20 +153,32 @@ def _split(L, probs, s) -> None:
         _lib.check(L.bpm_split_rows(sub, k, s), "bpm_split_rows")
 
 
-def x3_refresh_static() -> None:
-    """Split every static operand again (ParamStore.refresh_shadows, after the weight shadows changed).  A host-side
-    decision, outside any captured graph -- like the shadow refresh itself; the launch plans never split static operands
-    except the first time they meet one."""
-    if _X3_STATIC_SPLITS:
-        _split(_lib.lib(), list(_X3_STATIC_SPLITS.values()), _stream())
+class X3Cache:
+    """The split images of one owner's operands (a trunk's or a stand-alone plan's activations, a ParamStore's weight
+    shadows), held for as long as the owner lives.  `weights`: the cache that owns the static ranges -- operands that only
+    change at a refresh -- with their images and SplitProblems (the store's; default: this one)."""
 
+    def __init__(self, device, weights: "Optional[X3Cache]" = None):
+        self.device = device
+        self.weights = weights          # None: this cache itself (kept as None: a self-reference would leave the images to the gc)
+        self.images = {}                # (ptr, rows, cols, ld) -> split image
+        self.static = set()             # [lo, hi) address ranges of operands that only change at a refresh (weight shadows)
+        self.static_splits = {}         # (ptr, rows, cols, ld) -> SplitProblem of every static operand seen so far
+        self.epoch = 0                  # bumped once per forward pass (new_step)
+        self.fresh = {}                 # operand key -> epoch of its last split (host program order)
 
-_X3_EPOCH = [0]                 # bumped once per forward pass (x3_new_step)
-_X3_FRESH = {}                  # operand key -> epoch of its last split (host program order)
+    def add_static(self, lo: int, hi: int) -> None:
+        self.static.add((lo, hi))
 
+    def refresh_static(self) -> None:
+        """Split every static operand again (ParamStore.refresh_shadows, after the weight shadows changed).  A host-side
+        decision, outside any captured graph -- like the shadow refresh itself; the launch plans never split static operands
+        except the first time they meet one."""
+        if self.static_splits:
+            _split(_lib.lib(), list(self.static_splits.values()), _stream())
 
-def x3_new_step() -> None:
-    _X3_EPOCH[0] += 1
+    def new_step(self) -> None:
+        self.epoch += 1
 
 
 class _X3Plan:
@@ -187,10 +186,10 @@ class _X3Plan:
     Problems the split path does not take (fewer than 256 rows / columns / k, row bias, ...) stay behind in `rest` and run
     as exact fp32 products.  Operands listed in the table's `x3_presplit` attribute (set where the launch tables are
     built: forward activations a backward launch reads again, gradients an earlier launch of the same layer has split)
-    are not split again when their image is from this step."""
+    are not split again when their image is from this step.  The plan holds its cache, and so the images it points into."""
 
-    def __init__(self, arr, variant: int, n: Optional[int]):
-        self.n = n
+    def __init__(self, arr, variant: int, n: Optional[int], cache: X3Cache):
+        self.n, self.cache = n, cache
         cnt = len(arr) if n is None else n
         P = [arr[i] for i in range(cnt)]
         xk, yk = variant != GEMM_TN, variant == GEMM_NT
@@ -207,6 +206,7 @@ class _X3Plan:
             ids = {C.addressof(p) for p in take}
             self.rest = array(GemmProblem, [p for p in P if C.addressof(p) not in ids])
         presplit = getattr(arr, "x3_presplit", ())
+        weights = cache if cache.weights is None else cache.weights
         dyn, new_static, out = [], [], []
         seen = {}
         for p in take:
@@ -217,21 +217,23 @@ class _X3Plan:
                 ptr = getattr(p, side)
                 key = (ptr, rows, cols, ld)
                 ldp = (cols + 127) // 128 * 128
-                buf = _X3_BUFFERS.get(key)
+                static = any(lo <= ptr < hi for lo, hi in weights.static)
+                own = weights if static else cache            # a weight shadow's image belongs to the store's cache
+                buf = own.images.get(key)
                 if buf is None:
                     # torch.empty, NOT zeros: bpm_split_rows writes every column of both planes (pads included), and an
                     # initialising kernel on the allocating stream would race with the other stream's split of the same
                     # operand (main runs ahead of the side stream: its split + product would be wiped by the late fill)
-                    buf = _X3_BUFFERS[key] = torch.empty(rows, 2 * ldp, device="cuda", dtype=torch.bfloat16)
+                    buf = own.images[key] = torch.empty(rows, 2 * ldp, device=own.device, dtype=torch.bfloat16)
                 if key not in seen:
                     seen[key] = True
                     sp = _lib.SplitProblem()
                     sp.src, sp.dst, sp.R, sp.C, sp.ld, sp.ldp = ptr, buf.data_ptr(), rows, cols, ld, ldp
-                    if any(lo <= ptr < hi for lo, hi in _X3_STATIC):
-                        if key not in _X3_STATIC_SPLITS:
-                            _X3_STATIC_SPLITS[key] = sp
+                    if static:
+                        if key not in own.static_splits:
+                            own.static_splits[key] = sp
                             new_static.append(sp)
-                    elif ptr in presplit and _X3_FRESH.get(key) == _X3_EPOCH[0]:
+                    elif ptr in presplit and cache.fresh.get(key) == cache.epoch:
                         pass                          # an earlier launch of this step left the image (static launch order)
                     else:
                         dyn.append(sp)
@@ -243,7 +245,7 @@ class _X3Plan:
         self.gemm = array(GemmProblem, out)
         self.dyn = array(_lib.SplitProblem, dyn) if dyn else None
         if new_static:                                # first sight of a weight shadow: split it now (plans are built by eager
-            _split(_lib.lib(), new_static, _stream())  # launches, never inside a graph capture); later: x3_refresh_static()
+            _split(_lib.lib(), new_static, _stream())  # launches, never inside a graph capture); later: refresh_static()
 
     @staticmethod
     def _eligible(p) -> bool:
@@ -259,7 +261,7 @@ class _X3Plan:
             for sub, k in _chunks(self.dyn, _lib.SplitProblem, None):
                 _lib.check(L.bpm_split_rows(sub, k, s), "bpm_split_rows")
             for key in self._keys:
-                _X3_FRESH[key] = _X3_EPOCH[0]
+                self.cache.fresh[key] = self.cache.epoch
         _lib.check(L.bpm_gemm_grouped(_lib.BPM_BF16X3, variant, self.gemm, len(self.gemm), seed, s), "bpm_gemm_grouped(bf16x3)")
 
 

@@ -429,7 +429,7 @@ def launch(case, hs):
     names = ("A", "B", "C", "bias_n", "bias_m", "resid", "gate", "colsum", "colsum_a")
     dev = [{n: getattr(h, n).cuda() for n in names if hasattr(h, n)} for h in hs]
     arr = structs(case, lambda i, name: dev[i][name].data_ptr())
-    ops.gemm_grouped(case.dtype, case.variant, arr, seed=case.seed, x3=case.x3)
+    ops.gemm_grouped(case.dtype, case.variant, arr, seed=case.seed, x3=ops.X3Cache(torch.device("cuda")) if case.x3 else None)
     torch.cuda.synchronize()
     got = [SimpleNamespace(C=d["C"].cpu(), colsum=d["colsum"].cpu() if "colsum" in d else None,
                            colsum_a=d["colsum_a"].cpu() if "colsum_a" in d else None) for d in dev]

@@ -1074,7 +1074,7 @@ def test_audio_encoder_frontend_against_torch_and_reference_fixture(prec):
 @pytest.mark.parametrize("variant,M,N,K", [(GEMM_NT, 1024, 768, 768), (GEMM_NT, 1000, 3072, 768), (GEMM_NN, 1024, 768, 3072),
                                           (GEMM_NN, 900, 1024, 1000), (GEMM_TN, 768, 3072, 4096), (GEMM_TN, 768, 768, 1000)])
 def test_gemm_bf16x3_products(variant, M, N, K):
-    """The parity-grade fast products (ops.gemm_grouped(..., x3=True) on fp32 operands: bpm_split_rows + BPM_BF16X3 on the
+    """The parity-grade fast products (ops.gemm_grouped(..., x3=<an ops.X3Cache>) on fp32 operands: bpm_split_rows + BPM_BF16X3 on the
     LDS-DMA kernel, x y ~ hi hi + hi lo + lo hi) against fp64 on the SAME fp32 operands: <= 5e-5 of the result's scale
     (plain bf16 operands: ~4e-3), with the fused epilogues the encoder uses -- bias + residual + dropout -> f32,
     relu -> fp32 CT, bias gradient beside a weight gradient (column sums of X), += -- and ragged M / K."""
@@ -1098,7 +1098,7 @@ def test_gemm_bf16x3_products(variant, M, N, K):
     p = ops.gemm_problem(Ad, Bd, out, M, N, K, Ad.shape[1], Bd.shape[1], N, flags=F_KPAD)
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     arr = ops.array(ops.GemmProblem, [p] * max(3, -(-100 // tiles)))      # (a weight-gradient launch takes the split path when it fills ~a third of the chip)
-    ops.gemm_grouped(BPM_F32, variant, arr, x3=True)
+    ops.gemm_grouped(BPM_F32, variant, arr, x3=ops.X3Cache(torch.device(dev)))
     assert arr._x3_plan.ok, "this launch must take the split-bf16 path, not the exact fp32 fallback"
     e3 = float((out.cpu().double() - ref).abs().max()) / scale
     assert e3 <= 5e-5, f"bf16x3 max err / scale = {e3:.2e}"
@@ -1114,7 +1114,7 @@ def test_gemm_bf16x3_products(variant, M, N, K):
         ops.gemm_grouped(BPM_F32, variant, [ops.gemm_problem(Ad, Bd, acc, M, N, K, Ad.shape[1], Bd.shape[1], N, flags=F_KPAD | F_ACCUM,
                                                             colsum_a=cs)] +
                          [ops.gemm_problem(Ad, Bd, scratch[i % 2], M, N, K, Ad.shape[1], Bd.shape[1], N, flags=F_KPAD)
-                          for i in range(max(2, -(-100 // tiles)))], x3=True)
+                          for i in range(max(2, -(-100 // tiles)))], x3=ops.X3Cache(torch.device(dev)))
         close(acc, ref + base.cpu().double(), 5e-5, "accumulate")
         close(cs, A.double().sum(0), 5e-5, "colsum_a")
     else:                                       # forward / data-gradient epilogues
@@ -1123,7 +1123,7 @@ def test_gemm_bf16x3_products(variant, M, N, K):
         o2 = torch.full((M, pad32(N)), float("nan"), device=dev)
         ps = [ops.gemm_problem(Ad, Bd, o1, M, N, K, Ad.shape[1], Bd.shape[1], N, bias_n=bias, resid=resid, ldr=N, drop_p=0.25, drop_site=9, flags=F_KPAD),
               ops.gemm_problem(Ad, Bd, o2, M, N, K, Ad.shape[1], Bd.shape[1], pad32(N), bias_n=bias, flags=F_KPAD | F_RELU, out_kind=OUT_CT)]
-        ops.gemm_grouped(BPM_F32, variant, ps, seed=77, x3=True)
+        ops.gemm_grouped(BPM_F32, variant, ps, seed=77, x3=ops.X3Cache(torch.device(dev)))
         dm = drop_mult((M, N), 0.25, 77, 9).double()
         close(o1, (ref + bias.cpu().double()) * dm + resid.cpu().double(), 5e-5 * 2, "bias + dropout + residual")
         close(o2[:, :N], (ref + bias.cpu().double()).clamp_min(0), 5e-5, "relu -> CT (fp32)")
@@ -1158,7 +1158,7 @@ def test_gemm_bf16x3_at_the_model_launch_shapes(variant):
         probs.append(ops.gemm_problem(Ad, Bd, out, M, N, K, Ad.shape[1], Bd.shape[1], N, flags=F_KPAD, colsum_a=cs))
         refs.append(ref); outs.append(out); sums.append((cs, A.double().sum(0) if cs is not None else None)); keep += [Ad, Bd]
     arr = ops.array(ops.GemmProblem, probs)
-    ops.gemm_grouped(BPM_F32, variant, arr, x3=True)
+    ops.gemm_grouped(BPM_F32, variant, arr, x3=ops.X3Cache(torch.device(dev)))
     assert arr._x3_plan.ok
     torch.cuda.synchronize()
     for gi in range(G):

@@ -70,6 +70,8 @@ def digest(plan):
             return d
         if isinstance(a, (int, float, str, bool)) or a is None:
             return a
+        if isinstance(a, torch.Tensor):                  # a table a launch reads (kv_source_fwd / _bwd: the position table)
+            return {"tensor": ptr(a.data_ptr()), "shape": list(a.shape), "dtype": str(a.dtype)}
         raise TypeError(f"unexpected step argument {type(a)}")
 
     def step(s):
