@@ -705,6 +705,8 @@ class EncoderGroupPlan:
         # backward tables by (training, stores): stores = the first weight-gradient launch of each large matrix writes
         # instead of accumulating (the flat gradient buffer was not cleared: ParamStore.begin_backward(stores=True))
         self._bwd = {(t, f): self._build_bwd(t, f) for t in (True, False) for f in (True, False)}
+        for steps in (*self._fwd.values(), *self._bwd.values()):
+            self._check_steps(steps)
 
     def _alloc(self, e: EncoderDesc) -> dict:
         """Buffers of one encoder: the query chain and FFN of every kind, the self-attention block's (self-only and
@@ -1108,28 +1110,24 @@ class EncoderGroupPlan:
         return kv_steps + steps + ([JOIN] if self._kv else [])
 
 
-    def _exec(self, s, seed: int) -> None:
-        fn = s[0]
-        if fn is ops.gemm_grouped:
-            fn(s[1], s[2], s[3], seed)
-        elif fn in (ops.attn_fwd, ops.attn_bwd, ops.attn_bwd_dq, ops.attn_bwd_dkv, ops.rows_cast):
-            fn(s[1], s[2], seed)
-        elif fn is ops.expand_heads:
-            fn(s[1], s[2])
-        elif fn is ops.ln_fwd:
-            fn(s[1], s[2], s[3])
-        elif fn is ops.ln_bwd:
-            fn(s[1], s[2], self.dtype, seed)
-        elif fn is ops.unfold_grads:
-            fn(s[1], s[2], s[3], s[4])
-        elif fn is ops.add_n:
-            fn(s[1])
-        elif fn is ops.kv_source_fwd:
-            fn(s[1], s[2], s[3], s[4], s[5], seed)
-        elif fn is ops.kv_source_bwd:
-            fn(s[1], s[2], s[3], s[4], seed)
+    @staticmethod
+    def _exec(s, seed: int) -> None:
+        """Run one step (fn, *args): every ops launch function takes its dropout seed as the keyword `seed`."""
+        fn, *args = s
+        if fn in ops.SEEDED:
+            fn(*args, seed=seed)
         else:
-            raise RuntimeError("unknown step")
+            fn(*args)
+
+    @staticmethod
+    def _check_steps(steps) -> None:
+        """Refuse, when the tables are built, a step whose function is not an ops launch function."""
+        for s in steps:
+            if s is JOIN or s[0] in (MARK, WAIT):
+                continue
+            fn = s[1][0] if s[0] in (SIDE, SIDE2) else s[0]
+            if fn not in ops.STEP_FUNCTIONS:
+                raise ValueError(f"launch table: {getattr(fn, '__name__', fn)!r} is not a step function (ops.STEP_FUNCTIONS)")
 
     def _run(self, steps, seed: int, on_mark=None) -> None:
         """Launch a step table.  Plain steps go to the current ("main") stream.  (SIDE, step) goes to the side
@@ -1320,7 +1318,7 @@ class EncoderGroupPlan:
         pr = (lambda p: p) if training else (lambda p: 0.0)
         nn = lambda probs: self._gemm(GEMM_NN, probs)
         wg = lambda probs, presplit: (SIDE, self._gemm(GEMM_TN, probs, background=True, presplit=presplit))
-        ln = lambda probs: (ops.ln_bwd, A(LnProblem, probs), d)
+        ln = lambda probs: (ops.ln_bwd, A(LnProblem, probs), d, self.dtype)
         x3, lr = st.x3, self._lowrank
         steps = []
         for i in reversed(range(c.layers)):

@@ -5,10 +5,19 @@ are plain ctypes structures built once per (layer, op) and replayed every step
 with a fresh dropout seed; the call is enqueued on torch's current stream and a
 non-zero return code becomes a RuntimeError.  No arithmetic happens in Python,
 and there is no CPU fallback.
+
+Every entry point that takes an array of problems is launched by _grouped(): it
+finds the problem struct in _lib.SIGNATURES, walks the array in chunks of the
+library's group limit and calls entry(*pre, problems, count, *post, stream).
+
+A launch-table step (engine.EncoderGroupPlan) is a tuple (fn, *args) with fn one
+of STEP_FUNCTIONS; it is run as fn(*args, seed=seed) when fn is in SEEDED and as
+fn(*args) otherwise.  Both sets are defined at the end of this module.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import torch
@@ -69,20 +78,60 @@ def _f32(t, what):
     return _p(t)
 
 
+def _counter(t, what):
+    if t is not None and not isinstance(t, int) and (t.dtype != torch.int32 or t.numel() < 1):
+        raise ValueError(f"{what}: an int32 device counter")
+    return _p(t)
+
+
+def _f32_table(t, what: str, d: int):
+    """A [rows, d] table the kernels index by row: d floats per row, rows d floats apart (a view of whole rows is fine)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d or t.stride() != (d, 1):
+        raise ValueError(f"{what}: expected float32 [rows, {d}] with contiguous rows, got {t.dtype} {tuple(t.shape)}")
+    return _p(t)
+
+
+def _adam_scalars(what: str, ngroups: int, scale_dev, norm_dev, steps_dev, skipped_dev):
+    """The device scalars of the Adam entries, checked -> their four addresses in the entries' order."""
+    for t, nm in ((scale_dev, "scale_dev"), (norm_dev, "norm_dev")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
+            raise ValueError(f"{what}: {nm}: expected float32 (one device value), got {t.dtype}")
+    if steps_dev is not None and (steps_dev.dtype != torch.int32 or steps_dev.numel() < ngroups or not steps_dev.is_contiguous()):
+        raise ValueError(f"{what}: steps_dev: a contiguous tensor of one int32 device counter per group")
+    return _p(scale_dev), _p(norm_dev), _p(steps_dev), _counter(skipped_dev, f"{what}: skipped_dev")
+
+
 def array(cls, probs: Sequence):
     """ctypes array of problem structs (cache it; it is replayed every step)."""
     return (cls * len(probs))(*probs)
 
 
-def _chunks(arr, cls, n, limit=MAX_GROUP):
+def _as_array(cls, probs):
+    return probs if isinstance(probs, C.Array) else array(cls, probs)
+
+
+def _at(arr, i: int):
+    """Pointer to element i of a ctypes array."""
+    return C.cast(C.byref(arr, i * C.sizeof(arr._type_)), C.POINTER(arr._type_))
+
+
+_PROBLEM = {}       # entry point -> the struct of its problem array (the first POINTER(struct) of its signature)
+
+
+def _grouped(name: str, probs, pre=(), post=(), limit: int = MAX_GROUP, beside=None, n: Optional[int] = None) -> None:
+    """Launch the first n (default: all) problems through entry point `name`, `limit` at a time: one call
+    entry(*pre, problems, [beside,] count, *post, stream) per chunk.  post: the scalars behind the count, or a function
+    of the chunk's count that returns them; beside: a second ctypes array that advances with the problems."""
+    cls = _PROBLEM.get(name)
+    if cls is None:
+        cls = _PROBLEM[name] = next(t._type_ for t in _lib.SIGNATURES[name] if isinstance(t, type) and issubclass(t, C._Pointer))
+    arr = _as_array(cls, probs)
+    entry, s = getattr(_lib.lib(), name), _stream()
     n = len(arr) if n is None else n
     for i in range(0, n, limit):
         k = min(limit, n - i)
-        yield C.cast(C.byref(arr, i * C.sizeof(cls)), C.POINTER(cls)), k
-
-
-def _as_array(cls, probs):
-    return probs if isinstance(probs, C.Array) else array(cls, probs)
+        also = () if beside is None else (_at(beside, i),)
+        _lib.check(entry(*pre, _at(arr, i), *also, k, *(post(k) if callable(post) else post), s), name)
 
 
 # ----------------------------------------------------------------------------
@@ -122,19 +171,17 @@ def gemm_grouped(dtype: int, variant: int, probs, seed: int = 0, n: Optional[int
     cache = x3 or getattr(arr, "x3", None) or None
     if cache is not None and not isinstance(cache, X3Cache):
         raise TypeError(f"x3: an ops.X3Cache (the owner of the split images) or None, got {type(cache).__name__}")
-    L, s = _lib.lib(), _stream()
     if cache is not None and dtype == BPM_F32 and variant in _X3_VARIANTS:
         plan = getattr(arr, "_x3_plan", None)
         if plan is None or plan.n != n or plan.cache is not cache:
             plan = _X3Plan(arr, variant, n, cache)
             arr._x3_plan = plan              # tables are replayed every step; lists were turned into a fresh array above
         if plan.ok:
-            plan.run(L, variant, _seed(seed), s)
+            plan.run(_lib.lib(), variant, _seed(seed), _stream())
             if plan.rest is None:
                 return
             arr, n = plan.rest, None            # the problems the split path does not take: exact fp32 products
-    for sub, k in _chunks(arr, GemmProblem, n, GEMM_MAX_GROUP):
-        _lib.check(L.bpm_gemm_grouped(dtype, variant, sub, k, _seed(seed), s), "bpm_gemm_grouped")
+    _grouped("bpm_gemm_grouped", arr, (dtype, variant), (_seed(seed),), GEMM_MAX_GROUP, n=n)
 
 
 # ---- bf16x3: fp32 products as three bf16 MFMA products of split operands -------------------------------------------
@@ -144,13 +191,11 @@ def gemm_grouped(dtype: int, variant: int, probs, seed: int = 0, n: Optional[int
 # of the hot path are static) right before the launch; weight shadows -- operands inside a static range of the cache that
 # owns the weights -- are split again only after the shadows were refreshed.
 # lab knob: BPMULT_X3_ONLY=nt,nn restricts the split path to those operand arrangements (bisecting a parity failure)
-_X3_VARIANTS = {{"nt": GEMM_NT, "nn": GEMM_NN, "tn": GEMM_TN}[v] for v in __import__("os").environ.get("BPMULT_X3_ONLY", "nt,nn,tn").split(",") if v}
+_X3_VARIANTS = {{"nt": GEMM_NT, "nn": GEMM_NN, "tn": GEMM_TN}[v] for v in os.environ.get("BPMULT_X3_ONLY", "nt,nn,tn").split(",") if v}
 
 
-def _split(L, probs, s) -> None:
-    arr = _as_array(_lib.SplitProblem, probs)
-    for sub, k in _chunks(arr, _lib.SplitProblem, None):
-        _lib.check(L.bpm_split_rows(sub, k, s), "bpm_split_rows")
+def _split(probs) -> None:
+    _grouped("bpm_split_rows", probs)
 
 
 class X3Cache:
@@ -175,7 +220,7 @@ class X3Cache:
         decision, outside any captured graph -- like the shadow refresh itself; the launch plans never split static operands
         except the first time they meet one."""
         if self.static_splits:
-            _split(_lib.lib(), list(self.static_splits.values()), _stream())
+            _split(list(self.static_splits.values()))
 
     def new_step(self) -> None:
         self.epoch += 1
@@ -245,7 +290,7 @@ class _X3Plan:
         self.gemm = array(GemmProblem, out)
         self.dyn = array(_lib.SplitProblem, dyn) if dyn else None
         if new_static:                                # first sight of a weight shadow: split it now (plans are built by eager
-            _split(_lib.lib(), new_static, _stream())  # launches, never inside a graph capture); later: refresh_static()
+            _split(new_static)                        # launches, never inside a graph capture); later: refresh_static()
 
     @staticmethod
     def _eligible(p) -> bool:
@@ -258,8 +303,7 @@ class _X3Plan:
 
     def run(self, L, variant: int, seed: int, s: int) -> None:
         if self.dyn is not None:
-            for sub, k in _chunks(self.dyn, _lib.SplitProblem, None):
-                _lib.check(L.bpm_split_rows(sub, k, s), "bpm_split_rows")
+            _split(self.dyn)
             for key in self._keys:
                 self.cache.fresh[key] = self.cache.epoch
         _lib.check(L.bpm_gemm_grouped(_lib.BPM_BF16X3, variant, self.gemm, len(self.gemm), seed, s), "bpm_gemm_grouped(bf16x3)")
@@ -286,31 +330,19 @@ def attn_problem(Q, K, V, O, ldo, lse, B, H, T, S, dh, dhp, mask_off, *, dO=None
 
 
 def attn_fwd(dtype: int, probs, seed: int = 0) -> None:
-    arr = _as_array(AttnProblem, probs)
-    L, s = _lib.lib(), _stream()
-    for sub, k in _chunks(arr, AttnProblem, None):
-        _lib.check(L.bpm_attn_fwd(dtype, sub, k, _seed(seed), s), "bpm_attn_fwd")
+    _grouped("bpm_attn_fwd", probs, (dtype,), (_seed(seed),))
 
 
 def attn_bwd(dtype: int, probs, seed: int = 0) -> None:
-    arr = _as_array(AttnProblem, probs)
-    L, s = _lib.lib(), _stream()
-    for sub, k in _chunks(arr, AttnProblem, None):
-        _lib.check(L.bpm_attn_bwd(dtype, sub, k, _seed(seed), s), "bpm_attn_bwd")
+    _grouped("bpm_attn_bwd", probs, (dtype,), (_seed(seed),))
 
 
 def attn_bwd_dq(dtype: int, probs, seed: int = 0) -> None:
-    arr = _as_array(AttnProblem, probs)
-    L, s = _lib.lib(), _stream()
-    for sub, k in _chunks(arr, AttnProblem, None):
-        _lib.check(L.bpm_attn_bwd_dq(dtype, sub, k, _seed(seed), s), "bpm_attn_bwd_dq")
+    _grouped("bpm_attn_bwd_dq", probs, (dtype,), (_seed(seed),))
 
 
 def attn_bwd_dkv(dtype: int, probs, seed: int = 0) -> None:
-    arr = _as_array(AttnProblem, probs)
-    L, s = _lib.lib(), _stream()
-    for sub, k in _chunks(arr, AttnProblem, None):
-        _lib.check(L.bpm_attn_bwd_dkv(dtype, sub, k, _seed(seed), s), "bpm_attn_bwd_dkv")
+    _grouped("bpm_attn_bwd_dkv", probs, (dtype,), (_seed(seed),))
 
 
 def attn_kmasks(masks) -> "C.Array":
@@ -329,13 +361,7 @@ def _attn_kmask(name: str, dtype: int, probs, masks, seed: int) -> None:
     arr = _as_array(AttnProblem, probs)
     if len(masks) != len(arr):
         raise ValueError(f"{name}: one key mask per problem ({len(arr)} problems, {len(masks)} masks)")
-    L, s = _lib.lib(), _stream()
-    fn = getattr(L, name)
-    for i in range(0, len(arr), MAX_GROUP):
-        k = min(MAX_GROUP, len(arr) - i)
-        sub = C.cast(C.byref(arr, i * C.sizeof(AttnProblem)), C.POINTER(AttnProblem))
-        msub = C.cast(C.byref(masks, i * C.sizeof(_lib.AttnKMask)), C.POINTER(_lib.AttnKMask))
-        _lib.check(fn(dtype, sub, msub, k, _seed(seed), s), name)
+    _grouped(name, arr, (dtype,), (_seed(seed),), beside=masks)
 
 
 def attn_fwd_kmask(dtype: int, probs, masks, seed: int = 0) -> None:
@@ -366,9 +392,7 @@ def attn_maps(dtype: int, probs) -> None:
     if _DRY_RUN:
         _DRY_LAUNCHES.append((attn_maps, dtype, arr))
         return
-    L, s = _lib.lib(), _stream()
-    for sub, k in _chunks(arr, AttnMapProblem, None):
-        _lib.check(L.bpm_attn_maps(dtype, sub, k, s), "bpm_attn_maps")
+    _grouped("bpm_attn_maps", arr, (dtype,))
 
 
 # ----------------------------------------------------------------------------
@@ -382,15 +406,11 @@ def pack_problem(B, T, Cn, ld, *, src=None, dst=None, g=None, ldg=0, dsrc=None, 
 
 
 def pack_rows_fwd(dtype, probs, seed=0) -> None:
-    arr = _as_array(PackProblem, probs)
-    for sub, k in _chunks(arr, PackProblem, None):
-        _lib.check(_lib.lib().bpm_pack_rows_fwd(dtype, sub, k, _seed(seed), _stream()), "bpm_pack_rows_fwd")
+    _grouped("bpm_pack_rows_fwd", probs, (dtype,), (_seed(seed),))
 
 
 def pack_rows_bwd(probs, seed=0) -> None:
-    arr = _as_array(PackProblem, probs)
-    for sub, k in _chunks(arr, PackProblem, None):
-        _lib.check(_lib.lib().bpm_pack_rows_bwd(sub, k, _seed(seed), _stream()), "bpm_pack_rows_bwd")
+    _grouped("bpm_pack_rows_bwd", probs, (), (_seed(seed),))
 
 
 def pack_weights(dtype, table_dev: torch.Tensor, ndesc: int, total_blocks: int) -> None:
@@ -404,8 +424,22 @@ def device_table(descs) -> torch.Tensor:
     return t if _DRY_RUN else t.to("cuda")
 
 
+# Blocks a segment takes in a table-driven launch: the library's answer, or under _DRY_RUN (tables built without a GPU)
+# its restatement: csrc/rowops.hip's ADAM_CHUNK and SSQ_CHUNK (the segment's offset in its 16-byte line counts).
+# bpm_zero_segment_blocks has none: a dry run asks whatever stands in for the library, and the block counts that
+# tools/step_trace.py records are its stand-in's, not the library's
+_DRY_BLOCKS = {"bpm_adam_blocks": lambda n4: (n4 + 1023) // 1024,
+               "bpm_grad_sumsq_blocks": lambda ptr, n: ((ptr >> 2 & 3) + n + 4095) // 4096}
+
+
+def _blocks(name: str, *args) -> int:
+    if _DRY_RUN and name in _DRY_BLOCKS:
+        return _DRY_BLOCKS[name](*args)
+    return int(getattr(_lib.lib(), name)(*args))
+
+
 def adam_blocks(n4: int) -> int:
-    return int(_lib.lib().bpm_adam_blocks(n4)) if not _DRY_RUN else (n4 + 1023) // 1024
+    return _blocks("bpm_adam_blocks", n4)
 
 
 def adam_groups(groups) -> "C.Array":
@@ -426,16 +460,9 @@ def adam_step_groups(dtype, table_dev, nseg, nblk, master, grad, exp_avg, exp_av
     for t in (master, grad, exp_avg, exp_avg_sq):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != master.numel():
             raise ValueError("adam_step_groups: flat contiguous float32 buffers of one size")
-    for t, what in ((scale_dev, "scale_dev"), (norm_dev, "norm_dev")):
-        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
-            raise ValueError(f"adam_step_groups: {what} is a float32 device tensor")
-    if steps_dev is not None and (steps_dev.dtype != torch.int32 or steps_dev.numel() < len(groups) or not steps_dev.is_contiguous()):
-        raise ValueError("adam_step_groups: steps_dev is a contiguous int32 device tensor with one counter per group")
-    if skipped_dev is not None and (skipped_dev.dtype != torch.int32 or skipped_dev.numel() < 1):
-        raise ValueError("adam_step_groups: skipped_dev is an int32 device tensor")
+    scalars = _adam_scalars("adam_step_groups", len(groups), scale_dev, norm_dev, steps_dev, skipped_dev)
     _lib.check(_lib.lib().bpm_adam_step_groups(dtype, table_dev.data_ptr(), nseg, nblk, _p(master), _p(grad), _p(exp_avg), _p(exp_avg_sq),
-                                               groups, len(groups), grad_scale, _p(scale_dev), _p(norm_dev), _p(steps_dev),
-                                               _p(skipped_dev), int(bool(zero_grad)), _stream()),
+                                               groups, len(groups), grad_scale, *scalars, int(bool(zero_grad)), _stream()),
                "bpm_adam_step_groups")
 
 
@@ -471,21 +498,14 @@ def adam_step_sets(dtype, table, sets, groups, grad_scale, zero_grad, scale_dev=
     adam_sets(...), everything else as adam_step_groups."""
     table_dev, table_host, nseg, nblk = table
     sets_dev, sets_host, _ = sets
-    for t, what in ((scale_dev, "scale_dev"), (norm_dev, "norm_dev")):
-        if t is not None and (t.dtype != torch.float32 or t.numel() < 1):
-            raise ValueError(f"adam_step_sets: {what} is a float32 device tensor")
-    if steps_dev is not None and (steps_dev.dtype != torch.int32 or steps_dev.numel() < len(groups) or not steps_dev.is_contiguous()):
-        raise ValueError("adam_step_sets: steps_dev is a contiguous int32 device tensor with one counter per group")
-    if skipped_dev is not None and (skipped_dev.dtype != torch.int32 or skipped_dev.numel() < 1):
-        raise ValueError("adam_step_sets: skipped_dev is an int32 device tensor")
+    scalars = _adam_scalars("adam_step_sets", len(groups), scale_dev, norm_dev, steps_dev, skipped_dev)
     _lib.check(_lib.lib().bpm_adam_step_sets(dtype, table_dev.data_ptr(), table_host, nseg, nblk, sets_dev.data_ptr(), sets_host,
-                                             len(sets_host), groups, len(groups), grad_scale, _p(scale_dev), _p(norm_dev),
-                                             _p(steps_dev), _p(skipped_dev), int(bool(zero_grad)), _stream()),
+                                             len(sets_host), groups, len(groups), grad_scale, *scalars, int(bool(zero_grad)), _stream()),
                "bpm_adam_step_sets")
 
 
 def grad_sumsq_blocks(ptr: int, n: int) -> int:
-    return int(_lib.lib().bpm_grad_sumsq_blocks(ptr, n)) if not _DRY_RUN else ((ptr >> 2 & 3) + n + 4095) // 4096
+    return _blocks("bpm_grad_sumsq_blocks", ptr, n)
 
 
 def sumsq_table(segments):
@@ -527,12 +547,11 @@ def unfold_grads(table_dev: torch.Tensor, ndesc: int, total_blocks: int, store_d
 
 def zero_table(segments):
     """[(device address, element count)] -> (device table, ndesc, total blocks) for zero_segments."""
-    L = _lib.lib()
     descs, blk = [], 0
     for ptr, n in segments:
         z = _lib.ZeroDesc()
         z.p, z.n, z.blk0 = ptr, n, blk
-        blk += L.bpm_zero_segment_blocks(n)
+        blk += _blocks("bpm_zero_segment_blocks", n)
         descs.append(z)
     return device_table(descs), len(descs), blk
 
@@ -550,18 +569,11 @@ def embed_problem(x, out, T, B, *, accumulate=False, drop_p=0.0, drop_site=0, po
 
 
 def embed_pos_fwd(probs, table, d, scale, seed=0) -> None:
-    arr = _as_array(EmbedProblem, probs)
-    if table.dtype != torch.float32 or table.shape[1] != d or not table.is_contiguous():
-        raise ValueError("embed_pos_fwd: table must be contiguous fp32 [rows, d]")
-    for sub, k in _chunks(arr, EmbedProblem, None):
-        _lib.check(_lib.lib().bpm_embed_pos_fwd(sub, k, table.data_ptr(), table.shape[0], d, scale, _seed(seed), _stream()),
-                   "bpm_embed_pos_fwd")
+    _grouped("bpm_embed_pos_fwd", probs, (), (_f32_table(table, "embed_pos_fwd: table", d), table.shape[0], d, scale, _seed(seed)))
 
 
 def embed_pos_bwd(probs, d, scale, seed=0) -> None:
-    arr = _as_array(EmbedProblem, probs)
-    for sub, k in _chunks(arr, EmbedProblem, None):
-        _lib.check(_lib.lib().bpm_embed_pos_bwd(sub, k, d, scale, _seed(seed), _stream()), "bpm_embed_pos_bwd")
+    _grouped("bpm_embed_pos_bwd", probs, (), (d, scale, _seed(seed)))
 
 
 def kv_source_ok(d: int, T: int, B: int) -> bool:
@@ -588,24 +600,12 @@ def set_kv_source(p: KvSourceProblem, xk, xv) -> None:
     p.xk, p.xv = _f32(xk, "kv_source.xk"), _f32(xv, "kv_source.xv")
 
 
-def _kv_table(table, d):
-    if table.dtype != torch.float32 or table.shape[1] != d or not table.is_contiguous():
-        raise ValueError("kv_source: table must be contiguous fp32 [rows, d]")
-    return table.data_ptr(), table.shape[0]
-
-
 def kv_source_fwd(dtype, probs, table, d, scale, seed=0, eps=1e-5) -> None:
-    arr = _as_array(KvSourceProblem, probs)
-    tp, rows = _kv_table(table, d)
-    for sub, k in _chunks(arr, KvSourceProblem, None):
-        _lib.check(_lib.lib().bpm_kv_source_fwd(dtype, sub, k, tp, rows, d, scale, eps, _seed(seed), _stream()), "bpm_kv_source_fwd")
+    _grouped("bpm_kv_source_fwd", probs, (dtype,), (_f32_table(table, "kv_source: table", d), table.shape[0], d, scale, eps, _seed(seed)))
 
 
 def kv_source_bwd(probs, table, d, scale, seed=0) -> None:
-    arr = _as_array(KvSourceProblem, probs)
-    tp, rows = _kv_table(table, d)
-    for sub, k in _chunks(arr, KvSourceProblem, None):
-        _lib.check(_lib.lib().bpm_kv_source_bwd(sub, k, tp, rows, d, scale, _seed(seed), _stream()), "bpm_kv_source_bwd")
+    _grouped("bpm_kv_source_bwd", probs, (), (_f32_table(table, "kv_source: table", d), table.shape[0], d, scale, _seed(seed)))
 
 
 def ln_problem(x, gamma, beta, mean, rstd, R, *, out=None, ldo=0, out_f32=False, dy=None, ldy=0, add=None, dx=None,
@@ -623,9 +623,7 @@ def ln_problem(x, gamma, beta, mean, rstd, R, *, out=None, ldo=0, out_f32=False,
 
 
 def ln_fwd(dtype, probs, d, eps=1e-5) -> None:
-    arr = _as_array(LnProblem, probs)
-    for sub, k in _chunks(arr, LnProblem, None):
-        _lib.check(_lib.lib().bpm_ln_fwd(dtype, sub, k, d, eps, _stream()), "bpm_ln_fwd")
+    _grouped("bpm_ln_fwd", probs, (dtype,), (d, eps))
 
 
 def check_ln_rows(probs, d: int) -> None:
@@ -664,16 +662,16 @@ def _ln_workspace(n: int, d: int, device) -> torch.Tensor:
 def ln_bwd(probs, d, dtype=None, seed=0) -> None:
     """dtype / seed only matter for problems with a fused `cast` output.  Parameter / bias gradients go through a
     partial-sum workspace (no float atomics)."""
-    arr = _as_array(LnProblem, probs)
-    dt = BPM_F32 if dtype is None else dtype
-    dev = torch.device("cuda", torch.cuda.current_device())
-    for sub, k in _chunks(arr, LnProblem, None):
+    dev, seed = torch.device("cuda", torch.cuda.current_device()), _seed(seed)
+
+    def post(k):                    # the workspace of this chunk's count
         ws = _ln_workspace(k, d, dev)
-        try:
-            _lib.check(_lib.lib().bpm_ln_bwd_ws(dt, sub, k, d, _seed(seed), ws.data_ptr(), ws.numel() * 4, _stream()), "bpm_ln_bwd_ws")
-        except RuntimeError:
-            _LN_WS.clear()          # an aborted launch may leave ticket words set: start from fresh zeroed workspaces
-            raise
+        return d, seed, ws.data_ptr(), ws.numel() * 4
+    try:
+        _grouped("bpm_ln_bwd_ws", probs, (BPM_F32 if dtype is None else dtype,), post)
+    except RuntimeError:
+        _LN_WS.clear()              # an aborted launch may leave ticket words set: start from fresh zeroed workspaces
+        raise
 
 
 def cast_problem(a, lda, R, Cn, *, a_is_ct=False, b=None, ldb=0, dst_ct=None, ldd=0, ct_cols=0, dst_f32=None, ldf=0, colsum=None,
@@ -688,9 +686,7 @@ def cast_problem(a, lda, R, Cn, *, a_is_ct=False, b=None, ldb=0, dst_ct=None, ld
 
 
 def rows_cast(dtype, probs, seed=0) -> None:
-    arr = _as_array(CastProblem, probs)
-    for sub, k in _chunks(arr, CastProblem, None):
-        _lib.check(_lib.lib().bpm_rows_cast(dtype, sub, k, _seed(seed), _stream()), "bpm_rows_cast")
+    _grouped("bpm_rows_cast", probs, (dtype,), (_seed(seed),))
 
 
 def gelu_problem(u, ldu, R, Cn, *, u_is_ct=False, g=None, ldg=0, dg=None, lddg=0, du=None, lddu=0) -> "_lib.GeluProblem":
@@ -704,21 +700,11 @@ def gelu_problem(u, ldu, R, Cn, *, u_is_ct=False, g=None, ldg=0, dg=None, lddg=0
 
 
 def gelu_fwd(dtype: int, probs) -> None:
-    arr = _as_array(_lib.GeluProblem, probs)
-    for sub, k in _chunks(arr, _lib.GeluProblem, None):
-        _lib.check(_lib.lib().bpm_gelu_fwd(dtype, sub, k, _stream()), "bpm_gelu_fwd")
+    _grouped("bpm_gelu_fwd", probs, (dtype,))
 
 
 def gelu_bwd(dtype: int, probs) -> None:
-    arr = _as_array(_lib.GeluProblem, probs)
-    for sub, k in _chunks(arr, _lib.GeluProblem, None):
-        _lib.check(_lib.lib().bpm_gelu_bwd(dtype, sub, k, _stream()), "bpm_gelu_bwd")
-
-
-def _table(t, what: str, d: int):
-    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != d or t.stride(1) != 1 or t.stride(0) != d:
-        raise ValueError(f"{what}: a float32 [rows, {d}] table with contiguous rows")
-    return _p(t)
+    _grouped("bpm_gelu_bwd", probs, (dtype,))
 
 
 def _ids(t, what: str, B: int, L: int):
@@ -737,14 +723,12 @@ def bert_embed_problem(ids, seg, word, pos, typ, gamma, beta, *, x, s, mean, rst
     d = word.shape[1]
     p = _lib.BertEmbedProblem()
     p.ids, p.seg = _ids(ids, "bert_embed.ids", B, L), _ids(seg, "bert_embed.seg", B, L)
-    p.word, p.pos, p.type = _table(word, "bert_embed.word", d), _table(pos, "bert_embed.pos", d), _table(typ, "bert_embed.type", d)
+    p.word, p.pos, p.type = _f32_table(word, "bert_embed.word", d), _f32_table(pos, "bert_embed.pos", d), _f32_table(typ, "bert_embed.type", d)
     p.V, p.P, p.Tt = word.shape[0], pos.shape[0], typ.shape[0]
     p.gamma, p.beta, p.B, p.L = _f32(gamma, "bert_embed.gamma"), _f32(beta, "bert_embed.beta"), B, L
     p.x, p.xc, p.ldc = _f32(x, "bert_embed.x"), _p(xc), ldc
     p.s, p.mean, p.rstd = _f32(s, "bert_embed.s"), _f32(mean, "bert_embed.mean"), _f32(rstd, "bert_embed.rstd")
-    if bad.dtype != torch.int32 or bad.numel() < 1:
-        raise ValueError("bert_embed.bad: an int32 device counter")
-    p.bad, p.drop_p, p.drop_site = _p(bad), drop_p, drop_site
+    p.bad, p.drop_p, p.drop_site = _counter(bad, "bert_embed.bad"), drop_p, drop_site
     return p
 
 
@@ -801,9 +785,7 @@ def loss_problem(kind: int, reduction: int, logits, target, loss, B: int, Cn: in
         p.target, p.ldt = _f32(target, "loss.target"), Cn if ldt is None else ldt
     p.weight, p.ignore_index, p.loss = _f32(weight, "loss.weight"), ignore_index, _f32(loss, "loss.loss")
     p.dlogits_unit, p.ldd = _f32(dlogits_unit, "loss.dlogits_unit"), Cn if ldd is None else ldd
-    if bad is not None and not isinstance(bad, int) and (bad.dtype != torch.int32 or bad.numel() < 1):
-        raise ValueError("loss.bad: an int32 device counter")
-    p.bad = _p(bad)
+    p.bad = _counter(bad, "loss.bad")
     p.ws, p.ws_bytes = _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
     return p
 
@@ -839,9 +821,7 @@ def eval_desc(kind: int, Cn: int, capacity: int, *, max_batches: int = 0, score=
     p.score, p.predict, p.raw = _f32(score, "eval.score"), _f32(predict, "eval.predict"), _f32(raw, "eval.raw")
     p.target, p.losses = _f32(target, "eval.target"), _f32(losses, "eval.losses")
     p.pred, p.label = _bytes(pred, "eval.pred"), _bytes(label, "eval.label")
-    if bad is not None and not isinstance(bad, int) and (bad.dtype != torch.int32 or bad.numel() < 1):
-        raise ValueError("eval.bad: an int32 device counter")
-    p.bad = _p(bad)
+    p.bad = _counter(bad, "eval.bad")
     if result is not None and not isinstance(result, int) and result.dtype != torch.float64:
         raise ValueError(f"eval.result: expected float64, got {result.dtype}")
     if counts is not None and not isinstance(counts, int) and counts.dtype != torch.int64:
@@ -896,15 +876,11 @@ def expand_problem(q, dO, qexp, dOexp, B, H, T, dh, dhp, ld, *, Pd=None, S=0, db
 
 
 def expand_heads(dtype: int, probs) -> None:
-    arr = _as_array(_lib.ExpandProblem, probs)
-    for sub, k in _chunks(arr, _lib.ExpandProblem, None):
-        _lib.check(_lib.lib().bpm_expand_heads(dtype, sub, k, _stream()), "bpm_expand_heads")
+    _grouped("bpm_expand_heads", probs, (dtype,))
 
 
 def add_n(probs) -> None:
-    arr = _as_array(_lib.AddnProblem, probs)
-    for sub, k in _chunks(arr, _lib.AddnProblem, None):
-        _lib.check(_lib.lib().bpm_add_n(sub, k, _stream()), "bpm_add_n")
+    _grouped("bpm_add_n", probs)
 
 
 def gmu_problem(a1, a2, ag, x1, x2, R, *, out=None, dout=None, da1=None, da2=None, dag=None, ldg=0, dx1=None, dx2=None) -> GmuProblem:
@@ -917,15 +893,11 @@ def gmu_problem(a1, a2, ag, x1, x2, R, *, out=None, dout=None, da1=None, da2=Non
 
 
 def gmu2_fwd(probs, d) -> None:
-    arr = _as_array(GmuProblem, probs)
-    for sub, k in _chunks(arr, GmuProblem, None):
-        _lib.check(_lib.lib().bpm_gmu2_fwd(sub, k, d, _stream()), "bpm_gmu2_fwd")
+    _grouped("bpm_gmu2_fwd", probs, (), (d,))
 
 
 def gmu2_bwd(dtype, probs, d) -> None:
-    arr = _as_array(GmuProblem, probs)
-    for sub, k in _chunks(arr, GmuProblem, None):
-        _lib.check(_lib.lib().bpm_gmu2_bwd(dtype, sub, k, d, _stream()), "bpm_gmu2_bwd")
+    _grouped("bpm_gmu2_bwd", probs, (dtype,), (d,))
 
 
 # ----------------------------------------------------------------------------
@@ -937,3 +909,15 @@ def tail_fwd(desc, seed: int = 0) -> None:
 
 def tail_bwd(desc, grads) -> None:
     _lib.check(_lib.lib().bpm_tail_bwd(C.byref(desc), C.byref(grads), _stream()), "bpm_tail_bwd")
+
+
+# ----------------------------------------------------------------------------
+# launch-table steps: (fn, *args), run as fn(*args, seed=seed) if fn is in SEEDED, else as fn(*args)
+# ----------------------------------------------------------------------------
+# every launch function above that takes a dropout seed: as the keyword `seed`
+SEEDED = frozenset({gemm_grouped, attn_fwd, attn_bwd, attn_bwd_dq, attn_bwd_dkv, attn_fwd_kmask, attn_bwd_dq_kmask, attn_bwd_dkv_kmask,
+                    pack_rows_fwd, pack_rows_bwd, embed_pos_fwd, embed_pos_bwd, kv_source_fwd, kv_source_bwd, ln_bwd, rows_cast,
+                    bert_embed_fwd, tail_fwd})
+# every function that may stand in a step table: a launch on the current stream with no result
+STEP_FUNCTIONS = SEEDED | {attn_maps, ln_fwd, gelu_fwd, gelu_bwd, expand_heads, add_n, gmu2_fwd, gmu2_bwd, pack_weights, fold_bias,
+                           unfold_grads, zero_segments}

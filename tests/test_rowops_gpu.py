@@ -538,6 +538,21 @@ def test_add_n():
                 assert torch.equal(td.cpu(), t), f"add_n problem {k}: input {j} changed"
 
 
+def test_groups_past_the_launch_limit_reach_the_second_chunk():
+    """MAX_GROUP + 1 problems: the wrappers launch MAX_GROUP and then one, and the last problem is read at its own offset
+    in the array.  Sums of two small integers and copies are exact: compared bitwise."""
+    n = _lib.MAX_GROUP + 1
+    a = torch.arange(n * 16, dtype=torch.float32, device=DEV).view(n, 16)
+    b = (torch.arange(n * 16, dtype=torch.float32, device=DEV) % 7).view(n, 16) + 1
+    out = torch.full((n, 16), -1.0, device=DEV)
+    ops.add_n([ops.addn_problem(out[k], [a[k], b[k]]) for k in range(n)])
+    assert torch.equal(out, a + b)
+    src = torch.arange(n * 2 * 8, dtype=torch.float32, device=DEV).view(n, 2, 8) + 3
+    dst = torch.full((n, 2, 8), -1.0, device=DEV)
+    ops.rows_cast(BPM_F32, [ops.cast_problem(src[k], 8, 2, 8, dst_f32=dst[k], ldf=8) for k in range(n)])
+    assert torch.equal(dst, src)
+
+
 def test_zero_segments():
     """One table of five segments (1, 2 and 3 blocks of 4096 elements; one segment 4 bytes off 16-byte alignment) in a
     buffer of ones: the segments come back exactly zero, every gap still one."""
