@@ -43,6 +43,7 @@ ADAM_MAX_SETS, ADAM_SET_SHIFT = 4, 8         # == BPM_ADAM_MAX_SETS, BPM_ADAM_SE
 LOSS_BCE, LOSS_CE, LOSS_L1 = 0, 1, 2              # BPM_LOSS_* kinds
 LOSS_MEAN, LOSS_SUM, LOSS_NONE = 0, 1, 2          # BPM_LOSS_* reductions
 EVAL_MULTILABEL, EVAL_REGRESSION, EVAL_CLASSES = 0, 1, 2      # BPM_EVAL_* kinds
+EVAL_MAX_RANKS = 64              # == BPM_EVAL_MAX_RANKS
 
 
 def build(force: bool = False, verbose: bool = False, out: str | None = None, flags: tuple = (), objdir: str | None = None) -> str:
@@ -365,6 +366,9 @@ SIGNATURES = {
     "bpm_eval_ws_bytes": [_I, _I, _I],
     "bpm_eval_update": [C.POINTER(EvalDesc), _P],
     "bpm_eval_finalize": [C.POINTER(EvalDesc), _P],
+    "bpm_eval_image_bytes": [_I, _I, _I, _I],
+    "bpm_eval_pack": [C.POINTER(EvalDesc), _I, _I, _I, _I, _P, C.c_size_t, _P],
+    "bpm_eval_merge": [C.POINTER(EvalDesc), _P, C.c_size_t, _I, C.POINTER(_I), C.POINTER(_I), _P],
     "bpm_stream_create": [_I, C.POINTER(C.c_void_p)],
     "bpm_stream_priority_range": [C.POINTER(_I), C.POINTER(_I)],
     "bpm_prof_enable": [C.c_uint],
@@ -390,7 +394,7 @@ def load(path: str) -> C.CDLL:
     for name, args in SIGNATURES.items():
         fn = getattr(L, name)            # AttributeError if the symbol is missing
         fn.argtypes = args
-        fn.restype = C.c_char_p if name == "bpm_error_string" else C.c_size_t if name.endswith("_ws_bytes") else C.c_int
+        fn.restype = C.c_char_p if name == "bpm_error_string" else C.c_size_t if name.endswith("_bytes") else C.c_int
     v = L.bpm_version()
     if v != ABI_VERSION:
         raise HipLibraryError(f"{path}: ABI version {v}, this package binds version {ABI_VERSION} (include/bpmult_hip.h): rebuild it")

@@ -15,6 +15,10 @@
 //   ml_rows    thread = row: the row's own list (C elements: O(C^2) from L1), its F1 and whether every class is right.
 //   ml_final   block per list / per class: the partial sums in index order, the class's tp / fp / fn / tn, the loss mean.
 // Regression / classes: eval_rows_kernel (1024 rows per block) and eval_rows_final_kernel.
+//
+// Sharded evaluation: bpm_eval_pack copies a shard's rows, losses and bad counter into one image of 32-bit words,
+// bpm_eval_merge lays W such images into a store in rank order (one launch each, bit patterns only): the merged store is
+// the store of an unsharded evaluation, so finalize gives the same bits.
 #include "bpm_common.h"
 #include "../../include/bpmult_hip.h"
 
@@ -391,6 +395,110 @@ inline MlLayout ml_layout(size_t N, size_t C) {
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The exchange image of a shard: 32-bit words, every field as its bit pattern.  For an image of `rows` rows and `batches`
+// losses (E = rows C elements for BPM_EVAL_MULTILABEL, rows otherwise):
+//     [0] bad   [1] void mark   [2, 2 + batches) losses   then the 32-bit fields, E words each, then the byte fields,
+//     ceil(E / 4) words each, byte i of a field in bits 8 (i & 3) of its word i >> 2.
+// The void mark is 0 from pack; a rank that finds its shard is not what the ranks agreed on sets it in its slot instead of
+// packing, and a merge that meets one leaves bad = -1 for the one host read to find.
+// Fields in order -- multilabel: score | pred, label; regression: score, predict, raw, target; classes: predict, target |
+// label.  Words past the shard's own n rows / nb losses are zero.
+struct ImgLayout { size_t losses, w[4], b[2], total; int nw, nb; };
+inline ImgLayout img_layout(int kind, size_t rows, size_t batches, size_t C) {
+    ImgLayout L = {};
+    const size_t E = kind == BPM_EVAL_MULTILABEL ? rows * C : rows;
+    L.nw = kind == BPM_EVAL_MULTILABEL ? 1 : kind == BPM_EVAL_REGRESSION ? 4 : 2;
+    L.nb = kind == BPM_EVAL_MULTILABEL ? 2 : kind == BPM_EVAL_REGRESSION ? 0 : 1;
+    size_t o = 2;
+    L.losses = o; o += batches;
+    for (int k = 0; k < L.nw; ++k) { L.w[k] = o; o += E; }
+    for (int k = 0; k < L.nb; ++k) { L.b[k] = o; o += cdiv(E, 4); }
+    L.total = o;
+    return L;
+}
+
+struct ImgFields { uint32_t* w[4]; unsigned char* b[2]; };
+inline ImgFields img_fields(const bpm_eval_desc* d) {
+    ImgFields f = {};
+    if (d->kind == BPM_EVAL_MULTILABEL) {
+        f.w[0] = (uint32_t*)d->score; f.b[0] = d->pred; f.b[1] = d->label;
+    } else if (d->kind == BPM_EVAL_REGRESSION) {
+        f.w[0] = (uint32_t*)d->score; f.w[1] = (uint32_t*)d->predict; f.w[2] = (uint32_t*)d->raw; f.w[3] = (uint32_t*)d->target;
+    } else {
+        f.w[0] = (uint32_t*)d->predict; f.w[1] = (uint32_t*)d->target; f.b[0] = d->label;
+    }
+    return f;
+}
+
+struct PackP {
+    ImgFields f; ImgLayout L;
+    const uint32_t* losses; const int* bad;
+    uint32_t* image;
+    size_t words, E;                    // words of the image (all written), elements the shard holds
+    int nb;
+};
+
+// thread = one word of the image
+__global__ __launch_bounds__(NT) void eval_pack_kernel(PackP P) {
+    const size_t w = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (w >= P.words) return;
+    uint32_t v = 0;
+    if (w == 0) {
+        v = P.bad ? (uint32_t)P.bad[0] : 0u;
+    } else if (w < P.L.losses) {                            // the void mark: 0
+    } else if (w < P.L.w[0]) {
+        const size_t i = w - P.L.losses;
+        if (i < (size_t)P.nb) v = P.losses[i];
+    } else if (w < P.L.total) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < P.L.nw && w >= P.L.w[k] && w - P.L.w[k] < P.E) v = P.f.w[k][w - P.L.w[k]];
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (k < P.L.nb && w >= P.L.b[k]) {
+                const size_t i = (w - P.L.b[k]) * 4;       // a later byte field's words start past this one's: i >= E there
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (i + j < P.E) v |= (uint32_t)P.f.b[k][i + j] << (8 * j);
+            }
+    }
+    P.image[w] = v;
+}
+
+struct MergeP {
+    ImgFields f; ImgLayout L;
+    const uint32_t* images; size_t stride;      // words from one rank's image to the next
+    uint32_t* losses; int* bad;
+    int W, C;                                   // C: elements per row (1 unless multilabel)
+    int row0[BPM_EVAL_MAX_RANKS + 1], b0[BPM_EVAL_MAX_RANKS + 1];
+};
+
+// block = (256 elements, rank): thread = one element of that rank's shard, every field of it.  The byte fields land at
+// (row0 C + e), any residue mod 4: byte stores.
+__global__ __launch_bounds__(NT) void eval_merge_kernel(MergeP P) {
+    const int r = blockIdx.y;
+    const uint32_t* img = P.images + (size_t)r * P.stride;
+    const size_t e = (size_t)blockIdx.x * NT + threadIdx.x;
+    if (r == 0 && e == 0 && P.bad) {
+        int s = 0;
+        uint32_t mark = 0;
+        for (int q = 0; q < P.W; ++q) { s += (int)P.images[(size_t)q * P.stride]; mark |= P.images[(size_t)q * P.stride + 1]; }
+        P.bad[0] = mark ? -1 : s;
+    }
+    const size_t nb = (size_t)(P.b0[r + 1] - P.b0[r]);
+    if (e < nb) P.losses[(size_t)P.b0[r] + e] = img[P.L.losses + e];
+    const size_t E = (size_t)(P.row0[r + 1] - P.row0[r]) * P.C;
+    if (e >= E) return;
+    const size_t o = (size_t)P.row0[r] * P.C + e;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < P.L.nw) P.f.w[k][o] = img[P.L.w[k] + e];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (k < P.L.nb) P.f.b[k][o] = (unsigned char)(img[P.L.b[k] + (e >> 2)] >> (8 * (e & 3)));
+}
+
 }  // namespace
 
 extern "C" size_t bpm_eval_ws_bytes(int kind, int capacity, int C) {
@@ -472,6 +580,70 @@ extern "C" int bpm_eval_finalize(const bpm_eval_desc* d, void* stream) {
     hipLaunchKernelGGL(ml_rows_kernel, dim3(p.nr), dim3(NT), 0, s, p);
     BPM_CHECK_LAUNCH();
     hipLaunchKernelGGL(ml_final_kernel, dim3((unsigned)d->C + 3), dim3(NT), 0, s, p);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t bpm_eval_image_bytes(int kind, int rows, int batches, int C) {
+    if (!known(kind) || rows < 0 || batches < 0 || C < 1 || (kind == BPM_EVAL_REGRESSION && C != 1) || !sizes_ok(kind, rows, C)) return 0;
+    return img_layout(kind, (size_t)rows, (size_t)batches, (size_t)C).total * 4;
+}
+
+extern "C" int bpm_eval_pack(const bpm_eval_desc* d, int n, int nb, int rows, int batches, void* image, size_t image_bytes,
+                             void* stream) {
+    if (!d || !known(d->kind)) return BPM_ERR_ARG;
+    if (!store_ok(d) || !image || d->C < 1 || d->capacity < 1 || n < 0 || n > d->capacity || n > rows || nb < 0 ||
+        nb > d->max_batches || nb > batches || (nb && !d->losses))
+        return BPM_ERR_ARG;
+    if (d->kind == BPM_EVAL_REGRESSION && d->C != 1) return BPM_ERR_ARG;
+    if (!sizes_ok(d->kind, d->capacity, d->C) || !sizes_ok(d->kind, rows, d->C)) return BPM_ERR_ARG;
+    PackP p;
+    p.L = img_layout(d->kind, (size_t)rows, (size_t)batches, (size_t)d->C);
+    if ((image_bytes & 3) || image_bytes / 4 < p.L.total) return BPM_ERR_ARG;
+    if (!store_aligned(d) || !al(image, 4)) return BPM_ERR_ALIGN;
+    p.f = img_fields(d);
+    p.losses = (const uint32_t*)d->losses; p.bad = d->bad;
+    p.image = (uint32_t*)image;
+    p.words = image_bytes / 4;
+    p.E = (size_t)n * (d->kind == BPM_EVAL_MULTILABEL ? d->C : 1);
+    p.nb = nb;
+    const size_t blocks = cdiv(p.words, NT);
+    if (blocks > 0x7FFFFFFFull) return BPM_ERR_ARG;
+    hipLaunchKernelGGL(eval_pack_kernel, dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, p);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int bpm_eval_merge(const bpm_eval_desc* d, const void* images, size_t image_bytes, int W, const int* rows,
+                              const int* batches, void* stream) {
+    if (!d || !known(d->kind)) return BPM_ERR_ARG;
+    if (!store_ok(d) || !images || !rows || !batches || W < 1 || W > BPM_EVAL_MAX_RANKS || d->C < 1 || d->capacity < 1)
+        return BPM_ERR_ARG;
+    if (d->kind == BPM_EVAL_REGRESSION && d->C != 1) return BPM_ERR_ARG;
+    if (!sizes_ok(d->kind, d->capacity, d->C)) return BPM_ERR_ARG;
+    MergeP p;
+    long long nrows = 0, nbat = 0;
+    int rmax = 0, bmax = 0;
+    for (int r = 0; r < W; ++r) {
+        if (rows[r] < 0 || batches[r] < 0) return BPM_ERR_ARG;
+        p.row0[r] = (int)nrows; p.b0[r] = (int)nbat;
+        nrows += rows[r]; nbat += batches[r];
+        if (nrows > d->capacity || nbat > d->max_batches) return BPM_ERR_ARG;
+        rmax = rows[r] > rmax ? rows[r] : rmax; bmax = batches[r] > bmax ? batches[r] : bmax;
+    }
+    for (int r = W; r <= BPM_EVAL_MAX_RANKS; ++r) { p.row0[r] = (int)nrows; p.b0[r] = (int)nbat; }
+    if (nbat && !d->losses) return BPM_ERR_ARG;
+    p.L = img_layout(d->kind, (size_t)rmax, (size_t)bmax, (size_t)d->C);       // the common size: that of the largest shard
+    if ((image_bytes & 3) || image_bytes / 4 < p.L.total) return BPM_ERR_ARG;
+    if (!store_aligned(d) || !al(images, 4)) return BPM_ERR_ALIGN;
+    p.f = img_fields(d);
+    p.images = (const uint32_t*)images; p.stride = image_bytes / 4;
+    p.losses = (uint32_t*)d->losses; p.bad = d->bad;
+    p.W = W; p.C = d->kind == BPM_EVAL_MULTILABEL ? d->C : 1;
+    size_t work = (size_t)rmax * p.C;
+    work = work > (size_t)bmax ? work : (size_t)bmax;
+    const size_t blocks = cdiv(work > 0 ? work : 1, NT);                        // an all-empty merge still writes bad
+    hipLaunchKernelGGL(eval_merge_kernel, dim3((unsigned)blocks, (unsigned)W), dim3(NT), 0, (hipStream_t)stream, p);
     BPM_CHECK_LAUNCH();
     return 0;
 }

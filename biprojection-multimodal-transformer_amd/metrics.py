@@ -6,6 +6,9 @@ bpm_eval_finalize and reads one small buffer: the evaluation's single synchronis
 F1 / average precision in every averaging, the regression sums' metrics); training.model_eval arranges them into the
 reference's dict.  No scikit-learn: average precision is computed from integer rank counts (csrc/eval.hip, DESIGN.md
 section 5), bit-reproducible.  There is no CPU path.
+
+Under data parallelism each rank fills its own Evaluator from a share of the batches; `all_gather` (pack, one integer
+all_reduce, merge -- all on the device) leaves the store of the whole evaluation on every rank, bit for bit.
 """
 from __future__ import annotations
 
@@ -17,6 +20,9 @@ import torch
 from . import _lib, ops
 
 KINDS = {"multilabel": _lib.EVAL_MULTILABEL, "regression": _lib.EVAL_REGRESSION, "classes": _lib.EVAL_CLASSES}
+# gate dtypes by the code that all_gather exchanges
+_GATE_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.float64, torch.uint8, torch.int8, torch.int16, torch.int32,
+                torch.int64, torch.bool)
 
 
 def weighted_accuracy(tp, fp, fn, tn):
@@ -163,6 +169,183 @@ class Evaluator:
         self.nlosses += loss is not None
 
     # ------------------------------------------------------------------
+    # sharded evaluation: every rank fills its own store from a contiguous share of the batches, the shards are exchanged
+    # as images of 32-bit words and merged on the device in rank order (csrc/eval.hip)
+    def pack(self, rows: Optional[int] = None, batches: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The exchange image of the stored rows, their losses and the counter of refused targets: an int32 device tensor
+        laid out for a shard of up to `rows` rows and `batches` losses (default: what is stored), zero past the stored
+        data.  out: an int32 tensor to write it to (every element is written).  One launch, no host read."""
+        rows = self.n if rows is None else rows
+        batches = self.nlosses if batches is None else batches
+        if rows < self.n or batches < self.nlosses:
+            raise ValueError(f"pack: an image for {rows} rows / {batches} losses cannot hold the {self.n} / {self.nlosses} stored")
+        nbytes = ops.eval_image_bytes(KINDS[self.kind], rows, batches, self.C)
+        if nbytes == 0:
+            raise ValueError(f"pack: no image holds {rows} rows of {self.C} classes and {batches} losses")
+        if out is None:
+            out = torch.empty((nbytes // 4,), device=self.device, dtype=torch.int32)
+        with torch.cuda.device(self.device):
+            ops.eval_pack(self._desc, self.n, self.nlosses, out, rows=rows, batches=batches)
+        return out
+
+    def _shard_counts(self, rows, batches, losses=None):
+        """Per-rank rows / update calls / losses as int lists, refused where the merged evaluation would not fit or would
+        carry losses for some batches only."""
+        rows, batches = [int(v) for v in rows], [int(v) for v in batches]
+        losses = list(batches) if losses is None else [int(v) for v in losses]
+        W = len(rows)
+        if not 1 <= W <= _lib.EVAL_MAX_RANKS or len(batches) != W or len(losses) != W:
+            raise ValueError(f"merge: 1 to {_lib.EVAL_MAX_RANKS} shards with one row, batch and loss count each, got "
+                             f"{W} / {len(batches)} / {len(losses)}")
+        if min(rows) < 0 or min(batches) < 0 or min(losses) < 0:
+            raise ValueError(f"merge: negative counts in rows {rows}, batches {batches}, losses {losses}")
+        if sum(rows) > self.capacity:
+            raise ValueError(f"capacity: the shards hold {sum(rows)} rows, the capacity is {self.capacity}")
+        if sum(batches) > self.max_batches:
+            raise ValueError(f"max_batches: the shards hold {sum(batches)} batches of at most {self.max_batches}")
+        if any(l not in (0, b) for l, b in zip(losses, batches)) or (any(losses) and losses != batches):
+            raise ValueError(f"loss: given for some batches only (batches {batches}, losses {losses})")
+        return rows, batches, losses
+
+    def merge(self, images: torch.Tensor, rows, batches, losses=None) -> None:
+        """Fill the store from W images (int32 [W, words], each laid out for max(rows) rows and max(losses) losses, as
+        pack(max(rows), max(losses)) writes them): shard r's rows go behind those of the shards before it, in order, and
+        so do its losses; the counters of refused targets add.  rows / batches / losses: per shard, the rows, the update
+        calls and the losses it carries (default: one per update call; all or none of the batches carry one).  Sets n,
+        nbatches and nlosses; gates are not part of an image (all_gather moves them).  This evaluator's own image may be
+        among the sources.  One launch, no host read; a refusal leaves the store as it was."""
+        rows, batches, losses = self._shard_counts(rows, batches, losses)
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.int32 or images.dim() != 2 or images.shape[0] != len(rows):
+            raise ValueError(f"images: expected an int32 tensor [{len(rows)}, words]")
+        if not images.is_cuda:
+            raise RuntimeError("images: the evaluator needs CUDA (HIP) tensors; there is no CPU path")
+        need = ops.eval_image_bytes(KINDS[self.kind], max(rows), max(losses), self.C) // 4
+        if images.shape[1] < need:
+            raise ValueError(f"images: {images.shape[1]} words each, shards of up to {max(rows)} rows and {max(losses)} losses take {need}")
+        with torch.cuda.device(self.device):
+            ops.eval_merge(self._desc, images.contiguous(), rows, losses)
+        self.n, self.nbatches, self.nlosses = sum(rows), sum(batches), sum(losses)
+
+    def all_gather(self, process_group=None, counts=None, gates: Optional[bool] = None) -> None:
+        """The collective step of a sharded evaluation: pack this rank's shard, exchange the images, merge them in rank
+        order into every rank's store.  Afterwards compute() and predictions() behave on every rank as on one evaluator
+        that was fed all batches in order, bit for bit.  Without an initialised process group, or in a world of one, a
+        no-op.
+
+        counts: per rank (rows, batches) or (rows, batches, losses) -- losses default to batches -- when every rank knows
+        them already (from the shapes of a batch list that all ranks share).  Then nothing is read on the host, and kind,
+        C, the capacities and whether gates are kept are the caller's promise to be alike on all ranks.  Without counts
+        -- or when a rank holds no rows, which then cannot know whether the others keep gates -- rows, batches, losses,
+        kind, C, capacities and the gates' width and dtype are exchanged first: ONE SMALL HOST READ per evaluation, and a
+        mismatch raises ValueError on every rank alike.
+
+        The images travel at one common size (the largest shard's) as an int32 [W, words] buffer that is zero outside the
+        own slot, summed by all_reduce -- exact for every bit pattern, and served for device tensors by nccl and gloo
+        alike.  Gates, when kept, follow in a second all_reduce of their bytes, dtype and bits unchanged.  Every rank
+        issues the same collectives in the same order whatever its shard holds.
+
+        gates: whether the evaluation keeps gates, when the caller knows (model_eval passes its output_gates), so that no
+        rank decides on the second collective from what it happens to hold: False -- none, with counts no host read; True
+        -- the gates' width and dtype are exchanged with the counts (the host read above) and a rank with rows but
+        without gates makes every rank raise.  None: as this rank holds them, which with counts given is once more the
+        caller's promise.
+
+        A rank that finds its own shard is not what `counts` (or gates = False) promised still takes part in every
+        collective, with a voided image in place of its shard, and raises ValueError afterwards.  The other ranks cannot
+        raise at once without a host read; their merged store is INVALID (the voided shard's rows are zeros), its counter
+        of refused targets reads -1, and their compute() raises ValueError on it; predictions() must not be used then."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        W = dist.get_world_size(process_group)
+        if W == 1:
+            return
+        rank = dist.get_rank(process_group)
+        if counts is not None:
+            counts = [tuple(int(v) for v in c) for c in counts]
+            if len(counts) != W or any(len(c) not in (2, 3) for c in counts):
+                raise ValueError(f"counts: expected {W} entries (rows, batches[, losses]), got {counts}")
+            counts = [c if len(c) == 3 else c + (c[1],) for c in counts]
+        kept = self._gates is not None
+        mine = (self.n, self.nbatches, self.nlosses)
+        late = None                      # an error only this rank knows of: raised after the collectives, never in their place
+        with torch.cuda.device(self.device):
+            if counts is not None and all(c[0] > 0 for c in counts) and gates is not True:
+                rows, batches, losses = self._shard_counts(*zip(*counts))
+                if counts[rank] != mine:
+                    late = f"counts: rank {rank} was promised as (rows, batches, losses) = {counts[rank]} and holds {mine}"
+                elif gates is False and kept:
+                    late = f"gates: rank {rank} keeps gates in an all_gather that was told there are none"
+                gates = kept if gates is None else False
+                gate_width, gate_dtype = (self._gates.shape[1], self._gates.dtype) if gates else (0, None)
+            else:
+                meta = mine + (KINDS[self.kind], self.C, self.capacity, self.max_batches, int(kept),
+                               self._gates.shape[1] if kept else 0, _GATE_DTYPES.index(self._gates.dtype) if kept else 0)
+                table = torch.zeros((W, len(meta)), device=self.device, dtype=torch.int64)
+                table[rank] = torch.tensor(meta, dtype=torch.int64)
+                dist.all_reduce(table, op=dist.ReduceOp.SUM, group=process_group)
+                table = table.cpu().tolist()                                           # the one host read
+                if any(t[3:5] != table[0][3:5] for t in table):
+                    raise ValueError(f"all_gather: kind / C differ between ranks: {[tuple(t[3:5]) for t in table]}")
+                if any(t[5:7] != table[0][5:7] for t in table):
+                    raise ValueError(f"all_gather: capacity / max_batches differ between ranks: {[tuple(t[5:7]) for t in table]}")
+                if counts is not None and [tuple(t[:3]) for t in table] != counts:
+                    raise ValueError(f"counts: given {counts}, the ranks hold {[tuple(t[:3]) for t in table]}")
+                rows, batches, losses = self._shard_counts(*zip(*(t[:3] for t in table)))
+                holders = [t for t in table if t[0] > 0]
+                if any(t[7:] != holders[0][7:] for t in holders):
+                    raise ValueError(f"gates: kept on some ranks only, or of different width / dtype: {[tuple(t[7:]) for t in table]}")
+                found = bool(holders) and bool(holders[0][7])
+                if gates is not None and holders and gates != found:
+                    raise ValueError(f"gates: all_gather was told gates = {gates}, the ranks with rows say {found}")
+                gates = found
+                gate_width, gate_dtype = (holders[0][8], _GATE_DTYPES[holders[0][9]]) if gates else (0, None)
+            k, rmax, bmax = KINDS[self.kind], max(rows), max(losses)
+            images = torch.zeros((W, ops.eval_image_bytes(k, rmax, bmax, self.C) // 4), device=self.device, dtype=torch.int32)
+            if late is None:
+                self.pack(rmax, bmax, out=images[rank])
+            else:
+                images[rank, 1] = 1      # the void mark: every rank's merge leaves bad = -1 and its compute() raises
+            dist.all_reduce(images, op=dist.ReduceOp.SUM, group=process_group)
+            if gates:
+                slots = torch.zeros((W, self.gate_slot_bytes(rmax, gate_width, gate_dtype)), device=self.device, dtype=torch.uint8)
+                if late is None:
+                    self.pack_gates(slots[rank])
+                dist.all_reduce(slots.view(torch.int32), op=dist.ReduceOp.SUM, group=process_group)
+            if late is not None:
+                raise ValueError(late)
+            self.merge(images, rows, batches, losses)
+            if gates:
+                self.merge_gates(slots, rows, gate_width, gate_dtype)
+
+    @staticmethod
+    def gate_slot_bytes(rows: int, width: int, dtype: torch.dtype) -> int:
+        """Bytes of one rank's slot in the gates exchange: `rows` rows of `width` gates, rounded up to 8."""
+        return (rows * width * dtype.itemsize + 7) // 8 * 8
+
+    def pack_gates(self, out: torch.Tensor) -> None:
+        """The kept gates of the stored rows as bytes into the head of `out` (uint8, a slot of gate_slot_bytes that is zero
+        elsewhere); nothing when no gates are kept or no rows stored."""
+        if self._gates is not None and self.n:
+            flat = self._gates[:self.n].reshape(-1).view(torch.uint8)
+            out[:flat.numel()] = flat
+
+    def merge_gates(self, slots: torch.Tensor, rows, width: int, dtype: torch.dtype) -> None:
+        """Lay the gates of W shards (uint8 [W, slot bytes], as pack_gates fills them) behind each other in shard order,
+        dtype and bits unchanged: shard r's rows go to rows [sum(rows[:r]), ...), where merge() puts its predictions."""
+        if self._gates is None:
+            self._gates = torch.empty((self.capacity, width), device=self.device, dtype=dtype)
+        elif self._gates.shape[1] != width or self._gates.dtype != dtype:
+            raise ValueError(f"gates: [B, {width}] {dtype} into kept gates [B, {self._gates.shape[1]}] {self._gates.dtype}")
+        if sum(rows) > self.capacity:
+            raise ValueError(f"capacity: the shards hold {sum(rows)} rows, the capacity is {self.capacity}")
+        r0, row_bytes = 0, width * dtype.itemsize
+        for r, nr in enumerate(rows):
+            if nr:
+                self._gates[r0:r0 + nr] = slots[r, :nr * row_bytes].view(dtype).view(nr, width)
+            r0 += nr
+
+    # ------------------------------------------------------------------
     def compute(self) -> dict:
         """Finalize on the device and read the result buffer once (the evaluation's one sync).  Returns Python numbers and
         numpy arrays.  Every kind: `loss` (mean of the batch losses, NaN for none), `n`, `bad` (targets refused: neither 0
@@ -182,6 +365,9 @@ class Evaluator:
         res = host[:self._nres].view(np.float64)
         cnt = host[self._nres:self._nres + self._ncnt].astype(np.int64)
         bad = int(host[self._nres + self._ncnt:].view(np.int32)[0])
+        if bad < 0:
+            raise ValueError("compute: a rank voided its shard in all_gather (it held other rows, batches or gates than all ranks were "
+                             "promised; that rank has raised): the merged store is invalid")
         out = {"loss": float(res[0]), "bad": bad}
         if self.kind == "multilabel":
             Cn = self.C

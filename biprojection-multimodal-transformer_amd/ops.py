@@ -851,6 +851,35 @@ def eval_finalize(desc, N: int, nbatches: int) -> None:
     _lib.check(_lib.lib().bpm_eval_finalize(C.byref(desc), _stream()), "bpm_eval_finalize")
 
 
+def eval_image_bytes(kind: int, rows: int, batches: int, Cn: int) -> int:
+    """Bytes of the exchange image of a shard of up to `rows` rows and `batches` losses (0: arguments not accepted)."""
+    return int(_lib.lib().bpm_eval_image_bytes(kind, rows, batches, Cn))
+
+
+def _image(t, what):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"{what}: expected contiguous int32, got {t.dtype} with strides {t.stride()}")
+    return _p(t)
+
+
+def eval_pack(desc, n: int, nb: int, image, *, rows: Optional[int] = None, batches: Optional[int] = None) -> None:
+    """Rows [0, n), losses [0, nb) and the bad counter of desc's store into `image` (int32, every word written, zero past
+    the shard's data), laid out for (rows, batches): default (n, nb).  One launch, no host read."""
+    _lib.check(_lib.lib().bpm_eval_pack(C.byref(desc), n, nb, n if rows is None else rows, nb if batches is None else batches,
+                                        _image(image, "eval.image"), image.numel() * 4, _stream()), "bpm_eval_pack")
+
+
+def eval_merge(desc, images, rows, batches) -> None:
+    """images int32 [W, words], each laid out for (max(rows), max(batches)): rank r's rows to row sum(rows[:r]) of desc's
+    store, its losses to batch sum(batches[:r]), bad = the sum of the images' counters.  One launch, no host read."""
+    W = len(rows)
+    if images.dim() != 2 or images.shape[0] != W or len(batches) != W:
+        raise ValueError(f"eval.images: expected [W = {W}, words] and {W} batch counts, got {tuple(images.shape)} and {len(batches)}")
+    arr = C.c_int * W
+    _lib.check(_lib.lib().bpm_eval_merge(C.byref(desc), _image(images, "eval.images"), images.shape[1] * 4, W, arr(*rows), arr(*batches),
+                                         _stream()), "bpm_eval_merge")
+
+
 def addn_problem(out, ins) -> "_lib.AddnProblem":
     """out = sum(ins): contiguous fp32 tensors of one size (16-byte aligned); out may be one of them."""
     p = _lib.AddnProblem()

@@ -91,22 +91,41 @@ def get_criterion(args):
 
 def fit(model, optimizer, scheduler, train_batches: Callable[[], Iterable], forward_loss: Callable, evaluate: Callable,
         savedir: str, max_epochs: int, patience: int, gradient_accumulation_steps: int = 1, minimise: bool = False,
-        grad_sync=None, log: Optional[Callable[[str], None]] = None) -> dict:
+        grad_sync=None, log: Optional[Callable[[str], None]] = None, process_group=None) -> dict:
     """The reference's train() epoch loop (train.py:370-439) around any model / optimizer pair.
 
     train_batches() yields the batches of one epoch; forward_loss(model, batch) returns the scalar loss;
     evaluate(model) returns the tuning metric of the validation split.  grad_sync: an optional
-    distributed.GradSync -- only the last micro-step of an accumulation group exchanges gradients."""
+    distributed.GradSync -- only the last micro-step of an accumulation group exchanges gradients.
+
+    process_group (data parallelism, one process per GPU, all ranks on one save directory): only rank 0 writes the
+    checkpoints and every rank waits behind the write (a barrier per epoch); whether to resume is rank 0's decision,
+    broadcast, every rank then restores from checkpoint.pt, and a barrier keeps the first write behind the last read.
+    `evaluate` must return the same metric on every rank (make_evaluate(..., process_group=...) does): then
+    scheduler, best metric, n_no_improve and the stop decision stay identical on all ranks."""
     log = log or (lambda s: None)
+    writer = True
+    if process_group is not None:
+        import torch.distributed as dist
+        writer = _eval_world(process_group)[1] == 0
     start_epoch, global_step, n_no_improve = 0, 0, 0
     best_metric = float("inf") if minimise else -float("inf")
     ck = os.path.join(savedir, "checkpoint.pt")
-    if os.path.exists(ck):
+    resume = os.path.exists(ck)
+    if process_group is not None:
+        # whether to resume is rank 0's decision, taken before anybody can write: a rank that arrives late must not find
+        # (and resume from) the file that rank 0 has written for the first epoch in the meantime
+        flag = [resume]
+        dist.broadcast_object_list(flag, src=dist.get_global_rank(process_group, 0), group=process_group)
+        resume = flag[0]
+    if resume:
         c = torch.load(ck, map_location="cpu", weights_only=False)
         start_epoch, n_no_improve, best_metric = c["epoch"], c["n_no_improve"], c["best_metric"]
         model.load_state_dict(strip_module_prefix(c["state_dict"]), strict=False)
         optimizer.load_state_dict(c["optimizer"])
         scheduler.load_state_dict(c["scheduler"])
+    if process_group is not None:
+        dist.barrier(group=process_group)           # every rank has read the file before rank 0 may replace it
     history = []
     for i_epoch in range(start_epoch, max_epochs):
         losses = []
@@ -139,10 +158,12 @@ def fit(model, optimizer, scheduler, train_batches: Callable[[], Iterable], forw
             n_no_improve += 1
         history.append({"epoch": i_epoch, "loss": sum(losses) / max(len(losses), 1), "metric": tuning_metric,
                         "lr": optimizer.param_groups[0]["lr"], "improved": is_improvement})
-        if is_improvement:
+        if is_improvement and writer:
             save_checkpoint({"epoch": i_epoch + 1, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict(),
                              "scheduler": scheduler.state_dict(), "n_no_improve": n_no_improve, "best_metric": best_metric},
                             is_improvement, savedir)
+        if process_group is not None:
+            dist.barrier(group=process_group)       # nobody runs ahead of (or resumes from) a file half written
         if n_no_improve >= patience:
             log("No improvement. Breaking out of loop.")
             break
@@ -258,21 +279,64 @@ def arrange_metrics(args, m: dict) -> dict:
     return out
 
 
-def model_eval(model, criterion, batches, args, evaluator=None, output_gates: bool = False) -> dict:
+def shard_range(n_batches: int, world: int, rank: int) -> Tuple[int, int]:
+    """Rank `rank`'s share [lo, hi) of n_batches batches in a world of `world`: contiguous, in rank order, covering
+    [0, n_batches) exactly once, sizes differing by at most one.  With fewer batches than ranks some shares are empty."""
+    if n_batches < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_range: n_batches >= 0 and 0 <= rank < world, got {n_batches}, world {world}, rank {rank}")
+    return n_batches * rank // world, n_batches * (rank + 1) // world
+
+
+def _eval_world(process_group, presharded: bool = False) -> Tuple[int, int]:
+    """(world, rank) of a sharded evaluation, (1, 0) without a group."""
+    if process_group is None:
+        if presharded:
+            raise ValueError("presharded: needs a process_group (without one the batches are the whole evaluation)")
+        return 1, 0
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError("process_group: torch.distributed is not initialised")
+    return dist.get_world_size(process_group), dist.get_rank(process_group)
+
+
+def model_eval(model, criterion, batches, args, evaluator=None, output_gates: bool = False, process_group=None,
+               presharded: bool = False) -> dict:
     """The reference's model_eval (train.py:165-280) over model_forward and metrics.Evaluator: every batch is appended on
     the device (no loss.item(), no .cpu()), the metrics are computed there, and one buffer is read at the end.  Returns
     arrange_metrics' dict.  args: task, task_type, model, n_classes.  evaluator: a metrics.Evaluator to reuse (it is
     reset); without one, a store for exactly these batches is made.  With output_gates the GMU gates are kept in the
     evaluator (Evaluator.predictions()).  cmu-mosi: the logits [B, 1] are squeezed before the criterion, as
-    train.py:330 does."""
+    train.py:330 does.
+
+    process_group (data parallelism, one process per GPU): `batches` is the whole list, the same on every rank; this rank
+    forwards only batches[shard_range(len(batches), world, rank)], the evaluator holds the global row count, and
+    Evaluator.all_gather merges the shards in batch order with counts taken from the batch shapes (no further host
+    read while every rank has a batch and output_gates is off; with it the gates' shape is exchanged, one small read).  Every rank returns the same dict, bit for bit that of the evaluation without
+    a group.  presharded: `batches` is already this rank's share (a sharding loader); the merged order is then rank-major
+    and the counts are exchanged (one small host read; two when the evaluator has to be sized here)."""
     from .metrics import Evaluator
     kind = eval_kind(args)
     crit = criterion if kind != "regression" else (lambda out, tgt: criterion(out.squeeze(1) if out.dim() == 2 else out, tgt))
-    if evaluator is None:
+    world, rank = _eval_world(process_group, presharded)
+    counts = None
+    if world > 1 or evaluator is None:
         batches = list(batches)
-        rows = sum(int(b[0].shape[0]) for b in batches)
+    if world > 1 and not presharded:
+        sizes = [int(b[0].shape[0]) for b in batches]
+        spans = [shard_range(len(batches), world, r) for r in range(world)]
+        counts = [(sum(sizes[lo:hi]), hi - lo) for lo, hi in spans]
+        rows, nb = sum(sizes), len(batches)
+        batches = batches[spans[rank][0]:spans[rank][1]]
+    elif evaluator is None:
+        rows, nb = sum(int(b[0].shape[0]) for b in batches), len(batches)
+        if world > 1:                           # presharded: the global size is the sum over the ranks
+            import torch.distributed as dist
+            t = torch.tensor([rows, nb], dtype=torch.int64).to(next(model.parameters()).device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+            rows, nb = (int(v) for v in t.cpu())
+    if evaluator is None:
         dev = next(model.parameters()).device
-        evaluator = Evaluator(kind, 1 if kind == "regression" else int(args.n_classes), max(rows, 1), max(len(batches), 1), device=dev)
+        evaluator = Evaluator(kind, 1 if kind == "regression" else int(args.n_classes), max(rows, 1), max(nb, 1), device=dev)
     else:
         evaluator.reset()
     with torch.no_grad():
@@ -280,15 +344,19 @@ def model_eval(model, criterion, batches, args, evaluator=None, output_gates: bo
             r = model_forward(model, crit, batch, args.model, gmu_gate=output_gates)
             loss, out, tgt = r[0], r[1], r[2]
             evaluator.update(out, tgt, loss, r[3] if output_gates else None)
+    if world > 1:
+        evaluator.all_gather(process_group, counts, gates=output_gates)
     return arrange_metrics(args, evaluator.compute())
 
 
-def make_evaluate(criterion, batches_fn: Callable[[], Iterable], args, key: str) -> Callable:
+def make_evaluate(criterion, batches_fn: Callable[[], Iterable], args, key: str, process_group=None) -> Callable:
     """The `evaluate` callable of fit(): evaluate(model) runs model_eval over batches_fn() and returns metrics[key]
     (the reference tunes on "auc_pr_micro" for multilabel tasks and "weight_f1" otherwise, train.py:405-407).  One
     Evaluator is made at the first call, sized by that epoch's batches, and reused; `evaluate.metrics` keeps the last
-    dict."""
+    dict.  process_group: batches_fn() yields the whole validation split on every rank and model_eval shards it; the
+    metric is then the same on every rank."""
     state = {"evaluator": None}
+    _eval_world(process_group)
 
     def evaluate(model):
         from .metrics import Evaluator
@@ -299,7 +367,7 @@ def make_evaluate(criterion, batches_fn: Callable[[], Iterable], args, key: str)
             rows = sum(int(b[0].shape[0]) for b in batches)
             state["evaluator"] = Evaluator(kind, 1 if kind == "regression" else int(args.n_classes), max(rows, 1),
                                            max(len(batches), 1), device=next(model.parameters()).device)
-        evaluate.metrics = model_eval(model, criterion, batches, args, evaluator=state["evaluator"])
+        evaluate.metrics = model_eval(model, criterion, batches, args, evaluator=state["evaluator"], process_group=process_group)
         return evaluate.metrics[key]
 
     evaluate.metrics = None

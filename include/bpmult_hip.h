@@ -768,6 +768,45 @@ size_t bpm_eval_ws_bytes(int kind, int capacity, int C);
 int bpm_eval_update(const bpm_eval_desc* d, void* stream);
 int bpm_eval_finalize(const bpm_eval_desc* d, void* stream);
 
+/* Sharded evaluation (data parallelism): every rank evaluates a contiguous share of the batches into its own store;
+ * the shards are exchanged as images and merged on the device, in rank order, into every rank's store; the unchanged
+ * bpm_eval_finalize then runs everywhere.  Only bit patterns move, so the merged store -- and with it every metric --
+ * is bit-identical to an unsharded evaluation over the same batches.  One launch each, no host read.
+ *
+ * The exchange image: 32-bit words.  For `rows` rows and `batches` losses, with E = rows * C elements
+ * (BPM_EVAL_MULTILABEL) or E = rows (other kinds):
+ *     [0] bad    [1] void mark    [2, 2 + batches) losses    the 32-bit fields, E words each    the byte fields,
+ *     ceil(E / 4) words each, byte i of a field in bits 8 * (i % 4) of its word i / 4.
+ *   The void mark is 0 from bpm_eval_pack.  A rank that finds its shard is not what the ranks agreed on leaves its
+ *   slot zero and sets this word instead of packing; bpm_eval_merge then writes *bad = -1 (never a count), which the
+ *   caller's one host read finds on every rank.
+ *   BPM_EVAL_MULTILABEL  score | pred, label        BPM_EVAL_REGRESSION  score, predict, raw, target
+ *   BPM_EVAL_CLASSES     predict, target | label
+ * bpm_eval_image_bytes(kind, rows, batches, C): the bytes of that image (0 for arguments it does not accept: an unknown
+ * kind, rows < 0, batches < 0, C < 1, C != 1 for BPM_EVAL_REGRESSION, rows * C >= 2^31 for BPM_EVAL_MULTILABEL).
+ *
+ * bpm_eval_pack: rows [0, n), losses [0, nb) and *bad (0 when NULL) of the store in `d` into `image`, laid out for
+ * (rows, batches) >= (n, nb) -- ranks exchange images of one common size, that of the largest shard.  Every word of
+ * image[0, image_bytes / 4) is written; the words beyond the shard's own data are zero, so the image is a function of
+ * the shard alone and a sum of images that are zero outside one slot (an integer all-reduce) reproduces it.
+ *
+ * bpm_eval_merge: `images` holds W images, image_bytes apart, each laid out for (max rows[r], max batches[r]).  Rank
+ * r's rows go to rows [sum rows[:r], ...) of the store in `d`, its losses to losses [sum batches[:r], ...), and *bad
+ * (when not NULL) becomes the sum of the images' bad words.  rows / batches are HOST arrays of W ints, read before the
+ * call returns; a rank with zero rows and zero batches is legal, and so is a merge of nothing (only *bad is written).
+ * The store may be the one the local image was packed from (the images are separate memory: pack first).  The byte
+ * fields are written with byte stores: a shard may start at any residue of rows * C mod 4.
+ * BPM_ERR_ARG (nothing launched): NULL desc / image(s) / rows / batches or a NULL pointer that the kind uses, an unknown
+ * kind, C < 1 (C != 1 for BPM_EVAL_REGRESSION), capacity < 1, a negative count, n > capacity, n > rows, nb > batches,
+ * nb > max_batches, losses wanted with NULL losses, W outside [1, BPM_EVAL_MAX_RANKS], sum rows > capacity,
+ * sum batches > max_batches, image_bytes not a multiple of 4 or less than bpm_eval_image_bytes says.
+ * BPM_ERR_ALIGN: store or image pointers not 4-byte aligned. */
+#define BPM_EVAL_MAX_RANKS 64
+size_t bpm_eval_image_bytes(int kind, int rows, int batches, int C);
+int bpm_eval_pack(const bpm_eval_desc* d, int n, int nb, int rows, int batches, void* image, size_t image_bytes, void* stream);
+int bpm_eval_merge(const bpm_eval_desc* d, const void* images, size_t image_bytes, int W, const int* rows, const int* batches,
+                   void* stream);
+
 /* Engine plumbing (no reference counterpart): a non-blocking HIP stream at the device's lowest priority
  * (low_priority != 0) or at the default priority.  The host engine puts weight-gradient GEMMs and the
  * key/value-side chain there so that the dispatcher serves the critical-path stream first. */
