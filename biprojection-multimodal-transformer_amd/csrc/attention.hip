@@ -42,7 +42,6 @@ constexpr int NTHREADS = 256;
 constexpr int KT = 64;      // keys per tile (forward / dQ)
 constexpr int BPM_ATTN_W128 = 2;    // waves per SIMD at head_dim 128 (unified 256-register budget: no AGPR copies)
 constexpr int BPM_ATTN_WF = 5;      // waves per SIMD of the forward kernel at head_dim <= 32 (90 VGPRs; dQ / dKdV spill at 5)
-constexpr int BPM_BASE_PRIO = 1;      // see gemm.hip
 constexpr int BPM_ATTN_SETPRIO = 1;
 constexpr int BPM_ATTN_QT = 64;
 constexpr int BPM_ATTN_DKV_W32 = 4;

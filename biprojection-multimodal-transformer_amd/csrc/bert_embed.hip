@@ -15,12 +15,10 @@
 //            type table: per-block partial rows (SC_TROWS rows of ds each) for every type id.
 //   stage 2  word table: the wave of the chunk in which a split run STARTS adds the run's pieces in chunk order.
 //            type table: one thread per (type id, four columns) adds the partial rows in block order.
-#include "bpm_common.h"
-#include "../../include/bpmult_hip.h"
+#include "rows_common.h"      // NT, put4
 
 namespace {
 
-constexpr int NT = 256;
 constexpr int WPB = NT / 64;
 constexpr int SC_CH = 32;        // sorted positions per chunk of the word-table sum (<= 64: one ballot finds a piece's end)
 constexpr int SC_TROWS = 32;     // rows of ds per partial row of the type-table sum
@@ -29,11 +27,6 @@ BPM_DEV double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-template <typename CT>
-BPM_DEV void put4(void* p, size_t i, f32x4 v) {
-    if constexpr (sizeof(CT) == 4) *(f32x4*)((float*)p + i) = v;
-    else { bf16x4 o; o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3]; *(bf16x4*)((bf16_t*)p + i) = o; }
 }
 
 struct EmbFwdP {

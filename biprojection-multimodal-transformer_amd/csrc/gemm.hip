@@ -57,9 +57,6 @@ constexpr int BPM_TILED_MINW = 5;
 // s_setprio(1) around the MFMA cluster: alone the GEMMs gain 1-10 % (wgrad 85 -> 80 us), inside the training step they
 // then take issue slots from the critical-path kernels of the other stream and the step gets SLOWER (17.0 -> 17.4 ms)
 constexpr int BPM_SETPRIO = 0;
-// issue priority of critical-path kernels (forward / dgrad GEMMs not flagged BACKGROUND, attention, LayerNorm) over
-// the side stream's: 16.92 -> 16.63 ms/step
-constexpr int BPM_BASE_PRIO = 1;
 constexpr int BPM_DEEP_TN = 2;
 constexpr int BPM_DEEP_FWD = 1;
 constexpr int KS_FWD = 1, KS_WGRAD = 2;

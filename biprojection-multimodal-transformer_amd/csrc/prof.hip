@@ -1,9 +1,12 @@
-// Event-based launch profiler behind bpm_prof_* (include/bpmult_hip.h).
+// The library's housekeeping: bpm_version / bpm_error_string, the event-based launch profiler behind bpm_prof_*, the
+// stream helpers (include/bpmult_hip.h) and, in the -DBPM_LAB build, the record of the row files' dry launches.
+#include <cstdio>
 #include <mutex>
 #include <vector>
 
 #include "../../include/bpmult_hip.h"
 #include "bpm_prof.h"
+#include "rows_common.h"
 
 unsigned g_bpm_prof_mask = 0;
 
@@ -88,3 +91,51 @@ extern "C" int bpm_stream_priority_range(int* least, int* greatest) {
     if (!least || !greatest) return BPM_ERR_ARG;
     return (int)hipDeviceGetStreamPriorityRange(least, greatest);
 }
+
+extern "C" int bpm_version(void) { return BPM_ABI_VERSION; }
+
+extern "C" const char* bpm_error_string(int code) {
+    switch (code) {
+        case 0: return "ok";
+        case BPM_ERR_ARG: return "bpmult_hip: invalid argument (shape / pointer / mode)";
+        case BPM_ERR_ALIGN: return "bpmult_hip: operand not 16-byte aligned (pointer or leading dimension)";
+        default: return hipGetErrorString((hipError_t)code);
+    }
+}
+
+#ifdef BPM_LAB
+// Dry mode of rows_common.h's launch(): while it is on, an entry point of the row files runs its check, fill and choose
+// steps and returns its code, and every launch it would have made is noted here instead (nothing is dereferenced, no
+// device is needed).  bpm_debug_rows_dry(on) also forgets the notes; bpm_debug_rows_last(i, ...) reads note i back (the
+// kernel's instantiation as launch() spells it: the mangled name of its KernelTag) and returns how many launches were noted.
+int g_bpm_rows_dry = 0;
+
+namespace {
+struct RowsNote { const char* kernel; unsigned grid, block; const void* aux; };
+constexpr int ROWS_NOTES = 8;
+RowsNote g_rows_note[ROWS_NOTES];
+int g_rows_notes = 0;
+}  // namespace
+
+void bpm_rows_note(const char* kernel, unsigned grid, unsigned block, const void* aux) {
+    if (g_rows_notes < ROWS_NOTES) g_rows_note[g_rows_notes] = RowsNote{kernel, grid, block, aux};
+    ++g_rows_notes;
+}
+
+extern "C" int bpm_debug_rows_dry(int on) {
+    g_bpm_rows_dry = on;
+    g_rows_notes = 0;
+    return 0;
+}
+
+extern "C" int bpm_debug_rows_last(int i, char* kernel, int cap, unsigned* grid, unsigned* block, const void** aux) {
+    if (i >= 0 && i < g_rows_notes && i < ROWS_NOTES) {
+        const RowsNote& r = g_rows_note[i];
+        if (kernel && cap > 0) snprintf(kernel, (size_t)cap, "%s", r.kernel);
+        if (grid) *grid = r.grid;
+        if (block) *block = r.block;
+        if (aux) *aux = r.aux;
+    }
+    return g_rows_notes;
+}
+#endif

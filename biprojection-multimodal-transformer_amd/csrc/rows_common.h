@@ -1,0 +1,117 @@
+// What more than one family of row kernels uses (rows_pack.hip, rows_norm.hip, rows_elem.hip, adam.hip; bert_embed.hip
+// takes put4): the grouped-launch argument, small device helpers, and the shared pieces of the ONE shape of an entry
+// point -- check, fill, choose, launch: grp_begin, launch, with_ct, with_width.  Every row-kernel entry is GROUPED: one
+// launch serves up to BPM_MAX_GROUP independent problems (the encoders of one level run in lock-step), passed by value
+// in the kernel-argument segment; a block finds its problem from a prefix table of block counts.
+// Everything sits in the unnamed namespace, as the kernels of those files do: their symbols carry it.
+#pragma once
+#include <cmath>
+#include <type_traits>
+#include <typeinfo>
+
+#include "bpm_common.h"
+#include "../../include/bpmult_hip.h"
+
+#ifdef BPM_LAB
+// Dry mode of the lab build (prof.hip: bpm_debug_rows_dry / bpm_debug_rows_last): launch() notes what it would have
+// launched and launches nothing, so the launch decisions are testable without a GPU (tests/test_rowops_dispatch_cpu.py).
+#define BPM_HIDDEN __attribute__((visibility("hidden")))      // shared by the library's files, not exported
+extern BPM_HIDDEN int g_bpm_rows_dry;
+BPM_HIDDEN void bpm_rows_note(const char* kernel, unsigned grid, unsigned block, const void* aux);
+#endif
+
+namespace {
+constexpr int NT = 256;
+
+template <typename CT> BPM_DEV void put(void* p, size_t i, float v) { ((CT*)p)[i] = Tr<CT>::from_f(v); }
+template <typename CT>
+BPM_DEV void put4(void* p, size_t i, f32x4 v) {
+    if constexpr (sizeof(CT) == 4) *(f32x4*)((float*)p + i) = v;
+    else { bf16x4 o; o[0] = (bf16_t)v[0]; o[1] = (bf16_t)v[1]; o[2] = (bf16_t)v[2]; o[3] = (bf16_t)v[3]; *(bf16x4*)((bf16_t*)p + i) = o; }
+}
+
+inline unsigned blocks_for(size_t n, int per_block, unsigned cap) {
+    size_t g = (n + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
+
+template <typename P> struct Grp {
+    const uint64_t* seedp;              // dropout seed read at execution time (BPM_SEED_INDIRECT), or nullptr
+    int n;
+    unsigned blk0[BPM_MAX_GROUP + 1];   // prefix of block counts
+    P p[BPM_MAX_GROUP];
+};
+
+// block -> (problem index, block within problem, blocks of that problem)
+template <typename P>
+BPM_DEV const P& pick(const Grp<P>& g, unsigned& bid, unsigned& nblk) {
+    int pi = 0;
+#pragma unroll 1
+    for (int i = 1; i < g.n; ++i)
+        if (bid >= g.blk0[i]) pi = i;
+    nblk = g.blk0[pi + 1] - g.blk0[pi];
+    bid -= g.blk0[pi];
+    return g.p[pi];
+}
+
+template <typename D>
+BPM_DEV const D& find_desc(const D* __restrict__ tab, int ndesc, unsigned bid) {
+    int lo = 0, hi = ndesc - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[mid].blk0 <= bid) lo = mid; else hi = mid - 1;
+    }
+    return tab[lo];
+}
+
+constexpr unsigned CAP = 2048;   // blocks per problem for grid-stride kernels
+
+// Host side.  The prologue of every grouped entry: the null / count check and the header of the kernel argument.  What a
+// problem must satisfy, and the copy of its fields, stay with the entry.
+template <typename P, typename Q>
+inline bool grp_begin(Grp<P>& g, const Q* q, int n, uint64_t seed = 0) {
+    if (!q || n < 1 || n > BPM_MAX_GROUP) return false;
+    g.n = n; g.blk0[0] = 0; g.seedp = bpm_seed_ptr(seed);
+    return true;
+}
+
+#ifdef BPM_LAB
+template <auto K> struct KernelTag {};          // typeid(KernelTag<K>).name() spells the instantiation, arguments included
+template <typename T> const void* as_ptr(const T&) { return nullptr; }
+template <typename T> const void* as_ptr(T* p) { return (const void*)p; }
+#endif
+
+// Every launch of the row files: kernel K on `grid` blocks of `block` threads, no dynamic LDS.
+template <auto K, typename... A>
+inline int launch(unsigned grid, unsigned block, void* stream, const A&... args) {
+#ifdef BPM_LAB
+    if (g_bpm_rows_dry) {
+        const void* aux = nullptr;                 // the last pointer argument (a workspace, a counter array), if any
+        ((aux = as_ptr(args)), ...);
+        bpm_rows_note(typeid(KernelTag<K>).name(), grid, block, aux);
+        return 0;
+    }
+#endif
+    hipLaunchKernelGGL(K, dim3(grid), dim3(block), 0, (hipStream_t)stream, args...);
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+// f(CT()) with the compute type of `dtype`: bf16_t for BPM_BF16, float for anything else
+template <typename F> inline int with_ct(int dtype, F&& f) { return dtype == BPM_BF16 ? f(bf16_t()) : f(float()); }
+
+// Register widths W the one-wave-per-row kernels are instantiated at, UNIT columns each: the lists decide which
+// instantiations exist.
+template <int UNIT, int... W> struct Widths {};
+using VecWidths = Widths<256, 1, 2, 3, 4>;                    // NV of ln_*_vec_kernel and kv_source_*_kernel
+using RowWidths = Widths<64, 1, 2, 5, 8, 12, 16, 24, 32>;     // NE of ln_fwd_kernel and ln_bwd_kernel
+// f(std::integral_constant<int, W>()) for the first W of the list with span <= UNIT * W; BPM_ERR_ARG when none covers it
+template <int UNIT, int... W, typename F>
+inline int with_width(Widths<UNIT, W...>, int span, F&& f) {
+    int rc = BPM_ERR_ARG;
+    (void)((span <= UNIT * W && ((rc = f(std::integral_constant<int, W>())), true)) || ...);
+    return rc;
+}
+}  // namespace

@@ -425,7 +425,7 @@ def device_table(descs) -> torch.Tensor:
 
 
 # Blocks a segment takes in a table-driven launch: the library's answer, or under _DRY_RUN (tables built without a GPU)
-# its restatement: csrc/rowops.hip's ADAM_CHUNK and SSQ_CHUNK (the segment's offset in its 16-byte line counts).
+# its restatement: csrc/adam.hip's ADAM_CHUNK and SSQ_CHUNK (the segment's offset in its 16-byte line counts).
 # bpm_zero_segment_blocks has none: a dry run asks whatever stands in for the library, and the block counts that
 # tools/step_trace.py records are its stand-in's, not the library's
 _DRY_BLOCKS = {"bpm_adam_blocks": lambda n4: (n4 + 1023) // 1024,

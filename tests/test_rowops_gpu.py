@@ -1,4 +1,4 @@
-"""Row kernels (csrc/rowops.hip) at the sizes where they change regime, and the entry points no other kernel test
+"""Row kernels (csrc/rows_pack.hip, rows_norm.hip, rows_elem.hip, adam.hip) at the sizes where they change regime, and the entry points no other kernel test
 reaches: LayerNorm past its block caps and through the workspace hand-off, the column-sum kernel over many 128-row
 blocks, interleaved CT output, add_n, zero_segments, split_rows, device tables with several descriptors, the
 element-wise embed_pos path and the grid-stride caps of pack_rows / gmu2.

@@ -1,4 +1,4 @@
-"""The wide path of unfold_grads (csrc/rowops.hip: four columns per thread, the rows' 16-byte loads batched) and the
+"""The wide path of unfold_grads (csrc/rows_pack.hip: four columns per thread, the rows' 16-byte loads batched) and the
 four-channel path of embed_pos past its grid cap.
 
 unfold_grads: one table of four descriptors, so the binary search, the wide path and both reasons for the one-column path
