@@ -142,6 +142,10 @@ class AttnKMask(C.Structure):
     _fields_ = [("mask", C.c_void_p), ("ldm", C.c_int)]
 
 
+class AttnAMask(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("ldm", C.c_int), ("maskT", C.c_void_p), ("ldt", C.c_int)]
+
+
 class GeluProblem(C.Structure):
     _fields_ = [("u", C.c_void_p), ("ldu", C.c_int), ("u_is_ct", C.c_int), ("g", C.c_void_p), ("ldg", C.c_int),
                 ("dg", C.c_void_p), ("lddg", C.c_int), ("du", C.c_void_p), ("lddu", C.c_int), ("R", C.c_int), ("C", C.c_int)]
@@ -320,6 +324,10 @@ SIGNATURES = {
     "bpm_attn_bwd_dq_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), _I, _U64, _P],
     "bpm_attn_bwd_dkv_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), _I, _U64, _P],
     "bpm_attn_maps": [_I, C.POINTER(AttnMapProblem), _I, _P],
+    "bpm_attn_fwd_amask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnAMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_amask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnAMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_amask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnAMask), _I, _U64, _P],
+    "bpm_attn_maps_amask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnAMask), _I, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],

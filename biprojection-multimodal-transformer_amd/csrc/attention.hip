@@ -5,6 +5,9 @@
 //   key j visible to query i  iff  j - i < mask_off   (mask_off = 1 + |S-T|, or "infinite" without attn_mask)
 //   P = softmax_fp32(S) over visible keys;  Pd = dropout(P);  O = Pd V
 // No key-padding mask: zero-padded key rows take part.
+// Two further visibility rules are separate instantiations of the same block bodies (compile-time flags; the kernels
+// above never see them): the per-key byte mask of the *_kmask entries (KM) and the arbitrary additive fp32 [T, S] mask of
+// the *_amask entries (AM: the reference's attn_mask argument as a tensor, multihead_attention.py:113-115).
 // The [T,S] score matrix never touches HBM: forward keeps a running (max, sum)
 // per query and stores only LSE = max + ln(sum); backward recomputes P from
 // Q, K and LSE.
@@ -108,6 +111,20 @@ struct AGroupK {
     AMask m[BPM_MAX_GROUP];
 };
 static_assert(sizeof(AGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// Additive mask of the *_amask entries (the reference's attn_mask argument, multihead_attention.py:113-115): fp32 [T, ldm],
+// added to the score of (query i, key j) in every head of the problem; -inf hides the pair.  The forward and dQ kernels
+// hold one query per lane and 4 consecutive keys per register group: they read `mask` rows as float4.  The dK / dV and
+// maps kernels hold one key per lane and 4 consecutive queries per register group: they read the TRANSPOSE [S, ldt] the
+// caller supplies, again as float4 (reading `mask` down a column would be 16 scalar loads per lane and tile).  One
+// descriptor per kernel: m / ld are (mask, ldm) or (maskT, ldt).  A third argument block beside AGroup / AGroupK: without
+// AM none of this is compiled.
+struct AAdd { const float* m; int ld; };
+struct AGroupA {
+    AGroup g;
+    AAdd m[BPM_MAX_GROUP];
+};
+static_assert(sizeof(AGroupA) <= 4096, "kernel arguments are limited to 4 KiB");
 
 template <typename CT, int DHP> struct Cfg {
     static constexpr int SZ = sizeof(CT);
@@ -249,8 +266,13 @@ BPM_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_ex
 // j >= S: those keys are hidden without a load), pass through KT bytes of LDS behind the K / V images as 0 / 1, and every
 // lane reads the four words that cover its 16 keys.  A hidden key's score becomes -inf before the maximum, like a key
 // beyond the mask_off limit; a tile without any visible key is skipped.  Without KM none of this is compiled.
-template <typename CT, int DHP, bool KM>
-BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km) {
+// AM: with an additive mask (AAdd).  A lane's 16 keys of a tile are four groups of 4 consecutive columns of its query's
+// mask row: four float4 loads, issued before the score MFMAs and added to the scores before the visibility selects (so
+// whatever sits in columns >= S, which the limit hides, never survives).  Never read at q >= T or at a group that starts
+// at j >= S.  No tile is skipped; the running maximum takes the KM guard.
+template <typename CT, int DHP, bool KM, bool AM = false>
+BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km,
+                            const AAdd am = AAdd{nullptr, 0}) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
@@ -297,6 +319,8 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
         kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
         if constexpr (KM) stage_mask(0);
     }
+    const float* arow = nullptr;                       // AM: this lane's mask row
+    if constexpr (AM) arow = am.m + (size_t)min(q, P.T - 1) * am.ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -307,6 +331,15 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
         if (kt + 1 < ntile) {
             kst.load(Kh, (kt + 1) * KT, P.S, tid); vst.load(Vh, (kt + 1) * KT, P.S, tid);
             if constexpr (KM) stage_mask(kt + 1);
+        }
+        f32x4 am4[4];                                  // AM: mask of keys kt * KT + 16n + 4g + (0..3)
+        if constexpr (AM) {
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int jc = kt * KT + 16 * n + 4 * g;        // jc % 4 == 0 and ldm % 4 == 0: jc < S implies jc + 3 < ldm
+                am4[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (q < P.T && jc < P.S) am4[n] = *(const f32x4*)(arow + jc);
+            }
         }
         bool k_all = true;                             // KM: every key of the tile is visible (wave-uniform)
         if constexpr (KM) {
@@ -322,6 +355,7 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
 #pragma unroll
             for (int s = 0; s < C::NKS; ++s) a = Tr<CT>::mma(read_rowfrag<CT>(kimg, C::STRIDE, 16 * n, s, lane), qf[s], a);
             st[n] = a;
+            if constexpr (AM) st[n] += am4[n];
         }
         const int jb = kt * KT + 4 * g;                // key of element (n, r) is jb + 16n + r
         if (kt * KT + KT > lim_min) {                  // wave-uniform: only tiles that touch the mask edge pay for it
@@ -349,9 +383,9 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float m_new = fmaxf(m_run, mx);
-        // KM: a query may have met no visible key yet (holes in front): keep the exponents finite, every p is exp2(-inf) = 0
+        // KM / AM: a query may have met no visible key yet (holes in front): keep the exponents finite, every p is exp2(-inf) = 0
         float m_use = m_new;
-        if constexpr (KM) m_use = m_new == -INFINITY ? 0.f : m_new;
+        if constexpr (KM || AM) m_use = m_new == -INFINITY ? 0.f : m_new;
         const float alpha = fast_exp2((m_run - m_use) * LOG2E);
         const float mneg = -m_use * LOG2E;
         m_run = m_new;
@@ -465,8 +499,11 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 // every key / value-side product factors through [rows, S] matrices (engine.EncoderGroupPlan, "low-rank key side").
 // A separate instantiation: the stores would cost the T = S = 512 launches registers.
 // KM: per-key mask, staged as in the forward block (KTQ bytes of LDS behind the images).
-template <typename CT, int DHP, bool XP, bool KM>
-BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km) {
+// AM: additive mask, read as in the forward block (one float4 per 4 keys of the lane's query row) and added to the score
+// before lse is subtracted: a -inf entry gives exp2(-inf) = 0 whatever lse is, so no guard is needed here.
+template <typename CT, int DHP, bool XP, bool KM, bool AM = false>
+BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const AMask km,
+                               const AAdd am = AAdd{nullptr, 0}) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
@@ -537,6 +574,8 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
         kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
         if constexpr (KM) stage_mask(0);
     }
+    const float* arow = nullptr;                       // AM: this lane's mask row
+    if constexpr (AM) arow = am.m + (size_t)min(q, P.T - 1) * am.ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -547,6 +586,15 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
         if (kt + 1 < ntile) {
             kst.load(Kh, (kt + 1) * C::KTQ, P.S, tid); vst.load(Vh, (kt + 1) * C::KTQ, P.S, tid);
             if constexpr (KM) stage_mask(kt + 1);
+        }
+        f32x4 am4[C::KTQ / 16];                        // AM: mask of keys kt * KTQ + 16n + 4g + (0..3)
+        if constexpr (AM) {
+#pragma unroll
+            for (int n = 0; n < C::KTQ / 16; ++n) {
+                const int jc = kt * C::KTQ + 16 * n + 4 * g;    // jc % 4 == 0 and ldm % 4 == 0: jc < S implies jc + 3 < ldm
+                am4[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (q < P.T && jc < P.S) am4[n] = *(const f32x4*)(arow + jc);
+            }
         }
         bool k_all = true;                             // KM: every key of the tile is visible (wave-uniform)
         if constexpr (KM) {
@@ -571,6 +619,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
                     s_ = Tr<CT>::mma(read_rowfrag<CT>(kimg, C::STRIDE, 16 * n, s, lane), qf[s], s_);
                     dp = Tr<CT>::mma(read_rowfrag<CT>(vimg, C::STRIDE, 16 * n, s, lane), dof[s], dp);
                 }
+                if constexpr (AM) s_ += am4[n];
                 float dm[4] = {1.f, 1.f, 1.f, 1.f};
                 if (dropping) {
                     if (pair_ok) {
@@ -678,8 +727,12 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 // KM: per-key mask.  A lane owns one key: its byte is read once (never at j >= S); a hidden key sees no query row
 // (ilo past every row), so its probabilities are exp2(-inf) = 0 and its dK / dV rows are exact zeros.  A block without
 // any visible key skips its query tiles.
-template <typename CT, int DHP, bool KM>
-BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int kb, const AMask km) {
+// AM: additive mask through its transpose (AAdd holds maskT [S, ldt]): the lane's key row, one float4 per 4 queries of a
+// register group, never read at j >= S or at a group that starts at i >= T.  A -inf entry gives probability 0, so the
+// pair adds exactly nothing to dK / dV.
+template <typename CT, int DHP, bool KM, bool AM = false>
+BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int kb, const AMask km,
+                                const AAdd am = AAdd{nullptr, 0}) {
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* qimg = smem;
@@ -741,6 +794,8 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
         n_del = ok ? dl : 0.f;
     };
     if (qt_lo < qt_hi) stage(qt_lo);
+    const float* acol = nullptr;                       // AM: this lane's row of the transposed mask
+    if constexpr (AM) acol = am.m + (size_t)min(j, P.S - 1) * am.ld;
 #pragma unroll 1
     for (int qt = qt_lo; qt < qt_hi; ++qt) {
         __syncthreads();
@@ -749,6 +804,15 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
         if (tid < C::QTK) { s_lse[tid] = n_lse; s_del[tid] = n_del; }
         __syncthreads();
         if (qt + 1 < qt_hi) stage(qt + 1);
+        f32x4 am4[C::QTK / 16];                        // AM: mask of queries qt * QTK + 16u + 4g + (0..3) against key j
+        if constexpr (AM) {
+#pragma unroll
+            for (int u = 0; u < C::QTK / 16; ++u) {
+                const int ic = qt * C::QTK + 16 * u + 4 * g;    // ic % 4 == 0 and ldt % 4 == 0: ic < T implies ic + 3 < ldt
+                am4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (j < P.S && ic < P.T) am4[u] = *(const f32x4*)(acol + ic);
+            }
+        }
         const bool edge = (qt * C::QTK < ilo_max) || (qt * C::QTK + C::QTK > P.T);
         // one k-step of the dV / dK products (32 queries in bf16, 16 in f32) at a time: its scores, probabilities and
         // dS live only until its MFMAs (half the registers of doing the whole 64-query tile first)
@@ -765,6 +829,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
                     s_ = Tr<CT>::mma(read_rowfrag<CT>(qimg, C::STRIDE, 16 * u, s, lane), kf[s], s_);
                     dp = Tr<CT>::mma(read_rowfrag<CT>(doimg, C::STRIDE, 16 * u, s, lane), vf[s], dp);
                 }
+                if constexpr (AM) s_ += am4[u];
                 const f32x4 l4 = *(const f32x4*)(s_lse + 16 * u + 4 * g);
                 const f32x4 d4 = *(const f32x4*)(s_del + 16 * u + 4 * g);
                 const int ib = qt * C::QTK + 16 * u + 4 * g;       // query of element r is ib + r
@@ -868,6 +933,43 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 }
 
 // ---------------------------------------------------------------------------
+// the three kernels with an additive mask (bpm_attn_fwd_amask / _bwd_dq_amask / _bwd_dkv_amask)
+// ---------------------------------------------------------------------------
+// The same schedules, compiled for the occupancy of their unmasked siblings: the tile's mask values are 16 more live
+// registers (8 in the 32-row tiles of head_dim 256), which the allocator finds in 21 of the 24 instantiations without
+// scratch.  bf16 dK / dV at head_dim 64 spills 20 bytes per lane at three waves and bf16 dQ at 128 spills 32 at three:
+// measured at the first (MI355X, T = S = 512, all-zeros mask) 134 us at three waves against 146 - 151 at two without
+// spills, so both stay.  f32 dK / dV at head_dim 128 would spill 228 bytes at two waves: that one is compiled for one.
+template <typename CT>
+constexpr int attn_waves_am(int kernel, int dhp) {
+    return (sizeof(CT) == 4 && kernel == 2 && dhp == 128) ? 1 : attn_waves<CT>(kernel, dhp);
+}
+
+template <typename CT, int DHP, int WHICH>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves_am<CT>(WHICH, DHP), attn_waves_am<CT>(WHICH, DHP)))) void attn_amask_kernel(const AGroupA ga) {
+    typedef Cfg<CT, DHP> C;
+    constexpr int ROWS = WHICH == 0 ? KT : WHICH == 1 ? C::KTQ : C::QTK;
+    __shared__ __attribute__((aligned(16))) char smem[2 * ROWS * C::STRIDE + (WHICH == 2 ? 2 * C::QTK * 4 : 0)];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(ga.g, bid);
+    const AProb& P = ga.g.p[pi];
+    const AAdd am = ga.m[pi];
+    const DropCfg drop = bpm_resolve_drop(P.drop, ga.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2;
+    const int first = (P.pair || WHICH == 2) ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        const int blk = pass ? second : first;
+        if constexpr (WHICH == 0) attn_fwd_block<CT, DHP, false, true>(P, drop, smem, bh, blk, AMask{nullptr, 0}, am);
+        else if constexpr (WHICH == 1) attn_bwd_dq_block<CT, DHP, false, false, true>(P, drop, smem, bh, blk, AMask{nullptr, 0}, am);
+        else attn_bwd_dkv_block<CT, DHP, false, true>(P, drop, smem, bh, blk, AMask{nullptr, 0}, am);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // head-averaged attention maps: W[b][i][j] = (1/H) sum_h exp(S_h[i][j] - LSE_h[i])  (0 for a masked key)
 // ---------------------------------------------------------------------------
 // The probabilities before dropout, recomputed from the Q / K images and the LSE a forward pass left (what the backward
@@ -886,11 +988,12 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
 //   bf16  74 / 88 / 116 / 166  ->  4, 4, 4, 3 waves        f32  92 / 116 / 168 / 296  ->  4, 4, 3, 1 waves
 // (f32 at 256: 64 + 64 K-fragment and 64 staging registers; 14 registers spill at two waves, none at one -- the
 // parity-mode corner).  No instantiation spills: scratch size 0 in the gfx950 assembly of all eight.
+// With an additive mask (am) the tile's 16 mask registers spill at three waves (bf16 at 256: 60 bytes, f32 at 128: 52): two.
 template <typename CT>
-constexpr int map_waves(int dhp) {
+constexpr int map_waves(int dhp, bool am = false) {
     const bool bf = sizeof(CT) == 2;
     if (dhp <= 64 || (bf && dhp <= 128)) return 4;
-    if (dhp <= 128 || bf) return 3;
+    if (dhp <= 128 || bf) return am ? 2 : 3;
     return 1;
 }
 constexpr int MQT = 64;     // queries per tile of the maps kernel
@@ -908,8 +1011,19 @@ struct MGroup {
     MProb p[BPM_MAX_GROUP];
 };
 
-template <typename CT, int DHP>
-__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<CT>(DHP), map_waves<CT>(DHP)))) void attn_maps_kernel(const MGroup grp) {
+// AM (bpm_attn_maps_amask): the additive mask through its transpose, as in the dK / dV kernel (lane = key, four queries
+// per register group).  The tile's mask values are the same for every head: loaded once, before the head loop.
+struct MGroupA {
+    MGroup g;
+    AAdd m[BPM_MAX_GROUP];
+};
+static_assert(sizeof(MGroupA) <= 4096, "kernel arguments are limited to 4 KiB");
+BPM_DEV const MGroup& map_group(const MGroup& g) { return g; }
+BPM_DEV const MGroup& map_group(const MGroupA& g) { return g.g; }
+
+template <typename CT, int DHP, bool AM = false>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<CT>(DHP, AM), map_waves<CT>(DHP, AM)))) void attn_maps_kernel(const std::conditional_t<AM, MGroupA, MGroup> ga) {
+    const MGroup& grp = map_group(ga);
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     __shared__ __attribute__((aligned(16))) char smem[MQT * C::STRIDE + MQT * 4];
@@ -944,6 +1058,17 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_wa
     for (int u = 0; u < MQT / 16; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (i_first < i_end) {                              // block-uniform: a fully masked tile keeps its zeros
+        f32x4 am4[MQT / 16];                            // AM: mask of queries i0 + 16u + 4g + (0..3) against key j
+        if constexpr (AM) {
+            const AAdd am = ga.m[pi];
+            const float* acol = am.m + (size_t)min(j, P.S - 1) * am.ld;
+#pragma unroll
+            for (int u = 0; u < MQT / 16; ++u) {
+                const int ic = i0 + 16 * u + 4 * g;     // ic % 4 == 0 and ldt % 4 == 0: ic < T implies ic + 3 < ldt
+                am4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (j < P.S && ic < P.T) am4[u] = *(const f32x4*)(acol + ic);
+            }
+        }
         RowStage<CT, DHP, MQT> qst;
         frag kn[C::NKS];
         float n_lse = 0.f;
@@ -975,6 +1100,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_wa
                 f32x4 s_ = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < C::NKS; ++s) s_ = Tr<CT>::mma(read_rowfrag<CT>(qimg, C::STRIDE, 16 * u, s, lane), kf[s], s_);
+                if constexpr (AM) s_ += am4[u];
                 const f32x4 l4 = *(const f32x4*)(s_lse + 16 * u + 4 * g);
                 const int ib = i0 + 16 * u + 4 * g;                 // query row of element r is ib + r
                 f32x4 e4 = s_ * LOG2E + l4;
@@ -1152,6 +1278,74 @@ int attn_kmask(int which, int kind, int dtype, const bpm_attn_problem* probs, co
     return dtype == BPM_BF16 ? dispatch_kmask<bf16_t>(which, probs[0].dhp, gk, total, s) : dispatch_kmask<float>(which, probs[0].dhp, gk, total, s);
 }
 
+// the additive-mask kernels (which: 0 forward, 1 dQ, 2 dK / dV)
+template <typename CT>
+int dispatch_amask(int which, int dhp, const AGroupA& g, int total, hipStream_t s) {
+    dim3 grid(total), block(NTHREADS);
+#define BPM_ATTN_ACASE(D)                                                                                       \
+    case D:                                                                                                     \
+        if (which == 0) hipLaunchKernelGGL((attn_amask_kernel<CT, D, 0>), grid, block, 0, s, g);                \
+        else if (which == 1) hipLaunchKernelGGL((attn_amask_kernel<CT, D, 1>), grid, block, 0, s, g);           \
+        else hipLaunchKernelGGL((attn_amask_kernel<CT, D, 2>), grid, block, 0, s, g);                           \
+        break;
+    switch (dhp) {
+        BPM_ATTN_ACASE(32)
+        BPM_ATTN_ACASE(64)
+        BPM_ATTN_ACASE(128)
+        BPM_ATTN_ACASE(256)
+        default: return BPM_ERR_ARG;
+    }
+#undef BPM_ATTN_ACASE
+    BPM_CHECK_LAUNCH();
+    return 0;
+}
+
+// One additive mask as a kernel reads it: `transposed` false: (mask, ldm) against [T, S]; true: (maskT, ldt) against [S, T].
+// The forward-oriented array must be there in every entry (it is the mask; maskT only restates it).  float4 reads: the
+// base 16-byte aligned, the leading dimension a multiple of 4.
+int amask_desc(AAdd& a, const bpm_attn_amask& m, int T, int S, bool transposed) {
+    if (!m.mask || m.ldm < S || (m.ldm & 3) || ((uintptr_t)m.mask & 15)) return BPM_ERR_ARG;
+    if (transposed && (!m.maskT || m.ldt < T || (m.ldt & 3) || ((uintptr_t)m.maskT & 15))) return BPM_ERR_ARG;
+    a.m = transposed ? m.maskT : m.mask;
+    a.ld = transposed ? m.ldt : m.ldm;
+    return 0;
+}
+
+// host checks + argument block of one *_amask launch (which: 0 forward, 1 dQ, 2 dK / dV); nothing is launched on an error
+int fill_amask(AGroupA& ga, int dtype, const bpm_attn_problem* probs, const bpm_attn_amask* masks, int nprob, uint64_t seed, int* total,
+               int which) {
+    if (dtype != BPM_BF16 && dtype != BPM_F32) return BPM_ERR_ARG;
+    if (!masks) return BPM_ERR_ARG;
+    int rc = fill(ga.g, probs, nprob, which == 2, seed, total, which);
+    if (rc) return rc;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        if (!q.Q || !q.K || !q.V || !q.O || !q.lse) return BPM_ERR_ARG;
+        if (which != 0 && (!q.dO || !q.delta)) return BPM_ERR_ARG;
+        if (which == 1 && !q.dQ) return BPM_ERR_ARG;
+        if (which == 2 && (!q.dK || !q.dV)) return BPM_ERR_ARG;
+        if (q.dS || q.Pd) return BPM_ERR_ARG;                    // the score-gradient export has no masked instantiation
+        rc = amask_desc(ga.m[i], masks[i], q.T, q.S, which == 2);
+        if (rc) return rc;
+    }
+    for (int i = nprob; i < BPM_MAX_GROUP; ++i) { ga.m[i].m = nullptr; ga.m[i].ld = 0; }
+    return 0;
+}
+
+int attn_amask(int which, int kind, int dtype, const bpm_attn_problem* probs, const bpm_attn_amask* masks, int nprob, uint64_t seed,
+               void* stream) {
+    AGroupA ga;
+    int total = 0;
+    int rc = fill_amask(ga, dtype, probs, masks, nprob, seed, &total, which);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int sz = dtype == BPM_BF16 ? 2 : 4;
+    double mbytes = 0;                                           // every head of a problem reads the whole mask once (L2 serves the repeats)
+    for (int i = 0; i < nprob; ++i) mbytes += 4.0 * probs[i].T * probs[i].S;
+    BpmProfScope prof(kind, s, 4.0 * useful_pair_flops(probs, nprob), attn_bytes(probs, nprob, sz, which) + mbytes);
+    return dtype == BPM_BF16 ? dispatch_amask<bf16_t>(which, probs[0].dhp, ga, total, s) : dispatch_amask<float>(which, probs[0].dhp, ga, total, s);
+}
+
 }  // namespace
 
 #ifdef BPM_LAB
@@ -1229,12 +1423,26 @@ extern "C" int bpm_attn_bwd_dkv_kmask(int dtype, const bpm_attn_problem* probs, 
     return attn_kmask(2, BPM_K_ATTN_BWD_DKV, dtype, probs, masks, nprob, seed, stream);
 }
 
-// Head-averaged attention probabilities of finished forward passes (see attn_maps_kernel).
-extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int nprob, void* stream) {
+// Attention with an additive [T, S] mask (the reference's attn_mask argument): see bpm_attn_amask in include/bpmult_hip.h.
+extern "C" int bpm_attn_fwd_amask(int dtype, const bpm_attn_problem* probs, const bpm_attn_amask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_amask(0, BPM_K_ATTN_FWD, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dq_amask(int dtype, const bpm_attn_problem* probs, const bpm_attn_amask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_amask(1, BPM_K_ATTN_BWD_DQ, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dkv_amask(int dtype, const bpm_attn_problem* probs, const bpm_attn_amask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_amask(2, BPM_K_ATTN_BWD_DKV, dtype, probs, masks, nprob, seed, stream);
+}
+
+// Head-averaged attention probabilities of finished forward passes (see attn_maps_kernel); masks: the additive masks of
+// bpm_attn_maps_amask (read through their transposes), or nullptr.
+static int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_amask* masks, bool with_masks, int nprob, void* stream) {
     if (nprob < 1 || nprob > BPM_MAX_GROUP || !probs) return BPM_ERR_ARG;
     if (dtype != BPM_BF16 && dtype != BPM_F32) return BPM_ERR_ARG;
+    if (with_masks && !masks) return BPM_ERR_ARG;
     const int sz = dtype == BPM_BF16 ? 2 : 4;
-    MGroup g;
+    MGroupA ga;
+    MGroup& g = ga.g;
     g.nprob = nprob;
     long blk = 0;
     double flops = 0, bytes = 0;
@@ -1260,14 +1468,23 @@ extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int n
         const double ts = (double)q.B * q.T * q.S;
         flops += 2.0 * ts * q.H * q.dh;
         bytes += (double)q.B * q.H * ((double)(q.T + q.S) * q.dh * sz + q.T * 4.0) + ts * 4.0;      // Q, K, lse in; W out
+        if (with_masks) {
+            const int rc = amask_desc(ga.m[i], masks[i], q.T, q.S, true);
+            if (rc) return rc;
+            bytes += 4.0 * q.T * q.S;
+        }
     }
+    for (int i = with_masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) { ga.m[i].m = nullptr; ga.m[i].ld = 0; }
     hipStream_t s = (hipStream_t)stream;
     BpmProfScope prof(BPM_K_ATTN_MAPS, s, flops, bytes);
     dim3 grid((unsigned)blk), block(NTHREADS);
 #define BPM_MAPS_CASE(D)                                                                                         \
     case D:                                                                                                      \
-        if (dtype == BPM_BF16) hipLaunchKernelGGL((attn_maps_kernel<bf16_t, D>), grid, block, 0, s, g);          \
-        else hipLaunchKernelGGL((attn_maps_kernel<float, D>), grid, block, 0, s, g);                             \
+        if (with_masks) {                                                                                        \
+            if (dtype == BPM_BF16) hipLaunchKernelGGL((attn_maps_kernel<bf16_t, D, true>), grid, block, 0, s, ga);   \
+            else hipLaunchKernelGGL((attn_maps_kernel<float, D, true>), grid, block, 0, s, ga);                  \
+        } else if (dtype == BPM_BF16) hipLaunchKernelGGL((attn_maps_kernel<bf16_t, D, false>), grid, block, 0, s, g);   \
+        else hipLaunchKernelGGL((attn_maps_kernel<float, D, false>), grid, block, 0, s, g);                      \
         break;
     switch (probs[0].dhp) {
         BPM_MAPS_CASE(32)
@@ -1279,4 +1496,11 @@ extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int n
 #undef BPM_MAPS_CASE
     BPM_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int nprob, void* stream) {
+    return attn_maps_impl(dtype, probs, nullptr, false, nprob, stream);
+}
+extern "C" int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_amask* masks, int nprob, void* stream) {
+    return attn_maps_impl(dtype, probs, masks, true, nprob, stream);
 }

@@ -1,0 +1,310 @@
+"""`MultiheadAttention` with the reference's constructor, call signature and state_dict layout
+(bpmult/models/multihead_attention.py:17-135), executed on the HIP path.
+
+forward(query, key, value, attn_mask) is one autograd node.  Its launches are those of the engine's self-attention
+block (engine.py: _proj, _self_attn_fwd / _self_attn_bwd):
+
+  forward   rows_cast            query / key / value -> CT rows (one problem per distinct input)
+            gemm NT (grouped)    Q (alpha = dh^-0.5), K, V projections of in_proj_weight, OUT_HEADS epilogue
+            attn_fwd[_amask]     softmax(q k^T + attn_mask) v, dropout on the probabilities
+            gemm NT              out_proj
+            attn_maps[_amask]    the head-averaged weights (need_weights only)
+  backward  rows_cast            d(attn) -> CT, column sums = d(out_proj.bias)
+            gemm TN / NN         d(out_proj.weight); d(attention output), OUT_HEADS
+            attn_bwd_dq / _dkv   [_amask]
+            gemm TN (grouped)    the three row blocks of d(in_proj_weight), d(in_proj_bias) as colsum_a
+            gemm NN (grouped)    d(query), d(key), d(value)
+
+The parameters stay PyTorch's; their CT shadows are re-packed (bpm_pack_weights) when a version counter moves, the rule
+of models/bert.py with text_params = "torch".  An arbitrary additive mask is copied once into the layout the kernels read
+(rows padded to 4 columns, plus its transpose for the dK / dV and maps kernels) and kept until the tensor's data_ptr or
+_version changes.  The mask gets no gradient; add_bias_kv / add_zero_attn are refused.  No torch compute op runs here.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple
+
+import torch
+from torch import nn
+
+from .. import config, ops
+from .._lib import F_KPAD, GEMM_NN, GEMM_NT, GEMM_TN, OUT_HEADS, PackDesc
+from ..ops import pad32
+
+S_MHA_PROBS = 0x4d4841            # dropout site of the probabilities (any constant: the seed differs per call)
+
+
+def _dhp_for(dh: int) -> int:
+    for p in (32, 64, 128, 256):
+        if dh <= p:
+            return p
+    raise ValueError(f"MultiheadAttention: head_dim {dh} > 256 has no HIP attention kernel")
+
+
+class _Plan:
+    """Activation buffers of one (T, S, B, call form).  CT buffers are zero-initialised once: the launches write the
+    embed_dim / head_dim columns only, the pad columns stay zero (the GEMMs read whole padded rows)."""
+
+    def __init__(self, ex: "_Exec", T: int, S: int, B: int, form: str):
+        self.T, self.S, self.B, self.form = T, S, B, form
+        self.stamp = 0
+        d, ld, H, dhp, dev = ex.d, ex.ld, ex.H, ex.dhp, ex.device
+        ct = ops.ct_torch(ex.dtype)
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, device=dev, dtype=dt)
+        self.xq = z(T * B, ld, dt=ct)
+        self.xk = self.xq if form == "qkv" else z(S * B, ld, dt=ct)
+        self.xv = self.xk if form in ("qkv", "kv") else z(S * B, ld, dt=ct)
+        self.q, self.k, self.v = z(B, H, T, dhp, dt=ct), z(B, H, S, dhp, dt=ct), z(B, H, S, dhp, dt=ct)
+        self.o, self.lse = z(T * B, ld, dt=ct), z(B, H, T)
+        # backward
+        self.dy, self.dao, self.delta = z(T * B, ld, dt=ct), z(B, H, T, dhp, dt=ct), z(B, H, T)
+        self.dq, self.dk, self.dv = z(T * B, ld, dt=ct), z(S * B, ld, dt=ct), z(S * B, ld, dt=ct)
+        self.mask = None             # (ops.attn_amasks array, the tensors it points into) of the forward pass; None: no attn_mask
+        self.seed, self.drop_p = 0, 0.0
+
+
+class _Exec:
+    """Host driver of one module on one device and precision: CT weight shadows, plans, the mask cache."""
+
+    def __init__(self, mod: "MultiheadAttention", device: torch.device, prec: str):
+        if config.is_x3(prec):
+            raise ValueError("MultiheadAttention: precision 'bf16x3' is not available for the stand-alone module (its split "
+                             "images belong to an engine plan); use 'bf16' or 'f32'")
+        self.device, self.prec, self.dtype = device, prec, config.dtype_code(prec)
+        self.d, self.H, self.dh = mod.embed_dim, mod.num_heads, mod.head_dim
+        self.ld, self.dhp, self.scale = pad32(self.d), _dhp_for(self.dh), mod.head_dim ** -0.5
+        self.params = [p for p in (mod.in_proj_weight, mod.in_proj_bias, mod.out_proj.weight, mod.out_proj.bias) if p is not None]
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
+                raise RuntimeError("MultiheadAttention: parameters must be contiguous float32 tensors on the inputs' device")
+        self.key = (str(device), prec, tuple(p.data_ptr() for p in self.params))
+        d, ld = self.d, self.ld
+        ct = ops.ct_torch(self.dtype)
+        self.shadow = torch.zeros(4 * d * ld, device=device, dtype=ct)        # in_proj_weight [3d, ld] | out_proj.weight [d, ld]
+        descs, blk = [], 0
+        for src, off, rows in ((mod.in_proj_weight, 0, 3 * d), (mod.out_proj.weight, 3 * d * ld, d)):
+            pd = PackDesc()
+            pd.src, pd.dst = src.data_ptr(), self.shadow.data_ptr() + self.shadow.element_size() * off
+            pd.rows, pd.cols, pd.ld, pd.src_ld, pd.dst_ld, pd.blk0 = rows, d, ld, d, ld, blk
+            pd.colscale = None
+            blk += (rows * ld + 1023) // 1024
+            descs.append(pd)
+        self._pack = (ops.device_table(descs), len(descs), blk)
+        self._versions = None
+        self.plans: Dict[Tuple[int, int, int, str], _Plan] = {}
+        self._mask_key, self._mask = None, None
+
+    def wptr(self, which: int) -> int:
+        """Shadow of in_proj_weight rows [which d, (which + 1) d) (0 Q, 1 K, 2 V) or of out_proj.weight (3)."""
+        return self.shadow.data_ptr() + self.shadow.element_size() * which * self.d * self.ld
+
+    def refresh_shadows(self) -> None:
+        sig = tuple(p._version for p in self.params)
+        if sig != self._versions:
+            ops.pack_weights(self.dtype, *self._pack)
+            self._versions = sig
+
+    def plan(self, T: int, S: int, B: int, form: str) -> _Plan:
+        key = (T, S, B, form)
+        pl = self.plans.get(key)
+        if pl is None:
+            pl = self.plans[key] = _Plan(self, T, S, B, form)
+        return pl
+
+    def mask_for(self, attn_mask: torch.Tensor, T: int, S: int):
+        """The kernels' copy of attn_mask: fp32 [T, ldm] and its transpose [S, ldt], leading dimensions rounded up to 4
+        (pad columns are never used: zeros); rebuilt when the tensor's storage or version counter changes."""
+        key = (attn_mask.data_ptr(), attn_mask._version, tuple(attn_mask.shape), tuple(attn_mask.stride()), attn_mask.dtype, str(attn_mask.device))
+        if key != self._mask_key:
+            ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
+            m = torch.zeros(T, ldm, device=self.device)
+            mt = torch.zeros(S, ldt, device=self.device)
+            m[:, :S].copy_(attn_mask.detach())
+            mt[:, :T].copy_(attn_mask.detach().t())
+            # the source tensor is held too: while it lives, its address cannot name another tensor
+            self._mask = (ops.attn_amasks([(m, ldm, mt, ldt)]), m, mt, attn_mask)
+            self._mask_key = key
+        return self._mask
+
+    # -- forward -------------------------------------------------------------------------------------------------------
+    def forward(self, mod, query, key, value, form, attn_mask, need_weights, seed, training):
+        T, B, d = query.shape
+        S = key.shape[0]
+        self.refresh_shadows()
+        pl = self.plan(T, S, B, form)
+        pl.stamp += 1
+        dt, ld, H, dh, dhp = self.dtype, self.ld, self.H, self.dh, self.dhp
+        pl.mask = None if attn_mask is None else self.mask_for(attn_mask, T, S)
+        pl.seed, pl.drop_p = seed, (mod.attn_dropout if training else 0.0)
+        casts = [ops.cast_problem(query, d, T * B, d, dst_ct=pl.xq, ldd=ld)]
+        if form != "qkv":
+            casts.append(ops.cast_problem(key, d, S * B, d, dst_ct=pl.xk, ldd=ld))
+        if form == "sep":
+            casts.append(ops.cast_problem(value, d, S * B, d, dst_ct=pl.xv, ldd=ld))
+        ops.rows_cast(dt, casts, 0)
+        bias = mod.in_proj_bias
+        proj = [ops.gemm_problem(x, self.wptr(w), out, L * B, d, d, ld, ld, 0, bias_n=None if bias is None else bias[w * d:(w + 1) * d],
+                                 alpha=self.scale if w == 0 else 1.0, out_kind=OUT_HEADS, heads=(B, H, L, dh, dhp), flags=F_KPAD)
+                for w, (x, out, L) in enumerate(((pl.xq, pl.q, T), (pl.xk, pl.k, S), (pl.xv, pl.v, S)))]
+        ops.gemm_grouped(dt, GEMM_NT, proj, seed)
+        ap = [ops.attn_problem(pl.q, pl.k, pl.v, pl.o, ld, pl.lse, B, H, T, S, dh, dhp, 0, drop_p=pl.drop_p, drop_site=S_MHA_PROBS)]
+        if pl.mask is None:
+            ops.attn_fwd(dt, ap, seed)
+        else:
+            ops.attn_fwd_amask(dt, ap, pl.mask[0], seed)
+        out = torch.empty(T, B, d, device=self.device)
+        ops.gemm_grouped(dt, GEMM_NT, [ops.gemm_problem(pl.o, self.wptr(3), out, T * B, d, d, ld, ld, d, bias_n=mod.out_proj.bias,
+                                                        flags=F_KPAD)], seed)
+        weights = None
+        if need_weights:
+            weights = torch.empty(B, T, S, device=self.device)
+            mp = [ops.attn_map_problem(pl.q, pl.k, pl.lse, weights, S, B, H, T, S, dh, dhp, 0)]
+            if pl.mask is None:
+                ops.attn_maps(dt, mp)
+            else:
+                ops.attn_maps_amask(dt, mp, pl.mask[0])
+        return out, weights, pl
+
+    # -- backward ------------------------------------------------------------------------------------------------------
+    def backward(self, mod, pl: _Plan, dout: torch.Tensor):
+        """dout fp32 [T, B, d] -> d(query), d(key), d(value), and the parameter gradients in self.params order: fresh
+        tensors every call (autograd may keep them as .grad)."""
+        T, S, B = pl.T, pl.S, pl.B
+        dt, d, ld, H, dh, dhp, seed, dev = self.dtype, self.d, self.ld, self.H, self.dh, self.dhp, pl.seed, self.device
+        has_bias = mod.in_proj_bias is not None
+        g_ipw, g_wo = torch.empty(3 * d, d, device=dev), torch.empty(d, d, device=dev)       # written by their launches
+        g_ipb = torch.zeros(3 * d, device=dev) if has_bias else None                           # accumulated into: zeroed
+        g_ob = torch.zeros(d, device=dev) if mod.out_proj.bias is not None else None
+        ops.rows_cast(dt, [ops.cast_problem(dout, d, T * B, d, dst_ct=pl.dy, ldd=ld, colsum=g_ob)], 0)
+        ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy, pl.o, g_wo, d, d, T * B, ld, ld, d, flags=F_KPAD)], seed)
+        ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy, self.wptr(3), pl.dao, T * B, d, d, ld, ld, 0, out_kind=OUT_HEADS,
+                                                        heads=(B, H, T, dh, dhp), flags=F_KPAD)], seed)
+        ap = [ops.attn_problem(pl.q, pl.k, pl.v, pl.o, ld, pl.lse, B, H, T, S, dh, dhp, 0, dO=pl.dao, delta=pl.delta, dQ=pl.dq, lddq=ld,
+                               dK=pl.dk, lddk=ld, dV=pl.dv, lddv=ld, dq_scale=self.scale, drop_p=pl.drop_p, drop_site=S_MHA_PROBS)]
+        if pl.mask is None:
+            ops.attn_bwd_dq(dt, ap, seed)
+            ops.attn_bwd_dkv(dt, ap, seed)
+        else:
+            ops.attn_bwd_dq_amask(dt, ap, pl.mask[0], seed)
+            ops.attn_bwd_dkv_amask(dt, ap, pl.mask[0], seed)
+        sides = ((pl.dq, pl.xq, T), (pl.dk, pl.xk, S), (pl.dv, pl.xv, S))
+        ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(g, x, g_ipw.data_ptr() + 4 * w * d * d, d, d, L * B, ld, ld, d, flags=F_KPAD,
+                                                        colsum_a=g_ipb.data_ptr() + 4 * w * d if has_bias else None)
+                                       for w, (g, x, L) in enumerate(sides)], seed)
+        dx = [torch.empty(L, B, d, device=dev) for L in (T, S, S)]
+        ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(g, self.wptr(w), dx[w], L * B, d, d, ld, ld, d, flags=F_KPAD)
+                                       for w, (g, _, L) in enumerate(sides)], seed)
+        grads = [g for g in (g_ipw, g_ipb, g_wo, g_ob) if g is not None]
+        return dx[0], dx[1], dx[2], grads
+
+
+class _MhaFn(torch.autograd.Function):
+    """The whole call as one autograd node: (query, key, value, parameters) -> (attn, head-averaged weights or None)."""
+
+    @staticmethod
+    def forward(ctx, query, key, value, mod, ex, form, attn_mask, need_weights, seed, *params):
+        out, weights, plan = ex.forward(mod, query.detach().contiguous(), key.detach().contiguous(), value.detach().contiguous(), form,
+                                        attn_mask, need_weights, seed, mod.training)
+        ctx.mod, ctx.ex, ctx.plan, ctx.stamp = mod, ex, plan, plan.stamp
+        if weights is None:
+            return out, None
+        ctx.mark_non_differentiable(weights)
+        return out, weights
+
+    @staticmethod
+    def backward(ctx, dout, _dweights=None):
+        if ctx.stamp != ctx.plan.stamp:
+            raise RuntimeError("MultiheadAttention (HIP path): backward() of a forward pass that a later forward pass of the same "
+                               "shape has overwritten; run forward -> backward one call at a time")
+        dq, dk, dv, grads = ctx.ex.backward(ctx.mod, ctx.plan, dout.contiguous().float())
+        need = ctx.needs_input_grad
+        return ((dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None, None)
+                + tuple(g if n else None for g, n in zip(grads, need[9:])))
+
+
+class MultiheadAttention(nn.Module):
+    """Drop-in for bpmult.models.multihead_attention.MultiheadAttention (packed in-projection, :17-50).
+
+    forward(query, key, value, attn_mask=None, need_weights=True) -> (attn [T, B, d], weights [B, T, S] or None) on
+    [T,B,d] / [S,B,d] fp32 CUDA (HIP) tensors, in the reference's three call forms (query is key is value; key is value;
+    three tensors).  attn_mask: None or a float [T, S] tensor added to the scores of every head (-inf hides a pair; every
+    row must keep a visible key, or it is NaN as in the reference); it gets no gradient (requires_grad: ValueError).
+    One stated difference: `weights` are the head-averaged softmax probabilities BEFORE attention dropout, detached --
+    equal to the reference's in eval mode and whenever attn_dropout == 0 (in training with dropout the reference returns
+    the dropped, rescaled matrix); the departure TransformerEncoder.attention_maps() makes.  need_weights=False (an
+    extension) launches nothing for them and returns None.  add_bias_kv / add_zero_attn are not supported (ValueError).
+    Precision: the `precision` attribute, or config.precision() when it is None ('bf16' or 'f32').
+    TransformerEncoder constructs this class as a parameter container and runs its own grouped engine plan."""
+
+    def __init__(self, embed_dim: int, num_heads: int, attn_dropout: float = 0.0, bias: bool = True, add_bias_kv: bool = False,
+                 add_zero_attn: bool = False):
+        super().__init__()
+        if add_bias_kv or add_zero_attn:
+            raise ValueError("MultiheadAttention: add_bias_kv / add_zero_attn are not supported on the HIP path")
+        self.embed_dim, self.num_heads, self.attn_dropout = embed_dim, num_heads, attn_dropout
+        self.head_dim = embed_dim // num_heads
+        if self.head_dim * num_heads != embed_dim:
+            raise ValueError("embed_dim must be divisible by num_heads")
+        self.scaling = self.head_dim ** -0.5
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        if bias:
+            self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        else:
+            self.register_parameter("in_proj_bias", None)
+        self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
+        self.bias_k = self.bias_v = None
+        self.add_zero_attn = False
+        nn.init.xavier_uniform_(self.in_proj_weight)          # fan computed on the packed shape (:41-46)
+        nn.init.xavier_uniform_(self.out_proj.weight)
+        if bias:
+            nn.init.constant_(self.out_proj.bias, 0.0)
+        self.precision: Optional[str] = None                  # None -> config.precision() at first use
+        self._exec: Optional[_Exec] = None
+        self._step = 0
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)
+        self._exec = None                                     # .to() / .cuda(): plans, shadows and the mask copy go
+        return r
+
+    def invalidate_shadows(self) -> None:
+        """The next forward re-packs the CT weight shadows whatever the version counters say (after a write through
+        `p.data`, which moves none)."""
+        if self._exec is not None:
+            self._exec._versions = None
+
+    def _next_seed(self) -> int:                              # the formula of TransformerEncoder._next_seed
+        self._step += 1
+        return (torch.initial_seed() * 1000003 + self._step) & 0x7FFFFFFFFFFFFFFF
+
+    def _ensure_exec(self, device: torch.device) -> _Exec:
+        prec = self.precision or config.precision()
+        ex = self._exec
+        params = [p for p in (self.in_proj_weight, self.in_proj_bias, self.out_proj.weight, self.out_proj.bias) if p is not None]
+        if ex is None or ex.key != (str(device), prec, tuple(p.data_ptr() for p in params)):
+            ex = self._exec = _Exec(self, device, prec)
+        return ex
+
+    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True):
+        for t in (query, key, value):
+            if not t.is_cuda:
+                raise RuntimeError("MultiheadAttention: the HIP attention path needs CUDA (HIP) tensors; there is no CPU path")
+        if query.dim() != 3 or query.shape[2] != self.embed_dim:
+            raise ValueError(f"MultiheadAttention: query of shape {tuple(query.shape)}, expected [T, B, {self.embed_dim}]")
+        T, B, d = query.shape
+        if key.shape != value.shape or key.dim() != 3 or key.shape[1:] != (B, d):
+            raise ValueError(f"MultiheadAttention: key {tuple(key.shape)} / value {tuple(value.shape)}, expected two [S, {B}, {d}] tensors")
+        for t in (query, key, value):
+            if t.dtype != torch.float32:
+                raise ValueError(f"MultiheadAttention: expected float32 inputs, got {t.dtype}")
+        S = key.shape[0]
+        same = lambda a, b: a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
+        form = "qkv" if same(query, key) and same(key, value) else "kv" if same(key, value) else "sep"
+        if attn_mask is not None:
+            if not torch.is_tensor(attn_mask) or not attn_mask.is_floating_point() or tuple(attn_mask.shape) != (T, S):
+                raise ValueError(f"MultiheadAttention: attn_mask must be a float tensor of shape [{T}, {S}]")
+            if attn_mask.requires_grad:
+                raise ValueError("MultiheadAttention: attn_mask gets no gradient on the HIP path (requires_grad is set)")
+        ex = self._ensure_exec(query.device)
+        seed = self._next_seed()
+        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, *ex.params)

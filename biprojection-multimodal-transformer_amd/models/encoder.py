@@ -1,7 +1,9 @@
 """`TransformerEncoder` with the reference's constructor, forward signature and
 state_dict layout (bpmult/models/transformer.py:9-99), executed by the grouped
 HIP engine.  The sub-modules below are parameter containers that reproduce the
-reference's parameter names; none of them has a PyTorch forward.
+reference's parameter names; none of them has a PyTorch forward
+(MultiheadAttention, models/attention.py, has a HIP forward of its own that the
+encoder never calls).
 """
 from __future__ import annotations
 
@@ -13,23 +15,7 @@ from torch import nn
 
 from .. import config
 from ..engine import EncoderDesc, EncoderGroupPlan, GroupCfg, ParamStore, register_encoder_shadows
-
-
-class MultiheadAttention(nn.Module):
-    """Packed in-projection attention parameters (multihead_attention.py:17-50)."""
-
-    def __init__(self, embed_dim: int, num_heads: int, attn_dropout: float = 0.0):
-        super().__init__()
-        self.embed_dim, self.num_heads, self.attn_dropout = embed_dim, num_heads, attn_dropout
-        self.head_dim = embed_dim // num_heads
-        if self.head_dim * num_heads != embed_dim:
-            raise ValueError("embed_dim must be divisible by num_heads")
-        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
-        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
-        self.out_proj = nn.Linear(embed_dim, embed_dim, bias=True)
-        nn.init.xavier_uniform_(self.in_proj_weight)          # fan computed on the packed shape (:41-46)
-        nn.init.xavier_uniform_(self.out_proj.weight)
-        nn.init.constant_(self.out_proj.bias, 0.0)
+from .attention import MultiheadAttention          # a parameter container here: the encoder runs its own engine plan
 
 
 def _xavier_linear(i: int, o: int) -> nn.Linear:

@@ -395,6 +395,44 @@ def attn_maps(dtype: int, probs) -> None:
     _grouped("bpm_attn_maps", arr, (dtype,))
 
 
+def attn_amasks(masks) -> "C.Array":
+    """[(mask, ldm, maskT, ldt)] -> the host array of bpm_attn_amask the *_amask entries take beside the problems.  mask:
+    float32 device tensor [T, ldm] added to the scores of every head (-inf hides the pair; AND the problem's mask_off
+    rule), ldm >= S and a multiple of 4, 16-byte aligned; maskT: its transpose [S, ldt] under the same rules, which the
+    dK / dV and maps entries read (None, 0 for forward / dQ only).  Every query row needs a visible key (not checked)."""
+    arr = (_lib.AttnAMask * len(masks))()
+    for a, (m, ldm, mt, ldt) in zip(arr, masks):
+        a.mask, a.ldm, a.maskT, a.ldt = _f32(m, "additive attention mask"), ldm, _f32(mt, "additive attention mask (transpose)"), ldt
+    return arr
+
+
+def _attn_amask(name: str, dtype: int, probs, masks, seed: int) -> None:
+    arr = _as_array(AttnProblem, probs)
+    if len(masks) != len(arr):
+        raise ValueError(f"{name}: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
+    _grouped(name, arr, (dtype,), (_seed(seed),), beside=masks)
+
+
+def attn_fwd_amask(dtype: int, probs, masks, seed: int = 0) -> None:
+    """bpm_attn_fwd with an additive [T, S] mask: `masks` from attn_amasks(), one per problem."""
+    _attn_amask("bpm_attn_fwd_amask", dtype, probs, masks, seed)
+
+
+def attn_bwd_dq_amask(dtype: int, probs, masks, seed: int = 0) -> None:
+    _attn_amask("bpm_attn_bwd_dq_amask", dtype, probs, masks, seed)
+
+
+def attn_bwd_dkv_amask(dtype: int, probs, masks, seed: int = 0) -> None:
+    _attn_amask("bpm_attn_bwd_dkv_amask", dtype, probs, masks, seed)
+
+
+def attn_maps_amask(dtype: int, probs, masks) -> None:
+    arr = _as_array(AttnMapProblem, probs)
+    if len(masks) != len(arr):
+        raise ValueError(f"bpm_attn_maps_amask: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
+    _grouped("bpm_attn_maps_amask", arr, (dtype,), beside=masks)
+
+
 # ----------------------------------------------------------------------------
 # row kernels
 # ----------------------------------------------------------------------------
@@ -948,5 +986,6 @@ SEEDED = frozenset({gemm_grouped, attn_fwd, attn_bwd, attn_bwd_dq, attn_bwd_dkv,
                     pack_rows_fwd, pack_rows_bwd, embed_pos_fwd, embed_pos_bwd, kv_source_fwd, kv_source_bwd, ln_bwd, rows_cast,
                     bert_embed_fwd, tail_fwd})
 # every function that may stand in a step table: a launch on the current stream with no result
+# (the *_amask attention entries are called directly by models/attention.py and stand in no table)
 STEP_FUNCTIONS = SEEDED | {attn_maps, ln_fwd, gelu_fwd, gelu_bwd, expand_heads, add_n, gmu2_fwd, gmu2_bwd, pack_weights, fold_bias,
                            unfold_grads, zero_segments}

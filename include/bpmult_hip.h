@@ -195,6 +195,39 @@ typedef struct bpm_attn_map_problem {
 
 int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs /* host */, int nprob, void* stream);
 
+/* The same kernels with an ARBITRARY ADDITIVE MASK (the reference's attn_mask argument, multihead_attention.py:113-115:
+ * attn_weights += attn_mask.unsqueeze(0)): one bpm_attn_amask per problem, a parallel host array.  The score of
+ * (query i, key j) is q_i . k_j + mask[i*ldm + j] in every one of the problem's B*H heads (Q pre-scaled as everywhere).
+ * Entries are finite or -inf (+inf and NaN: undefined).  A -inf entry, or a key beyond the problem's mask_off limit (the
+ * two rules are ANDed), gets probability exactly 0.0f, adds nothing to lse and contributes exactly nothing to dK / dV.
+ * EVERY QUERY ROW MUST KEEP AT LEAST ONE VISIBLE KEY -- not checked; a row without one yields NaN, as in the reference.
+ * The mask receives no gradient.  Dropout indexes the probabilities as in the other entries.
+ *
+ * Layout and reads.  mask: device fp32 [T, ldm], ldm >= S, ldm % 4 == 0, base 16-byte aligned (a lane of the forward /
+ * dQ kernels reads the 4 consecutive keys of a register group as one 16-byte load).  The kernels read inside [T, ldm]
+ * only, and whatever sits in columns S .. ldm-1 never reaches a result.
+ * The dK / dV pass and the maps kernel hold one key per lane and walk query rows: they would read `mask` down a column.
+ * Choice made here: the caller supplies the TRANSPOSE, maskT: device fp32 [S, ldt], maskT[j*ldt + i] == mask[i*ldm + j],
+ * ldt >= T, ldt % 4 == 0, base 16-byte aligned, read the same way (columns T .. ldt-1 never reach a result).
+ * bpm_attn_bwd_dkv_amask and bpm_attn_maps_amask require it; bpm_attn_fwd_amask and bpm_attn_bwd_dq_amask ignore it (NULL is
+ * fine there).  The two arrays must agree -- not checked.
+ * BPM_ERR_ARG, before anything is launched (and without a GPU): a NULL masks array or `mask`, ldm < S, a broken alignment
+ * rule, a NULL / short / misaligned maskT where it is required, or dS / Pd set (no export here).
+ * With an all-zeros mask the results are bit-equal to the unmasked entries'. */
+typedef struct bpm_attn_amask {
+    const float* mask;  int ldm;    /* fp32 [T, ldm], ldm >= S: added to score (i, j) */
+    const float* maskT; int ldt;    /* its transpose, fp32 [S, ldt], ldt >= T: _bwd_dkv_amask and _maps_amask */
+} bpm_attn_amask;
+int bpm_attn_fwd_amask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_amask* masks /* host */, int nprob,
+                       uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_amask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_amask* masks /* host */, int nprob,
+                          uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_amask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_amask* masks /* host */, int nprob,
+                           uint64_t seed, void* stream);
+/* bpm_attn_maps of forward passes that ran with these masks (lse from bpm_attn_fwd_amask): a -inf entry is exactly 0.0f. */
+int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_amask* masks /* host */, int nprob,
+                        void* stream);
+
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,
  * problem arrays live in HOST memory and are copied into the kernel arguments.

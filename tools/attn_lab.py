@@ -11,6 +11,11 @@ forward launch of the same shapes in the same run -- it does one of the forward'
 so the forward time is its yardstick.  Shapes on record: the default (headline), the kernel point
 `--H 6 --dh 128 --T 50 --S 50 --B 64`, and head_dim 256 `--H 6 --dh 256`.
 
+--amask: also the additive-mask entries (bpm_attn_fwd_amask / _bwd_dq_amask / _bwd_dkv_amask) at the same shapes in the same
+run, twice: with an all-zeros [T, S] mask on top of the same mask_off rule (the unmasked launches' arithmetic plus the mask
+reads: the cost of the mask path), and with the future mask itself as a -inf tensor and no mask_off rule (what a caller
+pays who states a structured mask as a tensor: no tile is skipped).
+
 Algorithmic FLOPs per visible (query, key) pair and head: forward 4 dh, dQ pass 6 dh (S, dP, dQ), dK/dV pass 8 dh."""
 import argparse
 import json
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--drop-encoders", type=int, default=2, help="how many of the G encoders have attention dropout")
     ap.add_argument("--no-mask", action="store_true")
     ap.add_argument("--maps", action="store_true", help="also time bpm_attn_maps at the same shapes (after the forward has written LSE)")
+    ap.add_argument("--amask", action="store_true", help="also time the *_amask entries (all-zeros mask; the future mask as a tensor)")
     ap.add_argument("--pair", type=int, default=-1, help="tuning hook: bit k = kernel k (fwd, dQ, dK/dV) takes two blocks per workgroup")
     a = ap.parse_args()
     dev, ct = "cuda", torch.bfloat16
@@ -83,6 +89,23 @@ def main():
         us = _time(lambda: fn(BPM_BF16, arr, 5), a.iters)
         tf = fl * dh * pairs / us / 1e6
         res[name] = {"us": round(us, 1), "tflops": round(tf, 1), "bf16_peak_frac": round(tf / BF16_PEAK_TF, 3)}
+    if a.amask:
+        ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
+        zeros = (torch.zeros(T, ldm, device=dev), torch.zeros(S, ldt, device=dev))
+        hidden = (torch.arange(S)[None, :] - torch.arange(T)[:, None]) >= 1 + abs(S - T)
+        fm, ft = torch.zeros(T, ldm), torch.zeros(S, ldt)
+        fm[:, :S][hidden] = float("-inf")
+        ft[:, :T][hidden.t()] = float("-inf")
+        fut = (fm.to(dev), ft.to(dev))
+        free = ops.array(ops.AttnProblem, probs)          # the same problems without the mask_off rule
+        for p in free:
+            p.mask_off = 0
+        for tag, (m, mt), parr in (("amask_zeros", zeros, arr), ("amask_future_tensor", fut, free)):
+            am = ops.attn_amasks([(m, ldm, mt, ldt)] * G)
+            res[tag] = {}
+            for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
+                us = _time(lambda: fn(BPM_BF16, parr, am, 5), a.iters)
+                res[tag][name] = {"us": round(us, 1), "over_unmasked": round(us / res[name]["us"], 3)}
     if a.maps:
         # LSE of the last forward launch above is in place; maps and forward alternate in one timing loop each, three rounds
         wts = [torch.empty(B, T, S, device=dev) for _ in range(G)]
