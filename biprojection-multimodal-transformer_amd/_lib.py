@@ -21,7 +21,7 @@ SOURCES = ("gemm.hip", "attention.hip", "rows_pack.hip", "rows_norm.hip", "rows_
 HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h", "rows_common.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
-              "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
+              "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16, "attn_bwd_dbias": 17}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
 
 ABI_VERSION = 5                   # == BPM_ABI_VERSION of include/bpmult_hip.h; lib() refuses any other library
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
@@ -144,6 +144,15 @@ class AttnKMask(C.Structure):
 
 class AttnAMask(C.Structure):
     _fields_ = [("mask", C.c_void_p), ("ldm", C.c_int), ("maskT", C.c_void_p), ("ldt", C.c_int)]
+
+
+class AttnHMask(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("ldm", C.c_int), ("maskT", C.c_void_p), ("ldt", C.c_int),
+                ("head_stride", C.c_int64), ("head_strideT", C.c_int64)]
+
+
+class AttnDBias(C.Structure):
+    _fields_ = [("dB", C.c_void_p), ("lddb", C.c_int), ("head_stride", C.c_int64)]
 
 
 class GeluProblem(C.Structure):
@@ -328,6 +337,12 @@ SIGNATURES = {
     "bpm_attn_bwd_dq_amask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnAMask), _I, _U64, _P],
     "bpm_attn_bwd_dkv_amask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnAMask), _I, _U64, _P],
     "bpm_attn_maps_amask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnAMask), _I, _P],
+    "bpm_attn_bwd_dbias_ws_bytes": [C.POINTER(AttnProblem), C.POINTER(AttnDBias), _I],
+    "bpm_attn_bwd_dbias": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), C.POINTER(AttnDBias), _I, _U64, _P, C.c_size_t, _P],
+    "bpm_attn_fwd_hmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_hmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_hmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_maps_hmask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnHMask), _I, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],

@@ -1,24 +1,29 @@
 """`MultiheadAttention` with the reference's constructor, call signature and state_dict layout
 (bpmult/models/multihead_attention.py:17-135), executed on the HIP path.
 
-forward(query, key, value, attn_mask) is one autograd node.  Its launches are those of the engine's self-attention
+forward(query, key, value, attn_mask, attn_bias) is one autograd node.  Its launches are those of the engine's self-attention
 block (engine.py: _proj, _self_attn_fwd / _self_attn_bwd):
 
   forward   rows_cast            query / key / value -> CT rows (one problem per distinct input)
             gemm NT (grouped)    Q (alpha = dh^-0.5), K, V projections of in_proj_weight, OUT_HEADS epilogue
-            attn_fwd[_amask]     softmax(q k^T + attn_mask) v, dropout on the probabilities
+            attn_fwd[_amask]     softmax(q k^T + attn_mask + attn_bias) v, dropout on the probabilities
             gemm NT              out_proj
             attn_maps[_amask]    the head-averaged weights (need_weights only)
   backward  rows_cast            d(attn) -> CT, column sums = d(out_proj.bias)
             gemm TN / NN         d(out_proj.weight); d(attention output), OUT_HEADS
             attn_bwd_dq / _dkv   [_amask]
+            attn_bwd_dbias       d(attn_bias): the score gradient summed over samples (and heads), after the dQ pass;
+                                 only when attn_bias requires grad
             gemm TN (grouped)    the three row blocks of d(in_proj_weight), d(in_proj_bias) as colsum_a
             gemm NN (grouped)    d(query), d(key), d(value)
 
 The parameters stay PyTorch's; their CT shadows are re-packed (bpm_pack_weights) when a version counter moves, the rule
-of models/bert.py with text_params = "torch".  An arbitrary additive mask is copied once into the layout the kernels read
-(rows padded to 4 columns, plus its transpose for the dK / dV and maps kernels) and kept until the tensor's data_ptr or
-_version changes.  The mask gets no gradient; add_bias_kv / add_zero_attn are refused.  No torch compute op runs here.
+of models/bert.py with text_params = "torch".  The effective additive image, attn_mask + attn_bias, is built by torch
+copies (one add when both are given) in the layout the kernels read -- [Hm, T, ldm], rows padded to 4 columns, Hm = H for
+a per-head bias and 1 otherwise, plus its transpose [Hm, S, ldt] for the dK / dV and maps kernels -- and kept until either
+tensor's data_ptr or _version changes: a bias that an optimiser steps is copied again every forward (two copies of
+Hm T S floats).  attn_mask gets no gradient; attn_bias gets one from bpm_attn_bwd_dbias, whose workspace lives in the
+plan.  add_bias_kv / add_zero_attn are refused.
 """
 from __future__ import annotations
 
@@ -59,7 +64,8 @@ class _Plan:
         # backward
         self.dy, self.dao, self.delta = z(T * B, ld, dt=ct), z(B, H, T, dhp, dt=ct), z(B, H, T)
         self.dq, self.dk, self.dv = z(T * B, ld, dt=ct), z(S * B, ld, dt=ct), z(S * B, ld, dt=ct)
-        self.mask = None             # (ops.attn_amasks array, the tensors it points into) of the forward pass; None: no attn_mask
+        self.mask = None             # (ops.attn_amasks array, the tensors it points into) of the forward pass; None: no attn_mask / attn_bias
+        self.dbias_ws = {}           # heads of the bias gradient (1 or H) -> workspace of bpm_attn_bwd_dbias (None: no split)
         self.seed, self.drop_p = 0, 0.0
 
 
@@ -111,30 +117,38 @@ class _Exec:
             pl = self.plans[key] = _Plan(self, T, S, B, form)
         return pl
 
-    def mask_for(self, attn_mask: torch.Tensor, T: int, S: int):
-        """The kernels' copy of attn_mask: fp32 [T, ldm] and its transpose [S, ldt], leading dimensions rounded up to 4
-        (pad columns are never used: zeros); rebuilt when the tensor's storage or version counter changes."""
-        key = (attn_mask.data_ptr(), attn_mask._version, tuple(attn_mask.shape), tuple(attn_mask.stride()), attn_mask.dtype, str(attn_mask.device))
+    def mask_for(self, attn_mask: Optional[torch.Tensor], attn_bias: Optional[torch.Tensor], T: int, S: int):
+        """The kernels' copy of the effective image attn_mask + attn_bias: fp32 [Hm, T, ldm] and its transpose [Hm, S, ldt]
+        (Hm = H for an [H, T, S] bias, else 1: head stride 0), leading dimensions rounded up to 4 (pad columns are never
+        used: zeros); rebuilt when either tensor's storage or version counter changes."""
+        sig = lambda t: None if t is None else (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
+        key = (sig(attn_mask), sig(attn_bias))
         if key != self._mask_key:
             ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
-            m = torch.zeros(T, ldm, device=self.device)
-            mt = torch.zeros(S, ldt, device=self.device)
-            m[:, :S].copy_(attn_mask.detach())
-            mt[:, :T].copy_(attn_mask.detach().t())
-            # the source tensor is held too: while it lives, its address cannot name another tensor
-            self._mask = (ops.attn_amasks([(m, ldm, mt, ldt)]), m, mt, attn_mask)
+            Hm = self.H if attn_bias is not None and attn_bias.dim() == 3 else 1
+            m = torch.zeros(Hm, T, ldm, device=self.device)
+            mt = torch.zeros(Hm, S, ldt, device=self.device)
+            # detached views: they share the storage (and the version counter) but not the autograd graph of a non-leaf bias
+            srcs = [t.detach() for t in (attn_mask, attn_bias) if t is not None]
+            m[:, :, :S].copy_(srcs[0])
+            if len(srcs) == 2:
+                m[:, :, :S].add_(srcs[1])
+            mt[:, :, :T].copy_(m[:, :, :S].transpose(1, 2))
+            hs, hst = (T * ldm, S * ldt) if Hm > 1 else (0, 0)
+            # the source tensors are held too: while they live, their addresses cannot name other tensors
+            self._mask = (ops.attn_amasks([(m, ldm, mt, ldt, hs, hst)]), m, mt, srcs)
             self._mask_key = key
         return self._mask
 
     # -- forward -------------------------------------------------------------------------------------------------------
-    def forward(self, mod, query, key, value, form, attn_mask, need_weights, seed, training):
+    def forward(self, mod, query, key, value, form, attn_mask, attn_bias, need_weights, seed, training):
         T, B, d = query.shape
         S = key.shape[0]
         self.refresh_shadows()
         pl = self.plan(T, S, B, form)
         pl.stamp += 1
         dt, ld, H, dh, dhp = self.dtype, self.ld, self.H, self.dh, self.dhp
-        pl.mask = None if attn_mask is None else self.mask_for(attn_mask, T, S)
+        pl.mask = None if attn_mask is None and attn_bias is None else self.mask_for(attn_mask, attn_bias, T, S)
         pl.seed, pl.drop_p = seed, (mod.attn_dropout if training else 0.0)
         casts = [ops.cast_problem(query, d, T * B, d, dst_ct=pl.xq, ldd=ld)]
         if form != "qkv":
@@ -166,9 +180,10 @@ class _Exec:
         return out, weights, pl
 
     # -- backward ------------------------------------------------------------------------------------------------------
-    def backward(self, mod, pl: _Plan, dout: torch.Tensor):
-        """dout fp32 [T, B, d] -> d(query), d(key), d(value), and the parameter gradients in self.params order: fresh
-        tensors every call (autograd may keep them as .grad)."""
+    def backward(self, mod, pl: _Plan, dout: torch.Tensor, bias_shape=None):
+        """dout fp32 [T, B, d] -> d(query), d(key), d(value), d(attn_bias) (None unless bias_shape, the shape of the bias
+        that wants one, is given) and the parameter gradients in self.params order: fresh tensors every call (autograd
+        may keep them as .grad)."""
         T, S, B = pl.T, pl.S, pl.B
         dt, d, ld, H, dh, dhp, seed, dev = self.dtype, self.d, self.ld, self.H, self.dh, self.dhp, pl.seed, self.device
         has_bias = mod.in_proj_bias is not None
@@ -187,6 +202,9 @@ class _Exec:
         else:
             ops.attn_bwd_dq_amask(dt, ap, pl.mask[0], seed)
             ops.attn_bwd_dkv_amask(dt, ap, pl.mask[0], seed)
+        g_bias = None
+        if bias_shape is not None:
+            g_bias = self.bias_grad(pl, ap, bias_shape, seed)
         sides = ((pl.dq, pl.xq, T), (pl.dk, pl.xk, S), (pl.dv, pl.xv, S))
         ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(g, x, g_ipw.data_ptr() + 4 * w * d * d, d, d, L * B, ld, ld, d, flags=F_KPAD,
                                                         colsum_a=g_ipb.data_ptr() + 4 * w * d if has_bias else None)
@@ -195,17 +213,33 @@ class _Exec:
         ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(g, self.wptr(w), dx[w], L * B, d, d, ld, ld, d, flags=F_KPAD)
                                        for w, (g, _, L) in enumerate(sides)], seed)
         grads = [g for g in (g_ipw, g_ipb, g_wo, g_ob) if g is not None]
-        return dx[0], dx[1], dx[2], grads
+        return dx[0], dx[1], dx[2], g_bias, grads
 
+    def bias_grad(self, pl: _Plan, ap, bias_shape, seed: int) -> torch.Tensor:
+        """d(attn_bias) of the plan's last forward pass, after its dQ pass has left delta: fp32, bias_shape ([T, S]: summed
+        over samples and heads; [H, T, S]: over samples); a pair the effective image hides gets exactly 0."""
+        T, S = pl.T, pl.S
+        nimg = self.H if len(bias_shape) == 3 else 1
+        ldb = (S + 3) // 4 * 4
+        g = torch.empty(nimg, T, ldb, device=self.device)
+        outs = ops.attn_dbias([(g, ldb, T * ldb if nimg > 1 else 0)])
+        if nimg not in pl.dbias_ws:
+            n = ops.attn_dbias_ws_bytes(ap, outs)
+            pl.dbias_ws[nimg] = torch.empty((n + 3) // 4, device=self.device) if n else None
+        ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg])
+        g = g if ldb == S else g[:, :, :S].contiguous()
+        return g.reshape(bias_shape)
 
 class _MhaFn(torch.autograd.Function):
-    """The whole call as one autograd node: (query, key, value, parameters) -> (attn, head-averaged weights or None)."""
+    """The whole call as one autograd node: (query, key, value, attn_bias, parameters) -> (attn, head-averaged weights or
+    None)."""
 
     @staticmethod
-    def forward(ctx, query, key, value, mod, ex, form, attn_mask, need_weights, seed, *params):
+    def forward(ctx, query, key, value, mod, ex, form, attn_mask, need_weights, seed, attn_bias, *params):
         out, weights, plan = ex.forward(mod, query.detach().contiguous(), key.detach().contiguous(), value.detach().contiguous(), form,
-                                        attn_mask, need_weights, seed, mod.training)
+                                        attn_mask, attn_bias, need_weights, seed, mod.training)
         ctx.mod, ctx.ex, ctx.plan, ctx.stamp = mod, ex, plan, plan.stamp
+        ctx.bias_shape = None if attn_bias is None else tuple(attn_bias.shape)
         if weights is None:
             return out, None
         ctx.mark_non_differentiable(weights)
@@ -216,19 +250,24 @@ class _MhaFn(torch.autograd.Function):
         if ctx.stamp != ctx.plan.stamp:
             raise RuntimeError("MultiheadAttention (HIP path): backward() of a forward pass that a later forward pass of the same "
                                "shape has overwritten; run forward -> backward one call at a time")
-        dq, dk, dv, grads = ctx.ex.backward(ctx.mod, ctx.plan, dout.contiguous().float())
         need = ctx.needs_input_grad
-        return ((dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None, None)
-                + tuple(g if n else None for g, n in zip(grads, need[9:])))
+        dq, dk, dv, g_bias, grads = ctx.ex.backward(ctx.mod, ctx.plan, dout.contiguous().float(), ctx.bias_shape if need[9] else None)
+        return ((dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None, None, g_bias)
+                + tuple(g if n else None for g, n in zip(grads, need[10:])))
 
 
 class MultiheadAttention(nn.Module):
     """Drop-in for bpmult.models.multihead_attention.MultiheadAttention (packed in-projection, :17-50).
 
-    forward(query, key, value, attn_mask=None, need_weights=True) -> (attn [T, B, d], weights [B, T, S] or None) on
+    forward(query, key, value, attn_mask=None, need_weights=True, attn_bias=None) -> (attn [T, B, d], weights [B, T, S] or None) on
     [T,B,d] / [S,B,d] fp32 CUDA (HIP) tensors, in the reference's three call forms (query is key is value; key is value;
     three tensors).  attn_mask: None or a float [T, S] tensor added to the scores of every head (-inf hides a pair; every
     row must keep a visible key, or it is NaN as in the reference); it gets no gradient (requires_grad: ValueError).
+    attn_bias (an extension): None or a float32 tensor on the inputs' device, [T, S] (added to the scores of every head) or
+    [H, T, S] (head h of every sample gets attn_bias[h]), finite or -inf entries; the scores get attn_mask + attn_bias.  It
+    may require grad -- an nn.Parameter, or a non-leaf such as a gather from a relative-position table: its gradient (the
+    score gradient summed over samples, and over heads for [T, S]; exactly 0 where the effective entry is -inf) comes back
+    through autograd.  `weights` are taken under the same mask + bias.
     One stated difference: `weights` are the head-averaged softmax probabilities BEFORE attention dropout, detached --
     equal to the reference's in eval mode and whenever attn_dropout == 0 (in training with dropout the reference returns
     the dropped, rescaled matrix); the departure TransformerEncoder.attention_maps() makes.  need_weights=False (an
@@ -285,10 +324,7 @@ class MultiheadAttention(nn.Module):
             ex = self._exec = _Exec(self, device, prec)
         return ex
 
-    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True):
-        for t in (query, key, value):
-            if not t.is_cuda:
-                raise RuntimeError("MultiheadAttention: the HIP attention path needs CUDA (HIP) tensors; there is no CPU path")
+    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None):
         if query.dim() != 3 or query.shape[2] != self.embed_dim:
             raise ValueError(f"MultiheadAttention: query of shape {tuple(query.shape)}, expected [T, B, {self.embed_dim}]")
         T, B, d = query.shape
@@ -305,6 +341,19 @@ class MultiheadAttention(nn.Module):
                 raise ValueError(f"MultiheadAttention: attn_mask must be a float tensor of shape [{T}, {S}]")
             if attn_mask.requires_grad:
                 raise ValueError("MultiheadAttention: attn_mask gets no gradient on the HIP path (requires_grad is set)")
+        if attn_bias is not None:
+            if not torch.is_tensor(attn_bias) or attn_bias.dtype != torch.float32:
+                raise ValueError("MultiheadAttention: attn_bias must be a float32 tensor")
+            if tuple(attn_bias.shape) not in ((T, S), (self.num_heads, T, S)):
+                raise ValueError(f"MultiheadAttention: attn_bias of shape {tuple(attn_bias.shape)}, expected [{T}, {S}] or "
+                                 f"[{self.num_heads}, {T}, {S}]")
+            if attn_bias.device != query.device:
+                raise ValueError(f"MultiheadAttention: attn_bias on {attn_bias.device}, the inputs on {query.device}")
+            if config.is_x3(self.precision or config.precision()):
+                raise ValueError("MultiheadAttention: attn_bias is not available with precision 'bf16x3'; use 'bf16' or 'f32'")
+        for t in (query, key, value):             # after the argument checks: those need no device
+            if not t.is_cuda:
+                raise RuntimeError("MultiheadAttention: the HIP attention path needs CUDA (HIP) tensors; there is no CPU path")
         ex = self._ensure_exec(query.device)
         seed = self._next_seed()
-        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, *ex.params)
+        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, attn_bias, *ex.params)

@@ -396,13 +396,19 @@ def attn_maps(dtype: int, probs) -> None:
 
 
 def attn_amasks(masks) -> "C.Array":
-    """[(mask, ldm, maskT, ldt)] -> the host array of bpm_attn_amask the *_amask entries take beside the problems.  mask:
-    float32 device tensor [T, ldm] added to the scores of every head (-inf hides the pair; AND the problem's mask_off
-    rule), ldm >= S and a multiple of 4, 16-byte aligned; maskT: its transpose [S, ldt] under the same rules, which the
-    dK / dV and maps entries read (None, 0 for forward / dQ only).  Every query row needs a visible key (not checked)."""
-    arr = (_lib.AttnAMask * len(masks))()
-    for a, (m, ldm, mt, ldt) in zip(arr, masks):
+    """[(mask, ldm, maskT, ldt)] or [(mask, ldm, maskT, ldt, head_stride, head_strideT)] -> the host array of
+    bpm_attn_hmask (bpm_attn_amask plus the two head strides; the attn_*_amask wrappers below launch through the *_hmask
+    entries, which are the *_amask entries at stride 0) that they take beside the problems.  mask: float32 device tensor [T, ldm] added to the scores
+    of every head (-inf hides the pair; AND the problem's mask_off rule), ldm >= S and a multiple of 4, 16-byte aligned;
+    maskT: its transpose [S, ldt] under the same rules, which the dK / dV and maps entries read (None, 0 for forward / dQ
+    only).  The head strides (elements; the 4-tuple form: 0) turn them into H images [H, T, ldm] / [H, S, ldt], head h of
+    every sample reading its own.  Every query row needs a visible key (not checked)."""
+    arr = (_lib.AttnHMask * len(masks))()
+    for a, t in zip(arr, masks):
+        m, ldm, mt, ldt = t[:4]
+        hs, hst = t[4:] if len(t) == 6 else (0, 0)
         a.mask, a.ldm, a.maskT, a.ldt = _f32(m, "additive attention mask"), ldm, _f32(mt, "additive attention mask (transpose)"), ldt
+        a.head_stride, a.head_strideT = hs, hst
     return arr
 
 
@@ -410,7 +416,7 @@ def _attn_amask(name: str, dtype: int, probs, masks, seed: int) -> None:
     arr = _as_array(AttnProblem, probs)
     if len(masks) != len(arr):
         raise ValueError(f"{name}: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
-    _grouped(name, arr, (dtype,), (_seed(seed),), beside=masks)
+    _grouped(name.replace("_amask", "_hmask"), arr, (dtype,), (_seed(seed),), beside=masks)
 
 
 def attn_fwd_amask(dtype: int, probs, masks, seed: int = 0) -> None:
@@ -430,7 +436,41 @@ def attn_maps_amask(dtype: int, probs, masks) -> None:
     arr = _as_array(AttnMapProblem, probs)
     if len(masks) != len(arr):
         raise ValueError(f"bpm_attn_maps_amask: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
-    _grouped("bpm_attn_maps_amask", arr, (dtype,), beside=masks)
+    _grouped("bpm_attn_maps_hmask", arr, (dtype,), beside=masks)
+
+
+def attn_dbias(outs) -> "C.Array":
+    """[(dB, lddb, head_stride)] -> the host array of bpm_attn_dbias that bpm_attn_bwd_dbias takes beside the problems and
+    their masks.  dB: float32 device tensor [T, lddb] (head_stride 0: the gradient summed over samples and heads) or
+    [H, T, lddb] with head_stride elements between the images (summed over samples), lddb >= S and a multiple of 4,
+    16-byte aligned.  Columns >= S are left alone."""
+    arr = (_lib.AttnDBias * len(outs))()
+    for a, (dB, lddb, hs) in zip(arr, outs):
+        a.dB, a.lddb, a.head_stride = _f32(dB, "attention bias gradient"), lddb, hs
+    return arr
+
+
+def attn_dbias_ws_bytes(probs, outs) -> int:
+    """Bytes of workspace bpm_attn_bwd_dbias needs for these problems (0: the head sums are not split)."""
+    arr = _as_array(AttnProblem, probs)
+    if len(outs) != len(arr):
+        raise ValueError(f"bpm_attn_bwd_dbias_ws_bytes: one output per problem ({len(arr)} problems, {len(outs)} outputs)")
+    if len(arr) > MAX_GROUP:
+        raise ValueError(f"bpm_attn_bwd_dbias: at most {MAX_GROUP} problems per launch")
+    return int(_lib.lib().bpm_attn_bwd_dbias_ws_bytes(arr, outs, len(arr)))
+
+
+def attn_bwd_dbias(dtype: int, probs, masks, outs, seed: int = 0, ws=None) -> None:
+    """The gradient of the additive masks (`masks` from attn_amasks(), as the forward pass took them) into `outs` (from
+    attn_dbias()), after attn_bwd_dq[_amask] has left delta.  ws: a device tensor of at least attn_dbias_ws_bytes() bytes
+    (None when that is 0); one launch, so at most MAX_GROUP problems."""
+    arr = _as_array(AttnProblem, probs)
+    if len(masks) != len(arr) or len(outs) != len(arr):
+        raise ValueError(f"bpm_attn_bwd_dbias: one mask and one output per problem ({len(arr)} problems, {len(masks)} masks, {len(outs)} outputs)")
+    if len(arr) > MAX_GROUP:
+        raise ValueError(f"bpm_attn_bwd_dbias: at most {MAX_GROUP} problems per launch")
+    nbytes = 0 if ws is None else ws.numel() * ws.element_size()
+    _lib.check(_lib.lib().bpm_attn_bwd_dbias(dtype, arr, masks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()), "bpm_attn_bwd_dbias")
 
 
 # ----------------------------------------------------------------------------

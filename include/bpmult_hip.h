@@ -201,7 +201,8 @@ int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs /* host */, int n
  * Entries are finite or -inf (+inf and NaN: undefined).  A -inf entry, or a key beyond the problem's mask_off limit (the
  * two rules are ANDed), gets probability exactly 0.0f, adds nothing to lse and contributes exactly nothing to dK / dV.
  * EVERY QUERY ROW MUST KEEP AT LEAST ONE VISIBLE KEY -- not checked; a row without one yields NaN, as in the reference.
- * The mask receives no gradient.  Dropout indexes the probabilities as in the other entries.
+ * These entries give the mask no gradient (bpm_attn_bwd_dbias below computes it).  Dropout indexes the probabilities as in
+ * the other entries.
  *
  * Layout and reads.  mask: device fp32 [T, ldm], ldm >= S, ldm % 4 == 0, base 16-byte aligned (a lane of the forward /
  * dQ kernels reads the 4 consecutive keys of a register group as one 16-byte load).  The kernels read inside [T, ldm]
@@ -227,6 +228,52 @@ int bpm_attn_bwd_dkv_amask(int dtype, const bpm_attn_problem* probs /* host */, 
 /* bpm_attn_maps of forward passes that ran with these masks (lse from bpm_attn_fwd_amask): a -inf entry is exactly 0.0f. */
 int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_amask* masks /* host */, int nprob,
                         void* stream);
+
+/* PER-HEAD additive masks (a learned per-head attention bias): the four entries above with a head stride on the mask.
+ * bpm_attn_hmask is bpm_attn_amask plus head_stride / head_strideT (elements, applied to mask / maskT): 0 means one
+ * [T, ldm] image for all heads -- the *_amask entries, which are these entries at stride 0 (same kernels, same bits).
+ * Otherwise head h of every sample reads the image at mask + h*head_stride (maskT + h*head_strideT): H images under the
+ * layout and alignment rules above, each of them -- head_stride % 4 == 0, head_stride >= T*ldm (head_strideT >= S*ldt) and
+ * below 2^31, or BPM_ERR_ARG.  Per-sample masks do not exist.  The *_amask entries and their struct are unchanged, so
+ * BPM_ABI_VERSION stays. */
+typedef struct bpm_attn_hmask {
+    const float* mask;  int ldm;    /* as bpm_attn_amask */
+    const float* maskT; int ldt;
+    int64_t head_stride, head_strideT;  /* elements between the images of consecutive heads; 0: one image for all heads */
+} bpm_attn_hmask;
+int bpm_attn_fwd_hmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */, int nprob,
+                       uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_hmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */, int nprob,
+                          uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_hmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */, int nprob,
+                           uint64_t seed, void* stream);
+int bpm_attn_maps_hmask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_hmask* masks /* host */, int nprob,
+                        void* stream);
+
+/* The gradient of the additive mask (a learned attention bias): the gradient of the scores, which the fused kernels never
+ * materialise, summed over the samples -- and over the heads when one image serves them all.
+ *   dB[h*head_stride + i*lddb + j] = sum over b (and over h when head_stride == 0) of dS[b,h,i,j],
+ *   dS = P o (drop o dP - delta), P = exp(q.k + mask - lse), dP = dO . V^T
+ * in fp32.  Every (i, j) with i < T, j < S is written (a pair that a -inf entry or the mask_off rule hides: exactly 0.0f);
+ * nothing is written at j >= S.  Reads Q, K, V, dO, lse and the delta that bpm_attn_bwd_dq[_amask] left: issue it after
+ * that launch, as bpm_attn_bwd_dkv[_amask / _hmask].  Dropout draws the keep mask of the dQ pass (same hash, element index and
+ * drop_site), so the dS summed here is the dS that pass multiplied by K.  `masks` are the forward pass's (only mask / ldm /
+ * head_stride are read); head_stride of bpm_attn_dbias chooses the form of the RESULT independently of the mask's.
+ * A workgroup owns a 64 x 64 tile of one output image and sums the heads that feed it in a fixed order; when the launch
+ * would have fewer tiles than the chip holds workgroups at once, the head range of a tile is split over several workgroups,
+ * whose fp32 partial images go through `ws` and are added in index order by a second kernel: the result is
+ * bit-reproducible run to run (no float atomics).  bpm_attn_bwd_dbias_ws_bytes gives the workspace the same arrays
+ * need (0: no split); ws is 16-byte aligned device memory, owned by the launch until it has run.
+ * BPM_ERR_ARG, before anything is launched (and without a GPU): NULL arrays or pointers, lddb < S, lddb % 4 != 0, a
+ * misaligned dB, a head_stride that is non-zero and smaller than T*lddb or no multiple of 4, a short or misaligned
+ * workspace, dS / Pd set, problems of different dhp. */
+typedef struct bpm_attn_dbias {
+    float* dB; int lddb;            /* out: fp32 [T, lddb] (head_stride == 0) or H such images, lddb >= S, lddb % 4 == 0 */
+    int64_t head_stride;            /* elements between the images of consecutive heads; 0: one image, summed over heads */
+} bpm_attn_dbias;
+size_t bpm_attn_bwd_dbias_ws_bytes(const bpm_attn_problem* probs /* host */, const bpm_attn_dbias* outs /* host */, int nprob);
+int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */,
+                       const bpm_attn_dbias* outs /* host */, int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,

@@ -14,7 +14,10 @@ so the forward time is its yardstick.  Shapes on record: t
 --amask: also the additive-mask entries (bpm_attn_fwd_amask / _bwd_dq_amask / _bwd_dkv_amask) at the same shapes in the same
 run, twice: with an all-zeros [T, S] mask on top of the same mask_off rule (the unmasked launches' arithmetic plus the mask
 reads: the cost of the mask path), and with the future mask itself as a -inf tensor and no mask_off rule (what a caller
-pays who states a structured mask as a tensor: no tile is skipped).
+pays who states a structured mask as a tensor: no tile is skipped).  And the learned-bias launches (`dbias`): with an all-zeros
+mask and the same rule, for one encoder and for all G in one launch, bpm_attn_bwd_dbias in both forms (shared [T, S]: the
+head sums are split over workgroups when the launch has fewer than 256 tiles; per head [H, T, S]) beside the dQ and dK / dV
+launches of the same problems, and forward / dQ / dK / dV with H mask images through the head stride against one image.
 
 Algorithmic FLOPs per visible (query, key) pair and head: forward 4 dh, dQ pass 6 dh (S, dP, dQ), dK/dV pass 8 dh."""
 import argparse
@@ -106,6 +109,27 @@ def main():
             for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
                 us = _time(lambda: fn(BPM_BF16, parr, am, 5), a.iters)
                 res[tag][name] = {"us": round(us, 1), "over_unmasked": round(us / res[name]["us"], 3)}
+        # the learned-bias launches: all-zeros images, one per head through the head stride, and the bias gradient
+        zh = (torch.zeros(H, T, ldm, device=dev), torch.zeros(H, S, ldt, device=dev))
+        res["dbias"] = {}
+        for n in sorted({1, G}):
+            sub = ops.array(ops.AttnProblem, probs[:n])
+            am0 = ops.attn_amasks([(zeros[0], ldm, zeros[1], ldt)] * n)
+            amh = ops.attn_amasks([(zh[0], ldm, zh[1], ldt, T * ldm, S * ldt)] * n)
+            r = res["dbias"][f"{n}_problems"] = {}
+            for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
+                u0, uh = _time(lambda: fn(BPM_BF16, sub, am0, 5), a.iters), _time(lambda: fn(BPM_BF16, sub, amh, 5), a.iters)
+                r[name] = {"us_stride0": round(u0, 1), "us_head_stride": round(uh, 1), "head_over_stride0": round(uh / u0, 3)}
+            tiles = ((T + 63) // 64) * ((S + 63) // 64)
+            for form, nimg, am in (("shared", 1, am0), ("per_head", H, amh)):
+                g = [torch.empty(nimg, T, ldm, device=dev) for _ in range(n)]
+                outs = ops.attn_dbias([(x, ldm, T * ldm if nimg > 1 else 0) for x in g])
+                nws = ops.attn_dbias_ws_bytes(sub, outs)
+                ws = torch.empty(nws // 4, device=dev) if nws else None
+                us = _time(lambda: ops.attn_bwd_dbias(BPM_BF16, sub, am, outs, 5, ws=ws), a.iters)
+                splits = nws // (n * nimg * T * ldm * 4) if nws else 1
+                r["dbias_" + form] = {"us": round(us, 1), "over_dq": round(us / r["bwd_dq"]["us_head_stride" if nimg > 1 else "us_stride0"], 3),
+                                      "workgroups": n * nimg * tiles * splits, "splits_per_tile": splits, "workspace_mbytes": round(nws / 1e6, 2)}
     if a.maps:
         # LSE of the last forward launch above is in place; maps and forward alternate in one timing loop each, three rounds
         wts = [torch.empty(B, T, S, device=dev) for _ in range(G)]
