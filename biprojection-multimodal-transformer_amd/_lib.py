@@ -17,8 +17,8 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BPMULT_LIB", os.path.join(_HERE, "libbpmult_hip.so"))   # override: kernel-variant experiments
-SOURCES = ("gemm.hip", "attention.hip", "rows_pack.hip", "rows_norm.hip", "rows_elem.hip", "adam.hip", "bert_embed.hip", "loss.hip", "eval.hip", "tail.hip", "frontend.hip", "prof.hip")
-HEADERS = ("bpm_common.h", "bpm_prof.h", "gemm_dma.h", "rows_common.h")
+SOURCES = ("gemm.hip", "attention.hip", "attn_maps.hip", "attn_dbias.hip", "rows_pack.hip", "rows_norm.hip", "rows_elem.hip", "adam.hip", "bert_embed.hip", "loss.hip", "eval.hip", "tail.hip", "frontend.hip", "prof.hip")
+HEADERS = ("bpm_common.h", "bpm_launch.h", "bpm_prof.h", "gemm_dma.h", "rows_common.h", "attn_common.h")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
               "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16, "attn_bwd_dbias": 17}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
@@ -27,8 +27,8 @@ ABI_VERSION = 5                   # == BPM_ABI_VERSION of include/bpmult_hip.h; 
 # -DBPM_LAB build: the same kernels plus the two process-global tuning hooks (bpm_debug_gemm_force / bpm_debug_attn_pair)
 # that tools/gemm_lab.py, tools/attn_lab.py and three kernel tests use, the GEMM dispatcher's environment switches and its
 # decision query (bpm_debug_gemm_choice: tools/gemm_choice.py, tests/test_gemm_choice_cpu.py) and the dry mode of the row
-# files' launches (bpm_debug_rows_dry / _last: tools/rowops_dispatch.py, tests/test_rowops_dispatch_cpu.py); never loaded by
-# the product path
+# and attention files' launches (bpm_debug_rows_dry / _last: tools/rowops_dispatch.py, tests/test_rowops_dispatch_cpu.py,
+# tests/test_attn_dispatch_cpu.py); never loaded by the product path
 LAB_LIB_PATH = os.path.join(_HERE, "..", "build", "lab", "libbpmult_hip_lab.so")
 BPM_F32, BPM_BF16, BPM_BF16X3 = 0, 1, 2      # BPM_BF16X3: bpm_gemm_grouped only (split-bf16 operands, three products)
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -440,7 +440,7 @@ def bind_lab(L: C.CDLL) -> C.CDLL:
     L.bpm_debug_attn_pair.argtypes = [C.c_int]
     # (dtype, variant, problems, nprob, compute units, out[4 + 4 * nprob]): the dispatcher's decision, nothing launched
     L.bpm_debug_gemm_choice.argtypes = [C.c_int, C.c_int, C.POINTER(GemmProblem), C.c_int, C.c_int, C.POINTER(C.c_int)]
-    # dry mode of the row files' launches (on: note instead of launching, and forget the notes), and note i read back:
+    # dry mode of the row and attention files' launches (on: note instead of launching, and forget the notes), and note i read back:
     # (i, kernel[cap], cap, grid, block, last pointer argument) -> number of launches noted
     L.bpm_debug_rows_dry.argtypes = [C.c_int]
     L.bpm_debug_rows_last.argtypes = [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_void_p)]

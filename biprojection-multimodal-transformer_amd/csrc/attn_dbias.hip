@@ -1,0 +1,356 @@
+// Gradient of an additive attention mask (a learned bias) for BPMulT on gfx950: bpm_attn_bwd_dbias and its workspace query.
+// What it shares with the forward / backward kernels of attention.hip is in attn_common.h.
+#include "attn_common.h"
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// gradient of the additive mask: dB[img][i][j] = sum over the heads that read image img of dS[b,h,i,j]
+// ---------------------------------------------------------------------------
+// The dQ block body's first two products without the third: S^T = K Qs^T and dP^T = V dO^T, keys on the register rows, one
+// query per lane (the forward orientation: the lane's 4 consecutive keys of a register group are one float4 of its mask
+// row, and one float4 of the result).  A workgroup owns a 64-query x 64-key tile of one output image -- a wave 16 of its
+// queries -- and loops over a range of the heads that feed the image (every (b, h) for the shared form, every b of head
+// h for the per-head form): the head's 64 K / V rows pass through the LDS images (RowStage, loaded one head ahead), the
+// lane's Q / dO fragments, lse and delta come straight from global memory.  The dS tile stays in 16 fp32 accumulators per
+// lane and is stored once.  A pair the mask_off rule or a -inf entry hides has probability exp2(-inf) = 0 in every head:
+// its sum is exactly 0.0f.  Dropout: the hash, element index and site of the dQ pass.
+//
+// Filling the chip (dbias_choose): with fewer tiles than the chip holds workgroups at once (compute units x the waves per
+// SIMD the kernel is compiled for: a workgroup is one wave per SIMD), the head range of a tile is split over `nsplit`
+// workgroups; each writes its partial tile to the workspace image [split][img][T][ldp] and attn_dbias_sum_kernel adds the
+// splits in index order -- a fixed order of fp32 additions in both kernels, so the result is bit-reproducible.
+//
+// Waves per SIMD (dbias_waves): the largest occupancy at which no instantiation spills
+// (profiles/attn_dbias_resource_usage.txt).  bf16 / f32 registers at head_dim 32, 64, 128, 256 when compiled for the dQ
+// pass's occupancies: 96 (+ 84 bytes of scratch at five waves) / 128 (+ 20 at four) / 167 / 244 and 128 (+ 20 at four) /
+// 168 / 250 / 256 + 134 -- so one wave fewer than dQ at bf16 32 and 64 and at f32 32.
+template <typename CT>
+constexpr int dbias_waves(int dhp) {
+    const bool bf = sizeof(CT) == 2;
+    if (dhp <= 32) return bf ? 4 : 3;
+    if (dhp <= 64) return 3;
+    if (dhp <= 128) return bf ? 3 : 2;
+    return bf ? 2 : 1;
+}
+constexpr int DB_CUS = 256;          // split until the launch has DB_CUS x dbias_waves workgroups (the MI355X's compute units x residency) ...
+constexpr int DB_MIN_TERMS = 4;      // ... but keep at least this many heads per workgroup: below that the partial images cost more than they spread
+
+struct DProb {
+    const char* Q; const char* K; const char* V; const char* dO;
+    const float* lse; const float* delta;
+    const float* m; int ldm; int mhs;       // the additive mask, forward orientation, and its head stride
+    float* out; int ldo; int wlim;          // dB (nsplit == 1) or the partial images; columns < wlim of a row may be written
+    long ohs, osplit;                       // elements between images / between splits of `out`
+    int B, H, T, S;
+    int mask_off, qpos0, qstride;
+    int per_head;                           // image = head (terms: samples) instead of one image (terms: all B*H heads)
+    int nterm, nsplit, chunk;               // heads that feed an image; workgroups that share them; heads per workgroup
+    int blk0, nqt, nkt;
+    DropCfg drop;
+};
+struct DGroup {
+    const uint64_t* seedp;
+    int nprob;
+    DProb p[BPM_MAX_GROUP];
+};
+static_assert(sizeof(DGroup) <= 4096, "kernel arguments are limited to 4 KiB");
+
+template <typename CT, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_waves<CT>(DHP), dbias_waves<CT>(DHP)))) void attn_dbias_kernel(const DGroup grp) {
+    typedef Cfg<CT, DHP> C;
+    typedef typename Tr<CT>::frag frag;
+    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE];
+    char* kimg = smem;
+    char* vimg = smem + KT * C::STRIDE;
+
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    int pi = 0;
+#pragma unroll 1
+    for (int i = 1; i < grp.nprob; ++i)
+        if (bid >= grp.p[i].blk0) pi = i;
+    const DProb& P = grp.p[pi];
+    bid -= P.blk0;
+    const DropCfg drop = bpm_resolve_drop(P.drop, grp.seedp);
+    const int kt = bid % P.nkt, qb = (bid / P.nkt) % P.nqt;                 // key tiles of a query tile are neighbours
+    const int rest = bid / (P.nkt * P.nqt), sp = rest % P.nsplit, img = rest / P.nsplit;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = lane & 15, g = lane >> 4;
+    const int q0 = qb * 64 + wave * 16;               // wave-uniform first query
+    const int q = q0 + c;                             // this lane's query
+    const int jb = kt * KT + 4 * g;                   // key of element (n, r) is jb + 16n + r
+
+    f32x4 acc[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const int q_hi = min(P.T, qb * 64 + 64) - 1;
+    const int jend = min(P.S, P.qpos0 + q_hi * P.qstride + P.mask_off);      // one past the last key any query of this tile sees
+    const int lim = min(P.S, P.qpos0 + q * P.qstride + P.mask_off);          // this lane sees keys j < lim
+    const int lim_min = min(P.S, P.qpos0 + q0 * P.qstride + P.mask_off);     // every lane of the wave sees keys j < lim_min
+    const bool edge = kt * KT + KT > lim_min;
+    const int rel = lim - jb;
+    const bool dropping = drop.thresh != 0;
+    const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
+    const int t0 = sp * P.chunk, t1 = min(P.nterm, t0 + P.chunk);
+    auto head_of = [&](int t) { return P.per_head ? t * P.H + img : t; };    // term -> (b * H + h)
+
+    if (kt * KT < jend && t0 < t1) {                   // block-uniform: a tile the mask_off rule hides keeps its zeros
+        RowStage<CT, DHP, KT> kst, vst;
+        auto stage = [&](int t) {
+            const size_t bh = (size_t)head_of(t);
+            kst.load(P.K + bh * P.S * C::ROWB, kt * KT, P.S, tid);
+            vst.load(P.V + bh * P.S * C::ROWB, kt * KT, P.S, tid);
+        };
+        stage(t0);
+#pragma unroll 1
+        for (int t = t0; t < t1; ++t) {
+            const int bh = head_of(t), h = bh % P.H;
+            // this head's operands of the lane's query: issued before the barriers, used after them
+            frag qf[C::NKS], dof[C::NKS];
+            const char* Qh = P.Q + (size_t)bh * P.T * C::ROWB;
+            const char* dOh = P.dO + (size_t)bh * P.T * C::ROWB;
+#pragma unroll
+            for (int s = 0; s < C::NKS; ++s) {
+                qf[s] = load_frag<CT, DHP>(Qh, q, P.T, s, g);
+                dof[s] = load_frag<CT, DHP>(dOh, q, P.T, s, g);
+            }
+            const size_t srow = (size_t)bh * P.T + min(q, P.T - 1);
+            const float lse2 = (q < P.T) ? -P.lse[srow] * LOG2E : 0.f;
+            const float delta = (q < P.T) ? P.delta[srow] : 0.f;
+            const float* arow = P.m + (size_t)h * P.mhs + (size_t)min(q, P.T - 1) * P.ldm;
+            f32x4 am4[4];                              // mask of keys kt * KT + 16n + 4g + (0..3)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                const int jc = jb + 16 * n;            // jc % 4 == 0 and ldm % 4 == 0: jc < S implies jc + 3 < ldm
+                am4[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (q < P.T && jc < P.S) am4[n] = *(const f32x4*)(arow + jc);
+            }
+            __syncthreads();                           // every wave is done with the previous head's images
+            kst.store(kimg, tid);
+            vst.store(vimg, tid);
+            __syncthreads();
+            if (t + 1 < t1) stage(t + 1);
+            const uint32_t drow = ((uint32_t)bh * (uint32_t)P.T + (uint32_t)q) * (uint32_t)P.S;
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                f32x4 s_ = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < C::NKS; ++s) {
+                    s_ = Tr<CT>::mma(read_rowfrag<CT>(kimg, C::STRIDE, 16 * n, s, lane), qf[s], s_);
+                    dp = Tr<CT>::mma(read_rowfrag<CT>(vimg, C::STRIDE, 16 * n, s, lane), dof[s], dp);
+                }
+                s_ += am4[n];
+                float dm[4] = {1.f, 1.f, 1.f, 1.f};
+                if (dropping) {
+                    if (pair_ok) {
+                        bpm_drop_mult4(drop, drow + (uint32_t)(jb + 16 * n), dm[0], dm[1], dm[2], dm[3]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dm[r] = bpm_drop_mult(drop, drow + (uint32_t)(jb + 16 * n + r));
+                    }
+                }
+                f32x4 e4 = s_ * LOG2E + lse2;
+                if (edge) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e4[r] = (16 * n + r < rel) ? e4[r] : -INFINITY;   // exp2(-inf) = 0: masked before the exponential
+                }
+                f32x4 p4;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p4[r] = fast_exp2(e4[r]);
+                const f32x4 dm4 = f32x4{dm[0], dm[1], dm[2], dm[3]};
+                acc[n] += p4 * (dp * dm4 - delta);
+            }
+        }
+    }
+    if (q < P.T) {
+        float* orow = P.out + (size_t)sp * P.osplit + (size_t)img * P.ohs + (size_t)q * P.ldo;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            const int jc = jb + 16 * n;
+            if (jc + 4 <= P.wlim) *(f32x4*)(orow + jc) = acc[n];
+            else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (jc + r < P.wlim) orow[jc + r] = acc[n][r];
+            }
+        }
+    }
+}
+
+// dB = the partial images of a split launch, added in split order.  One thread per 4 consecutive keys of a row.
+struct DSumProb {
+    const float* part; int ldp; long phs, psplit;
+    float* dB; int lddb; long ohs;
+    int nimg, T, S, nsplit;
+    int c4;                 // float4 groups per row: (S + 3) / 4
+    unsigned blk0;
+};
+struct DSumGroup {
+    int nprob;
+    DSumProb p[BPM_MAX_GROUP];
+};
+static_assert(sizeof(DSumGroup) <= 4096, "kernel arguments are limited to 4 KiB");
+
+__global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_kernel(const DSumGroup grp) {
+    unsigned bid = blockIdx.x;
+    int pi = 0;
+#pragma unroll 1
+    for (int i = 1; i < grp.nprob; ++i)
+        if (bid >= grp.p[i].blk0) pi = i;
+    const DSumProb& P = grp.p[pi];
+    bid -= P.blk0;
+    const size_t idx = (size_t)bid * NTHREADS + threadIdx.x;
+    const size_t per_img = (size_t)P.T * P.c4;
+    if (idx >= per_img * P.nimg) return;
+    const int img = (int)(idx / per_img);
+    const size_t rem = idx - (size_t)img * per_img;
+    const int i = (int)(rem / P.c4), j = 4 * (int)(rem % P.c4);
+    const float* src = P.part + (size_t)img * P.phs + (size_t)i * P.ldp + j;      // ldp = 4 c4: whole groups
+    f32x4 v = *(const f32x4*)src;
+#pragma unroll 1
+    for (int s = 1; s < P.nsplit; ++s) v += *(const f32x4*)(src + (size_t)s * P.psplit);
+    float* dst = P.dB + (size_t)img * P.ohs + (size_t)i * P.lddb + j;
+    if (j + 4 <= P.S) *(f32x4*)dst = v;
+    else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (j + r < P.S) dst[r] = v[r];
+    }
+}
+
+// ---- bpm_attn_bwd_dbias: check / choose / fill / launch -----------------------------------------------------------------
+// check: everything about the problems and the outputs that can be refused on the host; nothing is dereferenced
+int dbias_check(const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int nprob) {
+    if (!group_ok(probs, nprob) || !outs) return BPM_ERR_ARG;
+    if (with_dhp(probs[0].dhp, [](auto) { return 0; }) != 0) return BPM_ERR_ARG;      // here up front: the workspace query chooses by it
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const bpm_attn_dbias& o = outs[i];
+        if (!geometry_ok(q, probs[0].dhp)) return BPM_ERR_ARG;
+        if (q.dS || q.Pd) return BPM_ERR_ARG;
+        if (!o.dB || o.lddb < q.S || (o.lddb & 3) || ((uintptr_t)o.dB & 15)) return BPM_ERR_ARG;
+        if (o.head_stride != 0 && (o.head_stride < (int64_t)q.T * o.lddb || (o.head_stride & 3))) return BPM_ERR_ARG;
+    }
+    return 0;
+}
+
+// choose: how many workgroups share the heads of one tile (1: no split, the tile goes straight to dB).  The launch's
+// tiles are counted over all problems; the head range is split until the launch has DB_CUS workgroups, while a workgroup
+// keeps at least DB_MIN_TERMS heads.  The target is DB_CUS x the bf16 kernel's waves per SIMD at this head_dim (the
+// workspace query does not know the compute type; the f32 kernels hold fewer workgroups at once and are merely split a
+// little further than they need).  Measured at B 8, H 12 x 64, T = S = 512: a target of DB_CUS
+// alone (4 splits, 256 workgroups of 24 heads) took 67 us against the per-head form's 36.  Returns the workspace the
+// splits need, in bytes (16-byte granules).
+struct DChoice { int nimg, nterm, nsplit, chunk, ldp; size_t ws_off; };
+size_t dbias_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int nprob) {
+    long tiles = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        ch[i].nimg = outs[i].head_stride != 0 ? q.H : 1;
+        ch[i].nterm = outs[i].head_stride != 0 ? q.B : q.B * q.H;
+        tiles += (long)ch[i].nimg * ((q.T + 63) / 64) * ((q.S + KT - 1) / KT);
+    }
+    const long target = (long)DB_CUS * dbias_waves<bf16_t>(probs[0].dhp);
+    const long want = tiles >= target ? 1 : (target + tiles - 1) / tiles;
+    size_t bytes = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        DChoice& c = ch[i];
+        long ns = (c.nterm + DB_MIN_TERMS - 1) / DB_MIN_TERMS;
+        if (ns > want) ns = want;
+        c.chunk = (int)((c.nterm + ns - 1) / ns);
+        c.nsplit = (c.nterm + c.chunk - 1) / c.chunk;           // no empty split: nsplit <= ns, and 1 only when ns is
+        c.ldp = (q.S + 3) / 4 * 4;
+        c.ws_off = bytes;
+        if (ns > 1) bytes += (size_t)ns * c.nimg * q.T * c.ldp * sizeof(float);      // by ns: monotone in the number of heads
+    }
+    return bytes;
+}
+
+// fill: the two argument blocks (the mask descriptors are checked here, by the rule of the other *_amask entries)
+int dbias_fill(DGroup& g, DSumGroup& sg, const DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_hmask* masks,
+               const bpm_attn_dbias* outs, int nprob, uint64_t seed, void* ws, long* total, long* sum_blocks) {
+    g.nprob = nprob;
+    g.seedp = bpm_seed_ptr(seed);
+    sg.nprob = 0;
+    long blk = 0, sblk = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const DChoice& c = ch[i];
+        DProb& p = g.p[i];
+        if (!q.Q || !q.K || !q.V || !q.dO || !q.lse || !q.delta) return BPM_ERR_ARG;
+        if (((uintptr_t)q.Q | (uintptr_t)q.K | (uintptr_t)q.V | (uintptr_t)q.dO) & 15) return BPM_ERR_ALIGN;
+        AAdd a;
+        const int rc = amask_desc(a, masks[i], q.T, q.S, false);
+        if (rc) return rc;
+        p.Q = (const char*)q.Q; p.K = (const char*)q.K; p.V = (const char*)q.V; p.dO = (const char*)q.dO;
+        p.lse = q.lse; p.delta = q.delta;
+        p.m = a.m; p.ldm = a.ld; p.mhs = a.hs;
+        p.B = q.B; p.H = q.H; p.T = q.T; p.S = q.S;
+        if (!positions(q, p)) return BPM_ERR_ARG;
+        p.per_head = outs[i].head_stride != 0;
+        p.nterm = c.nterm; p.nsplit = c.nsplit; p.chunk = c.chunk;
+        p.drop = bpm_make_drop(q.drop_p, seed, q.drop_site);
+        p.nqt = (q.T + 63) / 64; p.nkt = (q.S + KT - 1) / KT;
+        p.blk0 = (int)blk;
+        blk += (long)c.nimg * c.nsplit * p.nqt * p.nkt;
+        if (blk > (1l << 30)) return BPM_ERR_ARG;
+        if (c.nsplit == 1) {
+            p.out = outs[i].dB; p.ldo = outs[i].lddb; p.wlim = q.S; p.ohs = (long)outs[i].head_stride; p.osplit = 0;
+        } else {
+            p.out = (float*)((char*)ws + c.ws_off); p.ldo = c.ldp; p.wlim = c.ldp;
+            p.ohs = (long)q.T * c.ldp; p.osplit = (long)c.nimg * q.T * c.ldp;
+            DSumProb& s = sg.p[sg.nprob++];
+            s.part = p.out; s.ldp = c.ldp; s.phs = p.ohs; s.psplit = p.osplit;
+            s.dB = outs[i].dB; s.lddb = outs[i].lddb; s.ohs = (long)outs[i].head_stride;
+            s.nimg = c.nimg; s.T = q.T; s.S = q.S; s.nsplit = c.nsplit; s.c4 = c.ldp / 4;
+            s.blk0 = (unsigned)sblk;
+            sblk += ((long)c.nimg * q.T * s.c4 + NTHREADS - 1) / NTHREADS;
+        }
+    }
+    *total = blk; *sum_blocks = sblk;
+    return 0;
+}
+
+template <typename CT>
+int dbias_launch(int dhp, const DGroup& g, long total, const DSumGroup& sg, long sum_blocks, void* stream) {
+    const int rc = with_dhp(dhp, [&](auto d) { return launch<attn_dbias_kernel<CT, decltype(d)::value>>((unsigned)total, NTHREADS, stream, g); });
+    if (rc || sum_blocks <= 0) return rc;
+    return launch<attn_dbias_sum_kernel>((unsigned)sum_blocks, NTHREADS, stream, sg);
+}
+
+}  // namespace
+
+extern "C" size_t bpm_attn_bwd_dbias_ws_bytes(const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int nprob) {
+    DChoice ch[BPM_MAX_GROUP];
+    if (dbias_check(probs, outs, nprob)) return 0;
+    return dbias_choose(ch, probs, outs, nprob);
+}
+
+// The gradient of an additive mask (a learned attention bias): see bpm_attn_dbias in include/bpmult_hip.h.
+extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_dbias* outs,
+                                  int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    if (!dtype_ok(dtype)) return BPM_ERR_ARG;
+    if (!masks) return BPM_ERR_ARG;
+    int rc = dbias_check(probs, outs, nprob);
+    if (rc) return rc;
+    DChoice ch[BPM_MAX_GROUP];
+    const size_t need = dbias_choose(ch, probs, outs, nprob);
+    if (need > 0 && (!ws || ws_bytes < need || ((uintptr_t)ws & 15))) return BPM_ERR_ARG;
+    DGroup g;
+    DSumGroup sg;
+    long total = 0, sum_blocks = 0;
+    rc = dbias_fill(g, sg, ch, probs, masks, outs, nprob, seed, ws, &total, &sum_blocks);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int sz = dtype == BPM_BF16 ? 2 : 4;
+    double bytes = 0;                                            // Q, K, V, dO, lse, delta in; the mask in, dB out (partials: overhead)
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        bytes += (double)q.B * q.H * ((2.0 * q.T + 2.0 * q.S) * q.dh * sz + 2.0 * q.T * 4) + 4.0 * q.T * q.S * ch[i].nimg * 2;
+    }
+    BpmProfScope prof(BPM_K_ATTN_BWD_DBIAS, s, 4.0 * useful_pair_flops(probs, nprob), bytes);      // S and dP: two products
+    return with_ct(dtype, [&](auto ct) { return dbias_launch<decltype(ct)>(probs[0].dhp, g, total, sg, sum_blocks, stream); });
+}

@@ -1,12 +1,12 @@
 // The library's housekeeping: bpm_version / bpm_error_string, the event-based launch profiler behind bpm_prof_*, the
-// stream helpers (include/bpmult_hip.h) and, in the -DBPM_LAB build, the record of the row files' dry launches.
+// stream helpers (include/bpmult_hip.h) and, in the -DBPM_LAB build, the record of the row and attention files' dry launches.
 #include <cstdio>
 #include <mutex>
 #include <vector>
 
 #include "../../include/bpmult_hip.h"
 #include "bpm_prof.h"
-#include "rows_common.h"
+#include "bpm_launch.h"
 
 unsigned g_bpm_prof_mask = 0;
 
@@ -104,9 +104,9 @@ extern "C" const char* bpm_error_string(int code) {
 }
 
 #ifdef BPM_LAB
-// Dry mode of rows_common.h's launch(): while it is on, an entry point of the row files runs its check, fill and choose
-// steps and returns its code, and every launch it would have made is noted here instead (nothing is dereferenced, no
-// device is needed).  bpm_debug_rows_dry(on) also forgets the notes; bpm_debug_rows_last(i, ...) reads note i back (the
+// Dry mode of bpm_launch.h's launch(): while it is on, an entry point of the row files -- and, the names notwithstanding,
+// of the attention files, which launch through the same helper -- runs its check, fill and choose steps and returns its
+// code, and every launch it would have made is noted here instead (nothing is dereferenced, no device is needed).  bpm_debug_rows_dry(on) also forgets the notes; bpm_debug_rows_last(i, ...) reads note i back (the
 // kernel's instantiation as launch() spells it: the mangled name of its KernelTag) and returns how many launches were noted.
 int g_bpm_rows_dry = 0;
 

@@ -1,24 +1,17 @@
 // What more than one family of row kernels uses (rows_pack.hip, rows_norm.hip, rows_elem.hip, adam.hip; bert_embed.hip
 // takes put4): the grouped-launch argument, small device helpers, and the shared pieces of the ONE shape of an entry
-// point -- check, fill, choose, launch: grp_begin, launch, with_ct, with_width.  Every row-kernel entry is GROUPED: one
+// point -- check, fill, choose, launch: grp_begin, with_width, and launch / with_ct from bpm_launch.h (which the
+// attention files share).  Every row-kernel entry is GROUPED: one
 // launch serves up to BPM_MAX_GROUP independent problems (the encoders of one level run in lock-step), passed by value
 // in the kernel-argument segment; a block finds its problem from a prefix table of block counts.
 // Everything sits in the unnamed namespace, as the kernels of those files do: their symbols carry it.
 #pragma once
 #include <cmath>
 #include <type_traits>
-#include <typeinfo>
 
 #include "bpm_common.h"
+#include "bpm_launch.h"
 #include "../../include/bpmult_hip.h"
-
-#ifdef BPM_LAB
-// Dry mode of the lab build (prof.hip: bpm_debug_rows_dry / bpm_debug_rows_last): launch() notes what it would have
-// launched and launches nothing, so the launch decisions are testable without a GPU (tests/test_rowops_dispatch_cpu.py).
-#define BPM_HIDDEN __attribute__((visibility("hidden")))      // shared by the library's files, not exported
-extern BPM_HIDDEN int g_bpm_rows_dry;
-BPM_HIDDEN void bpm_rows_note(const char* kernel, unsigned grid, unsigned block, const void* aux);
-#endif
 
 namespace {
 constexpr int NT = 256;
@@ -76,31 +69,6 @@ inline bool grp_begin(Grp<P>& g, const Q* q, int n, uint64_t seed = 0) {
     g.n = n; g.blk0[0] = 0; g.seedp = bpm_seed_ptr(seed);
     return true;
 }
-
-#ifdef BPM_LAB
-template <auto K> struct KernelTag {};          // typeid(KernelTag<K>).name() spells the instantiation, arguments included
-template <typename T> const void* as_ptr(const T&) { return nullptr; }
-template <typename T> const void* as_ptr(T* p) { return (const void*)p; }
-#endif
-
-// Every launch of the row files: kernel K on `grid` blocks of `block` threads, no dynamic LDS.
-template <auto K, typename... A>
-inline int launch(unsigned grid, unsigned block, void* stream, const A&... args) {
-#ifdef BPM_LAB
-    if (g_bpm_rows_dry) {
-        const void* aux = nullptr;                 // the last pointer argument (a workspace, a counter array), if any
-        ((aux = as_ptr(args)), ...);
-        bpm_rows_note(typeid(KernelTag<K>).name(), grid, block, aux);
-        return 0;
-    }
-#endif
-    hipLaunchKernelGGL(K, dim3(grid), dim3(block), 0, (hipStream_t)stream, args...);
-    BPM_CHECK_LAUNCH();
-    return 0;
-}
-
-// f(CT()) with the compute type of `dtype`: bf16_t for BPM_BF16, float for anything else
-template <typename F> inline int with_ct(int dtype, F&& f) { return dtype == BPM_BF16 ? f(bf16_t()) : f(float()); }
 
 // Register widths W the one-wave-per-row kernels are instantiated at, UNIT columns each: the lists decide which
 // instantiations exist.

@@ -108,8 +108,9 @@ def main():
     }
     if args.out:
         with open(args.out, "w") as f:
-            json.dump(report, f, indent=0, separators=(",", ":"))
-            f.write("\n")
+            head = json.dumps({k: v for k, v in report.items() if k != "kernels"}, separators=(",", ":"))
+            rows = ",\n".join(json.dumps(k) + ":" + json.dumps(v, separators=(",", ":")) for k, v in kernels.items())
+            f.write(head[:-1] + ',"kernels":{\n' + rows + "\n}}\n")                 # a kernel per line
     print(json.dumps({k: v for k, v in report.items() if k != "kernels"}, indent=1))
     ok = not report["only_in_a"] and not report["only_in_b"] and not report["different"]
     sys.exit(0 if ok else 1)
