@@ -343,6 +343,13 @@ SIGNATURES = {
     "bpm_attn_bwd_dq_hmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), _I, _U64, _P],
     "bpm_attn_bwd_dkv_hmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), _I, _U64, _P],
     "bpm_attn_maps_hmask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnHMask), _I, _P],
+    "bpm_attn_maps_kmask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnKMask), _I, _P],
+    "bpm_attn_fwd_kamask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_kamask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_kamask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _U64, _P],
+    "bpm_attn_maps_kamask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _P],
+    "bpm_attn_bwd_dbias_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), C.POINTER(AttnKMask), C.POINTER(AttnDBias), _I, _U64, _P,
+                                 C.c_size_t, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],

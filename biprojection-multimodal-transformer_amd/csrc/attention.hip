@@ -8,7 +8,8 @@
 // Two further visibility rules are separate instantiations of the same block bodies (a compile-time mask type; the kernels
 // above never see them): the per-key byte mask of the *_kmask entries (KM) and the arbitrary additive fp32 [T, S] mask of
 // the *_amask entries (AM: the reference's attn_mask argument as a tensor, multihead_attention.py:113-115), one image for
-// all heads, or one per head through the *_hmask entries (a learned bias; its gradient is attn_dbias.hip).
+// all heads, or one per head through the *_hmask entries (a learned bias; its gradient is attn_dbias.hip); and both at once
+// (AKAdd: the *_kamask entries, a key_padding_mask beside an attn_mask / attn_bias).
 // This file: the three block bodies, their kernels and the forward / backward entries.  attn_maps.hip holds the
 // head-averaged maps, attn_common.h what the three files share.
 // The [T,S] score matrix never touches HBM: forward keeps a running (max, sum)
@@ -51,10 +52,10 @@ namespace {
 // mask row: four float4 loads, issued before the score MFMAs and added to the scores before the visibility selects (so
 // whatever sits in columns >= S, which the limit hides, never survives).  Never read at q >= T or at a group that starts
 // at j >= S.  No tile is skipped; the running maximum takes the KM guard.
-// M: the mask of the instantiation (NoMask, AMask or AAdd), mk its descriptor.
+// M: the mask of the instantiation (NoMask, AMask, AAdd or AKAdd: both), mk its descriptor.
 template <typename CT, int DHP, typename M>
 BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const M mk) {
-    constexpr bool KM = std::is_same_v<M, AMask>, AM = std::is_same_v<M, AAdd>;
+    constexpr bool KM = has_bytes<M>, AM = has_add<M>;      // has a byte mask / has an additive image
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
@@ -95,14 +96,14 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
     auto stage_mask = [&](int kt) {
         const int jm = kt * KT + tid;
         n_vis = 0;
-        if constexpr (KM) { if (tid < KT && jm < P.S) n_vis = mk.mask[(size_t)b * mk.ldm + jm] != 0; }
+        if constexpr (KM) { if (tid < KT && jm < P.S) n_vis = byte_of(mk).mask[(size_t)b * byte_of(mk).ldm + jm] != 0; }
     };
     if (ntile > 0) {
         kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
         if constexpr (KM) stage_mask(0);
     }
     const float* arow = nullptr;                       // AM: this lane's mask row
-    if constexpr (AM) arow = mk.m + (size_t)h * mk.hs + (size_t)min(q, P.T - 1) * mk.ld;
+    if constexpr (AM) arow = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(q, P.T - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -245,7 +246,8 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
 // before lse is subtracted: a -inf entry gives exp2(-inf) = 0 whatever lse is, so no guard is needed here.
 template <typename CT, int DHP, bool XP, typename M>
 BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int qb, const M mk) {
-    constexpr bool KM = std::is_same_v<M, AMask>, AM = std::is_same_v<M, AAdd>;
+    constexpr bool KM = has_bytes<M>, AM = has_add<M>;      // has a byte mask / has an additive image
+    static_assert(!XP || !KM, "the dS / Pd export would write over the byte mask that AKAdd carries in AProb::Pd (AGroupKA)");
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* kimg = smem;
@@ -310,14 +312,14 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
     auto stage_mask = [&](int kt) {
         const int jm = kt * C::KTQ + tid;
         n_vis = 0;
-        if constexpr (KM) { if (tid < C::KTQ && jm < P.S) n_vis = mk.mask[(size_t)b * mk.ldm + jm] != 0; }
+        if constexpr (KM) { if (tid < C::KTQ && jm < P.S) n_vis = byte_of(mk).mask[(size_t)b * byte_of(mk).ldm + jm] != 0; }
     };
     if (ntile > 0) {
         kst.load(Kh, 0, P.S, tid); vst.load(Vh, 0, P.S, tid);
         if constexpr (KM) stage_mask(0);
     }
     const float* arow = nullptr;                       // AM: this lane's mask row
-    if constexpr (AM) arow = mk.m + (size_t)h * mk.hs + (size_t)min(q, P.T - 1) * mk.ld;
+    if constexpr (AM) arow = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(q, P.T - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -434,7 +436,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
 // pair adds exactly nothing to dK / dV.
 template <typename CT, int DHP, typename M>
 BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem, const int bh, const int kb, const M mk) {
-    constexpr bool KM = std::is_same_v<M, AMask>, AM = std::is_same_v<M, AAdd>;
+    constexpr bool KM = has_bytes<M>, AM = has_add<M>;      // has a byte mask / has an additive image
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
     char* qimg = smem;
@@ -474,7 +476,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     int qt_hi = (P.T + C::QTK - 1) / C::QTK;
     if constexpr (KM) {
         bool kvis = false;
-        if (j < P.S) kvis = mk.mask[(size_t)b * mk.ldm + j] != 0;
+        if (j < P.S) kvis = byte_of(mk).mask[(size_t)b * byte_of(mk).ldm + j] != 0;
         if (!kvis) ilo = 1 << 30;
         if (__builtin_amdgcn_ballot_w64(!kvis) != 0) ilo_max = 1 << 30;                        // a hidden key in the wave: every tile tests
         if (!__syncthreads_or(kvis)) qt_hi = qt_lo;                                            // block-uniform: nothing to do but store zeros
@@ -497,7 +499,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     };
     if (qt_lo < qt_hi) stage(qt_lo);
     const float* acol = nullptr;                       // AM: this lane's row of the transposed mask
-    if constexpr (AM) acol = mk.m + (size_t)h * mk.hs + (size_t)min(j, P.S - 1) * mk.ld;
+    if constexpr (AM) acol = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(j, P.S - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int qt = qt_lo; qt < qt_hi; ++qt) {
         __syncthreads();
@@ -594,11 +596,12 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
 }
 
 // ---------------------------------------------------------------------------
-// the kernels: seven wrappers of one schedule
+// the kernels: eight wrappers of one schedule
 // ---------------------------------------------------------------------------
 // Kernel arguments: the unmasked kernels take AGroup and nothing else, the masked ones AGroup followed by one descriptor
-// per problem (AMask: the *_kmask entries, AAdd: the *_amask / *_hmask entries).  Two named structs, not one template: a
-// kernel's symbol spells its argument type, and the symbols are what profiles and tools know the kernels by.
+// per problem (AMask: the *_kmask entries, AAdd: the *_amask / *_hmask entries; both: the *_kamask entries, AGroupKA
+// below).  Named structs, not one template: a kernel's symbol spells its argument type, and the symbols are what
+// profiles and tools know the kernels by.
 struct AGroupK {
     AGroup g;
     AMask m[BPM_MAX_GROUP];
@@ -607,11 +610,19 @@ struct AGroupA {
     AGroup g;
     AAdd m[BPM_MAX_GROUP];
 };
+// Both masks (the *_kamask entries): AGroup and 18 x (AMask + AAdd) would be 4192 bytes, past the 4 KiB limit.  The masked
+// entries refuse the dS / Pd export, so in this family those fields of AProb carry the byte mask instead (Pd: the bytes,
+// xs_b: their leading dimension; dS stays NULL) -- set_byte_mask on the host, byte_mask_of in the kernel, nowhere else.
+// A type of its own, so that the kernel's symbol and the launch dispatch tell the family from AGroupA.
+struct AGroupKA : AGroupA {};
+inline void set_byte_mask(AProb& p, const AMask& k) { p.dS = nullptr; p.Pd = (char*)k.mask; p.xs_b = k.ldm; }
+BPM_DEV AMask byte_mask_of(const AProb& p) { return AMask{(const uint8_t*)p.Pd, p.xs_b}; }
 static_assert(sizeof(AGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(AGroupKA) <= 4096, "kernel arguments are limited to 4 KiB");
 static_assert(sizeof(AGroupA) <= 4096, "kernel arguments are limited to 4 KiB");
 
 // Every wrapper below: xcd_remap, pick the problem (and its mask), resolve dropout, pair the blocks, run the block body
-// once or twice.  The schedule is spelled out in each: folding the seven into one function (or even one spelling of
+// once or twice.  The schedule is spelled out in each: folding them into one function (or even one spelling of
 // pick) moved instructions in 18 to 47 of the 80 instantiations, and these kernels are tuned to the register.
 // Two 64-row blocks per workgroup, b and nblk - 1 - b: under the future mask block b has b + 1 (forward / dQ) or nblk - b
 // (dK / dV) tiles, so every pair carries the same work, and the per-block lead-in (operand loads, first tile, result
@@ -757,6 +768,42 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
     }
 }
 
+// ... and with both masks (bpm_attn_fwd_kamask / _bwd_dq_kamask / _bwd_dkv_kamask): the LDS of the *_kmask kernels (the
+// tile's mask bytes behind the K / V images), the registers of the *_amask kernels plus the byte-mask staging.  Compiled
+// for the occupancy of the *_amask sibling, one wave fewer where it would otherwise spill more than the sibling does: the
+// dQ pass in bf16 at every head_dim (12 / 20 / 176 / 32 bytes per lane at 32 / 64 / 128 / 256 against 0 / 0 / 32 / 0) and
+// in f32 at 128 (84 against 0), the bf16 forward at 256 (116 against 0).  What is left: DESIGN.md section 5.
+template <typename CT>
+constexpr int attn_waves_kam(int kernel, int dhp) {
+    const bool bf = sizeof(CT) == 2;
+    const bool lower = bf ? (kernel == 1 || (kernel == 0 && dhp == 256)) : (kernel == 1 && dhp == 128);
+    return attn_waves_am<CT>(kernel, dhp) - (lower ? 1 : 0);
+}
+
+template <typename CT, int DHP, int WHICH>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves_kam<CT>(WHICH, DHP), attn_waves_kam<CT>(WHICH, DHP)))) void attn_kamask_kernel(const AGroupKA ga) {
+    typedef Cfg<CT, DHP> C;
+    constexpr int ROWS = WHICH == 0 ? KT : WHICH == 1 ? C::KTQ : C::QTK;
+    __shared__ __attribute__((aligned(16))) char smem[2 * ROWS * C::STRIDE + (WHICH == 2 ? 2 * C::QTK * 4 : ROWS)];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(ga.g, bid);
+    const AProb& P = ga.g.p[pi];
+    const AKAdd kam = AKAdd{byte_mask_of(P), ga.m[pi]};
+    const DropCfg drop = bpm_resolve_drop(P.drop, ga.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2;
+    const int first = (P.pair || WHICH == 2) ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        const int blk = pass ? second : first;
+        if constexpr (WHICH == 0) attn_fwd_block<CT, DHP>(P, drop, smem, bh, blk, kam);
+        else if constexpr (WHICH == 1) attn_bwd_dq_block<CT, DHP, false>(P, drop, smem, bh, blk, kam);
+        else attn_bwd_dkv_block<CT, DHP>(P, drop, smem, bh, blk, kam);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side.  Every entry is check (attn_common.h) / fill / choose / launch.
 // ---------------------------------------------------------------------------
@@ -801,12 +848,18 @@ int fill(AGroup& g, const bpm_attn_problem* probs, int nprob, uint64_t seed, int
     return 0;
 }
 
-// fill of a masked launch (A: AGroupK with bpm_attn_kmask masks, AGroupA with bpm_attn_hmask masks; which: 0 forward,
-// 1 dQ, 2 dK / dV, which reads an additive mask through its transpose); nothing is launched on an error
+// the two mask arrays of a *_kamask entry as one argument of the shared shape (fill_masked / attn_masked)
+struct KAMasks { const bpm_attn_kmask* k; const bpm_attn_hmask* a; };
+inline bool masks_given(const KAMasks* m) { return m->k && m->a; }
+inline bool masks_given(const void* m) { return m != nullptr; }
+
+// fill of a masked launch (A: AGroupK with bpm_attn_kmask masks, AGroupA with bpm_attn_hmask masks, AGroupKA with both as
+// KAMasks; which: 0 forward, 1 dQ, 2 dK / dV, which reads an additive mask through its transpose); nothing is launched on
+// an error
 template <typename A, typename MK>
 int fill_masked(A& a, int dtype, const bpm_attn_problem* probs, const MK* masks, int nprob, uint64_t seed, int* total, int which) {
     if (!dtype_ok(dtype)) return BPM_ERR_ARG;
-    if (!masks) return BPM_ERR_ARG;
+    if (!masks_given(masks)) return BPM_ERR_ARG;
     int rc = fill(a.g, probs, nprob, seed, total, which);
     if (rc) return rc;
     if (!pointers_ok(probs, nprob, which)) return BPM_ERR_ARG;
@@ -814,8 +867,12 @@ int fill_masked(A& a, int dtype, const bpm_attn_problem* probs, const MK* masks,
         const bpm_attn_problem& q = probs[i];
         if (q.dS || q.Pd) return BPM_ERR_ARG;                    // the score-gradient export has no masked instantiation
         if constexpr (std::is_same_v<A, AGroupK>) {
-            if (!masks[i].mask || masks[i].ldm < q.S) return BPM_ERR_ARG;
-            a.m[i] = AMask{masks[i].mask, masks[i].ldm};
+            if ((rc = kmask_desc(a.m[i], masks[i], q.S)) != 0) return rc;
+        } else if constexpr (std::is_same_v<A, AGroupKA>) {
+            AMask k;
+            if ((rc = kmask_desc(k, masks->k[i], q.S)) != 0) return rc;
+            if ((rc = amask_desc(a.m[i], masks->a[i], q.T, q.S, which == 2)) != 0) return rc;
+            set_byte_mask(a.g.p[i], k);
         } else if ((rc = amask_desc(a.m[i], masks[i], q.T, q.S, which == 2)) != 0) return rc;
     }
     for (int i = nprob; i < BPM_MAX_GROUP; ++i) a.m[i] = {};
@@ -846,6 +903,7 @@ double attn_bytes(const bpm_attn_problem* probs, int nprob, int sz, int which) {
 template <typename A, typename CT, int D, int WHICH, bool XP = false>
 constexpr auto attn_kernel() {
     if constexpr (std::is_same_v<A, AGroupA>) return &attn_amask_kernel<CT, D, WHICH>;
+    else if constexpr (std::is_same_v<A, AGroupKA>) return &attn_kamask_kernel<CT, D, WHICH>;
     else if constexpr (std::is_same_v<A, AGroupK>)
         return WHICH == 0 ? &attn_fwd_kmask_kernel<CT, D> : WHICH == 1 ? &attn_bwd_dq_kmask_kernel<CT, D> : &attn_bwd_dkv_kmask_kernel<CT, D>;
     else if constexpr (WHICH == 1) return &attn_bwd_dq_kernel<CT, D, XP>;
@@ -874,7 +932,7 @@ int attn_masked(int which, int kind, int dtype, const bpm_attn_problem* probs, c
     int rc = fill_masked(a, dtype, probs, masks, nprob, seed, &total, which);
     if (rc) return rc;
     double mbytes = 0;
-    if constexpr (std::is_same_v<A, AGroupA>)
+    if constexpr (!std::is_same_v<A, AGroupK>)
         for (int i = 0; i < nprob; ++i) mbytes += 4.0 * probs[i].T * probs[i].S;
     BpmProfScope prof(kind, (hipStream_t)stream, 4.0 * useful_pair_flops(probs, nprob),
                       attn_bytes(probs, nprob, dtype == BPM_BF16 ? 2 : 4, which) + mbytes);
@@ -967,4 +1025,22 @@ extern "C" int bpm_attn_bwd_dq_hmask(int dtype, const bpm_attn_problem* probs, c
 }
 extern "C" int bpm_attn_bwd_dkv_hmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, int nprob, uint64_t seed, void* stream) {
     return attn_masked<AGroupA>(2, BPM_K_ATTN_BWD_DKV, dtype, probs, masks, nprob, seed, stream);
+}
+
+// Attention with a per-key padding mask AND an additive mask (one image or one per head): see bpm_attn_fwd_kamask in
+// include/bpmult_hip.h.
+extern "C" int bpm_attn_fwd_kamask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks, int nprob,
+                                   uint64_t seed, void* stream) {
+    const KAMasks m{kmasks, masks};
+    return attn_masked<AGroupKA>(0, BPM_K_ATTN_FWD, dtype, probs, &m, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dq_kamask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks, int nprob,
+                                      uint64_t seed, void* stream) {
+    const KAMasks m{kmasks, masks};
+    return attn_masked<AGroupKA>(1, BPM_K_ATTN_BWD_DQ, dtype, probs, &m, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dkv_kamask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks, int nprob,
+                                       uint64_t seed, void* stream) {
+    const KAMasks m{kmasks, masks};
+    return attn_masked<AGroupKA>(2, BPM_K_ATTN_BWD_DKV, dtype, probs, &m, nprob, seed, stream);
 }

@@ -90,6 +90,26 @@ struct NoMask {};           // the mask argument of the block bodies when there 
 // m + h * hs); 0: one image for all heads.
 struct AAdd { const float* m; int ld; int hs; };
 
+// Both at once (the *_kamask entries: a key_padding_mask beside an attn_mask / attn_bias): pair (b, h, i, j) is visible iff
+// the mask_off rule, the byte k.mask[b * k.ldm + j] != 0 and a.m[h * a.hs + i * a.ld + j] > -inf all say so.  The block
+// bodies compile their byte-mask part for AMask and AKAdd and their additive part for AAdd and AKAdd; the two parts do not
+// know of each other.  byte_of / add_of: the part of a descriptor a body reads (a reference to the descriptor itself for
+// the two single types, so their instantiations see the same value they always did).
+struct AKAdd { AMask k; AAdd a; };
+template <typename M> constexpr bool has_bytes = std::is_same_v<M, AMask> || std::is_same_v<M, AKAdd>;
+template <typename M> constexpr bool has_add = std::is_same_v<M, AAdd> || std::is_same_v<M, AKAdd>;
+BPM_DEV const AMask& byte_of(const AMask& m) { return m; }
+BPM_DEV const AMask& byte_of(const AKAdd& m) { return m.k; }
+BPM_DEV const AAdd& add_of(const AAdd& m) { return m; }
+BPM_DEV const AAdd& add_of(const AKAdd& m) { return m.a; }
+
+// The byte-mask switch of the maps and bias-gradient kernels (attn_maps.hip, attn_dbias.hip): it rides in the compute-type
+// argument -- attn_maps_kernel<WithBytes<bf16_t>, 64, ...> -- so the instantiations without it keep their template
+// arguments, which is what launch records and profiles spell them by.
+template <typename T> struct WithBytes {};
+template <typename T> struct CtOf { typedef T type; static constexpr bool bytes = false; };
+template <typename T> struct CtOf<WithBytes<T>> { typedef T type; static constexpr bool bytes = true; };
+
 template <typename CT, int DHP> struct Cfg {
     static constexpr int SZ = sizeof(CT);
     static constexpr int NKS = DHP / Tr<CT>::KSTEP;        // k-steps over head_dim
@@ -305,6 +325,13 @@ inline int amask_desc(AAdd& a, const bpm_attn_hmask& m, int T, int S, bool trans
     a.m = transposed ? m.maskT : m.mask;
     a.ld = transposed ? m.ldt : m.ldm;
     a.hs = (int)hs;
+    return 0;
+}
+
+// One byte mask as the kernels read it: bytes [B, ldm], ldm >= S (the kernels never read at j >= S: a tight [B, S] is legal).
+inline int kmask_desc(AMask& k, const bpm_attn_kmask& m, int S) {
+    if (!m.mask || m.ldm < S) return BPM_ERR_ARG;
+    k = AMask{m.mask, m.ldm};
     return 0;
 }
 

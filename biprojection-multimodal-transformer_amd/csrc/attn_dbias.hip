@@ -1,4 +1,5 @@
-// Gradient of an additive attention mask (a learned bias) for BPMulT on gfx950: bpm_attn_bwd_dbias and its workspace query.
+// Gradient of an additive attention mask (a learned bias) for BPMulT on gfx950: bpm_attn_bwd_dbias[_kmask] and the workspace
+// query.
 // What it shares with the forward / backward kernels of attention.hip is in attn_common.h.
 #include "attn_common.h"
 
@@ -56,13 +57,46 @@ struct DGroup {
 };
 static_assert(sizeof(DGroup) <= 4096, "kernel arguments are limited to 4 KiB");
 
-template <typename CT, int DHP>
-__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_waves<CT>(DHP), dbias_waves<CT>(DHP)))) void attn_dbias_kernel(const DGroup grp) {
+// KB (bpm_attn_bwd_dbias_kmask): the per-key byte masks of the forward pass, in an argument block of their own behind
+// DGroup (the kernel without KB keeps its arguments); the switch rides in the compute-type argument (WithBytes).  The head's sample decides the bytes: the tile's KT of them are
+// fetched one head ahead by the first KT threads (never at j >= S), pass through KT bytes of LDS behind the K / V images as
+// 0 / 1 and hide a key before the exponential, as the mask_off rule does: sample b adds exactly nothing at its hidden
+// keys.  A head whose sample hides the whole tile is skipped.  The order of the additions does not change.
+struct DGroupK {
+    DGroup g;
+    AMask k[BPM_MAX_GROUP];
+};
+static_assert(sizeof(DGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
+
+// Waves per SIMD with KB: the staging costs registers; one wave fewer where the kernel would spill at dbias_waves (bf16 at
+// head_dim 32 / 128 / 256: 12 / 76 / 12 bytes per lane, f32 at 64: 52).  dbias_choose keeps the bf16 target of the kernel
+// without KB: the workspace query does not know of the byte masks, and a launch split a little further is still correct.
+template <typename CT>
+constexpr int dbias_waves_kb(int dhp) {
+    const bool bf = sizeof(CT) == 2;
+    const bool lower = bf ? (dhp <= 32 || dhp == 128 || dhp == 256) : (dhp == 64);
+    return dbias_waves<CT>(dhp) - (lower ? 1 : 0);
+}
+
+BPM_DEV const DGroup& dbias_group(const DGroup& g) { return g; }
+BPM_DEV const DGroup& dbias_group(const DGroupK& g) { return g.g; }
+template <typename CTX>
+constexpr int dbias_waves_x(int dhp) {
+    return CtOf<CTX>::bytes ? dbias_waves_kb<typename CtOf<CTX>::type>(dhp) : dbias_waves<typename CtOf<CTX>::type>(dhp);
+}
+
+// CTX: the compute type, or WithBytes<compute type> for KB
+template <typename CTX, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_waves_x<CTX>(DHP), dbias_waves_x<CTX>(DHP)))) void attn_dbias_kernel(const std::conditional_t<CtOf<CTX>::bytes, DGroupK, DGroup> ga) {
+    typedef typename CtOf<CTX>::type CT;
+    constexpr bool KB = CtOf<CTX>::bytes;
+    const DGroup& grp = dbias_group(ga);
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
-    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE];
+    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE + (KB ? KT : 0)];
     char* kimg = smem;
     char* vimg = smem + KT * C::STRIDE;
+    uint8_t* smask = (uint8_t*)(smem + 2 * KT * C::STRIDE);    // KB only
 
     int bid = xcd_remap(blockIdx.x, gridDim.x);
     int pi = 0;
@@ -98,10 +132,16 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_
 
     if (kt * KT < jend && t0 < t1) {                   // block-uniform: a tile the mask_off rule hides keeps its zeros
         RowStage<CT, DHP, KT> kst, vst;
+        uint32_t n_vis = 0;                            // KB, threads < KT: the next head's visibility of key kt * KT + tid
         auto stage = [&](int t) {
             const size_t bh = (size_t)head_of(t);
             kst.load(P.K + bh * P.S * C::ROWB, kt * KT, P.S, tid);
             vst.load(P.V + bh * P.S * C::ROWB, kt * KT, P.S, tid);
+            if constexpr (KB) {
+                const int jm = kt * KT + tid;
+                n_vis = 0;
+                if (tid < KT && jm < P.S) n_vis = ga.k[pi].mask[(bh / P.H) * ga.k[pi].ldm + jm] != 0;
+            }
         };
         stage(t0);
 #pragma unroll 1
@@ -130,8 +170,13 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_
             __syncthreads();                           // every wave is done with the previous head's images
             kst.store(kimg, tid);
             vst.store(vimg, tid);
+            if constexpr (KB) { if (tid < KT) smask[tid] = (uint8_t)n_vis; }
             __syncthreads();
             if (t + 1 < t1) stage(t + 1);
+            if constexpr (KB) {
+                const uint32_t w = *(const uint32_t*)(smask + 4 * (lane & 15));
+                if (__builtin_amdgcn_ballot_w64(w != 0u) == 0) continue;      // no visible key (the same in every wave)
+            }
             const uint32_t drow = ((uint32_t)bh * (uint32_t)P.T + (uint32_t)q) * (uint32_t)P.S;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
@@ -155,6 +200,11 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_
                 if (edge) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) e4[r] = (16 * n + r < rel) ? e4[r] : -INFINITY;   // exp2(-inf) = 0: masked before the exponential
+                }
+                if constexpr (KB) {
+                    const uint32_t w = *(const uint32_t*)(smask + 16 * n + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) e4[r] = ((w >> (8 * r)) & 0xffu) ? e4[r] : -INFINITY;
                 }
                 f32x4 p4;
 #pragma unroll
@@ -269,9 +319,11 @@ size_t dbias_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_d
     return bytes;
 }
 
-// fill: the two argument blocks (the mask descriptors are checked here, by the rule of the other *_amask entries)
-int dbias_fill(DGroup& g, DSumGroup& sg, const DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_hmask* masks,
-               const bpm_attn_dbias* outs, int nprob, uint64_t seed, void* ws, long* total, long* sum_blocks) {
+// fill: the two argument blocks (the mask descriptors are checked here, by the rule of the other *_amask entries; the
+// byte masks, when there are any, by the rule of the *_kmask entries)
+int dbias_fill(DGroupK& gk, DSumGroup& sg, const DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_hmask* masks,
+               const bpm_attn_kmask* kmasks, const bpm_attn_dbias* outs, int nprob, uint64_t seed, void* ws, long* total, long* sum_blocks) {
+    DGroup& g = gk.g;
     g.nprob = nprob;
     g.seedp = bpm_seed_ptr(seed);
     sg.nprob = 0;
@@ -283,8 +335,10 @@ int dbias_fill(DGroup& g, DSumGroup& sg, const DChoice* ch, const bpm_attn_probl
         if (!q.Q || !q.K || !q.V || !q.dO || !q.lse || !q.delta) return BPM_ERR_ARG;
         if (((uintptr_t)q.Q | (uintptr_t)q.K | (uintptr_t)q.V | (uintptr_t)q.dO) & 15) return BPM_ERR_ALIGN;
         AAdd a;
-        const int rc = amask_desc(a, masks[i], q.T, q.S, false);
+        int rc = amask_desc(a, masks[i], q.T, q.S, false);
         if (rc) return rc;
+        gk.k[i] = AMask{nullptr, 0};
+        if (kmasks && (rc = kmask_desc(gk.k[i], kmasks[i], q.S)) != 0) return rc;
         p.Q = (const char*)q.Q; p.K = (const char*)q.K; p.V = (const char*)q.V; p.dO = (const char*)q.dO;
         p.lse = q.lse; p.delta = q.delta;
         p.m = a.m; p.ldm = a.ld; p.mhs = a.hs;
@@ -310,13 +364,17 @@ int dbias_fill(DGroup& g, DSumGroup& sg, const DChoice* ch, const bpm_attn_probl
             sblk += ((long)c.nimg * q.T * s.c4 + NTHREADS - 1) / NTHREADS;
         }
     }
+    for (int i = nprob; i < BPM_MAX_GROUP; ++i) gk.k[i] = AMask{nullptr, 0};
     *total = blk; *sum_blocks = sblk;
     return 0;
 }
 
 template <typename CT>
-int dbias_launch(int dhp, const DGroup& g, long total, const DSumGroup& sg, long sum_blocks, void* stream) {
-    const int rc = with_dhp(dhp, [&](auto d) { return launch<attn_dbias_kernel<CT, decltype(d)::value>>((unsigned)total, NTHREADS, stream, g); });
+int dbias_launch(int dhp, bool with_kmasks, const DGroupK& gk, long total, const DSumGroup& sg, long sum_blocks, void* stream) {
+    const int rc = with_dhp(dhp, [&](auto d) {
+        if (with_kmasks) return launch<attn_dbias_kernel<WithBytes<CT>, decltype(d)::value>>((unsigned)total, NTHREADS, stream, gk);
+        return launch<attn_dbias_kernel<CT, decltype(d)::value>>((unsigned)total, NTHREADS, stream, gk.g);
+    });
     if (rc || sum_blocks <= 0) return rc;
     return launch<attn_dbias_sum_kernel>((unsigned)sum_blocks, NTHREADS, stream, sg);
 }
@@ -329,9 +387,10 @@ extern "C" size_t bpm_attn_bwd_dbias_ws_bytes(const bpm_attn_problem* probs, con
     return dbias_choose(ch, probs, outs, nprob);
 }
 
-// The gradient of an additive mask (a learned attention bias): see bpm_attn_dbias in include/bpmult_hip.h.
-extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_dbias* outs,
-                                  int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+// The gradient of an additive mask (a learned attention bias): see bpm_attn_dbias in include/bpmult_hip.h.  kmasks: the
+// per-key byte masks of a forward pass through bpm_attn_fwd_kamask, or NULL (bpm_attn_bwd_dbias).
+extern "C" int bpm_attn_bwd_dbias_kmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_kmask* kmasks,
+                                        const bpm_attn_dbias* outs, int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
     if (!dtype_ok(dtype)) return BPM_ERR_ARG;
     if (!masks) return BPM_ERR_ARG;
     int rc = dbias_check(probs, outs, nprob);
@@ -339,10 +398,10 @@ extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, cons
     DChoice ch[BPM_MAX_GROUP];
     const size_t need = dbias_choose(ch, probs, outs, nprob);
     if (need > 0 && (!ws || ws_bytes < need || ((uintptr_t)ws & 15))) return BPM_ERR_ARG;
-    DGroup g;
+    DGroupK g;
     DSumGroup sg;
     long total = 0, sum_blocks = 0;
-    rc = dbias_fill(g, sg, ch, probs, masks, outs, nprob, seed, ws, &total, &sum_blocks);
+    rc = dbias_fill(g, sg, ch, probs, masks, kmasks, outs, nprob, seed, ws, &total, &sum_blocks);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int sz = dtype == BPM_BF16 ? 2 : 4;
@@ -352,5 +411,9 @@ extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, cons
         bytes += (double)q.B * q.H * ((2.0 * q.T + 2.0 * q.S) * q.dh * sz + 2.0 * q.T * 4) + 4.0 * q.T * q.S * ch[i].nimg * 2;
     }
     BpmProfScope prof(BPM_K_ATTN_BWD_DBIAS, s, 4.0 * useful_pair_flops(probs, nprob), bytes);      // S and dP: two products
-    return with_ct(dtype, [&](auto ct) { return dbias_launch<decltype(ct)>(probs[0].dhp, g, total, sg, sum_blocks, stream); });
+    return with_ct(dtype, [&](auto ct) { return dbias_launch<decltype(ct)>(probs[0].dhp, kmasks != nullptr, g, total, sg, sum_blocks, stream); });
+}
+extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_dbias* outs,
+                                  int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    return bpm_attn_bwd_dbias_kmask(dtype, probs, masks, nullptr, outs, nprob, seed, ws, ws_bytes, stream);
 }

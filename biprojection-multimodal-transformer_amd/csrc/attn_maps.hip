@@ -1,4 +1,5 @@
-// Head-averaged attention maps for BPMulT on gfx950 (bpm_attn_maps / _amask / _hmask): the kernel and its three entries.
+// Head-averaged attention maps for BPMulT on gfx950 (bpm_attn_maps / _amask / _hmask / _kmask / _kamask): the kernel and its
+// five entries.
 // What it shares with the forward / backward kernels of attention.hip is in attn_common.h.
 #include "attn_common.h"
 
@@ -55,13 +56,30 @@ struct MGroupA {
     MGroup g;
     AAdd m[BPM_MAX_GROUP];
 };
+// KB (bpm_attn_maps_kmask / _kamask): the per-key byte mask of the *_kmask entries, as in the dK / dV kernel: the lane
+// reads the byte of its key once (never at j >= S); a hidden key sees no query row, so every probability of its column is
+// exp2(-inf) = 0 in every head and the map holds exactly 0.0f there.  A tile without a visible key is skipped
+// block-uniformly.  The descriptors sit behind the additive ones in an argument block of their own (MGroupK), so the
+// instantiations without KB keep their argument layout.  The switch rides in the compute-type argument (WithBytes).  One more live register (ilo is per lane either way); no
+// instantiation needs another occupancy than its sibling without KB.
+struct MGroupK {
+    MGroupA a;              // a.m: used with AM only
+    AMask k[BPM_MAX_GROUP];
+};
 static_assert(sizeof(MGroupA) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(MGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
 BPM_DEV const MGroup& map_group(const MGroup& g) { return g; }
 BPM_DEV const MGroup& map_group(const MGroupA& g) { return g.g; }
+BPM_DEV const MGroup& map_group(const MGroupK& g) { return g.a.g; }
+BPM_DEV const AAdd& map_add(const MGroupA& g, int pi) { return g.m[pi]; }
+BPM_DEV const AAdd& map_add(const MGroupK& g, int pi) { return g.a.m[pi]; }
 
-template <typename CT, int DHP, bool AM = false, bool PH = false>
-__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<CT>(DHP, AM), map_waves<CT>(DHP, AM)))) void attn_maps_kernel(const std::conditional_t<AM, MGroupA, MGroup> ga) {
+// CTX: the compute type, or WithBytes<compute type> for KB
+template <typename CTX, int DHP, bool AM = false, bool PH = false>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<typename CtOf<CTX>::type>(DHP, AM), map_waves<typename CtOf<CTX>::type>(DHP, AM)))) void attn_maps_kernel(const std::conditional_t<CtOf<CTX>::bytes, MGroupK, std::conditional_t<AM, MGroupA, MGroup>> ga) {
     static_assert(AM || !PH, "a head stride belongs to an additive mask");
+    typedef typename CtOf<CTX>::type CT;
+    constexpr bool KB = CtOf<CTX>::bytes;
     const MGroup& grp = map_group(ga);
     typedef Cfg<CT, DHP> C;
     typedef typename Tr<CT>::frag frag;
@@ -87,8 +105,16 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_wa
 
     // query row i (time qpos0 + i*qstride) sees key j iff i >= first_row(j - mask_off + 1)   (the dK / dV kernel's rule)
     auto first_row = [&](int tmin) { const int a = tmin - P.qpos0; return a <= 0 ? 0 : (a + P.qstride - 1) / P.qstride; };
-    const int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
-    const int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);   // wave-uniform: rows at or above it need no test
+    int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
+    int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);         // wave-uniform: rows at or above it need no test
+    bool any_key = true;                                // KB: the tile has a visible key (block-uniform)
+    if constexpr (KB) {
+        bool kvis = false;
+        if (j < P.S) kvis = ga.k[pi].mask[(size_t)b * ga.k[pi].ldm + j] != 0;
+        if (!kvis) ilo = 1 << 30;
+        if (__builtin_amdgcn_ballot_w64(!kvis) != 0) ilo_max = 1 << 30;                          // a hidden key in the wave: every row tests
+        any_key = __syncthreads_or(kvis);
+    }
     const int i_first = first_row(kb * 64 - P.mask_off + 1);                                   // first query row that sees any key of the tile
     const int i_end = min(P.T, i0 + MQT);
 
@@ -96,10 +122,10 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_wa
 #pragma unroll
     for (int u = 0; u < MQT / 16; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if (i_first < i_end) {                              // block-uniform: a fully masked tile keeps its zeros
+    if (i_first < i_end && any_key) {                   // block-uniform: a fully masked tile keeps its zeros
         f32x4 am4[MQT / 16];                            // AM: mask of queries i0 + 16u + 4g + (0..3) against key j
         AAdd am = AAdd{nullptr, 0, 0};
-        if constexpr (AM) am = ga.m[pi];
+        if constexpr (AM) am = map_add(ga, pi);
         auto load_mask = [&](int h) {
             const float* acol = am.m + (size_t)h * am.hs + (size_t)min(j, P.S - 1) * am.ld;
 #pragma unroll
@@ -167,7 +193,7 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_wa
     }
 }
 
-// ---- bpm_attn_maps / _amask / _hmask: check / fill / choose / launch ---------------------------------------------------
+// ---- bpm_attn_maps / _amask / _hmask / _kmask / _kamask: check / fill / choose / launch ---------------------------------------------------
 // check: the pointers, geometry and alignment of one problem
 int maps_check(const bpm_attn_map_problem& q, int dhp0) {
     if (!q.Q || !q.K || !q.lse || !q.W) return BPM_ERR_ARG;
@@ -176,9 +202,10 @@ int maps_check(const bpm_attn_map_problem& q, int dhp0) {
     return 0;
 }
 
-// fill: the argument block and the grid; masks: the additive masks (read through their transposes), or nullptr.  Problem
-// by problem: check, the mask_off rule, the block limit, the mask descriptor.
-int maps_fill(MGroupA& ga, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, int nprob, long* total) {
+// fill: the argument block and the grid; masks: the additive masks (read through their transposes), or nullptr; kmasks:
+// the per-key byte masks, or nullptr.  Problem by problem: check, the mask_off rule, the block limit, the mask descriptors.
+int maps_fill(MGroupK& gk, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_kmask* kmasks, int nprob, long* total) {
+    MGroupA& ga = gk.a;
     MGroup& g = ga.g;
     g.nprob = nprob;
     long blk = 0;
@@ -194,9 +221,11 @@ int maps_fill(MGroupA& ga, const bpm_attn_map_problem* probs, const bpm_attn_hma
         p.blk0 = (int)blk;
         blk += (long)p.nqt * p.nkt * q.B;
         if (blk > (1l << 30)) return BPM_ERR_ARG;
+        if (kmasks && (rc = kmask_desc(gk.k[i], kmasks[i], q.S)) != 0) return rc;
         if (masks && (rc = amask_desc(ga.m[i], masks[i], q.T, q.S, true)) != 0) return rc;
     }
     for (int i = masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) ga.m[i] = AAdd{nullptr, 0, 0};
+    for (int i = kmasks ? nprob : 0; i < BPM_MAX_GROUP; ++i) gk.k[i] = AMask{nullptr, 0};
     *total = blk;
     return 0;
 }
@@ -208,11 +237,17 @@ bool maps_per_head(const MGroupA& ga, int nprob, bool with_masks) {
     return per_head;
 }
 
-int maps_launch(int dtype, int dhp, bool with_masks, bool per_head, const MGroupA& ga, long total, void* stream) {
+int maps_launch(int dtype, int dhp, bool with_masks, bool per_head, bool with_kmasks, const MGroupK& gk, long total, void* stream) {
+    const MGroupA& ga = gk.a;
     return with_ct(dtype, [&](auto ct) {
         return with_dhp(dhp, [&](auto d) {
             typedef decltype(ct) CT;
             constexpr int D = decltype(d)::value;
+            if (with_kmasks) {
+                if (per_head) return launch<attn_maps_kernel<WithBytes<CT>, D, true, true>>((unsigned)total, NTHREADS, stream, gk);
+                if (with_masks) return launch<attn_maps_kernel<WithBytes<CT>, D, true>>((unsigned)total, NTHREADS, stream, gk);
+                return launch<attn_maps_kernel<WithBytes<CT>, D, false>>((unsigned)total, NTHREADS, stream, gk);
+            }
             if (per_head) return launch<attn_maps_kernel<CT, D, true, true>>((unsigned)total, NTHREADS, stream, ga);
             if (with_masks) return launch<attn_maps_kernel<CT, D, true>>((unsigned)total, NTHREADS, stream, ga);
             return launch<attn_maps_kernel<CT, D, false>>((unsigned)total, NTHREADS, stream, ga.g);
@@ -221,14 +256,16 @@ int maps_launch(int dtype, int dhp, bool with_masks, bool per_head, const MGroup
 }
 
 // Head-averaged attention probabilities of finished forward passes (see attn_maps_kernel); masks: the additive masks of
-// bpm_attn_maps_amask (read through their transposes), or nullptr.
-int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, bool with_masks, int nprob, void* stream) {
+// bpm_attn_maps_amask (read through their transposes), or nullptr; kmasks: the byte masks of bpm_attn_maps_kmask, or nullptr.
+int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, bool with_masks,
+                   const bpm_attn_kmask* kmasks, bool with_kmasks, int nprob, void* stream) {
     if (!group_ok(probs, nprob)) return BPM_ERR_ARG;
     if (!dtype_ok(dtype)) return BPM_ERR_ARG;
-    if (with_masks && !masks) return BPM_ERR_ARG;
-    MGroupA ga;
+    if ((with_masks && !masks) || (with_kmasks && !kmasks)) return BPM_ERR_ARG;
+    MGroupK gk;
+    const MGroupA& ga = gk.a;
     long total = 0;
-    int rc = maps_fill(ga, probs, masks, nprob, &total);
+    int rc = maps_fill(gk, probs, masks, kmasks, nprob, &total);
     if (rc) return rc;
     const int sz = dtype == BPM_BF16 ? 2 : 4;
     double flops = 0, bytes = 0;
@@ -240,17 +277,25 @@ int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_
         if (with_masks) bytes += 4.0 * q.T * q.S;
     }
     BpmProfScope prof(BPM_K_ATTN_MAPS, (hipStream_t)stream, flops, bytes);
-    return maps_launch(dtype, probs[0].dhp, with_masks, maps_per_head(ga, nprob, with_masks), ga, total, stream);
+    return maps_launch(dtype, probs[0].dhp, with_masks, maps_per_head(ga, nprob, with_masks), with_kmasks, gk, total, stream);
 }
 
 }  // namespace
 
 extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int nprob, void* stream) {
-    return attn_maps_impl(dtype, probs, nullptr, false, nprob, stream);
+    return attn_maps_impl(dtype, probs, nullptr, false, nullptr, false, nprob, stream);
 }
 extern "C" int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_amask* masks, int nprob, void* stream) {
-    return attn_maps_impl(dtype, probs, HMasks(masks, nprob).p, true, nprob, stream);
+    return attn_maps_impl(dtype, probs, HMasks(masks, nprob).p, true, nullptr, false, nprob, stream);
 }
 extern "C" int bpm_attn_maps_hmask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, int nprob, void* stream) {
-    return attn_maps_impl(dtype, probs, masks, true, nprob, stream);
+    return attn_maps_impl(dtype, probs, masks, true, nullptr, false, nprob, stream);
+}
+// ... with a per-key byte mask (lse from bpm_attn_fwd_kmask), and with both masks (lse from bpm_attn_fwd_kamask)
+extern "C" int bpm_attn_maps_kmask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_kmask* kmasks, int nprob, void* stream) {
+    return attn_maps_impl(dtype, probs, nullptr, false, kmasks, true, nprob, stream);
+}
+extern "C" int bpm_attn_maps_kamask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks, int nprob,
+                                    void* stream) {
+    return attn_maps_impl(dtype, probs, masks, true, kmasks, true, nprob, stream);
 }

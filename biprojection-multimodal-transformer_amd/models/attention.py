@@ -1,19 +1,22 @@
 """`MultiheadAttention` with the reference's constructor, call signature and state_dict layout
 (bpmult/models/multihead_attention.py:17-135), executed on the HIP path.
 
-forward(query, key, value, attn_mask, attn_bias) is one autograd node.  Its launches are those of the engine's self-attention
+forward(query, key, value, attn_mask, attn_bias, key_padding_mask) is one autograd node.  Its launches are those of the engine's self-attention
 block (engine.py: _proj, _self_attn_fwd / _self_attn_bwd):
 
   forward   rows_cast            query / key / value -> CT rows (one problem per distinct input)
             gemm NT (grouped)    Q (alpha = dh^-0.5), K, V projections of in_proj_weight, OUT_HEADS epilogue
-            attn_fwd[_amask]     softmax(q k^T + attn_mask + attn_bias) v, dropout on the probabilities
+            attn_fwd[_amask | _kmask | _kamask]
+                                 softmax(q k^T + attn_mask + attn_bias) v over the keys key_padding_mask leaves, dropout
+                                 on the probabilities
             gemm NT              out_proj
-            attn_maps[_amask]    the head-averaged weights (need_weights only)
+            attn_maps[_amask | _kmask | _kamask]
+                                 the head-averaged weights (need_weights only)
   backward  rows_cast            d(attn) -> CT, column sums = d(out_proj.bias)
             gemm TN / NN         d(out_proj.weight); d(attention output), OUT_HEADS
-            attn_bwd_dq / _dkv   [_amask]
+            attn_bwd_dq / _dkv   [_amask | _kmask | _kamask]
             attn_bwd_dbias       d(attn_bias): the score gradient summed over samples (and heads), after the dQ pass;
-                                 only when attn_bias requires grad
+                                 only when attn_bias requires grad (with the key masks beside a key_padding_mask)
             gemm TN (grouped)    the three row blocks of d(in_proj_weight), d(in_proj_bias) as colsum_a
             gemm NN (grouped)    d(query), d(key), d(value)
 
@@ -23,10 +26,16 @@ copies (one add when both are given) in the layout the kernels read -- [Hm, T, l
 a per-head bias and 1 otherwise, plus its transpose [Hm, S, ldt] for the dK / dV and maps kernels -- and kept until either
 tensor's data_ptr or _version changes: a bias that an optimiser steps is copied again every forward (two copies of
 Hm T S floats).  attn_mask gets no gradient; attn_bias gets one from bpm_attn_bwd_dbias, whose workspace lives in the
-plan.  add_bias_kv / add_zero_attn are refused.
+plan.  key_padding_mask ([B, S], nonzero = padding) becomes the kernels' visibility bytes (uint8 [B, S], nonzero = visible)
+with one torch op (into a contiguous buffer: the mask may have any strides), kept until the tensor's data_ptr, _version or
+shape changes -- a cache of its own: a padding mask
+that changes every batch does not touch the additive image.  The family follows from what is given: neither -> the
+unmasked entries, an image alone -> _amask, a padding mask alone -> _kmask, both -> _kamask.
+add_bias_kv / add_zero_attn are refused.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -65,6 +74,7 @@ class _Plan:
         self.dy, self.dao, self.delta = z(T * B, ld, dt=ct), z(B, H, T, dhp, dt=ct), z(B, H, T)
         self.dq, self.dk, self.dv = z(T * B, ld, dt=ct), z(S * B, ld, dt=ct), z(S * B, ld, dt=ct)
         self.mask = None             # (ops.attn_amasks array, the tensors it points into) of the forward pass; None: no attn_mask / attn_bias
+        self.kmask = None            # (ops.attn_kmasks array, the bytes it points into) of the forward pass; None: no key_padding_mask
         self.dbias_ws = {}           # heads of the bias gradient (1 or H) -> workspace of bpm_attn_bwd_dbias (None: no split)
         self.seed, self.drop_p = 0, 0.0
 
@@ -99,6 +109,7 @@ class _Exec:
         self._versions = None
         self.plans: Dict[Tuple[int, int, int, str], _Plan] = {}
         self._mask_key, self._mask = None, None
+        self._kmask_key, self._kmask, self._kmask_src = None, None, None
 
     def wptr(self, which: int) -> int:
         """Shadow of in_proj_weight rows [which d, (which + 1) d) (0 Q, 1 K, 2 V) or of out_proj.weight (3)."""
@@ -140,8 +151,36 @@ class _Exec:
             self._mask_key = key
         return self._mask
 
+    def kmask_for(self, key_padding_mask: torch.Tensor):
+        """The kernels' copy of key_padding_mask: uint8 [B, S], nonzero where the key is VISIBLE (the *_kmask convention, the
+        opposite of the argument's); rebuilt when the tensor's storage, version counter or shape changes."""
+        t = key_padding_mask
+        key = (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
+        # the key holds for the tensor it was taken from only (a weak reference: the caller's mask is not kept alive, and
+        # once it is gone its address may name another tensor)
+        if key != self._kmask_key or self._kmask_src() is not t:
+            vis = torch.empty(t.shape, dtype=torch.bool, device=t.device)     # contiguous [B, S] whatever t's strides are
+            torch.eq(t, 0, out=vis)                                           # the one kernel
+            vis = vis.view(torch.uint8)                                       # renames bool's 0 / 1 bytes
+            self._kmask = (ops.attn_kmasks([(vis, t.shape[1])]), vis)
+            self._kmask_key, self._kmask_src = key, weakref.ref(t)
+        return self._kmask
+
+    # -- the four families: no mask, additive image, key bytes, both ----------------------------------------------------
+    @staticmethod
+    def _attn(pl: "_Plan", which: str, dt: int, probs, seed: int) -> None:
+        """which: 'fwd', 'bwd_dq' or 'bwd_dkv', through the entry of the plan's masks."""
+        if pl.mask is None and pl.kmask is None:
+            getattr(ops, f"attn_{which}")(dt, probs, seed)
+        elif pl.kmask is None:
+            getattr(ops, f"attn_{which}_amask")(dt, probs, pl.mask[0], seed)
+        elif pl.mask is None:
+            getattr(ops, f"attn_{which}_kmask")(dt, probs, pl.kmask[0], seed)
+        else:
+            getattr(ops, f"attn_{which}_kamask")(dt, probs, pl.kmask[0], pl.mask[0], seed)
+
     # -- forward -------------------------------------------------------------------------------------------------------
-    def forward(self, mod, query, key, value, form, attn_mask, attn_bias, need_weights, seed, training):
+    def forward(self, mod, query, key, value, form, attn_mask, attn_bias, need_weights, seed, training, key_padding_mask=None):
         T, B, d = query.shape
         S = key.shape[0]
         self.refresh_shadows()
@@ -149,6 +188,7 @@ class _Exec:
         pl.stamp += 1
         dt, ld, H, dh, dhp = self.dtype, self.ld, self.H, self.dh, self.dhp
         pl.mask = None if attn_mask is None and attn_bias is None else self.mask_for(attn_mask, attn_bias, T, S)
+        pl.kmask = None if key_padding_mask is None else self.kmask_for(key_padding_mask)
         pl.seed, pl.drop_p = seed, (mod.attn_dropout if training else 0.0)
         casts = [ops.cast_problem(query, d, T * B, d, dst_ct=pl.xq, ldd=ld)]
         if form != "qkv":
@@ -162,10 +202,7 @@ class _Exec:
                 for w, (x, out, L) in enumerate(((pl.xq, pl.q, T), (pl.xk, pl.k, S), (pl.xv, pl.v, S)))]
         ops.gemm_grouped(dt, GEMM_NT, proj, seed)
         ap = [ops.attn_problem(pl.q, pl.k, pl.v, pl.o, ld, pl.lse, B, H, T, S, dh, dhp, 0, drop_p=pl.drop_p, drop_site=S_MHA_PROBS)]
-        if pl.mask is None:
-            ops.attn_fwd(dt, ap, seed)
-        else:
-            ops.attn_fwd_amask(dt, ap, pl.mask[0], seed)
+        self._attn(pl, "fwd", dt, ap, seed)
         out = torch.empty(T, B, d, device=self.device)
         ops.gemm_grouped(dt, GEMM_NT, [ops.gemm_problem(pl.o, self.wptr(3), out, T * B, d, d, ld, ld, d, bias_n=mod.out_proj.bias,
                                                         flags=F_KPAD)], seed)
@@ -173,10 +210,14 @@ class _Exec:
         if need_weights:
             weights = torch.empty(B, T, S, device=self.device)
             mp = [ops.attn_map_problem(pl.q, pl.k, pl.lse, weights, S, B, H, T, S, dh, dhp, 0)]
-            if pl.mask is None:
+            if pl.mask is None and pl.kmask is None:
                 ops.attn_maps(dt, mp)
-            else:
+            elif pl.kmask is None:
                 ops.attn_maps_amask(dt, mp, pl.mask[0])
+            elif pl.mask is None:
+                ops.attn_maps_kmask(dt, mp, pl.kmask[0])
+            else:
+                ops.attn_maps_kamask(dt, mp, pl.kmask[0], pl.mask[0])
         return out, weights, pl
 
     # -- backward ------------------------------------------------------------------------------------------------------
@@ -196,12 +237,8 @@ class _Exec:
                                                         heads=(B, H, T, dh, dhp), flags=F_KPAD)], seed)
         ap = [ops.attn_problem(pl.q, pl.k, pl.v, pl.o, ld, pl.lse, B, H, T, S, dh, dhp, 0, dO=pl.dao, delta=pl.delta, dQ=pl.dq, lddq=ld,
                                dK=pl.dk, lddk=ld, dV=pl.dv, lddv=ld, dq_scale=self.scale, drop_p=pl.drop_p, drop_site=S_MHA_PROBS)]
-        if pl.mask is None:
-            ops.attn_bwd_dq(dt, ap, seed)
-            ops.attn_bwd_dkv(dt, ap, seed)
-        else:
-            ops.attn_bwd_dq_amask(dt, ap, pl.mask[0], seed)
-            ops.attn_bwd_dkv_amask(dt, ap, pl.mask[0], seed)
+        self._attn(pl, "bwd_dq", dt, ap, seed)
+        self._attn(pl, "bwd_dkv", dt, ap, seed)
         g_bias = None
         if bias_shape is not None:
             g_bias = self.bias_grad(pl, ap, bias_shape, seed)
@@ -217,7 +254,8 @@ class _Exec:
 
     def bias_grad(self, pl: _Plan, ap, bias_shape, seed: int) -> torch.Tensor:
         """d(attn_bias) of the plan's last forward pass, after its dQ pass has left delta: fp32, bias_shape ([T, S]: summed
-        over samples and heads; [H, T, S]: over samples); a pair the effective image hides gets exactly 0."""
+        over samples and heads; [H, T, S]: over samples); a pair the effective image hides gets exactly 0, and a sample
+        adds nothing at the keys its key_padding_mask hides."""
         T, S = pl.T, pl.S
         nimg = self.H if len(bias_shape) == 3 else 1
         ldb = (S + 3) // 4 * 4
@@ -226,7 +264,10 @@ class _Exec:
         if nimg not in pl.dbias_ws:
             n = ops.attn_dbias_ws_bytes(ap, outs)
             pl.dbias_ws[nimg] = torch.empty((n + 3) // 4, device=self.device) if n else None
-        ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg])
+        if pl.kmask is None:
+            ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg])
+        else:
+            ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg], kmasks=pl.kmask[0])
         g = g if ldb == S else g[:, :, :S].contiguous()
         return g.reshape(bias_shape)
 
@@ -235,9 +276,9 @@ class _MhaFn(torch.autograd.Function):
     None)."""
 
     @staticmethod
-    def forward(ctx, query, key, value, mod, ex, form, attn_mask, need_weights, seed, attn_bias, *params):
+    def forward(ctx, query, key, value, mod, ex, form, attn_mask, need_weights, seed, attn_bias, key_padding_mask, *params):
         out, weights, plan = ex.forward(mod, query.detach().contiguous(), key.detach().contiguous(), value.detach().contiguous(), form,
-                                        attn_mask, attn_bias, need_weights, seed, mod.training)
+                                        attn_mask, attn_bias, need_weights, seed, mod.training, key_padding_mask)
         ctx.mod, ctx.ex, ctx.plan, ctx.stamp = mod, ex, plan, plan.stamp
         ctx.bias_shape = None if attn_bias is None else tuple(attn_bias.shape)
         if weights is None:
@@ -252,14 +293,15 @@ class _MhaFn(torch.autograd.Function):
                                "shape has overwritten; run forward -> backward one call at a time")
         need = ctx.needs_input_grad
         dq, dk, dv, g_bias, grads = ctx.ex.backward(ctx.mod, ctx.plan, dout.contiguous().float(), ctx.bias_shape if need[9] else None)
-        return ((dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None, None, g_bias)
-                + tuple(g if n else None for g, n in zip(grads, need[10:])))
+        return ((dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None, None, g_bias, None)
+                + tuple(g if n else None for g, n in zip(grads, need[11:])))
 
 
 class MultiheadAttention(nn.Module):
     """Drop-in for bpmult.models.multihead_attention.MultiheadAttention (packed in-projection, :17-50).
 
-    forward(query, key, value, attn_mask=None, need_weights=True, attn_bias=None) -> (attn [T, B, d], weights [B, T, S] or None) on
+    forward(query, key, value, attn_mask=None, need_weights=True, attn_bias=None, key_padding_mask=None) -> (attn [T, B, d],
+    weights [B, T, S] or None) on
     [T,B,d] / [S,B,d] fp32 CUDA (HIP) tensors, in the reference's three call forms (query is key is value; key is value;
     three tensors).  attn_mask: None or a float [T, S] tensor added to the scores of every head (-inf hides a pair; every
     row must keep a visible key, or it is NaN as in the reference); it gets no gradient (requires_grad: ValueError).
@@ -268,6 +310,11 @@ class MultiheadAttention(nn.Module):
     may require grad -- an nn.Parameter, or a non-leaf such as a gather from a relative-position table: its gradient (the
     score gradient summed over samples, and over heads for [T, S]; exactly 0 where the effective entry is -inf) comes back
     through autograd.  `weights` are taken under the same mask + bias.
+    key_padding_mask (the reference's docstring, :56-58): None or a torch.bool / torch.uint8 tensor [B, S] on the inputs'
+    device; nonzero / True marks padding: that key is hidden for every head and query of its sample -- probability and
+    `weights` exactly 0, d(key) / d(value) rows of a padded position exactly 0 -- alone or beside attn_mask / attn_bias.
+    Query rows are never masked; every query row of every sample must keep a visible key under all masks together (not
+    checked; NaN otherwise).  It gets no gradient.
     One stated difference: `weights` are the head-averaged softmax probabilities BEFORE attention dropout, detached --
     equal to the reference's in eval mode and whenever attn_dropout == 0 (in training with dropout the reference returns
     the dropped, rescaled matrix); the departure TransformerEncoder.attention_maps() makes.  need_weights=False (an
@@ -324,7 +371,7 @@ class MultiheadAttention(nn.Module):
             ex = self._exec = _Exec(self, device, prec)
         return ex
 
-    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None):
+    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None, key_padding_mask=None):
         if query.dim() != 3 or query.shape[2] != self.embed_dim:
             raise ValueError(f"MultiheadAttention: query of shape {tuple(query.shape)}, expected [T, B, {self.embed_dim}]")
         T, B, d = query.shape
@@ -351,9 +398,18 @@ class MultiheadAttention(nn.Module):
                 raise ValueError(f"MultiheadAttention: attn_bias on {attn_bias.device}, the inputs on {query.device}")
             if config.is_x3(self.precision or config.precision()):
                 raise ValueError("MultiheadAttention: attn_bias is not available with precision 'bf16x3'; use 'bf16' or 'f32'")
+        if key_padding_mask is not None:
+            if not torch.is_tensor(key_padding_mask) or key_padding_mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("MultiheadAttention: key_padding_mask must be a torch.bool or torch.uint8 tensor (nonzero = padding)")
+            if tuple(key_padding_mask.shape) != (B, S):
+                raise ValueError(f"MultiheadAttention: key_padding_mask of shape {tuple(key_padding_mask.shape)}, expected [{B}, {S}]")
+            if key_padding_mask.device != query.device:
+                raise ValueError(f"MultiheadAttention: key_padding_mask on {key_padding_mask.device}, the inputs on {query.device}")
+            if config.is_x3(self.precision or config.precision()):
+                raise ValueError("MultiheadAttention: key_padding_mask is not available with precision 'bf16x3'; use 'bf16' or 'f32'")
         for t in (query, key, value):             # after the argument checks: those need no device
             if not t.is_cuda:
                 raise RuntimeError("MultiheadAttention: the HIP attention path needs CUDA (HIP) tensors; there is no CPU path")
         ex = self._ensure_exec(query.device)
         seed = self._next_seed()
-        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, attn_bias, *ex.params)
+        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, attn_bias, key_padding_mask, *ex.params)

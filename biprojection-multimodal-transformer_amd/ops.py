@@ -121,7 +121,8 @@ _PROBLEM = {}       # entry point -> the struct of its problem array (the first 
 def _grouped(name: str, probs, pre=(), post=(), limit: int = MAX_GROUP, beside=None, n: Optional[int] = None) -> None:
     """Launch the first n (default: all) problems through entry point `name`, `limit` at a time: one call
     entry(*pre, problems, [beside,] count, *post, stream) per chunk.  post: the scalars behind the count, or a function
-    of the chunk's count that returns them; beside: a second ctypes array that advances with the problems."""
+    of the chunk's count that returns them; beside: a second ctypes array that advances with the problems, or a tuple of
+    such arrays (in the entry's order)."""
     cls = _PROBLEM.get(name)
     if cls is None:
         cls = _PROBLEM[name] = next(t._type_ for t in _lib.SIGNATURES[name] if isinstance(t, type) and issubclass(t, C._Pointer))
@@ -130,7 +131,7 @@ def _grouped(name: str, probs, pre=(), post=(), limit: int = MAX_GROUP, beside=N
     n = len(arr) if n is None else n
     for i in range(0, n, limit):
         k = min(limit, n - i)
-        also = () if beside is None else (_at(beside, i),)
+        also = () if beside is None else tuple(_at(b, i) for b in (beside if isinstance(beside, tuple) else (beside,)))
         _lib.check(entry(*pre, _at(arr, i), *also, k, *(post(k) if callable(post) else post), s), name)
 
 
@@ -377,6 +378,17 @@ def attn_bwd_dkv_kmask(dtype: int, probs, masks, seed: int = 0) -> None:
     _attn_kmask("bpm_attn_bwd_dkv_kmask", dtype, probs, masks, seed)
 
 
+def attn_maps_kmask(dtype: int, probs, kmasks) -> None:
+    """bpm_attn_maps after attn_fwd_kmask: `kmasks` from attn_kmasks(), one per problem; a key its byte hides is exactly 0."""
+    arr = _as_array(AttnMapProblem, probs)
+    if len(kmasks) != len(arr):
+        raise ValueError(f"bpm_attn_maps_kmask: one key mask per problem ({len(arr)} problems, {len(kmasks)} masks)")
+    if _DRY_RUN:
+        _DRY_LAUNCHES.append((attn_maps_kmask, dtype, arr, kmasks))
+        return
+    _grouped("bpm_attn_maps_kmask", arr, (dtype,), beside=kmasks)
+
+
 def attn_map_problem(Q, K, lse, W, ldw, B, H, T, S, dh, dhp, mask_off, *, q_pos0=0, q_stride=1) -> AttnMapProblem:
     """One head-averaged attention map (bpm_attn_maps): Q / K / lse as attn_problem's after its forward, W fp32 [B, T, ldw]
     receives (1/H) sum_h softmax probabilities (before dropout; exactly 0 where the mask hides the key)."""
@@ -439,6 +451,40 @@ def attn_maps_amask(dtype: int, probs, masks) -> None:
     _grouped("bpm_attn_maps_hmask", arr, (dtype,), beside=masks)
 
 
+def _attn_kamask(name: str, dtype: int, probs, kmasks, masks, seed: int) -> None:
+    arr = _as_array(AttnProblem, probs)
+    if len(kmasks) != len(arr) or len(masks) != len(arr):
+        raise ValueError(f"{name}: one key mask and one additive mask per problem ({len(arr)} problems, {len(kmasks)} key masks, "
+                         f"{len(masks)} additive masks)")
+    _grouped(name, arr, (dtype,), (_seed(seed),), beside=(kmasks, masks))
+
+
+def attn_fwd_kamask(dtype: int, probs, kmasks, masks, seed: int = 0) -> None:
+    """bpm_attn_fwd with a per-key padding mask AND an additive mask: `kmasks` from attn_kmasks(), `masks` from
+    attn_amasks(), one of each per problem.  A pair is visible iff the mask_off rule, the key's byte and the additive entry
+    (> -inf) all say so; every query row of every sample needs a visible key (not checked)."""
+    _attn_kamask("bpm_attn_fwd_kamask", dtype, probs, kmasks, masks, seed)
+
+
+def attn_bwd_dq_kamask(dtype: int, probs, kmasks, masks, seed: int = 0) -> None:
+    _attn_kamask("bpm_attn_bwd_dq_kamask", dtype, probs, kmasks, masks, seed)
+
+
+def attn_bwd_dkv_kamask(dtype: int, probs, kmasks, masks, seed: int = 0) -> None:
+    _attn_kamask("bpm_attn_bwd_dkv_kamask", dtype, probs, kmasks, masks, seed)
+
+
+def attn_maps_kamask(dtype: int, probs, kmasks, masks) -> None:
+    arr = _as_array(AttnMapProblem, probs)
+    if len(kmasks) != len(arr) or len(masks) != len(arr):
+        raise ValueError(f"bpm_attn_maps_kamask: one key mask and one additive mask per problem ({len(arr)} problems, "
+                         f"{len(kmasks)} key masks, {len(masks)} additive masks)")
+    if _DRY_RUN:
+        _DRY_LAUNCHES.append((attn_maps_kamask, dtype, arr, kmasks, masks))
+        return
+    _grouped("bpm_attn_maps_kamask", arr, (dtype,), beside=(kmasks, masks))
+
+
 def attn_dbias(outs) -> "C.Array":
     """[(dB, lddb, head_stride)] -> the host array of bpm_attn_dbias that bpm_attn_bwd_dbias takes beside the problems and
     their masks.  dB: float32 device tensor [T, lddb] (head_stride 0: the gradient summed over samples and heads) or
@@ -460,17 +506,24 @@ def attn_dbias_ws_bytes(probs, outs) -> int:
     return int(_lib.lib().bpm_attn_bwd_dbias_ws_bytes(arr, outs, len(arr)))
 
 
-def attn_bwd_dbias(dtype: int, probs, masks, outs, seed: int = 0, ws=None) -> None:
+def attn_bwd_dbias(dtype: int, probs, masks, outs, seed: int = 0, ws=None, kmasks=None) -> None:
     """The gradient of the additive masks (`masks` from attn_amasks(), as the forward pass took them) into `outs` (from
     attn_dbias()), after attn_bwd_dq[_amask] has left delta.  ws: a device tensor of at least attn_dbias_ws_bytes() bytes
-    (None when that is 0); one launch, so at most MAX_GROUP problems."""
+    (None when that is 0); one launch, so at most MAX_GROUP problems.  kmasks: the key masks (attn_kmasks()) of a forward
+    pass through attn_fwd_kamask -- sample b adds nothing at the keys its byte hides (bpm_attn_bwd_dbias_kmask)."""
     arr = _as_array(AttnProblem, probs)
     if len(masks) != len(arr) or len(outs) != len(arr):
         raise ValueError(f"bpm_attn_bwd_dbias: one mask and one output per problem ({len(arr)} problems, {len(masks)} masks, {len(outs)} outputs)")
+    if kmasks is not None and len(kmasks) != len(arr):
+        raise ValueError(f"bpm_attn_bwd_dbias_kmask: one key mask per problem ({len(arr)} problems, {len(kmasks)} masks)")
     if len(arr) > MAX_GROUP:
         raise ValueError(f"bpm_attn_bwd_dbias: at most {MAX_GROUP} problems per launch")
     nbytes = 0 if ws is None else ws.numel() * ws.element_size()
-    _lib.check(_lib.lib().bpm_attn_bwd_dbias(dtype, arr, masks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()), "bpm_attn_bwd_dbias")
+    if kmasks is None:
+        _lib.check(_lib.lib().bpm_attn_bwd_dbias(dtype, arr, masks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()), "bpm_attn_bwd_dbias")
+    else:
+        _lib.check(_lib.lib().bpm_attn_bwd_dbias_kmask(dtype, arr, masks, kmasks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()),
+                   "bpm_attn_bwd_dbias_kmask")
 
 
 # ----------------------------------------------------------------------------

@@ -275,6 +275,43 @@ size_t bpm_attn_bwd_dbias_ws_bytes(const bpm_attn_problem* probs /* host */, con
 int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */,
                        const bpm_attn_dbias* outs /* host */, int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
+/* A PER-KEY PADDING MASK TOGETHER WITH AN ADDITIVE MASK (the reference's key_padding_mask beside its attn_mask, and a
+ * learned attn_bias): the *_kamask entries take one bpm_attn_kmask AND one bpm_attn_hmask per problem, two parallel host
+ * arrays.  Pair (sample b, head h, query i, key j) is visible iff all three rules say so: the problem's mask_off rule,
+ * kmask[b*ldm + j] != 0, and mask[h*head_stride + i*ldm + j] > -inf; the score of a visible pair is
+ * q_i . k_j + mask[h*head_stride + i*ldm + j].  A hidden pair behaves as in the two families: probability exactly 0.0f,
+ * nothing added to lse, exactly nothing contributed to dK / dV (a key whose byte hides it for sample b gets exactly zero
+ * dK / dV rows in that sample); a 64-key tile without a visible byte is skipped.  Query rows are never masked.
+ * EVERY QUERY ROW OF EVERY SAMPLE MUST KEEP AT LEAST ONE VISIBLE KEY under the three rules together -- not checked (the
+ * masks never travel to the host); a row without one yields NaN.
+ * The byte mask is read as in the *_kmask entries (never at j >= S: a tight [B, S] tensor is legal), the additive image as
+ * in the *_hmask entries (forward / dQ: mask; dK / dV and maps: maskT, required there).
+ * BPM_ERR_ARG, before anything is launched (and without a GPU): the union of the two families' rules -- a NULL array of
+ * either kind, a NULL byte mask or one with ldm < S, a NULL `mask`, ldm < S, ldm % 4 != 0 or a misaligned base of the
+ * additive image, a NULL / short / misaligned maskT where it is required, a broken head-stride rule, dS / Pd set, problems
+ * of different dhp.
+ * With an all-ones byte mask the results are bit-equal to the *_hmask entries', with an all-zeros image to the *_kmask
+ * entries'.
+ * bpm_attn_maps_kmask: bpm_attn_maps of forward passes through bpm_attn_fwd_kmask; a key the byte mask hides is exactly
+ * 0.0f in the map (all-ones: bit-equal to bpm_attn_maps).  bpm_attn_maps_kamask: the same after bpm_attn_fwd_kamask.
+ * bpm_attn_bwd_dbias_kmask: bpm_attn_bwd_dbias after bpm_attn_bwd_dq_kamask; sample b contributes nothing at the keys
+ * its byte mask hides (a key hidden in every sample: exactly 0.0f), same fixed summation order, no float atomics, same
+ * workspace (bpm_attn_bwd_dbias_ws_bytes).  kmasks == NULL: bpm_attn_bwd_dbias itself, same kernels, same bits.
+ * New entries only: BPM_ABI_VERSION stays. */
+int bpm_attn_maps_kmask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */, int nprob,
+                        void* stream);
+int bpm_attn_fwd_kamask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                        const bpm_attn_hmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_kamask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                           const bpm_attn_hmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_kamask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                            const bpm_attn_hmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_maps_kamask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                         const bpm_attn_hmask* masks /* host */, int nprob, void* stream);
+int bpm_attn_bwd_dbias_kmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_hmask* masks /* host */,
+                             const bpm_attn_kmask* kmasks /* host, or NULL */, const bpm_attn_dbias* outs /* host */, int nprob,
+                             uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,
  * problem arrays live in HOST memory and are copied into the kernel arguments.

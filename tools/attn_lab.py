@@ -19,6 +19,11 @@ mask and the same rule, for one encoder and for all G in one launch, bpm_attn_bw
 head sums are split over workgroups when the launch has fewer than 256 tiles; per head [H, T, S]) beside the dQ and dK / dV
 launches of the same problems, and forward / dQ / dK / dV with H mask images through the head stride against one image.
 
+--kamask: the combined-mask entries (bpm_attn_fwd_kamask / _bwd_dq_kamask / _bwd_dkv_kamask) beside the two families they are
+made of, on the same inputs in the same run, the three alternating in each of three rounds (median round on record): the
+*_hmask entries with an all-zeros image, the *_kmask entries and the *_kamask entries with an all-ones byte mask, and the
+latter two again with the last third of every sample's keys padded.  --f32 times everything in float32.
+
 Algorithmic FLOPs per visible (query, key) pair and head: forward 4 dh, dQ pass 6 dh (S, dP, dQ), dK/dV pass 8 dh."""
 import argparse
 import json
@@ -63,9 +68,12 @@ def main():
     ap.add_argument("--no-mask", action="store_true")
     ap.add_argument("--maps", action="store_true", help="also time bpm_attn_maps at the same shapes (after the forward has written LSE)")
     ap.add_argument("--amask", action="store_true", help="also time the *_amask entries (all-zeros mask; the future mask as a tensor)")
+    ap.add_argument("--kamask", action="store_true", help="also time the *_kamask entries beside the *_kmask and *_hmask entries")
+    ap.add_argument("--f32", action="store_true", help="float32 instead of bfloat16")
     ap.add_argument("--pair", type=int, default=-1, help="tuning hook: bit k = kernel k (fwd, dQ, dK/dV) takes two blocks per workgroup")
     a = ap.parse_args()
-    dev, ct = "cuda", torch.bfloat16
+    dev, ct = "cuda", torch.float32 if a.f32 else torch.bfloat16
+    DT = ops.BPM_F32 if a.f32 else BPM_BF16
     if a.pair >= 0:
         from bpmult_amd import _lib
         _lib.check(_lib.lab_library().__enter__().bpm_debug_attn_pair(a.pair), "bpm_debug_attn_pair")   # -DBPM_LAB build only
@@ -87,9 +95,10 @@ def main():
                                       drop_p=a.drop if e < a.drop_encoders else 0.0, drop_site=9 + 16 * e))
     arr = ops.array(ops.AttnProblem, probs)
     pairs = sum(min(S, t + off) for t in range(T)) * B * H * G
-    res = {"shape": dict(B=B, H=H, T=T, S=S, head_dim=dh, encoders=G, mask=not a.no_mask, drop=a.drop, drop_encoders=a.drop_encoders)}
+    res = {"shape": dict(B=B, H=H, T=T, S=S, head_dim=dh, encoders=G, mask=not a.no_mask, drop=a.drop, drop_encoders=a.drop_encoders,
+                         dtype="f32" if a.f32 else "bf16")}
     for name, fn, fl in (("fwd", ops.attn_fwd, 4), ("bwd_dq", ops.attn_bwd_dq, 6), ("bwd_dkv", ops.attn_bwd_dkv, 8)):
-        us = _time(lambda: fn(BPM_BF16, arr, 5), a.iters)
+        us = _time(lambda: fn(DT, arr, 5), a.iters)
         tf = fl * dh * pairs / us / 1e6
         res[name] = {"us": round(us, 1), "tflops": round(tf, 1), "bf16_peak_frac": round(tf / BF16_PEAK_TF, 3)}
     if a.amask:
@@ -107,7 +116,7 @@ def main():
             am = ops.attn_amasks([(m, ldm, mt, ldt)] * G)
             res[tag] = {}
             for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
-                us = _time(lambda: fn(BPM_BF16, parr, am, 5), a.iters)
+                us = _time(lambda: fn(DT, parr, am, 5), a.iters)
                 res[tag][name] = {"us": round(us, 1), "over_unmasked": round(us / res[name]["us"], 3)}
         # the learned-bias launches: all-zeros images, one per head through the head stride, and the bias gradient
         zh = (torch.zeros(H, T, ldm, device=dev), torch.zeros(H, S, ldt, device=dev))
@@ -118,7 +127,7 @@ def main():
             amh = ops.attn_amasks([(zh[0], ldm, zh[1], ldt, T * ldm, S * ldt)] * n)
             r = res["dbias"][f"{n}_problems"] = {}
             for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
-                u0, uh = _time(lambda: fn(BPM_BF16, sub, am0, 5), a.iters), _time(lambda: fn(BPM_BF16, sub, amh, 5), a.iters)
+                u0, uh = _time(lambda: fn(DT, sub, am0, 5), a.iters), _time(lambda: fn(DT, sub, amh, 5), a.iters)
                 r[name] = {"us_stride0": round(u0, 1), "us_head_stride": round(uh, 1), "head_over_stride0": round(uh / u0, 3)}
             tiles = ((T + 63) // 64) * ((S + 63) // 64)
             for form, nimg, am in (("shared", 1, am0), ("per_head", H, amh)):
@@ -126,19 +135,39 @@ def main():
                 outs = ops.attn_dbias([(x, ldm, T * ldm if nimg > 1 else 0) for x in g])
                 nws = ops.attn_dbias_ws_bytes(sub, outs)
                 ws = torch.empty(nws // 4, device=dev) if nws else None
-                us = _time(lambda: ops.attn_bwd_dbias(BPM_BF16, sub, am, outs, 5, ws=ws), a.iters)
+                us = _time(lambda: ops.attn_bwd_dbias(DT, sub, am, outs, 5, ws=ws), a.iters)
                 splits = nws // (n * nimg * T * ldm * 4) if nws else 1
                 r["dbias_" + form] = {"us": round(us, 1), "over_dq": round(us / r["bwd_dq"]["us_head_stride" if nimg > 1 else "us_stride0"], 3),
                                       "workgroups": n * nimg * tiles * splits, "splits_per_tile": splits, "workspace_mbytes": round(nws / 1e6, 2)}
+    if a.kamask:
+        ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
+        am = ops.attn_amasks([(torch.zeros(T, ldm, device=dev), ldm, torch.zeros(S, ldt, device=dev), ldt)] * G)
+        ones = torch.ones(B, S, dtype=torch.uint8, device=dev)
+        third = ones.clone()
+        third[:, S - S // 3:] = 0
+        res["kamask"] = {}
+        for tag, kb in (("all_ones", ones), ("third_padded", third)):
+            km = ops.attn_kmasks([(kb, S)] * G)
+            r = res["kamask"][tag] = {}
+            for name in ("fwd", "bwd_dq", "bwd_dkv"):
+                fh, fk, fka = (getattr(ops, f"attn_{name}_{fam}") for fam in ("amask", "kmask", "kamask"))
+                rounds = []
+                for _ in range(3):
+                    rounds.append((_time(lambda: fh(DT, arr, am, 5), a.iters), _time(lambda: fk(DT, arr, km, 5), a.iters),
+                                   _time(lambda: fka(DT, arr, km, am, 5), a.iters)))
+                uh, uk, uka = (sorted(x[i] for x in rounds)[1] for i in range(3))
+                r[name] = {"hmask_us": round(uh, 1), "kmask_us": round(uk, 1), "kamask_us": round(uka, 1),
+                           "kamask_over_hmask": round(uka / uh, 3), "kamask_over_kmask": round(uka / uk, 3),
+                           "rounds_hmask_kmask_kamask_us": [[round(x, 1) for x in y] for y in rounds]}
     if a.maps:
         # LSE of the last forward launch above is in place; maps and forward alternate in one timing loop each, three rounds
         wts = [torch.empty(B, T, S, device=dev) for _ in range(G)]
         mp = [ops.attn_map_problem(t["q"], t["k"], t["lse"], w, S, B, H, T, S, dh, dhp, off) for t, w in zip(keep, wts)]
         marr = ops.array(ops.AttnMapProblem, mp)
-        ops.attn_fwd(BPM_BF16, arr, 5)
+        ops.attn_fwd(DT, arr, 5)
         rounds = []
         for _ in range(3):
-            rounds.append((_time(lambda: ops.attn_fwd(BPM_BF16, arr, 5), a.iters), _time(lambda: ops.attn_maps(BPM_BF16, marr), a.iters)))
+            rounds.append((_time(lambda: ops.attn_fwd(DT, arr, 5), a.iters), _time(lambda: ops.attn_maps(DT, marr), a.iters)))
         f_us, m_us = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
         out_bytes = G * B * T * S * 4
         in_bytes = G * B * H * ((T + S) * dhp * 2 + T * 4)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Do two trees compile to the same kernels?  Needs hipcc, no GPU.
 
-    python tools/kernel_isa_diff.py A_DIR B_DIR [--out report.json] [--jobs 4]
+    python tools/kernel_isa_diff.py A_DIR B_DIR [--out report.json] [--jobs 4] [--by-instantiation]
 
 Every csrc/*.hip of both trees is compiled device-only to assembly (--cuda-device-only -S, otherwise the flags of
 _lib.build) and each file is split at its kernel symbols.  For every kernel of either tree the report says whether
@@ -9,7 +9,10 @@ _lib.build) and each file is split at its kernel symbols.  For every kernel of e
   descriptor  its .amdhsa_kernel ... .end_amdhsa_kernel block (registers, LDS, scratch, ...)
 are identical in the two builds, and which kernels only one tree has.  Kernels are matched by symbol over the whole
 tree, so one that moved to another file still meets its counterpart.  Exit status 0 when the two sets of symbols are
-equal and every kernel is identical in both respects.  It compares two builds; it looks for nothing inside them."""
+equal and every kernel is identical in both respects.  It compares two builds; it looks for nothing inside them.
+--by-instantiation matches kernels by name and template arguments alone (the mangled symbol without its parameter
+types): a kernel whose argument TYPE was renamed or respelled, which changes its symbol and nothing
+else, still meets its counterpart; the symbol inside the text is replaced by a placeholder on both sides."""
 import argparse
 import hashlib
 import json
@@ -86,21 +89,35 @@ def tree_kernels(root, jobs, tmp):
     return found
 
 
+def by_instantiation(found):
+    """found, keyed by the mangled name up to the end of the template arguments (the parameter types cut off)"""
+    out = {}
+    for sym, k in found.items():
+        m = re.match(r"(_ZN.*?EE)v", sym) or re.match(r"(_Z\d+\w+?I.*?E)v", sym)       # nested (namespace) name / plain name
+        key = m.group(1) if m else sym
+        assert key not in out, key
+        out[key] = {"file": k["file"], "code": k["code"].replace(sym, "<kernel>"), "desc": k["desc"].replace(sym, "<kernel>")}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("a_dir")
     ap.add_argument("b_dir")
     ap.add_argument("--out", help="write the report (JSON) here")
     ap.add_argument("--jobs", type=int, default=4)
+    ap.add_argument("--by-instantiation", action="store_true", help="match kernels by name and template arguments, not by symbol")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         a, b = tree_kernels(args.a_dir, args.jobs, tmp), tree_kernels(args.b_dir, args.jobs, tmp)
+    if args.by_instantiation:
+        a, b = by_instantiation(a), by_instantiation(b)
     both = sorted(set(a) & set(b))
     kernels = {k: {"a_file": a[k]["file"], "b_file": b[k]["file"], "code_identical": a[k]["code"] == b[k]["code"],
                    "descriptor_identical": a[k]["desc"] == b[k]["desc"], "instructions": a[k]["code"].count("\n") + 1,
                    "code_sha256": hashlib.sha256(b[k]["code"].encode()).hexdigest()[:16]} for k in both}
     report = {
-        "tool": "tools/kernel_isa_diff.py A_DIR B_DIR", "arch": ARCH, "flags": FLAGS,
+        "tool": "tools/kernel_isa_diff.py A_DIR B_DIR" + (" --by-instantiation" if args.by_instantiation else ""), "arch": ARCH, "flags": FLAGS,
         "kernels_a": len(a), "kernels_b": len(b), "only_in_a": sorted(set(a) - set(b)), "only_in_b": sorted(set(b) - set(a)),
         "identical": sum(v["code_identical"] and v["descriptor_identical"] for v in kernels.values()),
         "different": sorted(k for k, v in kernels.items() if not (v["code_identical"] and v["descriptor_identical"])),
