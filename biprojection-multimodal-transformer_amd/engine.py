@@ -527,6 +527,14 @@ class EncoderDesc:
 
 
 @dataclass
+class EncoderMasks:
+    """Which padding masks the forward calls of one encoder of a plan carry (EncoderGroupPlan(masks=...)): the content
+    comes with every forward call, the plan is built for their presence."""
+    self_keys: bool = False       # [B, T]: padding rows of the query sequence, hidden as keys of the self-attention block
+    cross_keys: bool = False      # [B, S]: padding rows of the key / value source, hidden as keys of the cross-attention block
+
+
+@dataclass
 class GroupCfg:
     d: int
     H: int
@@ -613,8 +621,26 @@ class EncoderGroupPlan:
     The per-block builders below (_ln0_* / _self_attn_* / _cross_attn_* / _ffn_*) append one encoder's problems of one
     layer to that layer's launch lists; _build_fwd / _build_bwd wire their operands and order the launches per kind."""
 
-    def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int, x3: "Optional[ops.X3Cache]" = None):
+    def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int, x3: "Optional[ops.X3Cache]" = None,
+                 masks: "Optional[Sequence[Optional[EncoderMasks]]]" = None):
         self.store, self.cfg, self.encs, self.B = store, cfg, list(encs), B
+        # PADDING MASKS (masks[e]: which key masks encoder e's forward calls carry; None / all-False everywhere: an unmasked
+        # plan, whose tables are what they always were).  A masked plan runs EVERY attention step through the *_kmask
+        # entries, one mask per problem: the plan owns one visibility buffer per encoder and attention block (_alloc: vis_s
+        # [B, T], vis_c [B, S]; uint8, nonzero = VISIBLE, the kernels' convention), the bpm_attn_kmask arrays below point at
+        # them for the plan's life, and forward() refills them from the caller's masks -- the tables stay fixed while the
+        # mask content changes from call to call.  A block that was given no mask keeps its buffer of ones.
+        self.masks = [EncoderMasks() if m is None else m for m in (masks if masks is not None else [None] * len(self.encs))]
+        if len(self.masks) != len(self.encs):
+            raise ValueError(f"masks: one entry per encoder ({len(self.encs)} encoders, {len(self.masks)} entries)")
+        self._masked = any(m.self_keys or m.cross_keys for m in self.masks)
+        for e, m in zip(self.encs, self.masks):
+            if m.self_keys and not (cfg.biprojection or cfg.self_only):
+                raise ValueError(f"encoder {e.prefix}: a self-attention key mask, but the crossmodal layer kind has no self-attention block")
+            if m.cross_keys and cfg.self_only:
+                raise ValueError(f"encoder {e.prefix}: a cross-attention key mask, but a self-attention-only plan has no key / value source")
+            if self._masked and (e.tail_rows or e.T_full is not None or e.q_pos0 or e.q_stride != 1):
+                raise ValueError(f"encoder {e.prefix}: padding masks are not available with tail_rows or a gathered query subset")
         # bf16x3 mode: the owner of the activations' split images -- the caller's (a trunk shares one between its plans), or
         # this plan's own (a stand-alone encoder); the weight shadows' images stay with the store
         self.x3 = x3 if x3 is not None or not store.x3 else ops.X3Cache(store.device, weights=store.x3_cache)
@@ -637,7 +663,8 @@ class EncoderGroupPlan:
         # elimination has T = 2: at hidden 768 this removes 1.5 of the step's 19.4 ms (the key / value weight gradients over
         # 4096 rows, the merged K = 6144 data gradient, the dK / dV pass).  Equal to the dK / dV route in real arithmetic; the
         # roundings differ (dS instead of dK is rounded to CT), fixtures F7 / F9 / F11 hold both.  Crossmodal groups only.
-        self._lowrank = (_LOWRANK and self._kv and not cfg.biprojection
+        # Off in a masked plan: the masked dQ entries have no dS / Pd export (attention.hip, fill_masked).
+        self._lowrank = (_LOWRANK and self._kv and not cfg.biprojection and not self._masked
                          and all(e.T * H * 4 <= d and e.S % 4 == 0 for e in self.encs) and self.dh <= 256)
         self.ld, self.ld4 = pad32(d), pad32(4 * d)
         self.scale = self.dh ** -0.5
@@ -659,6 +686,13 @@ class EncoderGroupPlan:
         self._acc0 = torch.zeros(nacc, device=dev, dtype=torch.float32)
         self._acc_off = 0
         self.buf: List[dict] = [self._alloc(e) for e in self.encs]
+        # one bpm_attn_kmask per encoder and block, in encoder order like the problems of every attention launch
+        self._km_self = self._km_cross = None
+        if self._masked:
+            if cfg.biprojection or not self._kv:
+                self._km_self = ops.attn_kmasks([(b["vis_s"], e.T) for e, b in zip(self.encs, self.buf)])
+            if self._kv:
+                self._km_cross = ops.attn_kmasks([(b["vis_c"], e.S) for e, b in zip(self.encs, self.buf)])
         if cfg.biprojection and any(e.T_full is not None for e in self.encs):
             raise ValueError("a gathered query subset is only exact for crossmodal (non-biprojection) encoders")
         self.table = sinusoid_table(max(max(e.T_full or e.T, e.S) for e in self.encs) + 2, d, dev)
@@ -813,6 +847,12 @@ class EncoderGroupPlan:
                 b["dke"], b["dve"] = z(Rk, d), z(Rk, d)
             b["dxk"], b["dxv"] = z(e.S, B, d), z(e.S, B, d)
         b["dxq"] = z(e.T, B, d)
+        if self._masked:
+            # key visibility of the plan's last forward, one byte per (sample, key), nonzero = visible: written by forward()
+            # as bool (torch.eq's own output type, one launch), read by the kernels through the uint8 view of the same bytes
+            for nm, n in ((("vis_s", e.T),) if has_self else ()) + ((("vis_c", e.S),) if self._kv else ()):
+                b[nm + "_b"] = torch.ones(B, n, device=dev, dtype=torch.bool)
+                b[nm] = b[nm + "_b"].view(torch.uint8)
         return b
 
     # -- helpers ----------------------------------------------------------------
@@ -1064,7 +1104,9 @@ class EncoderGroupPlan:
         pr = (lambda p: p) if training else (lambda p: 0.0)
         ln = lambda probs: (ops.ln_fwd, self.dtype, A(LnProblem, probs), d)
         nt = lambda probs: self._gemm(GEMM_NT, probs)
-        attn = lambda probs: (ops.attn_fwd, self.dtype, A(AttnProblem, probs))
+        # km: the block's key masks in a masked plan (_km_self / _km_cross), one per problem: the same step, the *_kmask entry
+        attn = lambda probs, km: (ops.attn_fwd, self.dtype, A(AttnProblem, probs)) if km is None else \
+            (ops.attn_fwd_kmask, self.dtype, A(AttnProblem, probs), km)
         steps, kv_steps = [], []
         if self._kv_fused:
             kv_steps = [(SIDE, (ops.kv_source_fwd, self.dtype, self._kvsrc[training], self.table, d, math.sqrt(d))), (MARK, "hat")]
@@ -1090,10 +1132,10 @@ class EncoderGroupPlan:
                     self._cross_attn_fwd(t, e, b, i, pr, b["xn"][i], b["x"][i])
                     self._ffn_fwd(t, e, b, i, pr, (b["st1m"][i], b["st1r"][i]))
             self_half = lambda: [ln(t["ln0"])] + ([(ops.rows_cast, self.dtype, A(CastProblem, t["s.gather"]))] if t["s.gather"] else []) \
-                + [nt(t["s.qkv"]), attn(t["s.att"]), nt(t["s.out"])]
+                + [nt(t["s.qkv"]), attn(t["s.att"], self._km_self), nt(t["s.out"])]
             # K/V side of every layer depends only on the (embedded) key/value sources: the side stream runs it
             # ahead of the query chain; the main stream waits for layer i's K/V heads just before attention i.
-            cross = lambda: [nt(t["c.q"]), (WAIT, i), attn(t["c.att"]), nt(t["c.out"])]
+            cross = lambda: [nt(t["c.q"]), (WAIT, i), attn(t["c.att"], self._km_cross), nt(t["c.out"])]
             ffn = [ln(t["f.ln"]), nt(t["f.fc1"]), nt(t["f.fc2"])]
             if not self._kv:
                 steps += self_half() + ffn
@@ -1196,14 +1238,33 @@ class EncoderGroupPlan:
                 main_dirty = True
 
     def forward(self, xq: Sequence[torch.Tensor], xk: Sequence[torch.Tensor], xv: Sequence[torch.Tensor], seed: int,
-                training: bool) -> List[torch.Tensor]:
+                training: bool, self_masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                cross_masks: Optional[Sequence[Optional[torch.Tensor]]] = None) -> List[torch.Tensor]:
         """xq[e]: fp32 [T_e,B,d]; xk[e], xv[e]: fp32 [S_e,B,d] key / value sources (the same tensor at every
         reference call site, mmtr.py:779-791; they still get independent embedding dropout, transformer.py:73-79).
         With fused key / value sources (the default) the plan keeps references to xk / xv until its next forward and
-        backward() reads them again: like any tensor saved for a backward pass they must not be modified in between."""
+        backward() reads them again: like any tensor saved for a backward pass they must not be modified in between.
+        self_masks[e] / cross_masks[e] (a masked plan: exactly the masks its EncoderMasks declare, None for the others):
+        bool / uint8 [B, T_e] / [B, S_e] on the plan's device, any strides, nonzero = PADDING; each is turned into the
+        plan's visibility buffer by one launch on the current stream, ahead of the tables -- no host synchronisation.  The
+        buffers belong to the plan like its activations: backward() and attention_maps() read what the last forward left."""
         c, B, d = self.cfg, self.B, self.cfg.d
         p = c.embed_dropout if training else 0.0
         emb = []
+        fills = []
+        for what, given, nm in (("self", self_masks, "vis_s"), ("cross", cross_masks, "vis_c")):
+            given = [None] * len(self.encs) if given is None else list(given)
+            for e, b, m, t in zip(self.encs, self.buf, self.masks, given):
+                want = m.self_keys if what == "self" else m.cross_keys
+                if (t is not None) != want:
+                    raise ValueError(f"encoder {e.prefix}: this plan was built {'with' if want else 'without'} a {what}-attention "
+                                     f"key mask, the call comes {'without' if want else 'with'} one")
+                if t is not None:
+                    n = e.T if what == "self" else e.S
+                    if t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != (B, n):
+                        raise ValueError(f"encoder {e.prefix}: {what}-attention key mask must be bool / uint8 [{B},{n}], got "
+                                         f"{tuple(t.shape)} {t.dtype}")
+                    fills.append((t, b[nm + "_b"]))
         if not self._kv:                        # one input per encoder (xk / xv are ignored and may be None)
             xk = xv = [None] * len(self.encs)
         for e, b, q, k, v in zip(self.encs, self.buf, xq, xk, xv):
@@ -1225,6 +1286,8 @@ class EncoderGroupPlan:
                 for i, (k, v) in enumerate(zip(ks, vs)):
                     ops.set_kv_source(arr[i], k, v)
         self._maps_ok = False
+        for t, vis in fills:                    # visible = (padding == 0): the one launch per mask
+            torch.eq(t, 0, out=vis)
         ops.embed_pos_fwd(emb, self.table, d, math.sqrt(d), seed)
         self._last = (seed, training)
         self._run(self._fwd[training], seed)
@@ -1294,6 +1357,7 @@ class EncoderGroupPlan:
                 raise IndexError(f"attention_maps: layer {i!r} out of range ({L} layers)")
         dev = self.store.device
         probs, res = [], []
+        kms = []                                 # masked plan: each map's key mask, the visibility buffer its block's forward read
         for k in eidx:
             e, b = self.encs[k], self.buf[k]
             per_layer = []
@@ -1304,10 +1368,14 @@ class EncoderGroupPlan:
                     W = torch.empty(self.B, Tq, S, device=dev, dtype=torch.float32)
                     probs.append(ops.attn_map_problem(q, kk, lse, W, S, self.B, self.cfg.H, Tq, S, self.dh, self.dhp, moff,
                                                       q_pos0=p0, q_stride=st_))
+                    if self._masked:
+                        kms.append((b["vis_s" if name == "self" else "vis_c"], S))
                     maps[name] = AttentionMap(W, steps)
                 per_layer.append(maps)
             res.append(per_layer)
-        if probs:
+        if probs and self._masked:
+            ops.attn_maps_kmask(self.dtype, probs, ops.attn_kmasks(kms))
+        elif probs:
             ops.attn_maps(self.dtype, probs)
         return res
 
@@ -1348,7 +1416,11 @@ class EncoderGroupPlan:
                 return [nn(t["f.dg2"])] + ([] if wg_late else [w]) + [nn(t["f.dg1"])] + ([w] if wg_late else []) + [ln(t["f.ln"])]
 
             def self_half(presplit):
-                return [nn(t["s.dgout"]), (ops.attn_bwd, self.dtype, A(AttnProblem, t["s.att"])), wg(t["s.wg"], presplit),
+                # masked plan: bpm_attn_bwd's two passes (dQ + delta, then dK / dV) through their *_kmask entries, in its order
+                satt = [(ops.attn_bwd, self.dtype, A(AttnProblem, t["s.att"]))] if self._km_self is None else \
+                    [(ops.attn_bwd_dq_kmask, self.dtype, A(AttnProblem, t["s.att"]), self._km_self),
+                     (ops.attn_bwd_dkv_kmask, self.dtype, A(AttnProblem, t["s.att"]), self._km_self)]
+                return [nn(t["s.dgout"])] + satt + [wg(t["s.wg"], presplit),
                         nn(t["s.dg_a"])] + ([nn(t["s.dg_b"])] if t["s.dg_b"] else []) + ([nn(t["s.dg_c"])] if t["s.dg_c"] else []) + \
                     ([nn(t["s.dgq"]), (ops.add_n, A(AddnProblem, t["s.scatter"]))] if t["s.dgq"] else []) + [ln(t["ln0"])]
 
@@ -1369,11 +1441,15 @@ class EncoderGroupPlan:
             # the backward critical path consumes them.  Temporaries are double-buffered by layer parity, so the
             # main chain only waits (WAIT) for the side work of two layers ago before overwriting them.
             wg_att = wg(t["c.wg"], t["c.grads"] + t["c.acts"] if x3 else ())
-            dkv = (ops.attn_bwd_dkv, self.dtype, A(AttnProblem, t["c.att"]))
+            # masked plan: the same two passes at the same places, through the *_kmask entries with the cross block's masks
+            catt = lambda fn, fn_km: (fn, self.dtype, A(AttnProblem, t["c.att"])) if self._km_cross is None else \
+                (fn_km, self.dtype, A(AttnProblem, t["c.att"]), self._km_cross)
+            dq_step = catt(ops.attn_bwd_dq, ops.attn_bwd_dq_kmask)
+            dkv = catt(ops.attn_bwd_dkv, ops.attn_bwd_dkv_kmask)
             # (bf16x3: the weight gradients are launched BEHIND the data-gradient products that split the same gradients --
             # dg_fc1 splits dh1, dg_q splits dq -- so that the side stream finds those images instead of splitting again)
             steps += [(WAIT, i + 2)] + ffn(t["f.grads"] + t["f.acts"] if x3 else (), x3) + \
-                [nn(t["c.dgout"]), (ops.attn_bwd_dq, self.dtype, A(AttnProblem, t["c.att"]))] + \
+                [nn(t["c.dgout"]), dq_step] + \
                 ([] if lr else [(SIDE if self._dkv_side == "1" else SIDE2, dkv) if self._dkv_side in ("1", "2") else dkv]) + \
                 ([] if x3 or lr else [wg_att]) + [nn(t["c.dgq"])] + ([wg_att] if x3 and not lr else [])
             # dK / dV (above) feed only side work: beside the main chain where the side stream has slack (see _DKV_SIDE_ENV)

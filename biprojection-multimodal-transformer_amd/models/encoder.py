@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from .. import config
-from ..engine import EncoderDesc, EncoderGroupPlan, GroupCfg, ParamStore, register_encoder_shadows
+from ..engine import EncoderDesc, EncoderGroupPlan, EncoderMasks, GroupCfg, ParamStore, register_encoder_shadows
 from .attention import MultiheadAttention          # a parameter container here: the encoder runs its own engine plan
 
 
@@ -46,14 +46,16 @@ class SinusoidalPositionalEmbedding(nn.Module):
 
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, x_q, x_k, x_v, enc):
-        """x_k / x_v None: the self-attention stack (the encoder's self-only plan; its only input is x_q)."""
-        plan = enc._plan_for(x_q, x_k)
+    def forward(ctx, anchor, x_q, x_k, x_v, enc, epm=None, kpm=None):
+        """x_k / x_v None: the self-attention stack (the encoder's self-only plan; its only input is x_q).  epm / kpm: the
+        padding masks of x_q's rows / of the key / value source's rows (TransformerEncoder.forward), or None."""
+        plan = enc._plan_for(x_q, x_k, epm is not None, kpm is not None)
         enc._store.refresh_shadows()
         if plan.x3 is not None:
             plan.x3.new_step()
         kv = ([None], [None]) if x_k is None else ([x_k.detach().contiguous()], [x_v.detach().contiguous()])
-        out = plan.forward([x_q.detach().contiguous()], *kv, enc._next_seed(), enc.training)[0]
+        masks = {} if epm is None and kpm is None else dict(self_masks=[epm], cross_masks=[kpm])
+        out = plan.forward([x_q.detach().contiguous()], *kv, enc._next_seed(), enc.training, **masks)[0]
         ctx.enc, ctx.plan = enc, plan
         enc._last_plan = plan
         return out.detach().clone()
@@ -65,8 +67,8 @@ class _EncoderFn(torch.autograd.Function):
         dq, dk, dv = plan.backward([dout])
         enc._store.end_backward()
         if dk[0] is None:
-            return None, dq[0].clone(), None, None, None
-        return None, dq[0].clone(), dk[0].clone(), dv[0].clone(), None
+            return None, dq[0].clone(), None, None, None, None, None
+        return None, dq[0].clone(), dk[0].clone(), dv[0].clone(), None, None, None
 
 
 class TransformerEncoder(nn.Module):
@@ -77,7 +79,25 @@ class TransformerEncoder(nn.Module):
     (the reference's condition, transformer.py:71,84): the self-attention stack over x_in's own T time steps, [T,B,d].
     In the biprojection layer kind that stack follows the reference's layer exactly: its FFN is normalised by
     layer_norms.2, and layer_norms.1 (maybe_layer_norm(1, after=True), the identity) gets no gradient -- it ends zero.
-    Both call forms run on the HIP engine and share one parameter store; plans are kept per call form and shape."""
+    Both call forms run on the HIP engine and share one parameter store; plans are kept per call form, shape and which
+    padding masks the call carries.
+
+    Padding masks (keyword-only; the reference's docstrings promise an encoder_padding_mask, transformer.py:62-63, :145-146,
+    and never implement one): torch.bool or torch.uint8 tensors on the inputs' device, any strides, nonzero / True =
+    padding, no gradient.
+      encoder_padding_mask [B, T]  the padding rows of x_in: hidden as KEYS of every self-attention block -- forward(x) of
+                                   either layer kind, and the self-attention block of the biprojection crossmodal call.  No
+                                   block of the plain crossmodal call would read it: ValueError there.
+      key_padding_mask [B, S]      the padding rows of x_in_k / x_in_v: hidden as keys of the cross-attention block.
+                                   ValueError in the self-attention call form, which has no key source.
+    A hidden key gets probability exactly 0 for every head and query row of its sample, ANDed with the future-mask rule
+    under attn_mask=True: d(x_in_k) / d(x_in_v) rows of padded positions are exactly 0, and in the self-attention forms a
+    padded row of x_in whose upstream gradient is 0 has d(x_in) exactly 0.  Query rows are never masked: the output rows
+    of padded query positions are computed like any other row, finite and unspecified.  Every query row of every sample
+    must keep a visible key under all rules together (not checked: the masks never travel to the host; NaN otherwise).
+    Right padding with at least one real row always satisfies it, under the causal rule too: key 0 is visible to every
+    row whenever mask_off >= 1.  Precisions 'bf16', 'f32' and 'bf16x3' (whose attention runs the f32 entries).
+    attention_maps() after a masked forward is taken under the same masks: exactly 0 at padded keys."""
 
     def __init__(self, embed_dim, num_heads, layers, attn_dropout=0.0, relu_dropout=0.0, res_dropout=0.0,
                  embed_dropout=0.0, attn_mask=False, biprojection=False):
@@ -119,26 +139,57 @@ class TransformerEncoder(nn.Module):
             self._anchor = torch.zeros(1, device=self._store.device, requires_grad=True)
         return self._store
 
-    def _plan_for(self, x_q, x_k) -> EncoderGroupPlan:
-        """x_k None: the self-attention-only plan of x_q's shape."""
+    def _plan_for(self, x_q, x_k, epm: bool = False, kpm: bool = False) -> EncoderGroupPlan:
+        """x_k None: the self-attention-only plan of x_q's shape.  epm / kpm: the call carries an encoder_padding_mask / a
+        key_padding_mask -- a plan of its own (a call without masks reaches the plan, under the key, it always did)."""
         st = self._ensure_store()
         T, B = x_q.shape[0], x_q.shape[1]
         key = ("self", T, B) if x_k is None else (T, x_k.shape[0], B)
+        if epm or kpm:
+            key += ("masks", epm, kpm)
         if key not in self._plans:
             S = T if x_k is None else x_k.shape[0]
             desc = EncoderDesc("", 0, T, S, self.attn_dropout)
-            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(self_only=x_k is None), [desc], B)
+            masks = dict(masks=[EncoderMasks(self_keys=epm, cross_keys=kpm)]) if epm or kpm else {}
+            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(self_only=x_k is None), [desc], B, **masks)
         return self._plans[key]
 
     def _next_seed(self) -> int:
         self._step += 1
         return (torch.initial_seed() * 1000003 + self._step) & 0x7FFFFFFFFFFFFFFF      # 63 bits: bit 63 marks a device-resident seed
 
-    def forward(self, x_in, x_in_k=None, x_in_v=None):
+    def _check_mask(self, name: str, mask, B: int, n: int, device) -> None:
+        """The checks of MultiheadAttention.forward's key_padding_mask; they need no device."""
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"TransformerEncoder: {name} must be a torch.bool or torch.uint8 tensor (nonzero = padding)")
+        if tuple(mask.shape) != (B, n):
+            raise ValueError(f"TransformerEncoder: {name} of shape {tuple(mask.shape)}, expected [{B}, {n}]")
+        if mask.device != device:
+            raise ValueError(f"TransformerEncoder: {name} on {mask.device}, the inputs on {device}")
+
+    def forward(self, x_in, x_in_k=None, x_in_v=None, *, encoder_padding_mask=None, key_padding_mask=None):
+        self_form = x_in_k is None or x_in_v is None   # transformer.py:71,84: the self-attention stack
+        if encoder_padding_mask is not None or key_padding_mask is not None:
+            if x_in.dim() != 3:
+                raise ValueError(f"TransformerEncoder: x_in of shape {tuple(x_in.shape)}, expected [T, B, {self.embed_dim}]")
+            T, B = x_in.shape[0], x_in.shape[1]
+            if key_padding_mask is not None:
+                if self_form:
+                    raise ValueError("TransformerEncoder: key_padding_mask marks the padding rows of x_in_k / x_in_v, and the "
+                                     "self-attention call form has no key source; the padding rows of x_in are encoder_padding_mask")
+                if x_in_k.dim() != 3:
+                    raise ValueError(f"TransformerEncoder: x_in_k of shape {tuple(x_in_k.shape)}, expected [S, {B}, {self.embed_dim}]")
+                self._check_mask("key_padding_mask", key_padding_mask, B, x_in_k.shape[0], x_in.device)
+            if encoder_padding_mask is not None:
+                if not self_form and not self.biprojection:
+                    raise ValueError("TransformerEncoder: encoder_padding_mask hides padding rows of x_in as self-attention keys, "
+                                     "and the crossmodal call of a plain (non-biprojection) encoder has no self-attention block "
+                                     "that would read it; the padding rows of x_in_k / x_in_v are key_padding_mask")
+                self._check_mask("encoder_padding_mask", encoder_padding_mask, B, T, x_in.device)
         self._ensure_store()
-        if x_in_k is None or x_in_v is None:           # transformer.py:71,84: the self-attention stack
-            return _EncoderFn.apply(self._anchor, x_in, None, None, self)
-        return _EncoderFn.apply(self._anchor, x_in, x_in_k, x_in_v, self)
+        if self_form:
+            return _EncoderFn.apply(self._anchor, x_in, None, None, self, encoder_padding_mask, None)
+        return _EncoderFn.apply(self._anchor, x_in, x_in_k, x_in_v, self, encoder_padding_mask, key_padding_mask)
 
     def attention_maps(self, layers=None):
         """Head-averaged attention maps of the most recent forward call (either call form): a list with one entry per
