@@ -360,6 +360,8 @@ SIGNATURES = {
     "bpm_pack_weights": [_I, _P, _I, C.c_uint, _P],
     "bpm_fold_bias": [C.c_void_p, _I, C.c_uint, _P],
     "bpm_unfold_grads": [C.c_void_p, _I, C.c_uint, _I, _P],
+    "bpm_unfold_grads_ws_bytes": [_I, C.c_uint, _I],
+    "bpm_unfold_grads_ws": [C.c_void_p, _I, C.c_uint, _I, _I, _P, C.c_size_t, _P],
     "bpm_zero_segment_blocks": [C.c_uint],
     "bpm_zero_segments": [C.c_void_p, _I, C.c_uint, _P],
     "bpm_embed_pos_fwd": [C.POINTER(EmbedProblem), _I, _P, _I, _I, _F, _U64, _P],
@@ -370,7 +372,11 @@ SIGNATURES = {
     "bpm_ln_bwd": [_I, C.POINTER(LnProblem), _I, _I, _U64, _P],
     "bpm_ln_bwd_ws": [_I, C.POINTER(LnProblem), _I, _I, _U64, _P, C.c_size_t, _P],
     "bpm_ln_bwd_ws_bytes": [_I, _I],
+    "bpm_ln_bwd_det_ws_bytes": [_I, _I],
+    "bpm_ln_bwd_det": [_I, C.POINTER(LnProblem), _I, _I, _U64, _P, C.c_size_t, _P],
     "bpm_rows_cast": [_I, C.POINTER(CastProblem), _I, _U64, _P],
+    "bpm_rows_cast_ws_bytes": [C.POINTER(CastProblem), _I],
+    "bpm_rows_cast_ws": [_I, C.POINTER(CastProblem), _I, _U64, _P, C.c_size_t, _P],
     "bpm_add_n": [C.POINTER(AddnProblem), _I, _P],
     "bpm_expand_heads": [_I, C.POINTER(ExpandProblem), _I, _P],
     "bpm_split_rows": [C.POINTER(SplitProblem), _I, _P],

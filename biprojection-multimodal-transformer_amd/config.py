@@ -21,6 +21,28 @@ def precision() -> str:
     return _PRECISION
 
 
+_DETERMINISTIC = os.environ.get("BPMULT_DETERMINISTIC", "0") not in ("", "0")
+
+
+def set_deterministic(flag: bool) -> None:
+    """Deterministic mode ("Deterministic mode"): every launch of forward, backward and FusedAdam.step leaves
+    the same bits on every run -- no float atomics: the linear layers' bias gradients ride on their weight-gradient
+    products (colsum_a), the row kernels' column sums go through partial-row workspaces.  Off by default; the default
+    path is unchanged by it.  Read where launch tables and plans are BUILT (a model's first forward at a batch size, a
+    captured graph), never per launch: switch it before, or call model.set_deterministic()."""
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(flag)
+
+
+def deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+def resolve_deterministic(flag) -> bool:
+    """A module's or argument's `deterministic` value: None means the process default."""
+    return _DETERMINISTIC if flag is None else bool(flag)
+
+
 def dtype_code(name: str) -> int:
     """Storage / compute type of the activations and weight shadows (bf16x3 keeps fp32 storage)."""
     if name not in PRECISIONS:

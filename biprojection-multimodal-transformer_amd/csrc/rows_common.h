@@ -59,6 +59,54 @@ BPM_DEV const D& find_desc(const D* __restrict__ tab, int ndesc, unsigned bid) {
     return tab[lo];
 }
 
+// Column sums without float atomics in TWO launches (deterministic mode: bpm_ln_bwd_det outside the vector kernels'
+// workspace route, bpm_rows_cast_ws): the first launch's blocks store their partial rows -- block b, array a at
+// part[(b * FIN_ARR + a) * ncol] -- with plain stores; this finishing launch runs one block per DISTINCT destination row,
+// which walks the problems in problem order, adds the partial rows of every (problem, array) that sums into its row in
+// block order, and makes one plain read-modify-write.  The kernel boundary orders the two; problems that share a row are
+// served by one owner, so nothing depends on the other problems of the launch beyond that stated order.
+constexpr int FIN_ARR = 3;
+struct ColFin {
+    int n, ncol, nown;                           // ncol: floats per partial row
+    int cols[BPM_MAX_GROUP];                     // live columns of problem i (<= ncol)
+    unsigned blk0[BPM_MAX_GROUP + 1];            // partial rows of problem i: blocks [blk0[i], blk0[i + 1])
+    float* dst[BPM_MAX_GROUP][FIN_ARR];          // where array a of problem i is added, or null
+    float* own[FIN_ARR * BPM_MAX_GROUP];         // the distinct destinations
+};
+
+inline void fin_begin(ColFin& f, int n, int ncol, const unsigned* blk0) {
+    f.n = n; f.ncol = ncol; f.nown = 0;
+    for (int i = 0; i <= n; ++i) f.blk0[i] = blk0[i];
+    for (int i = 0; i < n; ++i) {
+        f.cols[i] = ncol;
+        for (int a = 0; a < FIN_ARR; ++a) f.dst[i][a] = nullptr;
+    }
+}
+
+inline void fin_add(ColFin& f, int i, int a, float* dst) {
+    f.dst[i][a] = dst;
+    if (!dst) return;
+    for (int k = 0; k < f.nown; ++k)
+        if (f.own[k] == dst) return;
+    f.own[f.nown++] = dst;
+}
+
+template <int ARRS>      // (a template: only the files that launch it emit it)
+__global__ __launch_bounds__(256) void col_finish_kernel(const ColFin f, const float* part) {
+    static_assert(ARRS == FIN_ARR, "one layout of the partial rows");
+    float* dst = f.own[blockIdx.x];
+    for (int i = 0; i < f.n; ++i)                         // problem order; a thread owns its columns throughout
+        for (int a = 0; a < FIN_ARR; ++a) {
+            if (f.dst[i][a] != dst) continue;             // block-uniform
+            for (int c = threadIdx.x; c < f.cols[i]; c += 256) {
+                float s = 0.f;
+#pragma unroll 8
+                for (unsigned b = f.blk0[i]; b < f.blk0[i + 1]; ++b) s += part[((size_t)b * FIN_ARR + a) * f.ncol + c];
+                dst[c] += s;
+            }
+        }
+}
+
 constexpr unsigned CAP = 2048;   // blocks per problem for grid-stride kernels
 
 // Host side.  The prologue of every grouped entry: the null / count check and the header of the kernel argument.  What a

@@ -18,6 +18,45 @@ struct CastP {
     DropCfg drop;
 };
 
+// The partial rows of the workspace entry (bpm_rows_cast_ws, deterministic mode): row block rb of problem i stores its
+// column sums at part[(rb0[i] + rb) * FIN_ARR * ncol .. + C) for col_finish_kernel, instead of the atomics
+struct CastPart { float* part; int ncol; unsigned rb0[BPM_MAX_GROUP]; };
+
+BPM_DEV float* cast_part_row(const Grp<CastP>& grp, const CastPart& cp, unsigned rb) {
+    int pi = 0;
+#pragma unroll 1
+    for (int i = 1; i < grp.n; ++i)
+        if (blockIdx.x >= grp.blk0[i]) pi = i;
+    return cp.part + (size_t)(cp.rb0[pi] + rb) * FIN_ARR * cp.ncol;
+}
+
+// rows_cast_kernel (below) storing its column sums as partial rows: a copy of its body, expression for expression
+template <typename CT>
+__global__ __launch_bounds__(NT) void rows_cast_part_kernel(const Grp<CastP> grp, const CastPart cp) {
+    unsigned bid = blockIdx.x, nblk;
+    const CastP& P = pick(grp, bid, nblk);
+    const DropCfg drop = bpm_resolve_drop(P.drop, grp.seedp);
+    const int c = (bid % P.cblk) * NT + threadIdx.x;
+    const int r0 = (bid / P.cblk) * CAST_ROWS;
+    const int r1 = min(P.R, r0 + CAST_ROWS);
+    const int cmax = P.dct ? P.ctw : P.C;
+    if (c >= cmax) return;
+    float s = 0.f;
+    for (int r = r0; r < r1; ++r) {
+        float v = 0.f;
+        if (c < P.C) {
+            v = P.a_is_ct ? Tr<CT>::to_f(((const CT*)P.a)[(size_t)r * P.lda + c]) : ((const float*)P.a)[(size_t)r * P.lda + c];
+            if (P.b) v += P.b[(size_t)r * P.ldb + c];
+            v *= bpm_drop_mult(drop, (uint32_t)r * (uint32_t)P.C + (uint32_t)c);
+            if (P.df32) P.df32[(size_t)r * P.ldf + c] = v;
+            s += v;
+        }
+        if (P.dct) put<CT>(P.dct, (size_t)r * P.ldd + c, v);
+    }
+    if (P.colsum && c < P.C) cast_part_row(grp, cp, bid / P.cblk)[c] = s;
+}
+
+// (the default kernel keeps its own copy of the body, so that it compiles to the instructions it always did)
 template <typename CT>
 __global__ __launch_bounds__(NT) void rows_cast_kernel(const Grp<CastP> grp) {
     unsigned bid = blockIdx.x, nblk;
@@ -43,10 +82,49 @@ __global__ __launch_bounds__(NT) void rows_cast_kernel(const Grp<CastP> grp) {
     if (P.colsum && c < P.C) atomicAdd(P.colsum + c, s);
 }
 
+
 // Column sums only (bias gradients from a gradient matrix already in HBM): 4-column vector loads, several rows
 // per pass and four passes in flight per thread, LDS reduction, one atomic per column and workgroup.
 constexpr int CSUM_ROWS = 128;
 
+// colsum_kernel (below) storing its column sums as partial rows: a copy of its body, expression for expression
+template <typename CT>
+__global__ __launch_bounds__(NT) void colsum_part_kernel(const Grp<CastP> grp, const CastPart cp) {
+    __shared__ float red[NT * 4];
+    unsigned bid = blockIdx.x, nblk;
+    const CastP& P = pick(grp, bid, nblk);
+    const int CH = (P.C + 3) >> 2;                  // 4-column chunks per row (host: CH <= NT, rows padded to 4*CH)
+    const int rpp = NT / CH;                        // rows per pass
+    const int rr = threadIdx.x / CH, ch = threadIdx.x - rr * CH;
+    const int r0 = bid * CSUM_ROWS, r1 = min(P.R, r0 + CSUM_ROWS);
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (rr < rpp) {
+        auto ld = [&](int r) -> f32x4 {
+            const int rc = r < r1 ? r : r0;         // clamped, unconditional load; zeroed below
+            f32x4 v;
+            if (P.a_is_ct && sizeof(CT) == 2) {
+                const bf16x4 t = *(const bf16x4*)((const bf16_t*)P.a + (size_t)rc * P.lda + 4 * ch);
+                v = f32x4{(float)t[0], (float)t[1], (float)t[2], (float)t[3]};
+            } else {
+                v = *(const f32x4*)((const float*)P.a + (size_t)rc * P.lda + 4 * ch);
+            }
+            return r < r1 ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+        };
+        for (int r = r0 + rr; r < r1; r += 4 * rpp) {
+            const f32x4 a0 = ld(r), a1 = ld(r + rpp), a2 = ld(r + 2 * rpp), a3 = ld(r + 3 * rpp);
+            acc += (a0 + a1) + (a2 + a3);
+        }
+    }
+    *(f32x4*)(red + 4 * threadIdx.x) = acc;
+    __syncthreads();
+    for (int c = threadIdx.x; c < P.C; c += NT) {
+        float sum = 0.f;
+        for (int q = 0; q < rpp; ++q) sum += red[4 * (q * CH) + c];
+        cast_part_row(grp, cp, bid)[c] = sum;
+    }
+}
+
+// (as rows_cast_kernel: its own copy of the body)
 template <typename CT>
 __global__ __launch_bounds__(NT) void colsum_kernel(const Grp<CastP> grp) {
     __shared__ float red[NT * 4];
@@ -82,6 +160,7 @@ __global__ __launch_bounds__(NT) void colsum_kernel(const Grp<CastP> grp) {
         atomicAdd(P.colsum + c, sum);
     }
 }
+
 }  // namespace
 
 // Column sums only, of aligned matrices, in every problem: the vectorised reduction kernel (else rows_cast_kernel)
@@ -97,7 +176,8 @@ static bool choose_colsum(int dtype, const bpm_cast_problem* q, int n) {
     return only_sums;
 }
 
-extern "C" int bpm_rows_cast(int dtype, const bpm_cast_problem* q, int n, uint64_t seed, void* stream) {
+// part: null (bpm_rows_cast: column sums by float atomics) or the workspace of bpm_rows_cast_ws
+static int rows_cast_entry(int dtype, const bpm_cast_problem* q, int n, uint64_t seed, float* part, size_t part_bytes, void* stream) {
     Grp<CastP> g;
     if (!grp_begin(g, q, n, seed)) return BPM_ERR_ARG;
     for (int i = 0; i < n; ++i) {
@@ -118,10 +198,53 @@ extern "C" int bpm_rows_cast(int dtype, const bpm_cast_problem* q, int n, uint64
     for (int i = 0; i < n; ++i)
         g.blk0[i + 1] = g.blk0[i] + (colsum ? (unsigned)((q[i].R + CSUM_ROWS - 1) / CSUM_ROWS)
                                             : (unsigned)g.p[i].cblk * ((q[i].R + CAST_ROWS - 1) / CAST_ROWS));
+    if (part) {
+        // row blocks of each problem (a block of rows_cast_kernel is one of its cblk column blocks), the widest problem
+        CastPart cp;
+        unsigned rb0[BPM_MAX_GROUP + 1] = {0};
+        bool any = false;
+        cp.part = part; cp.ncol = 0;
+        for (int i = 0; i < n; ++i) {
+            const unsigned rb = (unsigned)((q[i].R + (colsum ? CSUM_ROWS : CAST_ROWS) - 1) / (colsum ? CSUM_ROWS : CAST_ROWS));
+            cp.rb0[i] = rb0[i];
+            rb0[i + 1] = rb0[i] + rb;
+            if (q[i].colsum) { any = true; if (q[i].C > cp.ncol) cp.ncol = q[i].C; }
+        }
+        if (any) {
+            if (((uintptr_t)part & 15) || part_bytes < (size_t)rb0[n] * FIN_ARR * cp.ncol * sizeof(float)) return BPM_ERR_ARG;
+            ColFin f;
+            fin_begin(f, n, cp.ncol, rb0);
+            for (int i = 0; i < n; ++i) { f.cols[i] = q[i].C; fin_add(f, i, 0, q[i].colsum); }
+            const int rc = with_ct(dtype, [&](auto ct) {
+                using CT = decltype(ct);
+                return colsum ? launch<colsum_part_kernel<CT>>(g.blk0[n], NT, stream, g, cp) : launch<rows_cast_part_kernel<CT>>(g.blk0[n], NT, stream, g, cp);
+            });
+            return rc ? rc : launch<col_finish_kernel<FIN_ARR>>((unsigned)f.nown, NT, stream, f, (const float*)part);
+        }
+    }
     return with_ct(dtype, [&](auto ct) {
         using CT = decltype(ct);
         return colsum ? launch<colsum_kernel<CT>>(g.blk0[n], NT, stream, g) : launch<rows_cast_kernel<CT>>(g.blk0[n], NT, stream, g);
     });
+}
+
+extern "C" int bpm_rows_cast(int dtype, const bpm_cast_problem* q, int n, uint64_t seed, void* stream) {
+    return rows_cast_entry(dtype, q, n, seed, nullptr, 0, stream);
+}
+
+extern "C" size_t bpm_rows_cast_ws_bytes(const bpm_cast_problem* q, int n) {
+    if (!q || n < 1 || n > BPM_MAX_GROUP) return 0;
+    size_t rb = 0, ncol = 0;
+    for (int i = 0; i < n; ++i) {
+        rb += (size_t)((q[i].R > 0 ? q[i].R : 0) + CAST_ROWS - 1) / CAST_ROWS;          // the finer of the two kernels' row blocks
+        if (q[i].colsum && q[i].C > 0 && (size_t)q[i].C > ncol) ncol = q[i].C;
+    }
+    return (rb * FIN_ARR * ncol + 4) * sizeof(float);
+}
+
+extern "C" int bpm_rows_cast_ws(int dtype, const bpm_cast_problem* q, int n, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    if (!ws) return BPM_ERR_ARG;
+    return rows_cast_entry(dtype, q, n, seed, (float*)ws, ws_bytes, stream);
 }
 
 namespace {

@@ -164,6 +164,87 @@ __global__ __launch_bounds__(NT) void ln_fwd_kernel(const Grp<LnP> grp, int d, f
 // dx = add + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma
 // dgamma += sum_rows dy * xhat,  dbeta += sum_rows dy   (atomics, one per column per block)
 // optional: cast[row, c] = CT(dx * dropout_mult(row*d + c)) (pad columns zeroed), csum += its column sums
+// ln_bwd_kernel (below) with the atomics replaced by plain stores of the block's three partial rows, part[(block * 3 + a)
+// * d .. + d) (a: dgamma, dbeta, cast sums), for col_finish_kernel (bpm_ln_bwd_det).  A copy of that kernel's body, kept
+// expression for expression so that dx and the cast output are the same bits; the default kernel is left as it was, so
+// that it compiles to the instructions it always did.
+template <typename CT, int NE>
+__global__ __launch_bounds__(NT) void ln_bwd_part_kernel(const Grp<LnP> grp, int d, float* part) {
+    __shared__ float red[3][NT / 64][512];   // 512 columns per pass
+    unsigned bid = blockIdx.x, nblk;
+    const LnP& P = pick(grp, bid, nblk);
+    const DropCfg drop = bpm_resolve_drop(P.drop, grp.seedp);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int wpb = NT / 64;
+    const bool fused = P.cast != nullptr;          // uniform per block
+    float ag[NE], ab[NE], ac[NE];
+#pragma unroll
+    for (int e = 0; e < NE; ++e) { ag[e] = 0.f; ab[e] = 0.f; ac[e] = 0.f; }
+    for (int row = bid * wpb + wv; row < P.R; row += nblk * wpb) {
+        const float mu = P.mean[row], rs = P.rstd[row];
+        const float* xr = P.x + (size_t)row * d;
+        const float* gr = P.dy + (size_t)row * P.ldy;
+        float xh[NE], gg[NE], av[NE];
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int c = lane + 64 * e;
+            if (c < d) {
+                const float dyv = gr[c];
+                av[e] = P.add ? P.add[(size_t)row * d + c] : 0.f;
+                xh[e] = (xr[c] - mu) * rs;
+                gg[e] = dyv * P.gamma[c];
+                ag[e] += dyv * xh[e];
+                ab[e] += dyv;
+                s1 += gg[e];
+                s2 += gg[e] * xh[e];
+            } else { xh[e] = 0.f; gg[e] = 0.f; av[e] = 0.f; }
+        }
+        s1 = wave_sum(s1) / d;
+        s2 = wave_sum(s2) / d;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const int c = lane + 64 * e;
+            if (c < d) {
+                const float v = av[e] + rs * (gg[e] - s1 - xh[e] * s2);
+                P.dx[(size_t)row * d + c] = v;
+                if (fused) {
+                    const float m = v * bpm_drop_mult(drop, (uint32_t)row * (uint32_t)d + (uint32_t)c);
+                    put<CT>(P.cast, (size_t)row * P.ldc + c, m);
+                    ac[e] += m;
+                }
+            } else if (fused && c < P.ldc) {
+                put<CT>(P.cast, (size_t)row * P.ldc + c, 0.f);
+            }
+        }
+    }
+    const bool want_g = P.dgamma != nullptr, want_c = fused && P.csum != nullptr;
+    if (!want_g && !want_c) return;     // uniform per block
+#pragma unroll
+    for (int e0 = 0; e0 < NE; e0 += 8) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const bool in = e0 + e < NE;
+            const int ei = in ? e0 + e : 0;
+            red[0][wv][lane + 64 * e] = in ? ag[ei] : 0.f;
+            red[1][wv][lane + 64 * e] = in ? ab[ei] : 0.f;
+            red[2][wv][lane + 64 * e] = in ? ac[ei] : 0.f;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 512; i += NT) {
+            const int c = e0 * 64 + i;
+            if (c < d) {
+                float sg = 0.f, sb = 0.f, sc = 0.f;
+#pragma unroll
+                for (int w = 0; w < NT / 64; ++w) { sg += red[0][w][i]; sb += red[1][w][i]; sc += red[2][w][i]; }
+                float* row = part + (size_t)blockIdx.x * 3 * d + c;
+                row[0] = sg; row[d] = sb; row[2 * d] = sc;
+            }
+        }
+    }
+}
+
 template <typename CT, int NE>
 __global__ __launch_bounds__(NT) void ln_bwd_kernel(const Grp<LnP> grp, int d) {
     __shared__ float red[3][NT / 64][512];   // 512 columns per pass
@@ -240,6 +321,7 @@ __global__ __launch_bounds__(NT) void ln_bwd_kernel(const Grp<LnP> grp, int d) {
         }
     }
 }
+
 
 // ---------------------------------------------------------------------------
 // Vector forms (d % 4 == 0, 16-byte aligned rows): a lane owns 4-column chunks lane, lane+64, ... (NV of them),
@@ -576,12 +658,38 @@ static int choose_ln_bwd(const bpm_ln_problem* q, int n, int d, int ct_size, voi
     return 0;
 }
 
-extern "C" int bpm_ln_bwd_ws(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+// strict (bpm_ln_bwd_det): a launch whose column sums would go out as float atomics is refused
+static int ln_bwd_entry(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, bool strict,
+                        void* stream) {
     if (dtype != BPM_F32 && dtype != BPM_BF16) return BPM_ERR_ARG;
     Grp<LnP> g;
     if (const int rc = fill_ln(g, q, n, d, true, seed)) return rc;
     LnChoice c;
     if (const int rc = choose_ln_bwd(q, n, d, dtype == BPM_BF16 ? 2 : 4, ws, ws_bytes, c)) return rc;
+    bool sums = false;
+    for (int i = 0; i < n; ++i) sums = sums || q[i].dgamma || (q[i].cast && q[i].cast_colsum);
+    if (strict && sums && !c.ws) {
+        // what bpm_ln_bwd_ws sends to float atomics -- the scalar family (d % 4 != 0, d > 1024), a misaligned row, problems
+        // that share a gradient row: the scalar kernel with partial rows, then col_finish_kernel (problem order, block order)
+        c = LnChoice{false, d, 4, 256, nullptr};
+        ln_blocks(g, c);
+        if (!ws || ((uintptr_t)ws & 15) || ws_bytes < ((size_t)g.blk0[n] * 3 * d + LN_WS_HEAD) * sizeof(float)) return BPM_ERR_ARG;
+        float* part = (float*)ws + LN_WS_HEAD;
+        ColFin f;
+        fin_begin(f, n, d, g.blk0);
+        for (int i = 0; i < n; ++i) {
+            fin_add(f, i, 0, q[i].dgamma);
+            fin_add(f, i, 1, q[i].dbeta);
+            fin_add(f, i, 2, q[i].cast ? q[i].cast_colsum : nullptr);
+        }
+        const int rc = with_ct(dtype, [&](auto ct) {
+            using CT = decltype(ct);
+            return with_width(RowWidths(), c.span, [&](auto w) {
+                return launch<ln_bwd_part_kernel<CT, decltype(w)::value>>(g.blk0[n], NT, stream, g, d, part);
+            });
+        });
+        return rc ? rc : launch<col_finish_kernel<FIN_ARR>>((unsigned)f.nown, NT, stream, f, (const float*)part);
+    }
     ln_blocks(g, c);
     return with_ct(dtype, [&](auto ct) {
         using CT = decltype(ct);
@@ -592,6 +700,19 @@ extern "C" int bpm_ln_bwd_ws(int dtype, const bpm_ln_problem* q, int n, int d, u
             return launch<ln_bwd_kernel<CT, decltype(w)::value>>(g.blk0[n], NT, stream, g, d);
         });
     });
+}
+
+extern "C" int bpm_ln_bwd_ws(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    return ln_bwd_entry(dtype, q, n, d, seed, ws, ws_bytes, false, stream);
+}
+
+// what either route of bpm_ln_bwd_det needs at most: 256 blocks per problem (the scalar kernel's cap), three rows each
+extern "C" size_t bpm_ln_bwd_det_ws_bytes(int n, int d) {
+    return ((size_t)(n > 0 ? n : 0) * 256 * 3 * (size_t)(d > 0 ? d : 0) + LN_WS_HEAD) * sizeof(float);
+}
+
+extern "C" int bpm_ln_bwd_det(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    return ln_bwd_entry(dtype, q, n, d, seed, ws, ws_bytes, true, stream);
 }
 
 extern "C" int bpm_ln_bwd(int dtype, const bpm_ln_problem* q, int n, int d, uint64_t seed, void* stream) {

@@ -182,8 +182,10 @@ BPM_DEV bool unf_wide(const bpm_unfold_desc& d) {
     return ((d.cols | d.ldw) & 3) == 0 && (a & 15) == 0;
 }
 
-template <bool STORE>
-BPM_DEV void unfold_wide(const bpm_unfold_desc& d, int r0, int r1, float* sums) {
+// PART (bpm_unfold_grads_ws): the block's column sums go to its partial rows part[0 .. cols) (dgamma) and
+// part[pstride .. pstride + cols) (dbeta), 16 bytes per lane write-through, instead of LDS and the float atomics
+template <bool STORE, bool PART = false>
+BPM_DEV void unfold_wide(const bpm_unfold_desc& d, int r0, int r1, float* sums, float* part = nullptr, int pstride = 0) {
     const int tid = threadIdx.x;
     for (int c0 = 0; c0 < d.cols; c0 += 4 * NT) {         // (block-uniform trip count: the barriers below)
         const int c = c0 + 4 * tid;
@@ -217,14 +219,37 @@ BPM_DEV void unfold_wide(const bpm_unfold_desc& d, int r0, int r1, float* sums) 
                 }
             }
         }
-        *(f32x4*)(sums + 4 * tid) = ag;
-        *(f32x4*)(sums + 4 * NT + 4 * tid) = ab;
-        __syncthreads();
-        for (int k = tid; k < 4 * NT && c0 + k < d.cols; k += NT) {
-            atomicAdd(d.dgamma + c0 + k, sums[k]);
-            atomicAdd(d.dbeta + c0 + k, sums[4 * NT + k]);
+        if constexpr (PART) {
+            if (c < d.cols) {                                 // (cols % 4 == 0: the thread's four columns are all live)
+                const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)part, 0, 2 * pstride * 4, 0x00020000);
+                __builtin_amdgcn_raw_buffer_store_b128((u32x4&)ag, rw, c * 4, 0, 16);
+                __builtin_amdgcn_raw_buffer_store_b128((u32x4&)ab, rw, (pstride + c) * 4, 0, 16);
+            }
+        } else {
+            *(f32x4*)(sums + 4 * tid) = ag;
+            *(f32x4*)(sums + 4 * NT + 4 * tid) = ab;
+            __syncthreads();
+            for (int k = tid; k < 4 * NT && c0 + k < d.cols; k += NT) {
+                atomicAdd(d.dgamma + c0 + k, sums[k]);
+                atomicAdd(d.dbeta + c0 + k, sums[4 * NT + k]);
+            }
+            __syncthreads();
         }
-        __syncthreads();
+    }
+}
+
+// one column of unfold_grads_kernel's one-column loop, expression for expression (the same dW and partial sums), for
+// unfold_grads_ws_kernel: dW's update over the block's rows, the two column sums returned
+BPM_DEV void unfold_column(const bpm_unfold_desc& d, int r0, int r1, int c, int store_dw, float& ag, float& ab) {
+    const float g = d.gamma[c], bt = d.beta[c];
+    ag = 0.f; ab = 0.f;
+    for (int r = r0; r < r1; ++r) {
+        const float f = d.dWf[(size_t)r * d.cols + c], w = d.W[(size_t)r * d.ldw + c], db = d.dbf[r];
+        const float v = unf_dw(f, g, db, bt);
+        float* o = d.dW + (size_t)r * d.ldw + c;
+        *o = store_dw ? v : *o + v;                   // store_dw: this launch is the first writer of dW this step
+        ag = fmaf(f, w, ag);
+        ab = fmaf(db, w, ab);
     }
 }
 
@@ -251,11 +276,92 @@ __global__ __launch_bounds__(NT) void unfold_grads_kernel(const bpm_unfold_desc*
     }
     if ((int)threadIdx.x < r1 - r0) d.dbias[r0 + threadIdx.x] += d.dbf[r0 + threadIdx.x];
 }
+
+// The same launch without float atomics (bpm_unfold_grads_ws): dW and dbias as above, bit for bit; the column sums of a
+// block go to its two partial rows in the workspace, and the block of a descriptor that draws the last ticket adds the
+// partial rows in block order and makes one plain read-modify-write into dgamma / dbeta -- one owner per column, a
+// fixed order, and nothing that depends on the other descriptors of the launch.  Hand-off as in ln_bwd_vec_kernel
+// (rows_norm.hip): partial rows stored write-through, every wave's stores drained, workgroup barrier, ticket by one lane
+// (agent scope); the last block acquires and reads with plain vector loads.  The ticket words are zeroed by the entry
+// ahead of every launch.  ws: UNF_WS_HEAD-padded ticket words (one per descriptor), then 2 * pstride floats per block.
+constexpr int UNF_WS_HEAD = 64;
+inline size_t unf_ws_head(int ndesc) { return ((size_t)ndesc + UNF_WS_HEAD - 1) / UNF_WS_HEAD * UNF_WS_HEAD; }
+
+__global__ __launch_bounds__(NT) void unfold_grads_ws_kernel(const bpm_unfold_desc* __restrict__ tab, int ndesc, int store_dw,
+                                                              unsigned* cnt, float* rows, int pstride) {
+    int di = 0, hi = ndesc - 1;
+    while (di < hi) {                                     // find_desc, keeping the index: the descriptor's ticket word
+        const int mid = (di + hi + 1) >> 1;
+        if (tab[mid].blk0 <= blockIdx.x) di = mid; else hi = mid - 1;
+    }
+    const bpm_unfold_desc d = tab[di];
+    const unsigned nblk = (unsigned)(d.rows + UNF_ROWS - 1) / UNF_ROWS;
+    const int r0 = (int)(blockIdx.x - d.blk0) * UNF_ROWS, r1 = min(d.rows, r0 + UNF_ROWS);
+    // host contract, checked so that nothing is ever read or written past the workspace: a partial row holds the
+    // descriptor's columns, its nblk blocks lie inside the grid, and a block beyond them draws no ticket
+    if (d.cols > pstride || d.blk0 + nblk > gridDim.x || r0 >= d.rows) return;
+    float* part = rows + (size_t)blockIdx.x * 2 * pstride;
+    // 16-byte partial rows: pstride % 4 == 0 and rows 16-byte aligned (entry), so the wide path's stores are aligned
+    const bool wide = unf_wide(d);
+    if (wide) {
+        if (store_dw) unfold_wide<true, true>(d, r0, r1, nullptr, part, pstride);
+        else unfold_wide<false, true>(d, r0, r1, nullptr, part, pstride);
+    } else for (int c = threadIdx.x; c < d.cols; c += NT) {
+        float ag, ab;
+        unfold_column(d, r0, r1, c, store_dw, ag, ab);
+        __hip_atomic_store(part + c, ag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(part + pstride + c, ab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if ((int)threadIdx.x < r1 - r0) d.dbias[r0 + threadIdx.x] += d.dbf[r0 + threadIdx.x];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    __shared__ int s_last;
+    if (threadIdx.x == 0) {
+        const unsigned ticket = __hip_atomic_fetch_add(cnt + di, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = ticket == nblk - 1;
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!s_last) return;
+    const float* first = rows + (size_t)d.blk0 * 2 * pstride;
+    for (int c = threadIdx.x; c < d.cols; c += NT) {      // block order, one column per thread: the same sum on both paths
+        float sg = 0.f, sb = 0.f;
+#pragma unroll 8
+        for (unsigned b = 0; b < nblk; ++b) {
+            sg += gload1(first + (size_t)b * 2 * pstride + c);
+            sb += gload1(first + (size_t)b * 2 * pstride + pstride + c);
+        }
+        d.dgamma[c] += sg;
+        d.dbeta[c] += sb;
+    }
+}
 }  // namespace
 
 extern "C" int bpm_unfold_grads(const bpm_unfold_desc* table_dev, int ndesc, unsigned total_blocks, int store_dw, void* stream) {
     if (!table_dev || ndesc < 1 || total_blocks < 1) return BPM_ERR_ARG;
     return launch<unfold_grads_kernel>(total_blocks, NT, stream, table_dev, ndesc, store_dw);
+}
+
+extern "C" size_t bpm_unfold_grads_ws_bytes(int ndesc, unsigned total_blocks, int max_cols) {
+    if (ndesc < 1 || max_cols < 1) return 0;
+    const size_t pstride = ((size_t)max_cols + 3) / 4 * 4;
+    return (unf_ws_head(ndesc) + (size_t)total_blocks * 2 * pstride) * sizeof(float);
+}
+
+extern "C" int bpm_unfold_grads_ws(const bpm_unfold_desc* table_dev, int ndesc, unsigned total_blocks, int store_dw, int max_cols,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    if (!table_dev || ndesc < 1 || total_blocks < 1 || max_cols < 1 || !ws) return BPM_ERR_ARG;
+    if (((uintptr_t)ws & 15) || ws_bytes < bpm_unfold_grads_ws_bytes(ndesc, total_blocks, max_cols)) return BPM_ERR_ARG;
+    const size_t head = unf_ws_head(ndesc);
+#ifdef BPM_LAB
+    if (!g_bpm_rows_dry)          // (the dry mode of the lab build touches no device)
+#endif
+    if (const hipError_t e = hipMemsetAsync(ws, 0, head * sizeof(float), (hipStream_t)stream); e != hipSuccess) return (int)e;
+    return launch<unfold_grads_ws_kernel>(total_blocks, NT, stream, table_dev, ndesc, store_dw, (unsigned*)ws, (float*)ws + head,
+                                          (max_cols + 3) / 4 * 4);
 }
 
 namespace {

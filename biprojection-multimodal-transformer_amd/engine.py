@@ -622,8 +622,14 @@ class EncoderGroupPlan:
     layer to that layer's launch lists; _build_fwd / _build_bwd wire their operands and order the launches per kind."""
 
     def __init__(self, store: ParamStore, cfg: GroupCfg, encs: Sequence[EncoderDesc], B: int, x3: "Optional[ops.X3Cache]" = None,
-                 masks: "Optional[Sequence[Optional[EncoderMasks]]]" = None):
+                 masks: "Optional[Sequence[Optional[EncoderMasks]]]" = None, deterministic: Optional[bool] = None):
         self.store, self.cfg, self.encs, self.B = store, cfg, list(encs), B
+        # DETERMINISTIC MODE (None: config.deterministic(), read HERE, where the tables are built -- a captured graph
+        # carries the mode it was captured in).  The backward tables then hold no launch that adds floats in hardware
+        # order (DESIGN.md, "Deterministic mode"): fc1.bias / fc2.bias / out_proj.bias ride on their weight-gradient
+        # products (_bias_route), unfold_grads and the LayerNorm backward go through their workspace entries.
+        from . import config
+        self.det = config.resolve_deterministic(deterministic)
         # PADDING MASKS (masks[e]: which key masks encoder e's forward calls carry; None / all-False everywhere: an unmasked
         # plan, whose tables are what they always were).  A masked plan runs EVERY attention step through the *_kmask
         # entries, one mask per problem: the plan owns one visibility buffer per encoder and attention block (_alloc: vis_s
@@ -741,6 +747,14 @@ class EncoderGroupPlan:
         self._bwd = {(t, f): self._build_bwd(t, f) for t in (True, False) for f in (True, False)}
         for steps in (*self._fwd.values(), *self._bwd.values()):
             self._check_steps(steps)
+        if self.det:                      # no backward step of a deterministic plan may reach an entry that adds with atomics
+            for steps in self._bwd.values():
+                for s in steps:
+                    s = s[1] if s is not JOIN and s[0] in (SIDE, SIDE2) else s
+                    if s is not JOIN and s[0] is ops.ln_bwd and not getattr(s[1], "det", False):
+                        raise ValueError("launch table: a LayerNorm-backward step of a deterministic plan is not marked (ops.ln_det)")
+                    if s is not JOIN and s[0] is ops.unfold_grads:
+                        raise ValueError("launch table: unfold_grads (float atomics) in a deterministic plan")
 
     def _alloc(self, e: EncoderDesc) -> dict:
         """Buffers of one encoder: the query chain and FFN of every kind, the self-attention block's (self-only and
@@ -880,6 +894,12 @@ class EncoderGroupPlan:
         """Layer i runs on rows {0, T-1} only (EncoderDesc.tail_rows, last layer)."""
         return b["tailp"] and i == self.cfg.layers - 1
 
+    def _bias_route(self, gptr):
+        """Where a linear layer's bias gradient (a device address) is summed: (on the epilogue / row kernel that has the
+        fp32 values -- float atomics or the LayerNorm workspace, the default --, as colsum_a of the layer's weight-gradient
+        product -- deterministic mode: one owner per column, k ascending, over the values as stored in CT).  One is None."""
+        return (None, gptr) if self.det else (gptr, None)
+
     # -- per-block problem builders -------------------------------------------------
     # Each appends encoder e's problems of layer i to the layer's launch lists t[name] (one launch per name, problems in
     # encoder order).  The caller passes what differs between the layer kinds: inputs, residuals, first-writer flags, drop
@@ -902,7 +922,8 @@ class EncoderGroupPlan:
         into dxs, in a tail_rows last layer) into the dense dx the layers below continue from.  Hand-off to the next layer
         down (i-1): its FFN-output gradient dyf = dropmask(dx) and fc2.bias gradient are fused into this launch."""
         st, c, d = self.store, self.cfg, self.cfg.d
-        nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=self.ld, cast_colsum=st.gptr(self._pn(e, i - 1, "fc2.bias")),
+        nxt = {} if i == 0 else dict(cast=b["dyf"][(i - 1) % 3], ldc=self.ld,
+                                     cast_colsum=self._bias_route(st.gptr(self._pn(e, i - 1, "fc2.bias")))[0],
                                      drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i - 1, S_RES2))
         t["ln0"].append(ops.ln_problem(b["x"][i], st.p(self._pn(e, i, "layer_norms.0.weight")), None, b["st0m"][i], b["st0r"][i],
                                        b["R"], dy=b["dxn"], ldy=d, add=b["dxs"] if self._tail(b, i) else b["dx"], dx=b["dx"],
@@ -948,11 +969,12 @@ class EncoderGroupPlan:
         tail = self._tail(b, i)
         xn = b["xn"][i]
         xq_in = b["xng"] if tail else xn
+        ob_sum, ob_ride = self._bias_route(GP("self_attn.out_proj.bias"))
         if cast is not None:
-            t["s.cast"].append(ops.cast_problem(cast[0], d, Rq, d, dst_ct=dy, ldd=ld, colsum=GP("self_attn.out_proj.bias"),
+            t["s.cast"].append(ops.cast_problem(cast[0], d, Rq, d, dst_ct=dy, ldd=ld, colsum=ob_sum,
                                                 drop_p=pr(c.res_dropout), drop_site=site(e.enc_id, i, cast[1])))
         t["s.acts"] += [o, xq_in, xn]
-        t["s.wg"].append(ops.gemm_problem(dy, o, GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=first))
+        t["s.wg"].append(ops.gemm_problem(dy, o, GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=first, colsum_a=ob_ride))
         t["s.dgout"].append(ops.gemm_problem(dy, st.sptr(wo), dao, Rq, d, d, ld, ld, 0, out_kind=OUT_HEADS,
                                              heads=(B, H, Tq, self.dh, self.dhp)))
         t["s.att"].append(ops.attn_problem(q, kk, v, o, ld, lse, B, H, Tq, e.T, self.dh, self.dhp, self._mask_off(e.T, e.T),
@@ -1024,7 +1046,8 @@ class EncoderGroupPlan:
         t["c.acts"] += [b["ao"][i], q_src] + ([] if lr else [b["khat"], b["vhat"]])
         # (the first writer of out_proj.weight / in_proj_weight rows [0, d) on the side stream; a biprojection
         # self-attention block below comes second and accumulates)
-        t["c.wg"].append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=acc1))
+        t["c.wg"].append(ops.gemm_problem(dy, b["ao"][i], GP("self_attn.out_proj.weight"), d, d, Rq, ld, ld, d, flags=acc1,
+                                          colsum_a=self._bias_route(GP("self_attn.out_proj.bias"))[1]))
         t["c.dgout"].append(ops.gemm_problem(dy, st.sptr(self._pn(e, i, "self_attn.out_proj.weight")), dao, Rq, d, d, ld, ld, 0,
                                              out_kind=OUT_HEADS, heads=(B, H, Tq, self.dh, self.dhp)))
         lrx = {}
@@ -1086,16 +1109,18 @@ class EncoderGroupPlan:
         inv_relu = 1.0 / (1.0 - pr(c.relu_dropout))
         t["f.grads"] += [dyf, dh1]
         t["f.acts"] += [b["h1"][i], b["xn2"][i]]
-        t["f.wg"].append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, Rq, ld, ld4, 4 * d, flags=acc1))
+        b1_sum, b1_ride = self._bias_route(GP("fc1.bias"))
+        t["f.wg"].append(ops.gemm_problem(dyf, b["h1"][i], GP("fc2.weight"), d, 4 * d, Rq, ld, ld4, 4 * d, flags=acc1,
+                                          colsum_a=self._bias_route(GP("fc2.bias"))[1]))
         t["f.dg2"].append(ops.gemm_problem(dyf, st.sptr(self._pn(e, i, "fc2.weight")), dh1, Rq, 4 * d, d, ld, ld4, ld4,
-                                           gate=b["h1"][i], ldg=ld4, gate_scale=inv_relu, colsum=GP("fc1.bias"), out_kind=OUT_CT))
-        t["f.wg"].append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, Rq, ld4, ld, d, flags=acc1))
+                                           gate=b["h1"][i], ldg=ld4, gate_scale=inv_relu, colsum=b1_sum, out_kind=OUT_CT))
+        t["f.wg"].append(ops.gemm_problem(dh1, b["xn2"][i], GP("fc1.weight"), 4 * d, d, Rq, ld4, ld, d, flags=acc1, colsum_a=b1_ride))
         t["f.dg1"].append(ops.gemm_problem(dh1, st.sptr(self._pn(e, i, "fc1.weight")), b["dxn"], Rq, d, 4 * d, ld4, ld, d))
         lnF = self._lnF
         t["f.ln"].append(ops.ln_problem(b["xmid"][i], st.p(self._pn(e, i, f"layer_norms.{lnF}.weight")), None, stats[0], stats[1], Rq,
                                         dy=b["dxn"], ldy=d, add=dx, dx=dx, dgamma=GP(f"layer_norms.{lnF}.weight"),
                                         dbeta=GP(f"layer_norms.{lnF}.bias"), cast=dy, ldc=ld,
-                                        cast_colsum=GP("self_attn.out_proj.bias"), drop_p=pr(c.res_dropout),
+                                        cast_colsum=self._bias_route(GP("self_attn.out_proj.bias"))[0], drop_p=pr(c.res_dropout),
                                         drop_site=site(e.enc_id, i, S_RES1)))
 
     # -- forward tables ---------------------------------------------------------
@@ -1386,7 +1411,7 @@ class EncoderGroupPlan:
         pr = (lambda p: p) if training else (lambda p: 0.0)
         nn = lambda probs: self._gemm(GEMM_NN, probs)
         wg = lambda probs, presplit: (SIDE, self._gemm(GEMM_TN, probs, background=True, presplit=presplit))
-        ln = lambda probs: (ops.ln_bwd, A(LnProblem, probs), d, self.dtype)
+        ln = lambda probs: (ops.ln_bwd, ops.ln_det(A(LnProblem, probs)) if self.det else A(LnProblem, probs), d, self.dtype)
         x3, lr = st.x3, self._lowrank
         steps = []
         for i in reversed(range(c.layers)):
@@ -1463,7 +1488,9 @@ class EncoderGroupPlan:
                 steps += [(SIDE, (ops.expand_heads, self.dtype, A(ExpandProblem, t["c.expand"]))), (SIDE, nn(t["c.lrqk"])), wg_att]
             # folded K/V gradients of this layer -> in_proj / LayerNorm parameter gradients; with it every gradient of
             # layer i is final once the side stream reaches MARK i and the main stream this point (all-reduce hook)
-            steps += [(SIDE, (ops.unfold_grads,) + self._unfold[i] + (stores and not c.biprojection,)), (MARK, i)]
+            store_dw = stores and not c.biprojection
+            unfold = (ops.unfold_grads_ws,) + self._unfold[i] + (d, store_dw) if self.det else (ops.unfold_grads,) + self._unfold[i] + (store_dw,)
+            steps += [(SIDE, unfold), (MARK, i)]
         if not self._kv:
             return steps + [JOIN]
         # d(khat), d(vhat): all layers' dK / dV against the stacked projection weights, one product over K = L ld per
@@ -1515,10 +1542,11 @@ class EncoderGroupPlan:
             fin.append(ops.ln_problem(b["x"][c.layers], st.p(e.prefix + "layer_norm.weight"), None, b["stf"][0], b["stf"][1], b["Rl"][-1],
                                       dy=g, ldy=d, dx=dx_top, dgamma=st.gptr(e.prefix + "layer_norm.weight"),
                                       dbeta=st.gptr(e.prefix + "layer_norm.bias"),
-                                      cast=b["dyf"][top % 3], ldc=self.ld, cast_colsum=st.gptr(self._pn(e, top, "fc2.bias")),
+                                      cast=b["dyf"][top % 3], ldc=self.ld,
+                                      cast_colsum=self._bias_route(st.gptr(self._pn(e, top, "fc2.bias")))[0],
                                       drop_p=c.res_dropout if training else 0.0, drop_site=site(e.enc_id, top, S_RES2)))
         if fin:
-            ops.ln_bwd(fin, d, self.dtype, seed)
+            ops.ln_bwd(fin, d, self.dtype, seed, deterministic=self.det)
         # on_layer(i, events): every parameter gradient of layer i (and, with the first call, of the final LayerNorm)
         # is complete once `events` have passed -- the data-parallel exchange starts there (distributed.GradSync)
         self._run(self._bwd[(training, stores)], seed, on_layer)

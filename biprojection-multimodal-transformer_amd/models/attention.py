@@ -14,6 +14,7 @@ block (engine.py: _proj, _self_attn_fwd / _self_attn_bwd):
                                  the head-averaged weights (need_weights only)
   backward  rows_cast            d(attn) -> CT, column sums = d(out_proj.bias)
             gemm TN / NN         d(out_proj.weight); d(attention output), OUT_HEADS
+                                 (deterministic mode, the `deterministic` attribute: d(out_proj.bias) as this product's colsum_a)
             attn_bwd_dq / _dkv   [_amask | _kmask | _kamask]
             attn_bwd_dbias       d(attn_bias): the score gradient summed over samples (and heads), after the dQ pass;
                                  only when attn_bias requires grad (with the key masks beside a key_padding_mask)
@@ -82,7 +83,8 @@ class _Plan:
 class _Exec:
     """Host driver of one module on one device and precision: CT weight shadows, plans, the mask cache."""
 
-    def __init__(self, mod: "MultiheadAttention", device: torch.device, prec: str):
+    def __init__(self, mod: "MultiheadAttention", device: torch.device, prec: str, det: bool = False):
+        self.det = det       # deterministic mode: d(out_proj.bias) rides on the out_proj weight-gradient product (backward)
         if config.is_x3(prec):
             raise ValueError("MultiheadAttention: precision 'bf16x3' is not available for the stand-alone module (its split "
                              "images belong to an engine plan); use 'bf16' or 'f32'")
@@ -93,7 +95,7 @@ class _Exec:
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
                 raise RuntimeError("MultiheadAttention: parameters must be contiguous float32 tensors on the inputs' device")
-        self.key = (str(device), prec, tuple(p.data_ptr() for p in self.params))
+        self.key = (str(device), prec, tuple(p.data_ptr() for p in self.params), det)
         d, ld = self.d, self.ld
         ct = ops.ct_torch(self.dtype)
         self.shadow = torch.zeros(4 * d * ld, device=device, dtype=ct)        # in_proj_weight [3d, ld] | out_proj.weight [d, ld]
@@ -231,8 +233,11 @@ class _Exec:
         g_ipw, g_wo = torch.empty(3 * d, d, device=dev), torch.empty(d, d, device=dev)       # written by their launches
         g_ipb = torch.zeros(3 * d, device=dev) if has_bias else None                           # accumulated into: zeroed
         g_ob = torch.zeros(d, device=dev) if mod.out_proj.bias is not None else None
-        ops.rows_cast(dt, [ops.cast_problem(dout, d, T * B, d, dst_ct=pl.dy, ldd=ld, colsum=g_ob)], 0)
-        ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy, pl.o, g_wo, d, d, T * B, ld, ld, d, flags=F_KPAD)], seed)
+        # d(out_proj.bias): the column sums of dout by the cast launch (float atomics), or -- deterministic mode -- of dy as
+        # stored, by the weight-gradient product that reads it (colsum_a: one owner per column, k ascending)
+        ops.rows_cast(dt, [ops.cast_problem(dout, d, T * B, d, dst_ct=pl.dy, ldd=ld, colsum=None if self.det else g_ob)], 0)
+        ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy, pl.o, g_wo, d, d, T * B, ld, ld, d, flags=F_KPAD,
+                                                        colsum_a=g_ob if self.det else None)], seed)
         ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy, self.wptr(3), pl.dao, T * B, d, d, ld, ld, 0, out_kind=OUT_HEADS,
                                                         heads=(B, H, T, dh, dhp), flags=F_KPAD)], seed)
         ap = [ops.attn_problem(pl.q, pl.k, pl.v, pl.o, ld, pl.lse, B, H, T, S, dh, dhp, 0, dO=pl.dao, delta=pl.delta, dQ=pl.dq, lddq=ld,
@@ -345,6 +350,7 @@ class MultiheadAttention(nn.Module):
         if bias:
             nn.init.constant_(self.out_proj.bias, 0.0)
         self.precision: Optional[str] = None                  # None -> config.precision() at first use
+        self.deterministic: Optional[bool] = None             # None -> config.deterministic(), read when the driver is built
         self._exec: Optional[_Exec] = None
         self._step = 0
 
@@ -367,8 +373,9 @@ class MultiheadAttention(nn.Module):
         prec = self.precision or config.precision()
         ex = self._exec
         params = [p for p in (self.in_proj_weight, self.in_proj_bias, self.out_proj.weight, self.out_proj.bias) if p is not None]
-        if ex is None or ex.key != (str(device), prec, tuple(p.data_ptr() for p in params)):
-            ex = self._exec = _Exec(self, device, prec)
+        det = config.resolve_deterministic(self.deterministic)
+        if ex is None or ex.key != (str(device), prec, tuple(p.data_ptr() for p in params), det):
+            ex = self._exec = _Exec(self, device, prec, det)
         return ex
 
     def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None, key_padding_mask=None):

@@ -164,6 +164,10 @@ class _Plan:
         ct = ops.ct_torch(st.dtype)
         R, ld, ldI, dhp = L * B, st.ld, st.ldI, st.dhp
         self.B, self.L, self.R = B, L, R
+        # deterministic mode, fixed with the plan: the two dense bias gradients that default mode takes as the LayerNorm
+        # backwards' cast_colsum ride on their weight-gradient products (colsum_a), and the LayerNorm backwards refuse
+        # a launch that would fall back to float atomics (bpm_ln_bwd_det)
+        self.det = config.resolve_deterministic(getattr(st, "deterministic", None))
         z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)
         self.x = [z(R, d) for _ in range(nl + 1)]             # layer inputs; x[nl] is the stack's output
         self.xc = [z(R, ld, dt=ct) for _ in range(nl)]
@@ -210,6 +214,7 @@ class BertLayerStack:
         check_config(cfg)
         self.bert = bert
         self.precision = precision
+        self.deterministic: Optional[bool] = None      # None -> config.deterministic(), read when a plan is built
         # text_params = "flat": the layer parameters are views into this store, which owns the CT shadows (written by the
         # fused optimizer kernel) and the flat gradient buffer the backward launches write into
         self.store = store
@@ -298,11 +303,13 @@ class BertLayerStack:
             self.store.mark_dirty()
 
     def _plan(self, B: int, L: int) -> _Plan:
-        pl = self._plans.get((B, L))
+        det = config.resolve_deterministic(self.deterministic)
+        key = (B, L, "det") if det else (B, L)               # a plan keeps the mode it was built in
+        pl = self._plans.get(key)
         if pl is None:
             if len(self._plans) >= 2:                         # activation sets are large: keep the two most recent shapes
                 self._plans.pop(next(iter(self._plans)))
-            pl = self._plans[(B, L)] = _Plan(self, B, L)
+            pl = self._plans[key] = _Plan(self, B, L)
         return pl
 
     def _P(self, layer: int, name: str) -> torch.Tensor:
@@ -398,16 +405,19 @@ class BertLayerStack:
         G = lambda i, n: grads[i * len(LAYER_PARAMS) + LAYER_PARAMS.index(n)]
         cur = 0
         pl.dx[cur].view(L, B, d).copy_(dout.transpose(0, 1))
+        ln_bwd = lambda probs, *a: ops.ln_bwd(probs, *a, deterministic=pl.det)
+        route = (lambda g: (None, g)) if pl.det else (lambda g: (g, None))      # (cast_colsum, colsum_a) of a dense bias gradient
         for i in reversed(range(self.n_layers)):
             P = lambda n, i=i: self._P(i, n)
             dxo, dxi = pl.dx[cur], pl.dx[cur ^ 1]
             m1, r1, m2, r2 = pl.stats[i]
             # output LayerNorm; its cast output is d(output.dense result) = dropmask(dy2) as CT, column sums = the dense bias gradient
-            ops.ln_bwd([ops.ln_problem(pl.y2[i], P("output.LayerNorm.weight"), None, m2, r2, R, dy=dxo, ldy=d, dx=pl.dy2,
-                                       dgamma=G(i, "output.LayerNorm.weight"), dbeta=G(i, "output.LayerNorm.bias"), cast=pl.dy2c, ldc=ld,
-                                       cast_colsum=G(i, "output.dense.bias"), drop_p=ph, drop_site=bert_site(i, S_FFN_OUT))], d, dt, seed)
+            ob_sum, ob_ride = route(G(i, "output.dense.bias"))
+            ln_bwd([ops.ln_problem(pl.y2[i], P("output.LayerNorm.weight"), None, m2, r2, R, dy=dxo, ldy=d, dx=pl.dy2,
+                                   dgamma=G(i, "output.LayerNorm.weight"), dbeta=G(i, "output.LayerNorm.bias"), cast=pl.dy2c, ldc=ld,
+                                   cast_colsum=ob_sum, drop_p=ph, drop_site=bert_site(i, S_FFN_OUT))], d, dt, seed)
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy2c, pl.g[i], G(i, "output.dense.weight"), d, I, R, ld, ldI, I,
-                                                            flags=F_KPAD | wacc)], seed)
+                                                            colsum_a=ob_ride, flags=F_KPAD | wacc)], seed)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy2c, self._sptr(i, "fc2"), pl.dg, R, I, d, ld, ldI, I, out_kind=OUT_F32,
                                                             flags=F_KPAD)], seed)
             ops.gelu_bwd(dt, [ops.gelu_problem(pl.u[i], ldI, R, I, u_is_ct=True, dg=pl.dg, lddg=I, du=pl.du, lddu=ldI)])
@@ -416,12 +426,13 @@ class BertLayerStack:
             # d(x1) = du Wi + dy2 (the residual branch rides in the epilogue)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.du, self._sptr(i, "fc1"), pl.dx1, R, d, I, ldI, ld, d, resid=pl.dy2, ldr=d,
                                                             flags=F_KPAD)], seed)
-            ops.ln_bwd([ops.ln_problem(pl.y1[i], P("attention.output.LayerNorm.weight"), None, m1, r1, R, dy=pl.dx1, ldy=d, dx=pl.dy1,
-                                       dgamma=G(i, "attention.output.LayerNorm.weight"), dbeta=G(i, "attention.output.LayerNorm.bias"),
-                                       cast=pl.dy1c, ldc=ld, cast_colsum=G(i, "attention.output.dense.bias"), drop_p=ph,
-                                       drop_site=bert_site(i, S_ATT_OUT))], d, dt, seed)
+            ab_sum, ab_ride = route(G(i, "attention.output.dense.bias"))
+            ln_bwd([ops.ln_problem(pl.y1[i], P("attention.output.LayerNorm.weight"), None, m1, r1, R, dy=pl.dx1, ldy=d, dx=pl.dy1,
+                                   dgamma=G(i, "attention.output.LayerNorm.weight"), dbeta=G(i, "attention.output.LayerNorm.bias"),
+                                   cast=pl.dy1c, ldc=ld, cast_colsum=ab_sum, drop_p=ph,
+                                   drop_site=bert_site(i, S_ATT_OUT))], d, dt, seed)
             ops.gemm_grouped(dt, GEMM_TN, [ops.gemm_problem(pl.dy1c, pl.ctx[i], G(i, "attention.output.dense.weight"), d, d, R, ld, ld, d,
-                                                            flags=F_KPAD | wacc)], seed)
+                                                            colsum_a=ab_ride, flags=F_KPAD | wacc)], seed)
             ops.gemm_grouped(dt, GEMM_NN, [ops.gemm_problem(pl.dy1c, self._sptr(i, "ao"), pl.dao, R, d, d, ld, ld, 0, out_kind=OUT_HEADS,
                                                             heads=heads, flags=F_KPAD)], seed)
             dq, dk, dv = pl.dqkv[:, :ld], pl.dqkv[:, ld:2 * ld], pl.dqkv[:, 2 * ld:]
@@ -565,7 +576,8 @@ class BertEmbeddingsHip:
             return self._backward_flat(st, pl, dy, ids, seg, need, (word, pos, typ, gamma, beta))
         gv = torch.zeros(2, d, device=dev, dtype=torch.float32) if affine else None
         ops.ln_bwd([ops.ln_problem(pl.s, gamma, None, pl.emean, pl.erstd, R, dy=dy, ldy=d, dx=pl.ds,
-                                   dgamma=gv[0] if affine else None, dbeta=gv[1] if affine else None)], d, st.dtype, pl.seed)
+                                   dgamma=gv[0] if affine else None, dbeta=gv[1] if affine else None)], d, st.dtype, pl.seed,
+                   deterministic=pl.det)
         out: List[Optional[torch.Tensor]] = [None, None, None, gv[0] if need[3] else None, gv[1] if need[4] else None]
         if any(need[:3]):
             kw = {}
@@ -594,7 +606,7 @@ class BertEmbeddingsHip:
         g = [store.g(n) for n in names]
         ops.ln_bwd([ops.ln_problem(pl.s, params[3], None, pl.emean, pl.erstd, pl.R, dy=dy, ldy=d, dx=pl.ds,
                                    dgamma=g[3] if need[3] or need[4] else None, dbeta=g[4] if need[3] or need[4] else None)],
-                   d, st.dtype, pl.seed)
+                   d, st.dtype, pl.seed, deterministic=pl.det)
         if any(need[:3]):
             lo = store.off[names[0]]
             hi = store.off[names[2]] + (params[2].numel() + store.ALIGN - 1) // store.ALIGN * store.ALIGN

@@ -143,6 +143,8 @@ class BertEncoder(nn.Module):
             raise ValueError("text_params='flat' needs text_encoder='hip' (the flat store holds the parameters whose gradients "
                              "the HIP layer stack writes)")
         self.precision: Optional[str] = getattr(args, "precision", None)
+        flag = getattr(args, "deterministic", None)             # None: config.deterministic(), read when the stack builds a plan
+        self.deterministic: Optional[bool] = None if flag is None else bool(flag)
         self.bert = None
         self.store_prefix = ""          # this module's name in the model ("enc."): the flat store uses the model's parameter names
         self._text_store = None
@@ -214,6 +216,7 @@ class BertEncoder(nn.Module):
             if self._stack is None:
                 self._stack = BertLayerStack(self.bert, self.precision, store=store)
             self._stack.precision = self.precision
+            self._stack.deterministic = self.deterministic
             self._stack.grad_ready = self._grad_ready
             if self.text_embeddings == "hip":
                 if self._embd is None:
@@ -270,8 +273,9 @@ class _Trunk(GraphCache):
                   for n, (q, src, key) in LEVEL2.items()]
         # bf16x3 mode: the split images of this trunk's activations live and go with it (the weight shadows' with the store)
         self.x3 = ops.X3Cache(dev, weights=st.x3_cache) if st.x3 else None
-        self.plan1 = EncoderGroupPlan(st, cfg1, e1, B, x3=self.x3)
-        self.plan2 = EncoderGroupPlan(st, cfg2, e2, B, x3=self.x3)
+        self.det = config.resolve_deterministic(getattr(model, "deterministic", None))       # read once, with the tables
+        self.plan1 = EncoderGroupPlan(st, cfg1, e1, B, x3=self.x3, deterministic=self.det)
+        self.plan2 = EncoderGroupPlan(st, cfg2, e2, B, x3=self.x3, deterministic=self.det)
         self.out1 = {n: b["out"] for n, b in zip(LEVEL1, self.plan1.buf)}
         self.out2 = {n: b["out"] for n, b in zip(LEVEL2, self.plan2.buf)}
         self.d1buf = {n: z(self.N[q], B, d) for n, (q, _, _) in LEVEL1.items()}   # d(level-1 outputs)
@@ -808,6 +812,9 @@ class _BPMulTBase(nn.Module):
         # `args.prune_unused_rows=False`, `set_prune_unused_rows(False)` or BPMULT_PRUNE=0 run the dense schedule.
         flag = getattr(args, "prune_unused_rows", None)
         self.prune_unused_rows = (os.environ.get("BPMULT_PRUNE", "1") != "0") if flag is None else bool(flag)
+        # deterministic mode (config.set_deterministic): None = the process default, read when a trunk's tables are built
+        flag = getattr(args, "deterministic", None)
+        self.deterministic: Optional[bool] = None if flag is None else bool(flag)
         d = self.d
         self.enc = BertEncoder(args)
         self.enc.store_prefix = "enc."
@@ -980,6 +987,14 @@ class _BPMulTBase(nn.Module):
         Fusion-GMU / time-map work on rows {0, N-1} only where nothing else is consumed; same logits and gradients,
         SURVEY A.10).  Launch tables are rebuilt on the next forward."""
         self.prune_unused_rows = bool(flag)
+        self._drop_trunks()
+
+    def set_deterministic(self, flag: Optional[bool]) -> None:
+        """Deterministic mode for this model (None: follow config.deterministic()): no launch of the trunk adds floats in
+        hardware order, so a fixed build, device, input and seed give the same bits on every run ("Deterministic
+        mode").  Launch tables and captured graphs are rebuilt on the next forward."""
+        self.deterministic = None if flag is None else bool(flag)
+        self.enc.deterministic = self.deterministic
         self._drop_trunks()
 
     def _next_seed(self) -> int:

@@ -114,6 +114,7 @@ class TransformerEncoder(nn.Module):
         self.normalize = True
         self.layer_norm = nn.LayerNorm(embed_dim)
         self.precision: Optional[str] = None          # None -> config.precision() at first use
+        self.deterministic: Optional[bool] = None     # None -> config.deterministic(), read when a plan is built
         self._store: Optional[ParamStore] = None
         self._plans = {}
         self._last_plan: Optional[EncoderGroupPlan] = None      # plan of the most recent forward call (attention_maps)
@@ -147,11 +148,14 @@ class TransformerEncoder(nn.Module):
         key = ("self", T, B) if x_k is None else (T, x_k.shape[0], B)
         if epm or kpm:
             key += ("masks", epm, kpm)
+        det = config.resolve_deterministic(self.deterministic)
+        if det:
+            key += ("det",)
         if key not in self._plans:
             S = T if x_k is None else x_k.shape[0]
             desc = EncoderDesc("", 0, T, S, self.attn_dropout)
             masks = dict(masks=[EncoderMasks(self_keys=epm, cross_keys=kpm)]) if epm or kpm else {}
-            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(self_only=x_k is None), [desc], B, **masks)
+            self._plans[key] = EncoderGroupPlan(st, self.group_cfg(self_only=x_k is None), [desc], B, deterministic=det, **masks)
         return self._plans[key]
 
     def _next_seed(self) -> int:

@@ -676,6 +676,33 @@ def unfold_grads(table_dev: torch.Tensor, ndesc: int, total_blocks: int, store_d
     _lib.check(_lib.lib().bpm_unfold_grads(table_dev.data_ptr(), ndesc, total_blocks, int(store_dw), _stream()), "bpm_unfold_grads")
 
 
+_UNFOLD_WS = {}
+_WS_RETIRED: list = []      # replaced workspaces of every row entry: a captured graph may still hold their addresses
+
+
+def _unfold_workspace(need: int, device) -> torch.Tensor:
+    """Per-(device, stream) partial-row workspace of bpm_unfold_grads_ws, as _ln_workspace: launches on one stream are
+    serialised and share it.  (The entry clears its ticket words itself.)  A workspace that a larger one replaces is
+    kept: a captured graph may still hold its address (a few MB each, one per growth step)."""
+    key = (str(device), _stream())
+    t = _UNFOLD_WS.get(key)
+    if t is None or t.numel() * 4 < need:
+        if t is not None:
+            _WS_RETIRED.append(t)
+        t = torch.zeros((need + 3) // 4, device=device, dtype=torch.float32)
+        _UNFOLD_WS[key] = t
+    return t
+
+
+def unfold_grads_ws(table_dev: torch.Tensor, ndesc: int, total_blocks: int, max_cols: int, store_dw: bool = False) -> None:
+    """unfold_grads without float atomics (deterministic mode): dgamma / dbeta from per-block partial rows, added in block
+    order by one owner.  max_cols: the widest descriptor's cols."""
+    L = _lib.lib()
+    ws = _unfold_workspace(L.bpm_unfold_grads_ws_bytes(ndesc, total_blocks, max_cols), table_dev.device)
+    _lib.check(L.bpm_unfold_grads_ws(table_dev.data_ptr(), ndesc, total_blocks, int(store_dw), max_cols, ws.data_ptr(),
+                                     ws.numel() * 4, _stream()), "bpm_unfold_grads_ws")
+
+
 def zero_table(segments):
     """[(device address, element count)] -> (device table, ndesc, total blocks) for zero_segments."""
     descs, blk = [], 0
@@ -778,28 +805,44 @@ def check_ln_rows(probs, d: int) -> None:
 _LN_WS = {}
 
 
-def _ln_workspace(n: int, d: int, device) -> torch.Tensor:
+def _ln_workspace(n: int, d: int, device, entry: str = "bpm_ln_bwd_ws_bytes") -> torch.Tensor:
     """Per-(device, stream) partial-sum workspace of bpm_ln_bwd_ws: launches on one stream are serialised, so they
-    can share it; the side stream gets its own."""
-    key = (str(device), _stream())
-    need = _lib.lib().bpm_ln_bwd_ws_bytes(n, d)
+    can share it; the side stream gets its own.  entry: the size query (bpm_ln_bwd_det's serves either of its routes, at
+    twice the size: deterministic launches keep a workspace of their own, so they do not grow the default one).  A
+    workspace that a larger one replaces is kept: a captured graph may still hold its address."""
+    key = (str(device), _stream()) + (() if entry == "bpm_ln_bwd_ws_bytes" else (entry,))
+    need = getattr(_lib.lib(), entry)(n, d)
     t = _LN_WS.get(key)
     if t is None or t.numel() * 4 < need:
+        if t is not None:
+            _WS_RETIRED.append(t)
         t = torch.zeros((need + 3) // 4, device=device, dtype=torch.float32)      # ticket words must start at zero
         _LN_WS[key] = t
     return t
 
 
-def ln_bwd(probs, d, dtype=None, seed=0) -> None:
+def ln_det(probs):
+    """The problems of a LayerNorm-backward STEP of a deterministic plan, marked where the launch table is built (a step
+    is (fn, *args) run with the seed as its only keyword, and the seeded step functions are a fixed set: the mode
+    travels on the array, as the bf16x3 flags of a GEMM step's array do).  EncoderGroupPlan.__init__ refuses a
+    deterministic plan with an unmarked LayerNorm-backward step."""
+    probs = _as_array(LnProblem, probs)
+    probs.det = True
+    return probs
+
+
+def ln_bwd(probs, d, dtype=None, seed=0, deterministic: bool = False) -> None:
     """dtype / seed only matter for problems with a fused `cast` output.  Parameter / bias gradients go through a
-    partial-sum workspace (no float atomics)."""
+    partial-sum workspace where the library can (no float atomics); deterministic (or an array marked by ln_det):
+    through bpm_ln_bwd_det, which computes them without atomics for every shape and never falls back."""
     dev, seed = torch.device("cuda", torch.cuda.current_device()), _seed(seed)
+    deterministic = deterministic or getattr(probs, "det", False)
 
     def post(k):                    # the workspace of this chunk's count
-        ws = _ln_workspace(k, d, dev)
+        ws = _ln_workspace(k, d, dev, "bpm_ln_bwd_det_ws_bytes") if deterministic else _ln_workspace(k, d, dev)
         return d, seed, ws.data_ptr(), ws.numel() * 4
     try:
-        _grouped("bpm_ln_bwd_ws", probs, (BPM_F32 if dtype is None else dtype,), post)
+        _grouped("bpm_ln_bwd_det" if deterministic else "bpm_ln_bwd_ws", probs, (BPM_F32 if dtype is None else dtype,), post)
     except RuntimeError:
         _LN_WS.clear()              # an aborted launch may leave ticket words set: start from fresh zeroed workspaces
         raise
@@ -818,6 +861,26 @@ def cast_problem(a, lda, R, Cn, *, a_is_ct=False, b=None, ldb=0, dst_ct=None, ld
 
 def rows_cast(dtype, probs, seed=0) -> None:
     _grouped("bpm_rows_cast", probs, (dtype,), (_seed(seed),))
+
+
+_CAST_WS = {}
+
+
+def rows_cast_ws(dtype, probs, seed=0) -> None:
+    """rows_cast with its column sums through a per-(device, stream) partial-row workspace and a finishing launch
+    instead of float atomics (bpm_rows_cast_ws, deterministic mode)."""
+    L, s, seed = _lib.lib(), _stream(), _seed(seed)
+    arr = _as_array(CastProblem, probs)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for i in range(0, len(arr), MAX_GROUP):
+        k = min(MAX_GROUP, len(arr) - i)
+        need = L.bpm_rows_cast_ws_bytes(_at(arr, i), k)
+        ws = _CAST_WS.get((str(dev), s))
+        if ws is None or ws.numel() * 4 < need:
+            if ws is not None:
+                _WS_RETIRED.append(ws)          # a captured graph may still hold its address
+            ws = _CAST_WS[(str(dev), s)] = torch.zeros((need + 3) // 4, device=dev, dtype=torch.float32)
+        _lib.check(L.bpm_rows_cast_ws(dtype, _at(arr, i), k, seed, ws.data_ptr(), ws.numel() * 4, s), "bpm_rows_cast_ws")
 
 
 def gelu_problem(u, ldu, R, Cn, *, u_is_ct=False, g=None, ldg=0, dg=None, lddg=0, du=None, lddu=0) -> "_lib.GeluProblem":
@@ -1081,4 +1144,4 @@ SEEDED = frozenset({gemm_grouped, attn_fwd, attn_bwd, attn_bwd_dq, attn_bwd_dkv,
 # every function that may stand in a step table: a launch on the current stream with no result
 # (the *_amask attention entries are called directly by models/attention.py and stand in no table)
 STEP_FUNCTIONS = SEEDED | {attn_maps, ln_fwd, gelu_fwd, gelu_bwd, expand_heads, add_n, gmu2_fwd, gmu2_bwd, pack_weights, fold_bias,
-                           unfold_grads, zero_segments}
+                           unfold_grads, unfold_grads_ws, zero_segments}

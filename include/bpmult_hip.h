@@ -367,6 +367,19 @@ typedef struct bpm_unfold_desc {
 } bpm_unfold_desc;
 /* store_dw != 0: dW is WRITTEN (this launch is the first writer of those rows this step: no zero-fill, no read). */
 int bpm_unfold_grads(const bpm_unfold_desc* table_dev, int ndesc, unsigned total_blocks, int store_dw, void* stream);
+/* The same without float atomics (deterministic mode).  dW and dbias: the same bits as bpm_unfold_grads.  dgamma / dbeta:
+ * every block stores its column sums as two partial rows in the workspace, and the block of a descriptor that finishes
+ * last adds them in block order and makes one plain read-modify-write into dgamma / dbeta -- bitwise reproducible, the
+ * same on the wide and the one-column path, and independent of the other descriptors of the launch.
+ * max_cols >= the cols of every descriptor (a wider descriptor is not processed); descriptor i owns the blocks
+ * [blk0, blk0 + ceil(rows / 16)).  ws: at least bpm_unfold_grads_ws_bytes(ndesc, total_blocks, max_cols) bytes, 16-byte
+ * aligned, private to the stream for the duration of the launch (its ticket words are cleared by the entry, on the
+ * stream, ahead of the kernel).  As with bpm_ln_bwd_ws the stream must OWN the dgamma / dbeta rows while the launch
+ * runs, and two descriptors of one launch must not share them.  BPM_ERR_ARG: a NULL table or workspace, a workspace
+ * that is misaligned or too small.  New entries only: BPM_ABI_VERSION stays. */
+size_t bpm_unfold_grads_ws_bytes(int ndesc, unsigned total_blocks, int max_cols);
+int bpm_unfold_grads_ws(const bpm_unfold_desc* table_dev, int ndesc, unsigned total_blocks, int store_dw, int max_cols,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* Zero a list of fp32 segments with one launch (device-resident table, built once).  A training step whose gradients
  * start from zero (zero_grad / `p.grad = None`, train.py:384-385,396-398) does not clear the whole flat gradient buffer:
@@ -456,6 +469,20 @@ int bpm_ln_bwd(int dtype, const bpm_ln_problem* probs, int n, int d, uint64_t se
  * re-zero (or re-create) the workspace after any error reported for its stream. */
 size_t bpm_ln_bwd_ws_bytes(int n, int d);
 int bpm_ln_bwd_ws(int dtype, const bpm_ln_problem* probs, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+/* bpm_ln_bwd_ws for deterministic mode: the same launch, but a call whose dgamma / dbeta / cast_colsum would go out as
+ * float atomics is computed without them: the vector kernels' workspace route where bpm_ln_bwd_ws takes it (the same
+ * bits), and otherwise -- the scalar family (d % 4 != 0 or d > 1024), a misaligned row, problems of one launch that share
+ * a gradient row -- the scalar kernel storing per-block partial rows, then a small finishing launch with one block per
+ * distinct gradient row, which adds the partial rows in problem order, block order inside a problem, and makes one plain
+ * read-modify-write (dx and the cast output: the bits of bpm_ln_bwd).  ws: at least bpm_ln_bwd_det_ws_bytes(n, d) bytes
+ * serves either route (16-byte aligned, private to the stream, zero when first used); a missing, misaligned or too small
+ * workspace is BPM_ERR_ARG and launches nothing -- never a fall-back to atomics.  The route is chosen for the whole
+ * launch: a problem that alone takes the vector route is summed by the second route (256 blocks of 4 rows instead of 64
+ * of 8) beside a problem that needs it, so its sums are independent of the other problems of a launch among launches
+ * that take the same route (a fixed table gives the same bits on every run either way).  Rows that overlap without
+ * being equal stay the caller's to avoid.  New entries only: BPM_ABI_VERSION stays. */
+int bpm_ln_bwd_det(int dtype, const bpm_ln_problem* probs, int n, int d, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
+size_t bpm_ln_bwd_det_ws_bytes(int n, int d);
 
 /* y = (a [+ b]) * dropout_mult(r*C + c); a is fp32 or (a_is_ct) CT.  Outputs,
  * each optional: CT copy [R, ldd] (pad zeroed), fp32 copy, column sums (+= by
@@ -472,6 +499,13 @@ typedef struct bpm_cast_problem {
     float drop_p; uint32_t drop_site;
 } bpm_cast_problem;
 int bpm_rows_cast(int dtype, const bpm_cast_problem* probs, int n, uint64_t seed, void* stream);
+/* bpm_rows_cast with its column sums computed without float atomics (deterministic mode), by either kernel of the
+ * entry: every row block stores its partial row in the workspace, and a finishing launch adds them per distinct colsum
+ * row in problem order, block order inside a problem, with one plain read-modify-write.  Every other output: the bits of
+ * bpm_rows_cast.  ws: at least bpm_rows_cast_ws_bytes(probs, n) bytes, 16-byte aligned, private to the stream for the two
+ * launches; BPM_ERR_ARG when it is NULL, misaligned or too small.  New entries only: BPM_ABI_VERSION stays. */
+size_t bpm_rows_cast_ws_bytes(const bpm_cast_problem* probs, int n);
+int bpm_rows_cast_ws(int dtype, const bpm_cast_problem* probs, int n, uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
 /* Exact (erf) GELU, HF's hidden_act = "gelu" between intermediate.dense and output.dense (BertIntermediate):
  *   forward   g = 0.5 u (1 + erf(u / sqrt 2)),  u fp32 or (u_is_ct) CT [R, ldu];  g written as CT [R, ldg] with the pad

@@ -138,6 +138,9 @@ def streaming_cases(ops, timeit, G, R=4096, d=768):
     for store in (0, 1):
         timeit(f"unfold_grads x{G} {rows}x{d} store_dw={store}", lambda: ops.unfold_grads(tab, G, nblk, store_dw=bool(store)),
                G * rows * d * 4 * (3 if store else 4))
+        # deterministic mode: dgamma / dbeta through per-block partial rows instead of float atomics
+        timeit(f"unfold_grads_ws x{G} {rows}x{d} store_dw={store}", lambda: ops.unfold_grads_ws(tab, G, nblk, d, store_dw=bool(store)),
+               G * rows * d * 4 * (3 if store else 4))
 
     # embed_pos: T*B = R rows
     T, B = R // 8, 8
