@@ -181,6 +181,10 @@ class AttnMapProblem(C.Structure):
                 ("mask_off", C.c_int), ("q_pos0", C.c_int), ("q_stride", C.c_int)]
 
 
+class AttnHeadMapProblem(C.Structure):
+    _fields_ = AttnMapProblem._fields_ + [("head_stride", C.c_int64), ("batch_stride", C.c_int64)]
+
+
 class PackProblem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("g", C.c_void_p), ("ldg", C.c_int), ("dsrc", C.c_void_p),
                 ("B", C.c_int), ("T", C.c_int), ("C", C.c_int), ("ld", C.c_int),
@@ -350,6 +354,11 @@ SIGNATURES = {
     "bpm_attn_maps_kamask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _P],
     "bpm_attn_bwd_dbias_kmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnHMask), C.POINTER(AttnKMask), C.POINTER(AttnDBias), _I, _U64, _P,
                                  C.c_size_t, _P],
+    "bpm_attn_head_maps": [_I, C.POINTER(AttnHeadMapProblem), _I, _P],
+    "bpm_attn_head_maps_kmask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnKMask), _I, _P],
+    "bpm_attn_head_maps_amask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnAMask), _I, _P],
+    "bpm_attn_head_maps_hmask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnHMask), _I, _P],
+    "bpm_attn_head_maps_kamask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],

@@ -1,5 +1,5 @@
 // What more than one family of attention kernels uses (attention.hip: forward / dQ / dK,dV with and without masks;
-// attn_maps.hip: head-averaged maps; attn_dbias.hip: the gradient of an additive mask): tile constants and occupancies,
+// attn_maps.hip: head-averaged and per-head maps; attn_dbias.hip: the gradient of an additive mask): tile constants and occupancies,
 // the kernel-argument structs, the LDS staging and store helpers, and the shared pieces of the ONE shape of an entry
 // point -- check, fill, choose, launch (launch / with_ct come from bpm_launch.h; with_dhp is here).
 // Everything sits in the unnamed namespace, as the kernels of those files do: their symbols carry it.

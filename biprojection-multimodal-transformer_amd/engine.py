@@ -553,9 +553,9 @@ SIDE, JOIN, MARK, WAIT, SIDE2 = "side", "join", "mark", "wait", "side2"
 
 
 class AttentionMap(NamedTuple):
-    """One head-averaged attention map (EncoderGroupPlan.attention_maps).  weights: fp32 [B, Tq, S], the caller's own
-    tensor.  query_steps: None when the Tq rows are all T time steps of the encoder's query sequence, else the time step
-    of each row (layers that only compute a few query rows: a gathered subset, or rows {0, T-1} of a tail_rows layer)."""
+    """One attention map (EncoderGroupPlan.attention_maps).  weights: fp32 [B, Tq, S] (head-averaged) or [B, H, Tq, S]
+    (per_head=True), the caller's own tensor.  query_steps: None when the Tq rows are all T time steps of the encoder's
+    query sequence, else the time step of each row (layers that only compute a few query rows: a gathered subset, or rows {0, T-1} of a tail_rows layer)."""
     weights: torch.Tensor
     query_steps: Optional[Tuple[int, ...]]
 _SIDE = os.environ.get("BPMULT_SIDE", "1") != "0"
@@ -1343,7 +1343,7 @@ class EncoderGroupPlan:
         """A captured graph of this plan's forward has just been replayed (no Python of forward() ran)."""
         self._maps_ok = True
 
-    def attention_maps(self, encoders=None, layers=None) -> List[List[Dict[str, AttentionMap]]]:
+    def attention_maps(self, encoders=None, layers=None, per_head: bool = False) -> List[List[Dict[str, AttentionMap]]]:
         """Head-averaged attention maps of the LAST forward of this plan: for each selected encoder (index or parameter
         prefix; None = all, in plan order) a list over the selected layers (None = all) of {block: AttentionMap}, block
         "cross" (crossmodal), "self" (self-only) or both (biprojection with a key / value source; self [B, Tq, T], cross
@@ -1357,7 +1357,12 @@ class EncoderGroupPlan:
         three buffers (_self_attn_bwd / _cross_attn_bwd pass them as Q / K / lse inputs of the attention problems; the
         low-rank route also reads qh in bpm_expand_heads; gradients go to dq / dqkvs / dao / delta / dkall / dSall ...),
         for every layer kind, so maps may be taken before or after backward(), until the plan's next forward.  Before any
-        forward, or after one that did not finish launching, this raises RuntimeError."""
+        forward, or after one that did not finish launching, this raises RuntimeError.
+
+        per_head=True: the probabilities of every head instead of their mean (bpm_attn_head_maps), W[b, h, i, j], contiguous
+        [B, H, Tq, S]; everything else as above (same buffers, same key masks, same query_steps, same rules about when).
+        A per-head map is H times the averaged one: B * H * Tq * S * 4 bytes, about 100 MB at the headline shape (T = S =
+        512), several GB for all maps of a model -- select `encoders` and `layers`."""
         if not self._maps_ok:
             raise RuntimeError("attention_maps: no finished forward pass of this plan (its Q / K / LSE buffers hold nothing to "
                                "compute the maps from); run forward first")
@@ -1390,18 +1395,18 @@ class EncoderGroupPlan:
                 maps = {}
                 for name, q, kk, lse, S, moff, p0, st_, steps in self._map_blocks(e, b, i):
                     Tq = b["Tl"][i]
-                    W = torch.empty(self.B, Tq, S, device=dev, dtype=torch.float32)
-                    probs.append(ops.attn_map_problem(q, kk, lse, W, S, self.B, self.cfg.H, Tq, S, self.dh, self.dhp, moff,
-                                                      q_pos0=p0, q_stride=st_))
+                    W = torch.empty((self.B, self.cfg.H, Tq, S) if per_head else (self.B, Tq, S), device=dev, dtype=torch.float32)
+                    problem = ops.attn_head_map_problem if per_head else ops.attn_map_problem
+                    probs.append(problem(q, kk, lse, W, S, self.B, self.cfg.H, Tq, S, self.dh, self.dhp, moff, q_pos0=p0, q_stride=st_))
                     if self._masked:
                         kms.append((b["vis_s" if name == "self" else "vis_c"], S))
                     maps[name] = AttentionMap(W, steps)
                 per_layer.append(maps)
             res.append(per_layer)
         if probs and self._masked:
-            ops.attn_maps_kmask(self.dtype, probs, ops.attn_kmasks(kms))
+            (ops.attn_head_maps_kmask if per_head else ops.attn_maps_kmask)(self.dtype, probs, ops.attn_kmasks(kms))
         elif probs:
-            ops.attn_maps(self.dtype, probs)
+            (ops.attn_head_maps if per_head else ops.attn_maps)(self.dtype, probs)
         return res
 
     # -- backward tables --------------------------------------------------------

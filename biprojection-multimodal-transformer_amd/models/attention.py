@@ -210,16 +210,19 @@ class _Exec:
                                                         flags=F_KPAD)], seed)
         weights = None
         if need_weights:
-            weights = torch.empty(B, T, S, device=self.device)
-            mp = [ops.attn_map_problem(pl.q, pl.k, pl.lse, weights, S, B, H, T, S, dh, dhp, 0)]
+            # need_weights == "heads" (average_attn_weights=False): one map per head, through the bpm_attn_head_maps family
+            heads = need_weights == "heads"
+            weights = torch.empty((B, H, T, S) if heads else (B, T, S), device=self.device)
+            mp = [(ops.attn_head_map_problem if heads else ops.attn_map_problem)(pl.q, pl.k, pl.lse, weights, S, B, H, T, S, dh, dhp, 0)]
+            maps = "attn_head_maps" if heads else "attn_maps"
             if pl.mask is None and pl.kmask is None:
-                ops.attn_maps(dt, mp)
+                getattr(ops, maps)(dt, mp)
             elif pl.kmask is None:
-                ops.attn_maps_amask(dt, mp, pl.mask[0])
+                getattr(ops, maps + "_amask")(dt, mp, pl.mask[0])
             elif pl.mask is None:
-                ops.attn_maps_kmask(dt, mp, pl.kmask[0])
+                getattr(ops, maps + "_kmask")(dt, mp, pl.kmask[0])
             else:
-                ops.attn_maps_kamask(dt, mp, pl.kmask[0], pl.mask[0])
+                getattr(ops, maps + "_kamask")(dt, mp, pl.kmask[0], pl.mask[0])
         return out, weights, pl
 
     # -- backward ------------------------------------------------------------------------------------------------------
@@ -305,8 +308,8 @@ class _MhaFn(torch.autograd.Function):
 class MultiheadAttention(nn.Module):
     """Drop-in for bpmult.models.multihead_attention.MultiheadAttention (packed in-projection, :17-50).
 
-    forward(query, key, value, attn_mask=None, need_weights=True, attn_bias=None, key_padding_mask=None) -> (attn [T, B, d],
-    weights [B, T, S] or None) on
+    forward(query, key, value, attn_mask=None, need_weights=True, attn_bias=None, key_padding_mask=None,
+    average_attn_weights=True) -> (attn [T, B, d], weights [B, T, S] ([B, H, T, S] with average_attn_weights=False) or None) on
     [T,B,d] / [S,B,d] fp32 CUDA (HIP) tensors, in the reference's three call forms (query is key is value; key is value;
     three tensors).  attn_mask: None or a float [T, S] tensor added to the scores of every head (-inf hides a pair; every
     row must keep a visible key, or it is NaN as in the reference); it gets no gradient (requires_grad: ValueError).
@@ -323,7 +326,10 @@ class MultiheadAttention(nn.Module):
     One stated difference: `weights` are the head-averaged softmax probabilities BEFORE attention dropout, detached --
     equal to the reference's in eval mode and whenever attn_dropout == 0 (in training with dropout the reference returns
     the dropped, rescaled matrix); the departure TransformerEncoder.attention_maps() makes.  need_weights=False (an
-    extension) launches nothing for them and returns None.  add_bias_kv / add_zero_attn are not supported (ValueError).
+    extension) launches nothing for them and returns None.  average_attn_weights=False (torch's name for the switch): the
+    probabilities of every head, [B, H, T, S] -- the tensor the reference averages (:121) -- under the same attn_mask,
+    attn_bias and key_padding_mask, before dropout, detached and non-differentiable like the averaged one; H times its
+    size (B * H * T * S * 4 bytes).  add_bias_kv / add_zero_attn are not supported (ValueError).
     Precision: the `precision` attribute, or config.precision() when it is None ('bf16' or 'f32').
     TransformerEncoder constructs this class as a parameter container and runs its own grouped engine plan."""
 
@@ -378,7 +384,8 @@ class MultiheadAttention(nn.Module):
             ex = self._exec = _Exec(self, device, prec, det)
         return ex
 
-    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None, key_padding_mask=None):
+    def forward(self, query, key, value, attn_mask=None, need_weights: bool = True, attn_bias=None, key_padding_mask=None,
+                average_attn_weights: bool = True):
         if query.dim() != 3 or query.shape[2] != self.embed_dim:
             raise ValueError(f"MultiheadAttention: query of shape {tuple(query.shape)}, expected [T, B, {self.embed_dim}]")
         T, B, d = query.shape
@@ -419,4 +426,5 @@ class MultiheadAttention(nn.Module):
                 raise RuntimeError("MultiheadAttention: the HIP attention path needs CUDA (HIP) tensors; there is no CPU path")
         ex = self._ensure_exec(query.device)
         seed = self._next_seed()
-        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, need_weights, seed, attn_bias, key_padding_mask, *ex.params)
+        want = False if not need_weights else True if average_attn_weights else "heads"
+        return _MhaFn.apply(query, key, value, self, ex, form, attn_mask, want, seed, attn_bias, key_padding_mask, *ex.params)

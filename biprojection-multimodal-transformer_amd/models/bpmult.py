@@ -857,7 +857,7 @@ class _BPMulTBase(nn.Module):
         self._store = None
         return r
 
-    def attention_maps(self, names=None, layers=None):
+    def attention_maps(self, names=None, layers=None, per_head: bool = False):
         """Head-averaged attention maps of the most recent forward call: a dict from encoder name (the reference's
         attribute names, "trans_l_with_a", ..., "trans_v_with_a2l"; `names` = None: all twelve) to a list with one entry
         per selected layer (`layers` = None: all), each a dict from attention block to engine.AttentionMap(weights,
@@ -874,7 +874,11 @@ class _BPMulTBase(nn.Module):
         and nothing at all unless this is called (the step itself is unchanged).  Works in both schedules, after eager
         launches and after a graph replay (the maps launch itself is never captured), in train and eval mode, under
         no_grad or not, before or after backward(), until the next forward call of this model; RuntimeError before the
-        first forward and after .to() / set_prune_unused_rows() dropped the activation buffers."""
+        first forward and after .to() / set_prune_unused_rows() dropped the activation buffers.
+
+        per_head=True: every head's probabilities instead of their mean -- weights [B, H, Tq, S] ([B, H, 2, S] for the two-row
+        layers), query_steps unchanged, same key masks, same rules.  One full map is then B * H * 512 * 512 * 4 bytes, about
+        100 MB at the headline shape, and all maps of a model run to several GB: select `names` and `layers`."""
         trunk = getattr(self, "_last_trunk", None)
         if trunk is None:
             raise RuntimeError("attention_maps: no forward pass to take the maps of (call forward first; .to() and "
@@ -891,7 +895,7 @@ class _BPMulTBase(nn.Module):
         for plan, level in ((trunk.plan1, LEVEL1), (trunk.plan2, LEVEL2)):
             sel = [n for n in names if n in level]
             if sel:
-                out.update(zip(sel, plan.attention_maps(sel, layers)))
+                out.update(zip(sel, plan.attention_maps(sel, layers, per_head)))
         return {n: out[n] for n in names}
 
     def _drop_trunks(self) -> None:

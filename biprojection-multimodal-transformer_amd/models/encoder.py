@@ -195,7 +195,7 @@ class TransformerEncoder(nn.Module):
             return _EncoderFn.apply(self._anchor, x_in, None, None, self, encoder_padding_mask, None)
         return _EncoderFn.apply(self._anchor, x_in, x_in_k, x_in_v, self, encoder_padding_mask, key_padding_mask)
 
-    def attention_maps(self, layers=None):
+    def attention_maps(self, layers=None, per_head: bool = False):
         """Head-averaged attention maps of the most recent forward call (either call form): a list with one entry per
         selected layer (None = all), each a dict from attention block to engine.AttentionMap(weights, query_steps) --
         {"cross": [B, T, S]} for the crossmodal call of a plain encoder, {"self": [B, T, T], "cross": [B, T, S]} for a
@@ -205,8 +205,12 @@ class TransformerEncoder(nn.Module):
         and whenever attn_dropout == 0 (in training with dropout the reference returns the dropped, rescaled matrix).
         Detached fp32 tensors owned by the caller; nothing is computed for layers that are not selected, and nothing at
         all unless this is called.  Valid in train and eval mode, under no_grad or not, before or after backward(),
-        until the next forward call; RuntimeError before the first one (or after .to() / .cuda() dropped the buffers)."""
+        until the next forward call; RuntimeError before the first one (or after .to() / .cuda() dropped the buffers).
+
+        per_head=True: every head's probabilities instead of their mean, weights [B, H, T, S] (the [B * H, T, S] tensor the
+        reference forms at multihead_attention.py:121, before it averages), same masks, same rules.  A map is then
+        B * H * T * S * 4 bytes -- H times the averaged one, about 100 MB at B = 32, H = 3, T = S = 512: select `layers`."""
         if self._last_plan is None:
             raise RuntimeError("attention_maps: no forward pass to take the maps of (call forward first; .to() / .cuda() drop "
                                "the activation buffers)")
-        return self._last_plan.attention_maps(None, layers)[0]
+        return self._last_plan.attention_maps(None, layers, per_head)[0]

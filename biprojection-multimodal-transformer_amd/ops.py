@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import (BPM_BF16, BPM_BF16X3, BPM_F32, F_ACCUM, F_ATOMIC, F_KPAD, F_RELU, GEMM_NN, GEMM_NT, GEMM_TN, GEMM_MAX_GROUP, MAX_GROUP, OUT_CT,
-                   OUT_F32, OUT_HEADS, AttnMapProblem, AttnProblem, CastProblem, EmbedProblem, GemmProblem, GmuProblem,
+                   OUT_F32, OUT_HEADS, AttnHeadMapProblem, AttnMapProblem, AttnProblem, CastProblem, EmbedProblem, GemmProblem, GmuProblem,
                    KvSourceProblem, LnProblem, PackProblem)
 
 
@@ -483,6 +483,55 @@ def attn_maps_kamask(dtype: int, probs, kmasks, masks) -> None:
         _DRY_LAUNCHES.append((attn_maps_kamask, dtype, arr, kmasks, masks))
         return
     _grouped("bpm_attn_maps_kamask", arr, (dtype,), beside=(kmasks, masks))
+
+
+def attn_head_map_problem(Q, K, lse, W, ldw, B, H, T, S, dh, dhp, mask_off, *, q_pos0=0, q_stride=1, head_stride=None,
+                          batch_stride=None) -> AttnHeadMapProblem:
+    """One per-head attention map (bpm_attn_head_maps): attn_map_problem with W fp32 [B, H, T, ldw], which receives the
+    softmax probabilities of every head (before dropout; exactly 0 where a mask hides the pair) -- H times the bytes of
+    the averaged map.  head_stride / batch_stride (elements; default: the dense T * ldw and H * head_stride) place the map
+    of (sample b, head h) at W + b * batch_stride + h * head_stride."""
+    p = AttnHeadMapProblem()
+    p.Q, p.K, p.lse, p.W, p.ldw = _p(Q), _p(K), _f32(lse, "lse"), _f32(W, "W"), ldw
+    p.B, p.H, p.T, p.S, p.dh, p.dhp, p.mask_off = B, H, T, S, dh, dhp, mask_off
+    p.q_pos0, p.q_stride = q_pos0, q_stride
+    p.head_stride = T * ldw if head_stride is None else head_stride
+    p.batch_stride = H * p.head_stride if batch_stride is None else batch_stride
+    return p
+
+
+def _attn_head_maps(fn, name: str, dtype: int, probs, *beside) -> None:
+    """The five per-head map launches: as their attn_maps* siblings (outside the step tables: recorded in dry mode)."""
+    arr = _as_array(AttnHeadMapProblem, probs)
+    if any(len(b) != len(arr) for b in beside):
+        raise ValueError(f"{name}: one mask of each kind per problem ({len(arr)} problems, {' / '.join(str(len(b)) for b in beside)} masks)")
+    if _DRY_RUN:
+        _DRY_LAUNCHES.append((fn, dtype, arr, *beside))
+        return
+    _grouped(name, arr, (dtype,), beside=beside if len(beside) > 1 else (beside[0] if beside else None))
+
+
+def attn_head_maps(dtype: int, probs) -> None:
+    _attn_head_maps(attn_head_maps, "bpm_attn_head_maps", dtype, probs)
+
+
+def attn_head_maps_kmask(dtype: int, probs, kmasks) -> None:
+    """bpm_attn_head_maps after attn_fwd_kmask: `kmasks` from attn_kmasks(), one per problem."""
+    _attn_head_maps(attn_head_maps_kmask, "bpm_attn_head_maps_kmask", dtype, probs, kmasks)
+
+
+def attn_head_maps_hmask(dtype: int, probs, masks) -> None:
+    """bpm_attn_head_maps after attn_fwd_amask / _hmask: `masks` from attn_amasks() (with their transposes), one per problem."""
+    _attn_head_maps(attn_head_maps_hmask, "bpm_attn_head_maps_hmask", dtype, probs, masks)
+
+
+def attn_head_maps_amask(dtype: int, probs, masks) -> None:
+    """attn_head_maps_hmask: attn_amasks() builds bpm_attn_hmask, and the *_amask entry is the *_hmask entry at stride 0."""
+    _attn_head_maps(attn_head_maps_amask, "bpm_attn_head_maps_hmask", dtype, probs, masks)
+
+
+def attn_head_maps_kamask(dtype: int, probs, kmasks, masks) -> None:
+    _attn_head_maps(attn_head_maps_kamask, "bpm_attn_head_maps_kamask", dtype, probs, kmasks, masks)
 
 
 def attn_dbias(outs) -> "C.Array":

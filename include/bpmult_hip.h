@@ -312,6 +312,37 @@ int bpm_attn_bwd_dbias_kmask(int dtype, const bpm_attn_problem* probs /* host */
                              const bpm_attn_kmask* kmasks /* host, or NULL */, const bpm_attn_dbias* outs /* host */, int nprob,
                              uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
+/* PER-HEAD attention maps: the five bpm_attn_maps* entries without the head average,
+ *   W[b][h][i][j] = exp(Q[b,h,i,:] . K[b,h,j,:] + mask - lse[b,h,i])   for a visible pair, exactly 0.0f for a hidden one
+ * -- the [B*H, T, S] probabilities the reference forms before it averages them (multihead_attention.py:121), before
+ * dropout.  Same arithmetic as the averaged kernel (the value written here is the addend that kernel sums for head h),
+ * same masks under the same rules (the additive image is read through maskT), same mask_off / q_pos0 / q_stride.
+ * bpm_attn_head_map_problem is bpm_attn_map_problem with W as fp32 [B, H, T, ldw] behind two strides in ELEMENTS:
+ * the map of (sample b, head h) starts at W + b*batch_stride + h*head_stride, its row i at + i*ldw;
+ * head_stride >= T*ldw and batch_stride >= H*head_stride.  Only W[b][h][i][0 .. S) is written: pad columns and any gap
+ * between heads or samples are left untouched.  The output is H times the averaged one (B*H*T*S*4 bytes).
+ * BPM_ERR_ARG, before anything is launched (and without a GPU): a NULL array or pointer, a geometry the averaged entries
+ * refuse, ldw < S, a stride below its minimum, problems of different dhp, and the mask rules of the sibling entry;
+ * BPM_ERR_ALIGN: Q / K not 16-byte aligned, lse / W not 4-byte aligned.  New entries only: BPM_ABI_VERSION stays. */
+typedef struct bpm_attn_head_map_problem {
+    const void* Q; const void* K;   /* as bpm_attn_map_problem */
+    const float* lse;
+    float* W; int ldw;              /* out: fp32 [B,H,T,ldw], ldw >= S */
+    int B, H, T, S, dh, dhp;
+    int mask_off;
+    int q_pos0, q_stride;
+    int64_t head_stride, batch_stride;  /* elements between the maps of consecutive heads / samples */
+} bpm_attn_head_map_problem;
+int bpm_attn_head_maps(int dtype, const bpm_attn_head_map_problem* probs /* host */, int nprob, void* stream);
+int bpm_attn_head_maps_kmask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                             int nprob, void* stream);
+int bpm_attn_head_maps_amask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_amask* masks /* host */,
+                             int nprob, void* stream);
+int bpm_attn_head_maps_hmask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_hmask* masks /* host */,
+                             int nprob, void* stream);
+int bpm_attn_head_maps_kamask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                              const bpm_attn_hmask* masks /* host */, int nprob, void* stream);
+
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,
  * problem arrays live in HOST memory and are copied into the kernel arguments.

@@ -10,6 +10,9 @@ shapes -- six lock-stepped encoders, B=8, H=12 heads of 64, T=S=512, future mask
 forward launch of the same shapes in the same run -- it does one of the forward's two products and the same exponentials,
 so the forward time is its yardstick.  Shapes on record: the default (headline), the kernel point
 `--H 6 --dh 128 --T 50 --S 50 --B 64`, and head_dim 256 `--H 6 --dh 256`.
+--maps --per-head: the per-head launch too (bpm_attn_head_maps: fp32 [B, H, T, S] out, H times the bytes), alternating with
+the averaged launch and the forward in the same three rounds; reports the bytes written and the achieved store rate of both
+(profiles/head_maps_lab.json holds the three shapes above).
 
 --amask: also the additive-mask entries (bpm_attn_fwd_amask / _bwd_dq_amask / _bwd_dkv_amask) at the same shapes in the same
 run, twice: with an all-zeros [T, S] mask on top of the same mask_off rule (the unmasked launches' arithmetic plus the mask
@@ -67,6 +70,7 @@ def main():
     ap.add_argument("--drop-encoders", type=int, default=2, help="how many of the G encoders have attention dropout")
     ap.add_argument("--no-mask", action="store_true")
     ap.add_argument("--maps", action="store_true", help="also time bpm_attn_maps at the same shapes (after the forward has written LSE)")
+    ap.add_argument("--per-head", action="store_true", help="with --maps: also time bpm_attn_head_maps on the same buffers")
     ap.add_argument("--amask", action="store_true", help="also time the *_amask entries (all-zeros mask; the future mask as a tensor)")
     ap.add_argument("--kamask", action="store_true", help="also time the *_kamask entries beside the *_kmask and *_hmask entries")
     ap.add_argument("--f32", action="store_true", help="float32 instead of bfloat16")
@@ -166,16 +170,35 @@ def main():
         marr = ops.array(ops.AttnMapProblem, mp)
         ops.attn_fwd(DT, arr, 5)
         rounds = []
+        if a.per_head:
+            hts = [torch.empty(B, H, T, S, device=dev) for _ in range(G)]
+            harr = ops.array(ops.AttnHeadMapProblem, [ops.attn_head_map_problem(t["q"], t["k"], t["lse"], w, S, B, H, T, S, dh, dhp, off)
+                                                      for t, w in zip(keep, hts)])
         for _ in range(3):
-            rounds.append((_time(lambda: ops.attn_fwd(DT, arr, 5), a.iters), _time(lambda: ops.attn_maps(DT, marr), a.iters)))
+            rounds.append((_time(lambda: ops.attn_fwd(DT, arr, 5), a.iters), _time(lambda: ops.attn_maps(DT, marr), a.iters))
+                          + ((_time(lambda: ops.attn_head_maps(DT, harr), a.iters),) if a.per_head else ()))
         f_us, m_us = sorted(r[0] for r in rounds)[1], sorted(r[1] for r in rounds)[1]
         out_bytes = G * B * T * S * 4
         in_bytes = G * B * H * ((T + S) * dhp * 2 + T * 4)
         rowsum = float((wts[0].double().sum(-1) - 1.0).abs().max())
         res["maps"] = {"us": round(m_us, 1), "fwd_us_same_run": round(f_us, 1), "maps_over_fwd": round(m_us / f_us, 3),
-                       "rounds_fwd_maps_us": [[round(x, 1) for x in r] for r in rounds],
+                       ("rounds_fwd_maps_head_us" if a.per_head else "rounds_fwd_maps_us"): [[round(x, 1) for x in r] for r in rounds],
                        "out_mbytes": round(out_bytes / 1e6, 1), "hbm_gbytes_per_s": round((out_bytes + in_bytes) / m_us / 1e3, 1),
-                       "tflops": round(2 * dh * B * H * G * T * S / m_us / 1e6, 1), "max_row_sum_error": rowsum}
+                       "tflops": round(2 * dh * B * H * G * T * S / m_us / 1e6, 1), "max_row_sum_error": rowsum,
+                       "store_gbytes_per_s": round(out_bytes / m_us / 1e3, 1)}
+        if a.per_head:
+            h_us = sorted(r[2] for r in rounds)[1]
+            mean = torch.zeros_like(wts[0])
+            for h in range(H):
+                mean += hts[0][:, h]
+            mean *= torch.ones((), device=dev) / H
+            res["head_maps"] = {"us": round(h_us, 1), "maps_us_same_run": round(m_us, 1), "head_over_maps": round(h_us / m_us, 3),
+                                "head_over_fwd": round(h_us / f_us, 3), "out_mbytes": round(H * out_bytes / 1e6, 1),
+                                "store_gbytes_per_s": round(H * out_bytes / h_us / 1e3, 1),
+                                "hbm_gbytes_per_s": round((H * out_bytes + in_bytes) / h_us / 1e3, 1),
+                                "tflops": round(2 * dh * B * H * G * T * S / h_us / 1e6, 1),
+                                "max_row_sum_error": float((hts[0].double().sum(-1) - 1.0).abs().max()),
+                                "head_sum_bit_equal_to_maps": bool(torch.equal(mean, wts[0]))}
     print(json.dumps(res))
 
 

@@ -81,11 +81,16 @@ def tree_kernels(root, jobs, tmp):
     tag = hashlib.sha1(os.path.abspath(root).encode()).hexdigest()[:8]
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         asms = list(ex.map(lambda f: compile_asm(os.path.join(csrc, f), os.path.join(tmp, f"{tag}_{f[:-4]}.s")), files))
-    found = {}
+    seen = {}
     for f, asm in zip(files, asms):
         for name, (code, desc) in kernels_of(asm).items():
-            assert name not in found, f"{name} in {found[name]['file']} and {f}"
-            found[name] = {"file": f, "code": code, "desc": desc}
+            seen.setdefault(name, []).append({"file": f, "code": code, "desc": desc})
+    # a kernel of a shared header (unnamed namespace) that several files instantiate has one symbol per file: those are
+    # matched as symbol@file
+    found = {}
+    for name, ks in seen.items():
+        for k in ks:
+            found[name if len(ks) == 1 else f"{name}@{k['file']}"] = k
     return found
 
 
