@@ -32,7 +32,9 @@
 // whole 128-byte stages inside their zero-padded rows (checked by the dispatcher).
 
 constexpr int BPM_EPI_AHEAD = 1;       // 16-row epilogue steps whose side operands are in flight ahead of their use (8-wave configurations)
-constexpr int BPM_DMA_EARLY = 1;       // see the k loop
+#ifndef BPM_DMA_EARLY
+#define BPM_DMA_EARLY 1       // see the k loop; lab builds: 0 never, 2 the 16-wave configuration only (weight gradients spread like NT)
+#endif
 #ifndef BPM_DMA_ABLATE
 #define BPM_DMA_ABLATE 0      // lab builds only (tools/gemm_lab.py): 1 no MFMA, 2 no DMA in the loop, 4 no epilogue
 #endif
@@ -56,6 +58,35 @@ template <int N> BPM_DEV void dma_wait() {
     static_assert(N >= 0 && N < 64, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+
+// One LDS-DMA piece: 64 lanes x 16 bytes from (descriptor, per-lane byte offset voff, wave-uniform byte offset soff)
+// to LDS bytes lds + 16 * lane.  Inline asm, not __builtin_amdgcn_raw_ptr_buffer_load_lds: the compiler's wait-count
+// pass tracks a builtin LDS-DMA as a pending LDS write and puts `s_waitcnt vmcnt(0)` in front of the next LDS read it
+// cannot tell apart from it -- every ds_read_b64_tr_b16 of a k-strided operand (the builtin carries no memory operand),
+// i.e. in the middle of each TN / NN stage, which drained the stage ring there (tools/gemm_dma_loop_waits.py lists
+// them).  An asm statement it does not count: the k loop's dma_wait<N> + barrier are the only
+// synchronisation of the ring, as they were meant to be.  Its own counted waits for ordinary loads (epilogue side
+// operands) stay correct: vector loads return in order, so a vmcnt(N) that does not know of older outstanding pieces
+// only waits for more.
+// Wait states the compiler does not insert around an asm statement: 1 between the M0 write and the LDS-DMA that reads
+// it (`s_nop 0`); 5 between a VALU write of an SGPR (v_readfirstlane feeding an "s" operand) and the VMEM instruction
+// that reads it (`s_nop 2` + the two instructions behind it).
+typedef u32x4 dma_rsrc_t;
+// the words of __builtin_amdgcn_make_buffer_rsrc(p, 0, bytes, 0x00020000): 48-bit base, stride 0 (raw buffer), range
+// check on the byte offset against `bytes`
+BPM_DEV dma_rsrc_t dma_rsrc(const void* p, int bytes) {
+    const uint64_t a = (uint64_t)p;
+    return dma_rsrc_t{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, (uint32_t)bytes, 0x00020000u};
+}
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"       // "clobber list contains reserved registers: m0": it is written, so it is listed
+BPM_DEV void dma_issue(dma_rsrc_t rsrc, const char* lds, int voff, int soff) {
+    typedef __attribute__((address_space(3))) const char* ldsp;
+    const uint32_t dst = (uint32_t)(uintptr_t)(ldsp)lds;
+    asm volatile("s_nop 2\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+                 ::"s"(dst), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
+}
+#pragma clang diagnostic pop
 
 // ---------------------------------------------------------------------------
 // Wide epilogue.  The MFMA leaves a lane with 4 consecutive n of 16 different rows per instruction, so a direct store
@@ -210,12 +241,10 @@ struct DmaSide {
     }
     static BPM_DEV int stage_step(int ld) { return KCONTIG ? ROWB : DKT * ld * 2; }
 
-    // DMA instruction j of this wave for one stage (soff: byte offset of the stage's k position).  A __device__
-    // function: with the LDS-DMA builtin directly in the kernel's lambda the host pass silently drops the kernel stub.
+    // DMA instruction j of this wave for one stage (soff: byte offset of the stage's k position)
     template <int J>
-    static BPM_DEV void issue_one(__amdgpu_buffer_rsrc_t rsrc, char* img, int voff, int soff, int ld, int wave) {
-        typedef __attribute__((address_space(3))) void* ldsp;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (ldsp)(img + piece_lds(wave, J)), 16, voff, soff + piece_goff(ld, J), 0, 0);
+    static BPM_DEV void issue_one(dma_rsrc_t rsrc, char* img, int voff, int soff, int ld, int wave) {
+        dma_issue(rsrc, img + piece_lds(wave, J), voff, soff + piece_goff(ld, J));
     }
 
     // MFMA operand of the 16 rows starting at r0 (multiple of 16), k-step ks (0 / 1) of the stage
@@ -234,13 +263,35 @@ struct DmaSide {
         for (int j = 0; j < 4; ++j) { f[j] = lo[j]; f[4 + j] = hi[j]; }
         return f;
     }
+
+    // The same k-strided fragment from ONE per-lane register (the 16-wave configuration, 128 registers): frag() keeps a
+    // swizzled address per fragment and half alive across the loop -- 16 registers when both operands are k-strided,
+    // which spilled, and the reloads' waits drained the stage ring.  Every lane-dependent term of the address is
+    // col_lane(); 16 rows further is 2 chunks further and the next sub-image 2^14 bytes, both wave-uniform bits that
+    // XOR in (the swizzle only XORs chunk bits; a lane's k-row offset stays below the sub-image size), and the half 4
+    // k-rows on differs by 1 KB and chunk bit 0 (k0 + 4: (k >> 2) & 3 goes from 0 / 2 to 1 / 3).
+    static BPM_DEV int col_lane(int lane) {
+        const int r = lane & 15, g = lane >> 4;
+        return dma_col_off(8 * g + (r >> 2), (r & 3) >> 1) + 8 * (r & 1);
+    }
+    static BPM_DEV bf16x8 frag_lane(const char* img, int lb, int r0, int ks) {
+        static_assert(KCONTIG || DKT == 64, "a sub-image is 2^14 bytes");
+        typedef bf16x4 __attribute__((address_space(3))) * lds4;
+        const int c = (r0 >> 7) * SUB_BYTES | (((r0 & 127) >> 3) << 4);       // wave-uniform
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(img + (lb ^ c) + 8192 * ks));
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(img + (lb ^ c ^ 16) + 8192 * ks + 1024));
+        bf16x8 f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { f[j] = lo[j]; f[4 + j] = hi[j]; }
+        return f;
+    }
 };
 
 // Part Q (0..3) of a stage's DMA instructions: the X pieces then the Y pieces of this wave, dealt over four quarters
 // of the stage's MFMA work so that the issue cost of a DMA (tens of cycles each, MI355X_MICROARCH cycle constants)
 // is spread between MFMA groups instead of heading the stage.
 template <typename SX, typename SY, int Q, int F = 0>
-BPM_DEV void dma_issue_part(__amdgpu_buffer_rsrc_t rsx, __amdgpu_buffer_rsrc_t rsy, char* bx, int vx, int vy, int sx, int sy,
+BPM_DEV void dma_issue_part(dma_rsrc_t rsx, dma_rsrc_t rsy, char* bx, int vx, int vy, int sx, int sy,
                             int ldx, int ldy, int wave) {
     constexpr int LPS = SX::PER_WAVE + SY::PER_WAVE;
     if constexpr (F < LPS) {
@@ -295,8 +346,8 @@ void gemm_dma_kernel(const Group grp) {
     // buffer then never reads past the parent's last row (rows * ld from the view's first element would)
     // (X3: a split image is a whole allocation of rows x ld elements with zero pad columns in both planes: the range check
     // only has to cut off rows past M / N and k-rows past K)
-    const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)P.X, 0, X3 ? (XK ? P.M : P.K) * P.ldx * 2 : desc_bytes(XK ? P.M : P.K, P.ldx, XK ? nkt * DKT : (P.M + 7) & ~7, 2, (P.flags & BPM_GEMM_A_OVERLAP) != 0), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)P.Y, 0, X3 ? (YK ? P.N : P.K) * P.ldy * 2 : desc_bytes(YK ? P.N : P.K, P.ldy, YK ? nkt * DKT : (P.N + 7) & ~7, 2, (P.flags & BPM_GEMM_B_OVERLAP) != 0), 0x00020000);
+    const dma_rsrc_t rsx = dma_rsrc(P.X, X3 ? (XK ? P.M : P.K) * P.ldx * 2 : desc_bytes(XK ? P.M : P.K, P.ldx, XK ? nkt * DKT : (P.M + 7) & ~7, 2, (P.flags & BPM_GEMM_A_OVERLAP) != 0));
+    const dma_rsrc_t rsy = dma_rsrc(P.Y, X3 ? (YK ? P.N : P.K) * P.ldy * 2 : desc_bytes(YK ? P.N : P.K, P.ldy, YK ? nkt * DKT : (P.N + 7) & ~7, 2, (P.flags & BPM_GEMM_B_OVERLAP) != 0));
     const int vx = SX::voffset(P.ldx, m0, wave, lane), vy = SY::voffset(P.ldy, n0, wave, lane);
     const int stepx = SX::stage_step(P.ldx), stepy = SY::stage_step(P.ldy);
     const int ldx = P.ldx, ldy = P.ldy;
@@ -334,9 +385,27 @@ void gemm_dma_kernel(const Group grp) {
     for (int s = 0; s < NS - 1; ++s)
         if (s < nkt) stage(s, s);
 
+    // 16 waves, both operands k-strided: fragment addresses from one register (DmaSide::frag_lane), made opaque in every
+    // iteration so that the per-fragment addresses are not hoisted out of the loop and kept in registers after all
+    constexpr bool LANE_FRAG = NW == 16 && !XK && !YK;
+    [[maybe_unused]] int flane = SX::col_lane(lane);
+
+    // Synchronisation of the ring -- all of it by hand: the LDS-DMA pieces are asm statements (dma_issue) that the
+    // compiler's wait-count pass does not see, so it adds no vmcnt wait of its own to this loop
+    // (tools/gemm_dma_loop_waits.py checks the assembly of every instantiation).  Stage s lives in buffer s % NS.
+    //   read after write: a wave's pieces complete in order, so at the top of iteration kt `dma_wait<N>` with N = this
+    //     wave's pieces of the stages younger than kt (NS == 3: one stage, LPS pieces, while one follows; else 0) leaves
+    //     its share of stage kt landed; the barrier behind it does the same for every other wave's share.  Only then
+    //     are fragments of buffer kt % NS read.
+    //   write after read: stage kt + NS - 1 goes to the buffer stage kt - 1 was read from.  Every wave's reads of it
+    //     were issued in iteration kt - 1 and have returned at `lgkmcnt(0)` before the same barrier; the refill is
+    //     issued behind that barrier.  (The fragments of iteration kt are consumed by MFMAs the compiler orders with
+    //     its own lgkmcnt waits: LDS reads are its loads, counted as before.)
+    //   epilogue: `dma_wait<0>` behind the loop, then a barrier before the stage buffers become transpose blocks.
     int buf = 0;
 #pragma unroll 1
     for (int kt = 0; kt < nkt; ++kt) {
+        if constexpr (LANE_FRAG) asm volatile("" : "+v"(flane));
         if (kt == 1) BPM_TRACE_CLK(2);                               // first stage consumed: the pipeline is full
         // stage kt has landed once at most the younger stages' DMAs are outstanding (this wave's share), and for the
         // other waves' shares once every wave has passed the barrier behind that wait
@@ -356,10 +425,18 @@ void gemm_dma_kernel(const Group grp) {
             // reads cost: FFN weight gradients 279 -> 320 us, so those keep all four fragments up front)
             constexpr bool YLATE = DKT == 32 && XS;
             bf16x8 fx[TMW], fy[4];
+            auto xfrag = [&](int b) {
+                if constexpr (LANE_FRAG && !XK) return SX::frag_lane(ix, flane, wm * WROWS + 16 * b, ks);
+                else return SX::frag(ix, wm * WROWS + 16 * b, ks, lane);
+            };
+            auto yfrag = [&](int a) {
+                if constexpr (LANE_FRAG && !YK) return SY::frag_lane(iy, flane, wn * 64 + 16 * a, ks);
+                else return SY::frag(iy, wn * 64 + 16 * a, ks, lane);
+            };
 #pragma unroll
-            for (int b = 0; b < TMW; ++b) fx[b] = SX::frag(ix, wm * WROWS + 16 * b, ks, lane);
+            for (int b = 0; b < TMW; ++b) fx[b] = xfrag(b);
 #pragma unroll
-            for (int a = 0; a < (YLATE ? 2 : 4); ++a) fy[a] = SY::frag(iy, wn * 64 + 16 * a, ks, lane);
+            for (int a = 0; a < (YLATE ? 2 : 4); ++a) fy[a] = yfrag(a);
             if constexpr (XS) {
                 if (do_xs && seg_of(kt) != 1) {            // (X3: segments 0 and 2 carry X's hi and lo planes; segment 1 repeats hi)
                     bf16x8 one;
@@ -372,7 +449,7 @@ void gemm_dma_kernel(const Group grp) {
             }
             // 1: the 16-wave configuration and the weight-gradient product request the whole next stage right behind the
             // barrier (4 / 8 DMAs per wave) instead of a quarter of it between MFMA groups
-            constexpr bool EARLY = BPM_DMA_EARLY != 0 && (NW == 16 || (!XK && !YK));
+            constexpr bool EARLY = BPM_DMA_EARLY != 0 && (NW == 16 || (BPM_DMA_EARLY == 1 && !XK && !YK));
             if (more && !(BPM_DMA_ABLATE & 2)) {
                 if constexpr (EARLY) {
                     if (ks == 0) stage(kt + NS - 1, nbuf);
@@ -389,7 +466,7 @@ void gemm_dma_kernel(const Group grp) {
             }
             if constexpr (YLATE) {
 #pragma unroll
-                for (int a = 2; a < 4; ++a) fy[a - 2] = SY::frag(iy, wn * 64 + 16 * a, ks, lane);
+                for (int a = 2; a < 4; ++a) fy[a - 2] = yfrag(a);
             }
 #pragma unroll
             for (int a = 2; a < 4; ++a)
