@@ -18,7 +18,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BPMULT_LIB", os.path.join(_HERE, "libbpmult_hip.so"))   # override: kernel-variant experiments
 SOURCES = ("gemm.hip", "attention.hip", "attn_maps.hip", "attn_dbias.hip", "rows_pack.hip", "rows_norm.hip", "rows_elem.hip", "adam.hip", "bert_embed.hip", "loss.hip", "eval.hip", "tail.hip", "frontend.hip", "prof.hip")
-HEADERS = ("bpm_common.h", "bpm_launch.h", "bpm_prof.h", "gemm_dma.h", "rows_common.h", "attn_common.h")
+HEADERS = ("bpm_common.h", "bpm_launch.h", "bpm_prof.h", "gemm_dma.h", "rows_common.h", "attn_common.h",
+           "attn_maps_body.inc", "attn_head_maps_body.inc", "attn_dbias_body.inc")
 ARCH = "gfx950"
 PROF_KINDS = {"gemm_nt": 0, "gemm_nn": 1, "gemm_tn": 2, "attn_fwd": 3, "attn_bwd_dq": 4, "attn_bwd_dkv": 5,
               "gemm_dma_nt": 13, "gemm_dma_nn": 14, "gemm_dma_tn": 15, "attn_maps": 16, "attn_bwd_dbias": 17}      # gemm_*: the 128 x 64 kernel; gemm_dma_*: the LDS-DMA kernel
@@ -153,6 +154,14 @@ class AttnHMask(C.Structure):
 
 class AttnDBias(C.Structure):
     _fields_ = [("dB", C.c_void_p), ("lddb", C.c_int), ("head_stride", C.c_int64)]
+
+
+class AttnBMask(C.Structure):        # bpm_attn_bmask: AttnHMask plus the two sample strides
+    _fields_ = AttnHMask._fields_ + [("batch_stride", C.c_int64), ("batch_strideT", C.c_int64)]
+
+
+class AttnDBiasB(C.Structure):       # bpm_attn_dbias_b
+    _fields_ = AttnDBias._fields_ + [("batch_stride", C.c_int64)]
 
 
 class GeluProblem(C.Structure):
@@ -359,6 +368,19 @@ SIGNATURES = {
     "bpm_attn_head_maps_amask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnAMask), _I, _P],
     "bpm_attn_head_maps_hmask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnHMask), _I, _P],
     "bpm_attn_head_maps_kamask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnHMask), _I, _P],
+    "bpm_attn_fwd_bmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_bmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_bmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_maps_bmask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnBMask), _I, _P],
+    "bpm_attn_head_maps_bmask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnBMask), _I, _P],
+    "bpm_attn_fwd_kbmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_bwd_dq_kbmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_bwd_dkv_kbmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnKMask), C.POINTER(AttnBMask), _I, _U64, _P],
+    "bpm_attn_maps_kbmask": [_I, C.POINTER(AttnMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnBMask), _I, _P],
+    "bpm_attn_head_maps_kbmask": [_I, C.POINTER(AttnHeadMapProblem), C.POINTER(AttnKMask), C.POINTER(AttnBMask), _I, _P],
+    "bpm_attn_bwd_dbias_bmask_ws_bytes": [C.POINTER(AttnProblem), C.POINTER(AttnDBiasB), _I],
+    "bpm_attn_bwd_dbias_bmask": [_I, C.POINTER(AttnProblem), C.POINTER(AttnBMask), C.POINTER(AttnKMask), C.POINTER(AttnDBiasB), _I, _U64, _P,
+                                 C.c_size_t, _P],
     "bpm_gelu_fwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_gelu_bwd": [_I, C.POINTER(GeluProblem), _I, _P],
     "bpm_bert_embed_fwd": [_I, C.POINTER(BertEmbedProblem), _I, _F, _U64, _P],

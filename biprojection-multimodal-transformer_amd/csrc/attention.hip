@@ -103,7 +103,7 @@ BPM_DEV void attn_fwd_block(const AProb& P, const DropCfg& drop, char* smem, con
         if constexpr (KM) stage_mask(0);
     }
     const float* arow = nullptr;                       // AM: this lane's mask row
-    if constexpr (AM) arow = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(q, P.T - 1) * add_of(mk).ld;
+    if constexpr (AM) arow = image_of(add_of(mk), b, h) + (size_t)min(q, P.T - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -319,7 +319,7 @@ BPM_DEV void attn_bwd_dq_block(const AProb& P, const DropCfg& drop, char* smem, 
         if constexpr (KM) stage_mask(0);
     }
     const float* arow = nullptr;                       // AM: this lane's mask row
-    if constexpr (AM) arow = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(q, P.T - 1) * add_of(mk).ld;
+    if constexpr (AM) arow = image_of(add_of(mk), b, h) + (size_t)min(q, P.T - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int kt = 0; kt < ntile; ++kt) {
         __syncthreads();
@@ -499,7 +499,7 @@ BPM_DEV void attn_bwd_dkv_block(const AProb& P, const DropCfg& drop, char* smem,
     };
     if (qt_lo < qt_hi) stage(qt_lo);
     const float* acol = nullptr;                       // AM: this lane's row of the transposed mask
-    if constexpr (AM) acol = add_of(mk).m + (size_t)h * add_of(mk).hs + (size_t)min(j, P.S - 1) * add_of(mk).ld;
+    if constexpr (AM) acol = image_of(add_of(mk), b, h) + (size_t)min(j, P.S - 1) * add_of(mk).ld;
 #pragma unroll 1
     for (int qt = qt_lo; qt < qt_hi; ++qt) {
         __syncthreads();
@@ -617,6 +617,15 @@ struct AGroupA {
 struct AGroupKA : AGroupA {};
 inline void set_byte_mask(AProb& p, const AMask& k) { p.dS = nullptr; p.Pd = (char*)k.mask; p.xs_b = k.ldm; }
 BPM_DEV AMask byte_mask_of(const AProb& p) { return AMask{(const uint8_t*)p.Pd, p.xs_b}; }
+// Per-sample images (the *_bmask / *_kbmask entries): AGroup and 18 x AAddB (24 bytes) are 3616 + 432 = 4048 bytes; the
+// family with key bytes carries them in AProb as AGroupKA does.
+struct AGroupB {
+    AGroup g;
+    AAddB m[BPM_MAX_GROUP];
+};
+struct AGroupKB : AGroupB {};
+static_assert(sizeof(AGroupB) <= 4096, "kernel arguments are limited to 4 KiB");
+static_assert(sizeof(AGroupKB) <= 4096, "kernel arguments are limited to 4 KiB");
 static_assert(sizeof(AGroupK) <= 4096, "kernel arguments are limited to 4 KiB");
 static_assert(sizeof(AGroupKA) <= 4096, "kernel arguments are limited to 4 KiB");
 static_assert(sizeof(AGroupA) <= 4096, "kernel arguments are limited to 4 KiB");
@@ -804,6 +813,57 @@ __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_w
     }
 }
 
+// ... and the last two with one image per sample (bpm_attn_*_bmask / *_kbmask: AAddB, the image of (b, h) at
+// m + b * bs + h * hs).  Instantiations of their own, so the kernels above keep their registers; the sample's offset is one
+// more wave-uniform 64-bit product per block.  Compiled for the occupancy of the sibling above: no instantiation spills
+// more than its sibling does (profiles/attn_bmask_resource_usage.txt).
+template <typename CT, int DHP, int WHICH>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves_am<CT>(WHICH, DHP), attn_waves_am<CT>(WHICH, DHP)))) void attn_bmask_kernel(const AGroupB ga) {
+    typedef Cfg<CT, DHP> C;
+    constexpr int ROWS = WHICH == 0 ? KT : WHICH == 1 ? C::KTQ : C::QTK;
+    __shared__ __attribute__((aligned(16))) char smem[2 * ROWS * C::STRIDE + (WHICH == 2 ? 2 * C::QTK * 4 : 0)];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(ga.g, bid);
+    const AProb& P = ga.g.p[pi];
+    const AAddB am = ga.m[pi];
+    const DropCfg drop = bpm_resolve_drop(P.drop, ga.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2;
+    const int first = (P.pair || WHICH == 2) ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        const int blk = pass ? second : first;
+        if constexpr (WHICH == 0) attn_fwd_block<CT, DHP>(P, drop, smem, bh, blk, am);
+        else if constexpr (WHICH == 1) attn_bwd_dq_block<CT, DHP, false>(P, drop, smem, bh, blk, am);
+        else attn_bwd_dkv_block<CT, DHP>(P, drop, smem, bh, blk, am);
+    }
+}
+template <typename CT, int DHP, int WHICH>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(attn_waves_kam<CT>(WHICH, DHP), attn_waves_kam<CT>(WHICH, DHP)))) void attn_kbmask_kernel(const AGroupKB ga) {
+    typedef Cfg<CT, DHP> C;
+    constexpr int ROWS = WHICH == 0 ? KT : WHICH == 1 ? C::KTQ : C::QTK;
+    __shared__ __attribute__((aligned(16))) char smem[2 * ROWS * C::STRIDE + (WHICH == 2 ? 2 * C::QTK * 4 : ROWS)];
+    if (BPM_BASE_PRIO) __builtin_amdgcn_s_setprio(BPM_BASE_PRIO);
+    int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int pi = pick_index(ga.g, bid);
+    const AProb& P = ga.g.p[pi];
+    const AKAddB kam = AKAddB{byte_mask_of(P), ga.m[pi]};
+    const DropCfg drop = bpm_resolve_drop(P.drop, ga.g.seedp);
+    const int nb2 = P.pair ? (P.nblk + 1) >> 1 : P.nblk;
+    const int bh = bid / nb2;
+    const int first = (P.pair || WHICH == 2) ? bid % nb2 : P.nblk - 1 - bid % nb2, second = P.pair ? P.nblk - 1 - first : first;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass && second == first) break;
+        const int blk = pass ? second : first;
+        if constexpr (WHICH == 0) attn_fwd_block<CT, DHP>(P, drop, smem, bh, blk, kam);
+        else if constexpr (WHICH == 1) attn_bwd_dq_block<CT, DHP, false>(P, drop, smem, bh, blk, kam);
+        else attn_bwd_dkv_block<CT, DHP>(P, drop, smem, bh, blk, kam);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host side.  Every entry is check (attn_common.h) / fill / choose / launch.
 // ---------------------------------------------------------------------------
@@ -850,7 +910,9 @@ int fill(AGroup& g, const bpm_attn_problem* probs, int nprob, uint64_t seed, int
 
 // the two mask arrays of a *_kamask entry as one argument of the shared shape (fill_masked / attn_masked)
 struct KAMasks { const bpm_attn_kmask* k; const bpm_attn_hmask* a; };
+struct KBMasks { const bpm_attn_kmask* k; const bpm_attn_bmask* a; };      // ... of a *_kbmask entry
 inline bool masks_given(const KAMasks* m) { return m->k && m->a; }
+inline bool masks_given(const KBMasks* m) { return m->k && m->a; }
 inline bool masks_given(const void* m) { return m != nullptr; }
 
 // fill of a masked launch (A: AGroupK with bpm_attn_kmask masks, AGroupA with bpm_attn_hmask masks, AGroupKA with both as
@@ -873,6 +935,13 @@ int fill_masked(A& a, int dtype, const bpm_attn_problem* probs, const MK* masks,
             if ((rc = kmask_desc(k, masks->k[i], q.S)) != 0) return rc;
             if ((rc = amask_desc(a.m[i], masks->a[i], q.T, q.S, which == 2)) != 0) return rc;
             set_byte_mask(a.g.p[i], k);
+        } else if constexpr (std::is_same_v<A, AGroupKB>) {
+            AMask k;
+            if ((rc = kmask_desc(k, masks->k[i], q.S)) != 0) return rc;
+            if ((rc = bmask_desc(a.m[i], masks->a[i], q.H, q.T, q.S, which == 2)) != 0) return rc;
+            set_byte_mask(a.g.p[i], k);
+        } else if constexpr (std::is_same_v<A, AGroupB>) {
+            if ((rc = bmask_desc(a.m[i], masks[i], q.H, q.T, q.S, which == 2)) != 0) return rc;
         } else if ((rc = amask_desc(a.m[i], masks[i], q.T, q.S, which == 2)) != 0) return rc;
     }
     for (int i = nprob; i < BPM_MAX_GROUP; ++i) a.m[i] = {};
@@ -904,6 +973,8 @@ template <typename A, typename CT, int D, int WHICH, bool XP = false>
 constexpr auto attn_kernel() {
     if constexpr (std::is_same_v<A, AGroupA>) return &attn_amask_kernel<CT, D, WHICH>;
     else if constexpr (std::is_same_v<A, AGroupKA>) return &attn_kamask_kernel<CT, D, WHICH>;
+    else if constexpr (std::is_same_v<A, AGroupB>) return &attn_bmask_kernel<CT, D, WHICH>;
+    else if constexpr (std::is_same_v<A, AGroupKB>) return &attn_kbmask_kernel<CT, D, WHICH>;
     else if constexpr (std::is_same_v<A, AGroupK>)
         return WHICH == 0 ? &attn_fwd_kmask_kernel<CT, D> : WHICH == 1 ? &attn_bwd_dq_kmask_kernel<CT, D> : &attn_bwd_dkv_kmask_kernel<CT, D>;
     else if constexpr (WHICH == 1) return &attn_bwd_dq_kernel<CT, D, XP>;
@@ -932,7 +1003,10 @@ int attn_masked(int which, int kind, int dtype, const bpm_attn_problem* probs, c
     int rc = fill_masked(a, dtype, probs, masks, nprob, seed, &total, which);
     if (rc) return rc;
     double mbytes = 0;
-    if constexpr (!std::is_same_v<A, AGroupK>)
+    if constexpr (std::is_same_v<A, AGroupB> || std::is_same_v<A, AGroupKB>) {      // one image per sample and / or head that has its own
+        for (int i = 0; i < nprob; ++i)
+            mbytes += 4.0 * probs[i].T * probs[i].S * (a.m[i].bs ? probs[i].B : 1) * (a.m[i].hs ? probs[i].H : 1);
+    } else if constexpr (!std::is_same_v<A, AGroupK>)
         for (int i = 0; i < nprob; ++i) mbytes += 4.0 * probs[i].T * probs[i].S;
     BpmProfScope prof(kind, (hipStream_t)stream, 4.0 * useful_pair_flops(probs, nprob),
                       attn_bytes(probs, nprob, dtype == BPM_BF16 ? 2 : 4, which) + mbytes);
@@ -1043,4 +1117,31 @@ extern "C" int bpm_attn_bwd_dkv_kamask(int dtype, const bpm_attn_problem* probs,
                                        uint64_t seed, void* stream) {
     const KAMasks m{kmasks, masks};
     return attn_masked<AGroupKA>(2, BPM_K_ATTN_BWD_DKV, dtype, probs, &m, nprob, seed, stream);
+}
+
+// Attention with one additive image per sample (and per head): see bpm_attn_bmask in include/bpmult_hip.h.  Kernels of
+// their own (attn_bmask_kernel / attn_kbmask_kernel); at batch stride 0 the bits of the *_hmask / *_kamask entries.
+extern "C" int bpm_attn_fwd_bmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_bmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_masked<AGroupB>(0, BPM_K_ATTN_FWD, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dq_bmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_bmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_masked<AGroupB>(1, BPM_K_ATTN_BWD_DQ, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dkv_bmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_bmask* masks, int nprob, uint64_t seed, void* stream) {
+    return attn_masked<AGroupB>(2, BPM_K_ATTN_BWD_DKV, dtype, probs, masks, nprob, seed, stream);
+}
+extern "C" int bpm_attn_fwd_kbmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_bmask* masks, int nprob,
+                                   uint64_t seed, void* stream) {
+    const KBMasks m{kmasks, masks};
+    return attn_masked<AGroupKB>(0, BPM_K_ATTN_FWD, dtype, probs, &m, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dq_kbmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_bmask* masks, int nprob,
+                                      uint64_t seed, void* stream) {
+    const KBMasks m{kmasks, masks};
+    return attn_masked<AGroupKB>(1, BPM_K_ATTN_BWD_DQ, dtype, probs, &m, nprob, seed, stream);
+}
+extern "C" int bpm_attn_bwd_dkv_kbmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_bmask* masks, int nprob,
+                                       uint64_t seed, void* stream) {
+    const KBMasks m{kmasks, masks};
+    return attn_masked<AGroupKB>(2, BPM_K_ATTN_BWD_DKV, dtype, probs, &m, nprob, seed, stream);
 }

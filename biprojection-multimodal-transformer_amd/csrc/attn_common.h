@@ -96,12 +96,25 @@ struct AAdd { const float* m; int ld; int hs; };
 // know of each other.  byte_of / add_of: the part of a descriptor a body reads (a reference to the descriptor itself for
 // the two single types, so their instantiations see the same value they always did).
 struct AKAdd { AMask k; AAdd a; };
-template <typename M> constexpr bool has_bytes = std::is_same_v<M, AMask> || std::is_same_v<M, AKAdd>;
-template <typename M> constexpr bool has_add = std::is_same_v<M, AAdd> || std::is_same_v<M, AKAdd>;
+
+// Per-sample additive images (the *_bmask / *_kbmask entries: torch's 3-D attn_mask [B*H, T, S], a time-distance bias): AAdd
+// plus bs, the elements between the images of consecutive samples -- (sample b, head h) reads m + b * bs + h * hs; the four
+// combinations of zero and non-zero strides are the images [T, S], [H, T, S], [B, 1, T, S] and [B, H, T, S].  A descriptor
+// type of its own with its own instantiations: the kernels that take AAdd keep their arguments and their code.
+struct AAddB { const float* m; int ld; int hs; int bs; };
+struct AKAddB { AMask k; AAddB a; };
+template <typename M> constexpr bool has_bytes = std::is_same_v<M, AMask> || std::is_same_v<M, AKAdd> || std::is_same_v<M, AKAddB>;
+template <typename M> constexpr bool has_add = std::is_same_v<M, AAdd> || std::is_same_v<M, AKAdd> || std::is_same_v<M, AAddB> || std::is_same_v<M, AKAddB>;
 BPM_DEV const AMask& byte_of(const AMask& m) { return m; }
 BPM_DEV const AMask& byte_of(const AKAdd& m) { return m.k; }
+BPM_DEV const AMask& byte_of(const AKAddB& m) { return m.k; }
 BPM_DEV const AAdd& add_of(const AAdd& m) { return m; }
 BPM_DEV const AAdd& add_of(const AKAdd& m) { return m.a; }
+BPM_DEV const AAddB& add_of(const AAddB& m) { return m; }
+BPM_DEV const AAddB& add_of(const AKAddB& m) { return m.a; }
+// the image (sample b, head h) reads: its first element (offsets in 64 bits)
+BPM_DEV const float* image_of(const AAdd& a, int, int h) { return a.m + (size_t)h * a.hs; }
+BPM_DEV const float* image_of(const AAddB& a, int b, int h) { return a.m + (size_t)b * a.bs + (size_t)h * a.hs; }
 
 // The byte-mask switch of the maps and bias-gradient kernels (attn_maps.hip, attn_dbias.hip): it rides in the compute-type
 // argument -- attn_maps_kernel<WithBytes<bf16_t>, 64, ...> -- so the instantiations without it keep their template
@@ -327,6 +340,27 @@ inline int amask_desc(AAdd& a, const bpm_attn_hmask& m, int T, int S, bool trans
     a.hs = (int)hs;
     return 0;
 }
+
+// One per-sample mask (bpm_attn_bmask): the rules of amask_desc for the image(s) of one sample, and for a non-zero batch
+// stride those of a head stride one level up: a multiple of 4 elements, at least the images of one sample long (H head
+// strides, or one image when the head stride is 0), and within 31 bits.
+inline int bmask_desc(AAddB& a, const bpm_attn_bmask& m, int H, int T, int S, bool transposed) {
+    AAdd one;
+    const bpm_attn_hmask hm{m.mask, m.ldm, m.maskT, m.ldt, m.head_stride, m.head_strideT};
+    const int rc = amask_desc(one, hm, T, S, transposed);
+    if (rc) return rc;
+    auto stride_ok = [&](int64_t bs, int64_t hs, int64_t image) {
+        return bs == 0 || (!(bs & 3) && bs <= 0x7fffffff && bs >= (hs != 0 ? (int64_t)H * hs : image));
+    };
+    if (!stride_ok(m.batch_stride, m.head_stride, (int64_t)T * m.ldm)) return BPM_ERR_ARG;
+    if (transposed && !stride_ok(m.batch_strideT, m.head_strideT, (int64_t)S * m.ldt)) return BPM_ERR_ARG;
+    a = AAddB{one.m, one.ld, one.hs, (int)(transposed ? m.batch_strideT : m.batch_stride)};
+    return 0;
+}
+
+// either of the two, by the descriptor's type (the fills that serve both families)
+inline int image_desc(AAdd& a, const bpm_attn_hmask& m, int, int T, int S, bool transposed) { return amask_desc(a, m, T, S, transposed); }
+inline int image_desc(AAddB& a, const bpm_attn_bmask& m, int H, int T, int S, bool transposed) { return bmask_desc(a, m, H, T, S, transposed); }
 
 // One byte mask as the kernels read it: bytes [B, ldm], ldm >= S (the kernels never read at j >= S: a tight [B, S] is legal).
 inline int kmask_desc(AMask& k, const bpm_attn_kmask& m, int S) {

@@ -78,155 +78,44 @@ constexpr int dbias_waves_kb(int dhp) {
     return dbias_waves<CT>(dhp) - (lower ? 1 : 0);
 }
 
+// PS (bpm_attn_bwd_dbias_bmask): per-sample masks and the per-sample result forms.  DProb plus the sample stride of the
+// mask, the map (image, term) -> head that replaces per_head, and the second stride of the result -- in an argument
+// block of its own (the byte masks ride in it; KB stays the switch), so the kernels above keep their arguments and code:
+//   result    images     terms of an image      head b*H + h of (img, t)      imul, tmul     image img is written at
+//   [T,S]     1          the B*H heads          t                             0, 1           0
+//   [H,T,S]   H          the B samples          t*H + img                     1, H           img*ohs
+//   [B,1,T,S] B          the H heads            img*H + t                     H, 1           img*obs
+//   [B,H,T,S] B*H        1                      img                           1, 0           (img / H)*obs + (img % H)*ohs
+// The terms of an image are added in ascending t, as in the kernel without PS: at batch strides 0 the same bits.
+struct DProbB : DProb {
+    int mbs;                                // elements between the mask images of consecutive samples
+    int imul, tmul;                         // head of (img, t) = img * imul + t * tmul
+    int odiv; long obs;                     // image img at out + (img / odiv) * obs + (img % odiv) * ohs
+};
+struct DGroupB {
+    const uint64_t* seedp;
+    int nprob;
+    DProbB p[BPM_MAX_GROUP];
+    AMask k[BPM_MAX_GROUP];
+};
+static_assert(sizeof(DGroupB) <= 4096, "kernel arguments are limited to 4 KiB");
+
 BPM_DEV const DGroup& dbias_group(const DGroup& g) { return g; }
 BPM_DEV const DGroup& dbias_group(const DGroupK& g) { return g.g; }
+BPM_DEV const DGroupB& dbias_group(const DGroupB& g) { return g; }
 template <typename CTX>
 constexpr int dbias_waves_x(int dhp) {
     return CtOf<CTX>::bytes ? dbias_waves_kb<typename CtOf<CTX>::type>(dhp) : dbias_waves<typename CtOf<CTX>::type>(dhp);
 }
 
-// CTX: the compute type, or WithBytes<compute type> for KB
 template <typename CTX, int DHP>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_waves_x<CTX>(DHP), dbias_waves_x<CTX>(DHP)))) void attn_dbias_kernel(const std::conditional_t<CtOf<CTX>::bytes, DGroupK, DGroup> ga) {
-    typedef typename CtOf<CTX>::type CT;
-    constexpr bool KB = CtOf<CTX>::bytes;
-    const DGroup& grp = dbias_group(ga);
-    typedef Cfg<CT, DHP> C;
-    typedef typename Tr<CT>::frag frag;
-    __shared__ __attribute__((aligned(16))) char smem[2 * KT * C::STRIDE + (KB ? KT : 0)];
-    char* kimg = smem;
-    char* vimg = smem + KT * C::STRIDE;
-    uint8_t* smask = (uint8_t*)(smem + 2 * KT * C::STRIDE);    // KB only
-
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int pi = 0;
-#pragma unroll 1
-    for (int i = 1; i < grp.nprob; ++i)
-        if (bid >= grp.p[i].blk0) pi = i;
-    const DProb& P = grp.p[pi];
-    bid -= P.blk0;
-    const DropCfg drop = bpm_resolve_drop(P.drop, grp.seedp);
-    const int kt = bid % P.nkt, qb = (bid / P.nkt) % P.nqt;                 // key tiles of a query tile are neighbours
-    const int rest = bid / (P.nkt * P.nqt), sp = rest % P.nsplit, img = rest / P.nsplit;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int q0 = qb * 64 + wave * 16;               // wave-uniform first query
-    const int q = q0 + c;                             // this lane's query
-    const int jb = kt * KT + 4 * g;                   // key of element (n, r) is jb + 16n + r
-
-    f32x4 acc[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int q_hi = min(P.T, qb * 64 + 64) - 1;
-    const int jend = min(P.S, P.qpos0 + q_hi * P.qstride + P.mask_off);      // one past the last key any query of this tile sees
-    const int lim = min(P.S, P.qpos0 + q * P.qstride + P.mask_off);          // this lane sees keys j < lim
-    const int lim_min = min(P.S, P.qpos0 + q0 * P.qstride + P.mask_off);     // every lane of the wave sees keys j < lim_min
-    const bool edge = kt * KT + KT > lim_min;
-    const int rel = lim - jb;
-    const bool dropping = drop.thresh != 0;
-    const bool pair_ok = (P.S & 3) == 0;               // row starts are multiples of 4: keys (4m .. 4m+3) are one hash quad
-    const int t0 = sp * P.chunk, t1 = min(P.nterm, t0 + P.chunk);
-    auto head_of = [&](int t) { return P.per_head ? t * P.H + img : t; };    // term -> (b * H + h)
-
-    if (kt * KT < jend && t0 < t1) {                   // block-uniform: a tile the mask_off rule hides keeps its zeros
-        RowStage<CT, DHP, KT> kst, vst;
-        uint32_t n_vis = 0;                            // KB, threads < KT: the next head's visibility of key kt * KT + tid
-        auto stage = [&](int t) {
-            const size_t bh = (size_t)head_of(t);
-            kst.load(P.K + bh * P.S * C::ROWB, kt * KT, P.S, tid);
-            vst.load(P.V + bh * P.S * C::ROWB, kt * KT, P.S, tid);
-            if constexpr (KB) {
-                const int jm = kt * KT + tid;
-                n_vis = 0;
-                if (tid < KT && jm < P.S) n_vis = ga.k[pi].mask[(bh / P.H) * ga.k[pi].ldm + jm] != 0;
-            }
-        };
-        stage(t0);
-#pragma unroll 1
-        for (int t = t0; t < t1; ++t) {
-            const int bh = head_of(t), h = bh % P.H;
-            // this head's operands of the lane's query: issued before the barriers, used after them
-            frag qf[C::NKS], dof[C::NKS];
-            const char* Qh = P.Q + (size_t)bh * P.T * C::ROWB;
-            const char* dOh = P.dO + (size_t)bh * P.T * C::ROWB;
-#pragma unroll
-            for (int s = 0; s < C::NKS; ++s) {
-                qf[s] = load_frag<CT, DHP>(Qh, q, P.T, s, g);
-                dof[s] = load_frag<CT, DHP>(dOh, q, P.T, s, g);
-            }
-            const size_t srow = (size_t)bh * P.T + min(q, P.T - 1);
-            const float lse2 = (q < P.T) ? -P.lse[srow] * LOG2E : 0.f;
-            const float delta = (q < P.T) ? P.delta[srow] : 0.f;
-            const float* arow = P.m + (size_t)h * P.mhs + (size_t)min(q, P.T - 1) * P.ldm;
-            f32x4 am4[4];                              // mask of keys kt * KT + 16n + 4g + (0..3)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                const int jc = jb + 16 * n;            // jc % 4 == 0 and ldm % 4 == 0: jc < S implies jc + 3 < ldm
-                am4[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (q < P.T && jc < P.S) am4[n] = *(const f32x4*)(arow + jc);
-            }
-            __syncthreads();                           // every wave is done with the previous head's images
-            kst.store(kimg, tid);
-            vst.store(vimg, tid);
-            if constexpr (KB) { if (tid < KT) smask[tid] = (uint8_t)n_vis; }
-            __syncthreads();
-            if (t + 1 < t1) stage(t + 1);
-            if constexpr (KB) {
-                const uint32_t w = *(const uint32_t*)(smask + 4 * (lane & 15));
-                if (__builtin_amdgcn_ballot_w64(w != 0u) == 0) continue;      // no visible key (the same in every wave)
-            }
-            const uint32_t drow = ((uint32_t)bh * (uint32_t)P.T + (uint32_t)q) * (uint32_t)P.S;
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                f32x4 s_ = f32x4{0.f, 0.f, 0.f, 0.f}, dp = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < C::NKS; ++s) {
-                    s_ = Tr<CT>::mma(read_rowfrag<CT>(kimg, C::STRIDE, 16 * n, s, lane), qf[s], s_);
-                    dp = Tr<CT>::mma(read_rowfrag<CT>(vimg, C::STRIDE, 16 * n, s, lane), dof[s], dp);
-                }
-                s_ += am4[n];
-                float dm[4] = {1.f, 1.f, 1.f, 1.f};
-                if (dropping) {
-                    if (pair_ok) {
-                        bpm_drop_mult4(drop, drow + (uint32_t)(jb + 16 * n), dm[0], dm[1], dm[2], dm[3]);
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) dm[r] = bpm_drop_mult(drop, drow + (uint32_t)(jb + 16 * n + r));
-                    }
-                }
-                f32x4 e4 = s_ * LOG2E + lse2;
-                if (edge) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e4[r] = (16 * n + r < rel) ? e4[r] : -INFINITY;   // exp2(-inf) = 0: masked before the exponential
-                }
-                if constexpr (KB) {
-                    const uint32_t w = *(const uint32_t*)(smask + 16 * n + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e4[r] = ((w >> (8 * r)) & 0xffu) ? e4[r] : -INFINITY;
-                }
-                f32x4 p4;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) p4[r] = fast_exp2(e4[r]);
-                const f32x4 dm4 = f32x4{dm[0], dm[1], dm[2], dm[3]};
-                acc[n] += p4 * (dp * dm4 - delta);
-            }
-        }
-    }
-    if (q < P.T) {
-        float* orow = P.out + (size_t)sp * P.osplit + (size_t)img * P.ohs + (size_t)q * P.ldo;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-            const int jc = jb + 16 * n;
-            if (jc + 4 <= P.wlim) *(f32x4*)(orow + jc) = acc[n];
-            else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (jc + r < P.wlim) orow[jc + r] = acc[n][r];
-            }
-        }
-    }
+#include "attn_dbias_body.inc"
+}
+// ... with per-sample masks and results (bpm_attn_bwd_dbias_bmask), at the occupancy of the sibling above
+template <typename CTX, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(dbias_waves_x<CTX>(DHP), dbias_waves_x<CTX>(DHP)))) void attn_dbias_bmask_kernel(const DGroupB ga) {
+#include "attn_dbias_body.inc"
 }
 
 // dB = the partial images of a split launch, added in split order.  One thread per 4 consecutive keys of a row.
@@ -243,13 +132,22 @@ struct DSumGroup {
 };
 static_assert(sizeof(DSumGroup) <= 4096, "kernel arguments are limited to 4 KiB");
 
-__global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_kernel(const DSumGroup grp) {
+// ... and into a result with a sample stride (DProbB's rule for where image img goes)
+struct DSumProbB : DSumProb { int odiv; long obs; };
+struct DSumGroupB {
+    int nprob;
+    DSumProbB p[BPM_MAX_GROUP];
+};
+static_assert(sizeof(DSumGroupB) <= 4096, "kernel arguments are limited to 4 KiB");
+
+template <typename G>
+BPM_DEV void attn_dbias_sum_body(const G& grp) {
     unsigned bid = blockIdx.x;
     int pi = 0;
 #pragma unroll 1
     for (int i = 1; i < grp.nprob; ++i)
         if (bid >= grp.p[i].blk0) pi = i;
-    const DSumProb& P = grp.p[pi];
+    const auto& P = grp.p[pi];
     bid -= P.blk0;
     const size_t idx = (size_t)bid * NTHREADS + threadIdx.x;
     const size_t per_img = (size_t)P.T * P.c4;
@@ -261,7 +159,9 @@ __global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_kernel(const DSumGrou
     f32x4 v = *(const f32x4*)src;
 #pragma unroll 1
     for (int s = 1; s < P.nsplit; ++s) v += *(const f32x4*)(src + (size_t)s * P.psplit);
-    float* dst = P.dB + (size_t)img * P.ohs + (size_t)i * P.lddb + j;
+    float* dst;
+    if constexpr (std::is_same_v<G, DSumGroupB>) dst = P.dB + (size_t)(img / P.odiv) * P.obs + (size_t)(img % P.odiv) * P.ohs + (size_t)i * P.lddb + j;
+    else dst = P.dB + (size_t)img * P.ohs + (size_t)i * P.lddb + j;
     if (j + 4 <= P.S) *(f32x4*)dst = v;
     else {
 #pragma unroll
@@ -269,6 +169,8 @@ __global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_kernel(const DSumGrou
             if (j + r < P.S) dst[r] = v[r];
     }
 }
+__global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_kernel(const DSumGroup grp) { attn_dbias_sum_body(grp); }
+__global__ __launch_bounds__(NTHREADS) void attn_dbias_sum_bmask_kernel(const DSumGroupB grp) { attn_dbias_sum_body(grp); }
 
 // ---- bpm_attn_bwd_dbias: check / choose / fill / launch -----------------------------------------------------------------
 // check: everything about the problems and the outputs that can be refused on the host; nothing is dereferenced
@@ -294,12 +196,11 @@ int dbias_check(const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int n
 // alone (4 splits, 256 workgroups of 24 heads) took 67 us against the per-head form's 36.  Returns the workspace the
 // splits need, in bytes (16-byte granules).
 struct DChoice { int nimg, nterm, nsplit, chunk, ldp; size_t ws_off; };
-size_t dbias_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int nprob) {
+// (dbias_split: the choice itself, from the images and terms the result's form implies -- ch[i].nimg / nterm are set)
+size_t dbias_split(DChoice* ch, const bpm_attn_problem* probs, int nprob) {
     long tiles = 0;
     for (int i = 0; i < nprob; ++i) {
         const bpm_attn_problem& q = probs[i];
-        ch[i].nimg = outs[i].head_stride != 0 ? q.H : 1;
-        ch[i].nterm = outs[i].head_stride != 0 ? q.B : q.B * q.H;
         tiles += (long)ch[i].nimg * ((q.T + 63) / 64) * ((q.S + KT - 1) / KT);
     }
     const long target = (long)DB_CUS * dbias_waves<bf16_t>(probs[0].dhp);
@@ -317,6 +218,14 @@ size_t dbias_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_d
         if (ns > 1) bytes += (size_t)ns * c.nimg * q.T * c.ldp * sizeof(float);      // by ns: monotone in the number of heads
     }
     return bytes;
+}
+size_t dbias_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_dbias* outs, int nprob) {
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        ch[i].nimg = outs[i].head_stride != 0 ? q.H : 1;
+        ch[i].nterm = outs[i].head_stride != 0 ? q.B : q.B * q.H;
+    }
+    return dbias_split(ch, probs, nprob);
 }
 
 // fill: the two argument blocks (the mask descriptors are checked here, by the rule of the other *_amask entries; the
@@ -416,4 +325,133 @@ extern "C" int bpm_attn_bwd_dbias_kmask(int dtype, const bpm_attn_problem* probs
 extern "C" int bpm_attn_bwd_dbias(int dtype, const bpm_attn_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_dbias* outs,
                                   int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
     return bpm_attn_bwd_dbias_kmask(dtype, probs, masks, nullptr, outs, nprob, seed, ws, ws_bytes, stream);
+}
+
+// ---- bpm_attn_bwd_dbias_bmask: the same four steps with per-sample masks and the four result forms ----------------------------
+namespace {
+
+int dbias_b_check(const bpm_attn_problem* probs, const bpm_attn_dbias_b* outs, int nprob) {
+    if (!group_ok(probs, nprob) || !outs) return BPM_ERR_ARG;
+    if (with_dhp(probs[0].dhp, [](auto) { return 0; }) != 0) return BPM_ERR_ARG;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const bpm_attn_dbias_b& o = outs[i];
+        if (!geometry_ok(q, probs[0].dhp)) return BPM_ERR_ARG;
+        if (q.dS || q.Pd) return BPM_ERR_ARG;
+        if (!o.dB || o.lddb < q.S || (o.lddb & 3) || ((uintptr_t)o.dB & 15)) return BPM_ERR_ARG;
+        if (o.head_stride != 0 && (o.head_stride < (int64_t)q.T * o.lddb || (o.head_stride & 3))) return BPM_ERR_ARG;
+        const int64_t sample = o.head_stride != 0 ? (int64_t)q.H * o.head_stride : (int64_t)q.T * o.lddb;
+        if (o.batch_stride != 0 && (o.batch_stride < sample || (o.batch_stride & 3) || o.batch_stride > 0x7fffffff)) return BPM_ERR_ARG;
+    }
+    return 0;
+}
+
+// choose: the images and terms of each result form (the table at DProbB), then the split of bpm_attn_bwd_dbias
+size_t dbias_b_choose(DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_dbias_b* outs, int nprob) {
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const bool ph = outs[i].head_stride != 0, ps = outs[i].batch_stride != 0;
+        ch[i].nimg = (ph ? q.H : 1) * (ps ? q.B : 1);
+        ch[i].nterm = (ph ? 1 : q.H) * (ps ? 1 : q.B);
+    }
+    return dbias_split(ch, probs, nprob);
+}
+
+int dbias_b_fill(DGroupB& g, DSumGroupB& sg, const DChoice* ch, const bpm_attn_problem* probs, const bpm_attn_bmask* masks,
+                 const bpm_attn_kmask* kmasks, const bpm_attn_dbias_b* outs, int nprob, uint64_t seed, void* ws, long* total, long* sum_blocks) {
+    g.nprob = nprob;
+    g.seedp = bpm_seed_ptr(seed);
+    sg.nprob = 0;
+    long blk = 0, sblk = 0;
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const bpm_attn_dbias_b& o = outs[i];
+        const DChoice& c = ch[i];
+        DProbB& p = g.p[i];
+        if (!q.Q || !q.K || !q.V || !q.dO || !q.lse || !q.delta) return BPM_ERR_ARG;
+        if (((uintptr_t)q.Q | (uintptr_t)q.K | (uintptr_t)q.V | (uintptr_t)q.dO) & 15) return BPM_ERR_ALIGN;
+        AAddB a;
+        int rc = bmask_desc(a, masks[i], q.H, q.T, q.S, false);
+        if (rc) return rc;
+        g.k[i] = AMask{nullptr, 0};
+        if (kmasks && (rc = kmask_desc(g.k[i], kmasks[i], q.S)) != 0) return rc;
+        p.Q = (const char*)q.Q; p.K = (const char*)q.K; p.V = (const char*)q.V; p.dO = (const char*)q.dO;
+        p.lse = q.lse; p.delta = q.delta;
+        p.m = a.m; p.ldm = a.ld; p.mhs = a.hs; p.mbs = a.bs;
+        p.B = q.B; p.H = q.H; p.T = q.T; p.S = q.S;
+        if (!positions(q, p)) return BPM_ERR_ARG;
+        const bool ph = o.head_stride != 0, ps = o.batch_stride != 0;
+        p.per_head = ph;
+        p.imul = ps ? (ph ? 1 : q.H) : (ph ? 1 : 0);
+        p.tmul = ps ? (ph ? 0 : 1) : (ph ? q.H : 1);
+        // where image img of the RESULT goes; the partial images of a split are dense, one after the other
+        const int odiv = ps && ph ? q.H : 1;
+        const long obs = ps ? (long)o.batch_stride : (long)o.head_stride;
+        p.nterm = c.nterm; p.nsplit = c.nsplit; p.chunk = c.chunk;
+        p.drop = bpm_make_drop(q.drop_p, seed, q.drop_site);
+        p.nqt = (q.T + 63) / 64; p.nkt = (q.S + KT - 1) / KT;
+        p.blk0 = (int)blk;
+        blk += (long)c.nimg * c.nsplit * p.nqt * p.nkt;
+        if (blk > (1l << 30)) return BPM_ERR_ARG;
+        if (c.nsplit == 1) {
+            p.out = o.dB; p.ldo = o.lddb; p.wlim = q.S; p.osplit = 0;
+            p.odiv = odiv; p.obs = obs; p.ohs = (long)o.head_stride;
+        } else {
+            p.out = (float*)((char*)ws + c.ws_off); p.ldo = c.ldp; p.wlim = c.ldp;
+            p.odiv = 1; p.obs = (long)q.T * c.ldp; p.ohs = 0; p.osplit = (long)c.nimg * q.T * c.ldp;
+            DSumProbB& s = sg.p[sg.nprob++];
+            s.part = p.out; s.ldp = c.ldp; s.phs = p.obs; s.psplit = p.osplit;
+            s.dB = o.dB; s.lddb = o.lddb; s.ohs = (long)o.head_stride; s.odiv = odiv; s.obs = obs;
+            s.nimg = c.nimg; s.T = q.T; s.S = q.S; s.nsplit = c.nsplit; s.c4 = c.ldp / 4;
+            s.blk0 = (unsigned)sblk;
+            sblk += ((long)c.nimg * q.T * s.c4 + NTHREADS - 1) / NTHREADS;
+        }
+    }
+    for (int i = nprob; i < BPM_MAX_GROUP; ++i) g.k[i] = AMask{nullptr, 0};
+    *total = blk; *sum_blocks = sblk;
+    return 0;
+}
+
+template <typename CT>
+int dbias_b_launch(int dhp, bool with_kmasks, const DGroupB& g, long total, const DSumGroupB& sg, long sum_blocks, void* stream) {
+    const int rc = with_dhp(dhp, [&](auto d) {
+        if (with_kmasks) return launch<attn_dbias_bmask_kernel<WithBytes<CT>, decltype(d)::value>>((unsigned)total, NTHREADS, stream, g);
+        return launch<attn_dbias_bmask_kernel<CT, decltype(d)::value>>((unsigned)total, NTHREADS, stream, g);
+    });
+    if (rc || sum_blocks <= 0) return rc;
+    return launch<attn_dbias_sum_bmask_kernel>((unsigned)sum_blocks, NTHREADS, stream, sg);
+}
+
+}  // namespace
+
+extern "C" size_t bpm_attn_bwd_dbias_bmask_ws_bytes(const bpm_attn_problem* probs, const bpm_attn_dbias_b* outs, int nprob) {
+    DChoice ch[BPM_MAX_GROUP];
+    if (dbias_b_check(probs, outs, nprob)) return 0;
+    return dbias_b_choose(ch, probs, outs, nprob);
+}
+
+// The bias gradient under per-sample masks, in any of the four result forms: see bpm_attn_dbias_b in include/bpmult_hip.h.
+extern "C" int bpm_attn_bwd_dbias_bmask(int dtype, const bpm_attn_problem* probs, const bpm_attn_bmask* masks, const bpm_attn_kmask* kmasks,
+                                        const bpm_attn_dbias_b* outs, int nprob, uint64_t seed, void* ws, size_t ws_bytes, void* stream) {
+    if (!dtype_ok(dtype)) return BPM_ERR_ARG;
+    if (!masks) return BPM_ERR_ARG;
+    int rc = dbias_b_check(probs, outs, nprob);
+    if (rc) return rc;
+    DChoice ch[BPM_MAX_GROUP];
+    const size_t need = dbias_b_choose(ch, probs, outs, nprob);
+    if (need > 0 && (!ws || ws_bytes < need || ((uintptr_t)ws & 15))) return BPM_ERR_ARG;
+    DGroupB g;
+    DSumGroupB sg;
+    long total = 0, sum_blocks = 0;
+    rc = dbias_b_fill(g, sg, ch, probs, masks, kmasks, outs, nprob, seed, ws, &total, &sum_blocks);
+    if (rc) return rc;
+    const int sz = dtype == BPM_BF16 ? 2 : 4;
+    double bytes = 0;                                            // as bpm_attn_bwd_dbias: every image of the mask in, every image of dB out
+    for (int i = 0; i < nprob; ++i) {
+        const bpm_attn_problem& q = probs[i];
+        const double mimg = (double)(masks[i].head_stride ? q.H : 1) * (masks[i].batch_stride ? q.B : 1);
+        bytes += (double)q.B * q.H * ((2.0 * q.T + 2.0 * q.S) * q.dh * sz + 2.0 * q.T * 4) + 4.0 * q.T * q.S * (mimg + ch[i].nimg);
+    }
+    BpmProfScope prof(BPM_K_ATTN_BWD_DBIAS, (hipStream_t)stream, 4.0 * useful_pair_flops(probs, nprob), bytes);
+    return with_ct(dtype, [&](auto ct) { return dbias_b_launch<decltype(ct)>(probs[0].dhp, kmasks != nullptr, g, total, sg, sum_blocks, stream); });
 }

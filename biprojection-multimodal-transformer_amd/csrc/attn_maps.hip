@@ -73,124 +73,33 @@ BPM_DEV const MGroup& map_group(const MGroupA& g) { return g.g; }
 BPM_DEV const MGroup& map_group(const MGroupK& g) { return g.a.g; }
 BPM_DEV const AAdd& map_add(const MGroupA& g, int pi) { return g.m[pi]; }
 BPM_DEV const AAdd& map_add(const MGroupK& g, int pi) { return g.a.m[pi]; }
+// Per-sample images (bpm_attn_maps_bmask / _kbmask): the descriptors are AAddB, in argument blocks of their own behind the
+// same MGroup, so the kernels above keep theirs.  The image of (b, h) is loaded inside the head loop (the PH path) whatever
+// the head stride is: with one image per sample the heads re-read it from L2.
+struct MGroupB {
+    MGroup g;
+    AAddB m[BPM_MAX_GROUP];
+};
+struct MGroupKB {
+    MGroupB a;
+    AMask k[BPM_MAX_GROUP];
+};
+static_assert(sizeof(MGroupKB) <= 4096, "kernel arguments are limited to 4 KiB");
+BPM_DEV const MGroup& map_group(const MGroupB& g) { return g.g; }
+BPM_DEV const MGroup& map_group(const MGroupKB& g) { return g.a.g; }
+BPM_DEV const AAddB& map_add(const MGroupB& g, int pi) { return g.m[pi]; }
+BPM_DEV const AAddB& map_add(const MGroupKB& g, int pi) { return g.a.m[pi]; }
+template <typename G> constexpr bool per_sample_group = std::is_same_v<G, MGroupB> || std::is_same_v<G, MGroupKB>;
 
-// CTX: the compute type, or WithBytes<compute type> for KB
 template <typename CTX, int DHP, bool AM = false, bool PH = false>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<typename CtOf<CTX>::type>(DHP, AM), map_waves<typename CtOf<CTX>::type>(DHP, AM)))) void attn_maps_kernel(const std::conditional_t<CtOf<CTX>::bytes, MGroupK, std::conditional_t<AM, MGroupA, MGroup>> ga) {
-    static_assert(AM || !PH, "a head stride belongs to an additive mask");
-    typedef typename CtOf<CTX>::type CT;
-    constexpr bool KB = CtOf<CTX>::bytes;
-    const MGroup& grp = map_group(ga);
-    typedef Cfg<CT, DHP> C;
-    typedef typename Tr<CT>::frag frag;
-    __shared__ __attribute__((aligned(16))) char smem[MQT * C::STRIDE + MQT * 4];
-    char* qimg = smem;
-    float* s_lse = (float*)(smem + MQT * C::STRIDE);            // -lse * log2(e) of the tile's query rows
-
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int pi = 0;
-#pragma unroll 1
-    for (int i = 1; i < grp.nprob; ++i)
-        if (bid >= grp.p[i].blk0) pi = i;
-    const MProb& P = grp.p[pi];
-    bid -= P.blk0;
-    const int kb = bid % P.nkt, qt = (bid / P.nkt) % P.nqt, b = bid / (P.nkt * P.nqt);     // key tiles of a query tile are neighbours
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int j0 = kb * 64 + wave * 16;                 // wave-uniform first key
-    const int j = j0 + c;                               // this lane's key
-    const int i0 = qt * MQT;                            // first query row of the tile
-    float* Wb = P.W + ((size_t)b * P.T + i0) * P.ldw;   // row i0 of this batch element's map
-
-    // query row i (time qpos0 + i*qstride) sees key j iff i >= first_row(j - mask_off + 1)   (the dK / dV kernel's rule)
-    auto first_row = [&](int tmin) { const int a = tmin - P.qpos0; return a <= 0 ? 0 : (a + P.qstride - 1) / P.qstride; };
-    int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
-    int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);         // wave-uniform: rows at or above it need no test
-    bool any_key = true;                                // KB: the tile has a visible key (block-uniform)
-    if constexpr (KB) {
-        bool kvis = false;
-        if (j < P.S) kvis = ga.k[pi].mask[(size_t)b * ga.k[pi].ldm + j] != 0;
-        if (!kvis) ilo = 1 << 30;
-        if (__builtin_amdgcn_ballot_w64(!kvis) != 0) ilo_max = 1 << 30;                          // a hidden key in the wave: every row tests
-        any_key = __syncthreads_or(kvis);
-    }
-    const int i_first = first_row(kb * 64 - P.mask_off + 1);                                   // first query row that sees any key of the tile
-    const int i_end = min(P.T, i0 + MQT);
-
-    f32x4 acc[MQT / 16];
-#pragma unroll
-    for (int u = 0; u < MQT / 16; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (i_first < i_end && any_key) {                   // block-uniform: a fully masked tile keeps its zeros
-        f32x4 am4[MQT / 16];                            // AM: mask of queries i0 + 16u + 4g + (0..3) against key j
-        AAdd am = AAdd{nullptr, 0, 0};
-        if constexpr (AM) am = map_add(ga, pi);
-        auto load_mask = [&](int h) {
-            const float* acol = am.m + (size_t)h * am.hs + (size_t)min(j, P.S - 1) * am.ld;
-#pragma unroll
-            for (int u = 0; u < MQT / 16; ++u) {
-                const int ic = i0 + 16 * u + 4 * g;     // ic % 4 == 0 and ldt % 4 == 0: ic < T implies ic + 3 < ldt
-                am4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (j < P.S && ic < P.T) am4[u] = *(const f32x4*)(acol + ic);
-            }
-        };
-        if constexpr (AM && !PH) load_mask(0);
-        RowStage<CT, DHP, MQT> qst;
-        frag kn[C::NKS];
-        float n_lse = 0.f;
-        auto stage = [&](int h) {
-            const size_t bh = (size_t)b * P.H + h;
-            qst.load(P.Q + bh * P.T * C::ROWB, i0, P.T, tid);
-            const char* Kh = P.K + bh * P.S * C::ROWB;
-#pragma unroll
-            for (int s = 0; s < C::NKS; ++s) kn[s] = load_frag<CT, DHP>(Kh, j, P.S, s, g);
-            const int i = i0 + (tid & (MQT - 1));
-            const bool ok = i < P.T;
-            const float l = P.lse[bh * P.T + (ok ? i : 0)];
-            n_lse = ok ? -l * LOG2E : 0.f;
-        };
-        stage(0);
-        const bool edge = (i0 < ilo_max) || (i0 + MQT > P.T);
-#pragma unroll 1
-        for (int h = 0; h < P.H; ++h) {
-            __syncthreads();
-            qst.store(qimg, tid);
-            if (tid < MQT) s_lse[tid] = n_lse;
-            frag kf[C::NKS];
-#pragma unroll
-            for (int s = 0; s < C::NKS; ++s) kf[s] = kn[s];
-            __syncthreads();
-            if (h + 1 < P.H) stage(h + 1);
-            if constexpr (PH) load_mask(h);
-#pragma unroll
-            for (int u = 0; u < MQT / 16; ++u) {
-                f32x4 s_ = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < C::NKS; ++s) s_ = Tr<CT>::mma(read_rowfrag<CT>(qimg, C::STRIDE, 16 * u, s, lane), kf[s], s_);
-                if constexpr (AM) s_ += am4[u];
-                const f32x4 l4 = *(const f32x4*)(s_lse + 16 * u + 4 * g);
-                const int ib = i0 + 16 * u + 4 * g;                 // query row of element r is ib + r
-                f32x4 e4 = s_ * LOG2E + l4;
-                if (edge) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) e4[r] = (ib + r >= ilo && ib + r < P.T) ? e4[r] : -INFINITY;   // exp2(-inf) = 0
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[u][r] += fast_exp2(e4[r]);
-            }
-        }
-    }
-    if (j < P.S) {
-        const float inv = 1.f / (float)P.H;
-#pragma unroll
-        for (int u = 0; u < MQT / 16; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * u + 4 * g + r;
-                if (i0 + row < P.T) Wb[(size_t)row * P.ldw + j] = acc[u][r] * inv;
-            }
-    }
+#include "attn_maps_body.inc"
+}
+// ... with one image per sample (bpm_attn_maps_bmask / _kbmask), at the occupancy of the per-head instantiation above
+template <typename CTX, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(map_waves<typename CtOf<CTX>::type>(DHP, true), map_waves<typename CtOf<CTX>::type>(DHP, true)))) void attn_maps_bmask_kernel(const std::conditional_t<CtOf<CTX>::bytes, MGroupKB, MGroupB> ga) {
+    constexpr bool AM = true, PH = true;
+#include "attn_maps_body.inc"
 }
 
 // ---- bpm_attn_maps / _amask / _hmask / _kmask / _kamask: check / fill / choose / launch ---------------------------------------------------
@@ -204,8 +113,10 @@ int maps_check(const bpm_attn_map_problem& q, int dhp0) {
 
 // fill: the argument block and the grid; masks: the additive masks (read through their transposes), or nullptr; kmasks:
 // the per-key byte masks, or nullptr.  Problem by problem: check, the mask_off rule, the block limit, the mask descriptors.
-int maps_fill(MGroupK& gk, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_kmask* kmasks, int nprob, long* total) {
-    MGroupA& ga = gk.a;
+// GK / HM: MGroupK with bpm_attn_hmask masks, or MGroupKB with bpm_attn_bmask masks (one image per sample).
+template <typename GK, typename HM>
+int maps_fill(GK& gk, const bpm_attn_map_problem* probs, const HM* masks, const bpm_attn_kmask* kmasks, int nprob, long* total) {
+    auto& ga = gk.a;
     MGroup& g = ga.g;
     g.nprob = nprob;
     long blk = 0;
@@ -222,9 +133,9 @@ int maps_fill(MGroupK& gk, const bpm_attn_map_problem* probs, const bpm_attn_hma
         blk += (long)p.nqt * p.nkt * q.B;
         if (blk > (1l << 30)) return BPM_ERR_ARG;
         if (kmasks && (rc = kmask_desc(gk.k[i], kmasks[i], q.S)) != 0) return rc;
-        if (masks && (rc = amask_desc(ga.m[i], masks[i], q.T, q.S, true)) != 0) return rc;
+        if (masks && (rc = image_desc(ga.m[i], masks[i], q.H, q.T, q.S, true)) != 0) return rc;
     }
-    for (int i = masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) ga.m[i] = AAdd{nullptr, 0, 0};
+    for (int i = masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) ga.m[i] = {};
     for (int i = kmasks ? nprob : 0; i < BPM_MAX_GROUP; ++i) gk.k[i] = AMask{nullptr, 0};
     *total = blk;
     return 0;
@@ -255,15 +166,30 @@ int maps_launch(int dtype, int dhp, bool with_masks, bool per_head, bool with_km
     });
 }
 
+// the per-sample family: one instantiation per compute type, head_dim and byte-mask switch
+bool maps_per_head(const MGroupB&, int, bool) { return true; }
+int maps_launch(int dtype, int dhp, bool, bool, bool with_kmasks, const MGroupKB& gk, long total, void* stream) {
+    return with_ct(dtype, [&](auto ct) {
+        return with_dhp(dhp, [&](auto d) {
+            typedef decltype(ct) CT;
+            constexpr int D = decltype(d)::value;
+            if (with_kmasks) return launch<attn_maps_bmask_kernel<WithBytes<CT>, D>>((unsigned)total, NTHREADS, stream, gk);
+            return launch<attn_maps_bmask_kernel<CT, D>>((unsigned)total, NTHREADS, stream, gk.a);
+        });
+    });
+}
+
 // Head-averaged attention probabilities of finished forward passes (see attn_maps_kernel); masks: the additive masks of
 // bpm_attn_maps_amask (read through their transposes), or nullptr; kmasks: the byte masks of bpm_attn_maps_kmask, or nullptr.
-int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_hmask* masks, bool with_masks,
+// GK: MGroupK (masks: bpm_attn_hmask), or MGroupKB (masks: bpm_attn_bmask, one image per sample).
+template <typename GK = MGroupK, typename HM = bpm_attn_hmask>
+int attn_maps_impl(int dtype, const bpm_attn_map_problem* probs, const HM* masks, bool with_masks,
                    const bpm_attn_kmask* kmasks, bool with_kmasks, int nprob, void* stream) {
     if (!group_ok(probs, nprob)) return BPM_ERR_ARG;
     if (!dtype_ok(dtype)) return BPM_ERR_ARG;
     if ((with_masks && !masks) || (with_kmasks && !kmasks)) return BPM_ERR_ARG;
-    MGroupK gk;
-    const MGroupA& ga = gk.a;
+    GK gk;
+    const auto& ga = gk.a;
     long total = 0;
     int rc = maps_fill(gk, probs, masks, kmasks, nprob, &total);
     if (rc) return rc;
@@ -332,114 +258,26 @@ struct HGroupM {
 static_assert(sizeof(HGroupM) <= 4096, "kernel arguments are limited to 4 KiB");
 BPM_DEV const HGroup& head_group(const HGroup& g) { return g; }
 BPM_DEV const HGroup& head_group(const HGroupM& g) { return g.g; }
+// per-sample images (bpm_attn_head_maps_bmask / _kbmask): HGroupM with AAddB descriptors, an argument block of its own
+struct HGroupB {
+    HGroup g;
+    AAddB m[BPM_MAX_GROUP];
+    AMask k[BPM_MAX_GROUP];
+};
+static_assert(sizeof(HGroupB) <= 4096, "kernel arguments are limited to 4 KiB");
+BPM_DEV const HGroup& head_group(const HGroupB& g) { return g.g; }
 
 // CTX: the compute type, or WithBytes<compute type> for the byte mask (KB); AM: an additive image, read through its
 // transpose from the head's image (head stride 0: the one image)
 template <typename CTX, int DHP, bool AM = false>
 __global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(head_map_waves<typename CtOf<CTX>::type>(DHP), head_map_waves<typename CtOf<CTX>::type>(DHP)))) void attn_head_maps_kernel(const std::conditional_t<CtOf<CTX>::bytes || AM, HGroupM, HGroup> ga) {
-    typedef typename CtOf<CTX>::type CT;
-    constexpr bool KB = CtOf<CTX>::bytes;
-    const HGroup& grp = head_group(ga);
-    typedef Cfg<CT, DHP> C;
-    typedef typename Tr<CT>::frag frag;
-    constexpr int QBYTES = MQT * C::STRIDE + MQT * 4, TBYTES = MQT * HM_LD * 4;
-    __shared__ __attribute__((aligned(16))) char smem[QBYTES > TBYTES ? QBYTES : TBYTES];
-    char* qimg = smem;
-    float* s_lse = (float*)(smem + MQT * C::STRIDE);            // -lse * log2(e) of the tile's query rows
-    float* tile = (float*)smem;                                 // the finished tile, once the image has been read
-
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int pi = 0;
-#pragma unroll 1
-    for (int i = 1; i < grp.nprob; ++i)
-        if (bid >= grp.p[i].blk0) pi = i;
-    const HProb& P = grp.p[pi];
-    bid -= P.blk0;
-    const int per = P.nkt * P.nqt;
-    const int kb = bid % P.nkt, qt = (bid / P.nkt) % P.nqt, bh = bid / per;     // key tiles of a query tile are neighbours
-    const int h = bh % P.H, b = bh / P.H;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    const int j0 = kb * 64 + wave * 16;                 // wave-uniform first key
-    const int j = j0 + c;                               // this lane's key
-    const int i0 = qt * MQT;                            // first query row of the tile
-    float* Wt = P.W + (size_t)b * P.bs + (size_t)h * P.hs + (size_t)i0 * P.ldw + kb * 64;     // the tile's first element
-
-    // query row i (time qpos0 + i*qstride) sees key j iff i >= first_row(j - mask_off + 1)   (attn_maps_kernel's rule)
-    auto first_row = [&](int tmin) { const int a = tmin - P.qpos0; return a <= 0 ? 0 : (a + P.qstride - 1) / P.qstride; };
-    int ilo = (j < P.S) ? first_row(j - P.mask_off + 1) : (1 << 30);
-    int ilo_max = (j0 + 15 < P.S) ? first_row(j0 + 15 - P.mask_off + 1) : (1 << 30);         // wave-uniform: rows at or above it need no test
-    bool any_key = true;                                // KB: the tile has a visible key (block-uniform)
-    if constexpr (KB) {
-        bool kvis = false;
-        if (j < P.S) kvis = ga.k[pi].mask[(size_t)b * ga.k[pi].ldm + j] != 0;
-        if (!kvis) ilo = 1 << 30;
-        if (__builtin_amdgcn_ballot_w64(!kvis) != 0) ilo_max = 1 << 30;                          // a hidden key in the wave: every row tests
-        any_key = __syncthreads_or(kvis);
-    }
-    const int i_first = first_row(kb * 64 - P.mask_off + 1);                                   // first query row that sees any key of the tile
-    const int i_end = min(P.T, i0 + MQT);
-    const int nrow = i_end - i0, ncol = min(64, P.S - kb * 64);                                // the part of the tile inside [T, S)
-    const int r0 = wave * (MQT / 4);                    // the store: this wave's sixteen rows, lane = key
-
-    if (i_first < i_end && any_key) {                   // block-uniform
-        f32x4 am4[MQT / 16];                            // AM: mask of queries i0 + 16u + 4g + (0..3) against key j
-        if constexpr (AM) {
-            const AAdd am = ga.m[pi];
-            const float* acol = am.m + (size_t)h * am.hs + (size_t)min(j, P.S - 1) * am.ld;
-#pragma unroll
-            for (int u = 0; u < MQT / 16; ++u) {
-                const int ic = i0 + 16 * u + 4 * g;     // ic % 4 == 0 and ldt % 4 == 0: ic < T implies ic + 3 < ldt
-                am4[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (j < P.S && ic < P.T) am4[u] = *(const f32x4*)(acol + ic);
-            }
-        }
-        frag kf[C::NKS];
-        {
-            RowStage<CT, DHP, MQT> qst;
-            qst.load(P.Q + (size_t)bh * P.T * C::ROWB, i0, P.T, tid);
-            const char* Kh = P.K + (size_t)bh * P.S * C::ROWB;
-#pragma unroll
-            for (int s = 0; s < C::NKS; ++s) kf[s] = load_frag<CT, DHP>(Kh, j, P.S, s, g);
-            const int i = i0 + (tid & (MQT - 1));
-            const bool ok = i < P.T;
-            const float l = P.lse[(size_t)bh * P.T + (ok ? i : 0)];
-            qst.store(qimg, tid);
-            if (tid < MQT) s_lse[tid] = ok ? -l * LOG2E : 0.f;
-        }
-        __syncthreads();
-        const bool edge = (i0 < ilo_max) || (i0 + MQT > P.T);
-        f32x4 p4[MQT / 16];
-#pragma unroll
-        for (int u = 0; u < MQT / 16; ++u) {
-            f32x4 s_ = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < C::NKS; ++s) s_ = Tr<CT>::mma(read_rowfrag<CT>(qimg, C::STRIDE, 16 * u, s, lane), kf[s], s_);
-            if constexpr (AM) s_ += am4[u];
-            const f32x4 l4 = *(const f32x4*)(s_lse + 16 * u + 4 * g);
-            const int ib = i0 + 16 * u + 4 * g;                 // query row of element r is ib + r
-            f32x4 e4 = s_ * LOG2E + l4;
-            if (edge) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) e4[r] = (ib + r >= ilo && ib + r < P.T) ? e4[r] : -INFINITY;   // exp2(-inf) = 0
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p4[u][r] = fast_exp2(e4[r]);
-        }
-        __syncthreads();                                // every wave has read the image and the LSE: the tile takes their place
-#pragma unroll
-        for (int u = 0; u < MQT / 16; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tile[(16 * u + 4 * g + r) * HM_LD + wave * 16 + c] = p4[u][r];
-        __syncthreads();
-        if (lane < ncol) {
-#pragma unroll 4
-            for (int r = r0; r < min(r0 + MQT / 4, nrow); ++r) Wt[(size_t)r * P.ldw + lane] = tile[r * HM_LD + lane];
-        }
-    } else if (lane < ncol) {                           // a fully hidden tile: zeros, row by row
-        for (int r = r0; r < min(r0 + MQT / 4, nrow); ++r) Wt[(size_t)r * P.ldw + lane] = 0.f;
-    }
+#include "attn_head_maps_body.inc"
+}
+// ... with one image per sample (bpm_attn_head_maps_bmask / _kbmask)
+template <typename CTX, int DHP>
+__global__ __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(head_map_waves<typename CtOf<CTX>::type>(DHP), head_map_waves<typename CtOf<CTX>::type>(DHP)))) void attn_head_maps_bmask_kernel(const HGroupB ga) {
+    constexpr bool AM = true;
+#include "attn_head_maps_body.inc"
 }
 
 // ---- bpm_attn_head_maps / _amask / _hmask / _kmask / _kamask: check / fill / choose / launch -------------------------------
@@ -454,7 +292,9 @@ int head_maps_check(const bpm_attn_head_map_problem& q, int dhp0) {
 }
 
 // fill: the argument block and the grid, as maps_fill; one workgroup per (sample, head, query tile, key tile)
-int head_maps_fill(HGroupM& gm, const bpm_attn_head_map_problem* probs, const bpm_attn_hmask* masks, const bpm_attn_kmask* kmasks, int nprob, long* total) {
+// GM / HM: HGroupM with bpm_attn_hmask masks, or HGroupB with bpm_attn_bmask masks (one image per sample).
+template <typename GM, typename HM>
+int head_maps_fill(GM& gm, const bpm_attn_head_map_problem* probs, const HM* masks, const bpm_attn_kmask* kmasks, int nprob, long* total) {
     HGroup& g = gm.g;
     g.nprob = nprob;
     long blk = 0;
@@ -474,9 +314,9 @@ int head_maps_fill(HGroupM& gm, const bpm_attn_head_map_problem* probs, const bp
         blk += tiles * q.B * q.H;
         if (blk > (1l << 30)) return BPM_ERR_ARG;
         if (kmasks && (rc = kmask_desc(gm.k[i], kmasks[i], q.S)) != 0) return rc;
-        if (masks && (rc = amask_desc(gm.m[i], masks[i], q.T, q.S, true)) != 0) return rc;
+        if (masks && (rc = image_desc(gm.m[i], masks[i], q.H, q.T, q.S, true)) != 0) return rc;
     }
-    for (int i = masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) gm.m[i] = AAdd{nullptr, 0, 0};
+    for (int i = masks ? nprob : 0; i < BPM_MAX_GROUP; ++i) gm.m[i] = {};
     for (int i = kmasks ? nprob : 0; i < BPM_MAX_GROUP; ++i) gm.k[i] = AMask{nullptr, 0};
     *total = blk;
     return 0;
@@ -498,13 +338,26 @@ int head_maps_launch(int dtype, int dhp, bool with_masks, bool with_kmasks, cons
     });
 }
 
-// Per-head attention probabilities of finished forward passes (see attn_head_maps_kernel); masks / kmasks as attn_maps_impl
-int attn_head_maps_impl(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_hmask* masks, bool with_masks,
+int head_maps_launch(int dtype, int dhp, bool, bool with_kmasks, const HGroupB& gm, long total, void* stream) {
+    return with_ct(dtype, [&](auto ct) {
+        return with_dhp(dhp, [&](auto d) {
+            typedef decltype(ct) CT;
+            constexpr int D = decltype(d)::value;
+            if (with_kmasks) return launch<attn_head_maps_bmask_kernel<WithBytes<CT>, D>>((unsigned)total, NTHREADS, stream, gm);
+            return launch<attn_head_maps_bmask_kernel<CT, D>>((unsigned)total, NTHREADS, stream, gm);
+        });
+    });
+}
+
+// Per-head attention probabilities of finished forward passes (see attn_head_maps_kernel); masks / kmasks / the template
+// arguments as attn_maps_impl
+template <typename GM = HGroupM, typename HM = bpm_attn_hmask>
+int attn_head_maps_impl(int dtype, const bpm_attn_head_map_problem* probs, const HM* masks, bool with_masks,
                         const bpm_attn_kmask* kmasks, bool with_kmasks, int nprob, void* stream) {
     if (!group_ok(probs, nprob)) return BPM_ERR_ARG;
     if (!dtype_ok(dtype)) return BPM_ERR_ARG;
     if ((with_masks && !masks) || (with_kmasks && !kmasks)) return BPM_ERR_ARG;
-    HGroupM gm;
+    GM gm;
     long total = 0;
     int rc = head_maps_fill(gm, probs, masks, kmasks, nprob, &total);
     if (rc) return rc;
@@ -524,7 +377,7 @@ int attn_head_maps_impl(int dtype, const bpm_attn_head_map_problem* probs, const
 }  // namespace
 
 extern "C" int bpm_attn_maps(int dtype, const bpm_attn_map_problem* probs, int nprob, void* stream) {
-    return attn_maps_impl(dtype, probs, nullptr, false, nullptr, false, nprob, stream);
+    return attn_maps_impl(dtype, probs, (const bpm_attn_hmask*)nullptr, false, nullptr, false, nprob, stream);
 }
 extern "C" int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_amask* masks, int nprob, void* stream) {
     return attn_maps_impl(dtype, probs, HMasks(masks, nprob).p, true, nullptr, false, nprob, stream);
@@ -534,7 +387,7 @@ extern "C" int bpm_attn_maps_hmask(int dtype, const bpm_attn_map_problem* probs,
 }
 // ... with a per-key byte mask (lse from bpm_attn_fwd_kmask), and with both masks (lse from bpm_attn_fwd_kamask)
 extern "C" int bpm_attn_maps_kmask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_kmask* kmasks, int nprob, void* stream) {
-    return attn_maps_impl(dtype, probs, nullptr, false, kmasks, true, nprob, stream);
+    return attn_maps_impl(dtype, probs, (const bpm_attn_hmask*)nullptr, false, kmasks, true, nprob, stream);
 }
 extern "C" int bpm_attn_maps_kamask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks, int nprob,
                                     void* stream) {
@@ -543,7 +396,7 @@ extern "C" int bpm_attn_maps_kamask(int dtype, const bpm_attn_map_problem* probs
 
 // ---- the per-head maps: the five entries above, one map per head -----------------------------------------------------------
 extern "C" int bpm_attn_head_maps(int dtype, const bpm_attn_head_map_problem* probs, int nprob, void* stream) {
-    return attn_head_maps_impl(dtype, probs, nullptr, false, nullptr, false, nprob, stream);
+    return attn_head_maps_impl(dtype, probs, (const bpm_attn_hmask*)nullptr, false, nullptr, false, nprob, stream);
 }
 extern "C" int bpm_attn_head_maps_amask(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_amask* masks, int nprob, void* stream) {
     return attn_head_maps_impl(dtype, probs, HMasks(masks, nprob).p, true, nullptr, false, nprob, stream);
@@ -552,9 +405,25 @@ extern "C" int bpm_attn_head_maps_hmask(int dtype, const bpm_attn_head_map_probl
     return attn_head_maps_impl(dtype, probs, masks, true, nullptr, false, nprob, stream);
 }
 extern "C" int bpm_attn_head_maps_kmask(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_kmask* kmasks, int nprob, void* stream) {
-    return attn_head_maps_impl(dtype, probs, nullptr, false, kmasks, true, nprob, stream);
+    return attn_head_maps_impl(dtype, probs, (const bpm_attn_hmask*)nullptr, false, kmasks, true, nprob, stream);
 }
 extern "C" int bpm_attn_head_maps_kamask(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_hmask* masks,
                                          int nprob, void* stream) {
     return attn_head_maps_impl(dtype, probs, masks, true, kmasks, true, nprob, stream);
+}
+
+// ---- both kinds of maps under one additive image per sample (see bpm_attn_bmask), alone or beside key bytes ----------------
+extern "C" int bpm_attn_maps_bmask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_bmask* masks, int nprob, void* stream) {
+    return attn_maps_impl<MGroupKB>(dtype, probs, masks, true, nullptr, false, nprob, stream);
+}
+extern "C" int bpm_attn_maps_kbmask(int dtype, const bpm_attn_map_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_bmask* masks, int nprob,
+                                    void* stream) {
+    return attn_maps_impl<MGroupKB>(dtype, probs, masks, true, kmasks, true, nprob, stream);
+}
+extern "C" int bpm_attn_head_maps_bmask(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_bmask* masks, int nprob, void* stream) {
+    return attn_head_maps_impl<HGroupB>(dtype, probs, masks, true, nullptr, false, nprob, stream);
+}
+extern "C" int bpm_attn_head_maps_kbmask(int dtype, const bpm_attn_head_map_problem* probs, const bpm_attn_kmask* kmasks, const bpm_attn_bmask* masks,
+                                         int nprob, void* stream) {
+    return attn_head_maps_impl<HGroupB>(dtype, probs, masks, true, kmasks, true, nprob, stream);
 }

@@ -32,6 +32,12 @@ with one torch op (into a contiguous buffer: the mask may have any strides), kep
 shape changes -- a cache of its own: a padding mask
 that changes every batch does not touch the additive image.  The family follows from what is given: neither -> the
 unmasked entries, an image alone -> _amask, a padding mask alone -> _kmask, both -> _kamask.
+attn_mask and attn_bias may also be per sample -- [Bm, Hm, T, S] with Bm in {1, B}, Hm in {1, H}, or torch's 3-D
+[B*H, T, S] -- and attn_mask may be torch.bool (True hides); the one form attn_bias keeps refusing is the 4-D
+[B, H, T, S] with B > 1 and H > 1, which is passed as [B*H, T, S].  effective_image() below builds their broadcast sum in the
+smallest common form, [Bm, Hm, T, ldm] plus the transpose (2 Bm Hm T S 4 bytes); with Bm = B the same wrappers launch the
+per-sample entries (_bmask / _kbmask, kernels of their own), and the bias gradient comes back in the bias's own shape
+(bpm_attn_bwd_dbias_bmask: [B*H, T, S] is the score gradient itself, [B, 1, T, S] its sum over the heads of a sample).
 add_bias_kv / add_zero_attn are refused.
 """
 from __future__ import annotations
@@ -56,6 +62,63 @@ def _dhp_for(dh: int) -> int:
     raise ValueError(f"MultiheadAttention: head_dim {dh} > 256 has no HIP attention kernel")
 
 
+_FORMS = "[T, S], [H, T, S], [Bm, Hm, T, S] with Bm in {1, B} and Hm in {1, H}, or torch's [B*H, T, S] (index b*H + h)"
+
+
+def image_lead(shape, B: int, H: int, T: int, S: int, what: str = "attn_mask") -> Tuple[int, int]:
+    """(Bm, Hm) of an additive image of `shape`, read as [Bm, Hm, T, S]: [T, S] -> (1, 1); [H, T, S] -> (1, H) (a 3-D
+    tensor whose leading dimension is H keeps the per-head meaning; for B == 1 the two readings coincide); [B*H, T, S] ->
+    (B, H); [Bm, Hm, T, S] as it stands -- except an attn_bias with Bm = B > 1 and Hm = H > 1, refused as before this
+    function existed: it is passed as [B*H, T, S].  Any other shape: ValueError naming the accepted forms."""
+    shape = tuple(shape)
+    if shape[-2:] == (T, S):
+        if len(shape) == 2:
+            return 1, 1
+        if len(shape) == 3 and shape[0] == H:
+            return 1, H
+        if len(shape) == 3 and shape[0] == B * H:
+            return B, H
+        if len(shape) == 4 and shape[0] in (1, B) and shape[1] in (1, H):
+            # a 4-D attn_bias with B > 1 samples AND H > 1 heads stays refused, as it always was: that bias is spelled
+            # [B*H, T, S] (bias.reshape(B * H, T, S), a view: the gradient flows through it)
+            if what != "attn_bias" or shape[0] == 1 or shape[1] == 1:
+                return shape[0], shape[1]
+            raise ValueError(f"MultiheadAttention: attn_bias of shape {shape}; a bias per sample and head is passed in torch's 3-D "
+                             f"form [B*H, T, S] = [{B * H}, {T}, {S}] (index b*H + h); the other forms are {_FORMS}")
+    if what == "attn_mask":
+        raise ValueError(f"MultiheadAttention: attn_mask must be a float or torch.bool tensor of shape {_FORMS} with B={B}, H={H}, "
+                         f"T={T}, S={S}; got {shape}")
+    raise ValueError(f"MultiheadAttention: {what} of shape {shape}; expected {_FORMS} with B={B}, H={H}, T={T}, S={S}")
+
+
+def effective_image(attn_mask: Optional[torch.Tensor], attn_bias: Optional[torch.Tensor], B: int, H: int, T: int, S: int):
+    """The image the kernels read for attn_mask + attn_bias, broadcast to the smallest common form (per sample if either
+    argument is, per head if either is): (m, mt, ldm, ldt, head_stride, head_strideT, batch_stride, batch_strideT) with m
+    fp32 [Bm, Hm, T, ldm], mt its transpose [Bm, Hm, S, ldt], leading dimensions rounded up to 4 (pad columns: zeros) and
+    the strides in elements, 0 where the image is shared.  A torch.bool attn_mask hides where it is True (-inf / 0).  A
+    pure function of its arguments on whatever device they live; it takes no part in autograd."""
+    parts = []
+    for t, what in ((attn_mask, "attn_mask"), (attn_bias, "attn_bias")):
+        if t is None:
+            continue
+        bm, hm = image_lead(t.shape, B, H, T, S, what)
+        t = t.detach()      # shares the storage (and the version counter), not the autograd graph of a non-leaf bias
+        if t.dtype == torch.bool:
+            t = torch.zeros(t.shape, device=t.device).masked_fill_(t, float("-inf"))
+        parts.append(t.reshape(bm, hm, T, S).float())
+    Bm, Hm = max(p.shape[0] for p in parts), max(p.shape[1] for p in parts)
+    ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
+    m = torch.zeros(Bm, Hm, T, ldm, device=parts[0].device)
+    mt = torch.zeros(Bm, Hm, S, ldt, device=parts[0].device)
+    m[..., :S].copy_(parts[0].expand(Bm, Hm, T, S))
+    if len(parts) == 2:
+        m[..., :S].add_(parts[1])
+    mt[..., :T].copy_(m[..., :S].transpose(2, 3))
+    hs, hst = (T * ldm, S * ldt) if Hm > 1 else (0, 0)
+    bs, bst = (Hm * T * ldm, Hm * S * ldt) if Bm > 1 else (0, 0)
+    return m, mt, ldm, ldt, hs, hst, bs, bst
+
+
 class _Plan:
     """Activation buffers of one (T, S, B, call form).  CT buffers are zero-initialised once: the launches write the
     embed_dim / head_dim columns only, the pad columns stay zero (the GEMMs read whole padded rows)."""
@@ -76,7 +139,7 @@ class _Plan:
         self.dq, self.dk, self.dv = z(T * B, ld, dt=ct), z(S * B, ld, dt=ct), z(S * B, ld, dt=ct)
         self.mask = None             # (ops.attn_amasks array, the tensors it points into) of the forward pass; None: no attn_mask / attn_bias
         self.kmask = None            # (ops.attn_kmasks array, the bytes it points into) of the forward pass; None: no key_padding_mask
-        self.dbias_ws = {}           # heads of the bias gradient (1 or H) -> workspace of bpm_attn_bwd_dbias (None: no split)
+        self.dbias_ws = {}           # (samples, heads) of the bias gradient's form -> workspace of bpm_attn_bwd_dbias (None: no split)
         self.seed, self.drop_p = 0, 0.0
 
 
@@ -130,26 +193,19 @@ class _Exec:
             pl = self.plans[key] = _Plan(self, T, S, B, form)
         return pl
 
-    def mask_for(self, attn_mask: Optional[torch.Tensor], attn_bias: Optional[torch.Tensor], T: int, S: int):
-        """The kernels' copy of the effective image attn_mask + attn_bias: fp32 [Hm, T, ldm] and its transpose [Hm, S, ldt]
-        (Hm = H for an [H, T, S] bias, else 1: head stride 0), leading dimensions rounded up to 4 (pad columns are never
-        used: zeros); rebuilt when either tensor's storage or version counter changes."""
+    def mask_for(self, attn_mask: Optional[torch.Tensor], attn_bias: Optional[torch.Tensor], T: int, S: int, B: int):
+        """The kernels' copy of the effective image attn_mask + attn_bias (effective_image: fp32 [Bm, Hm, T, ldm] and its
+        transpose, Bm = B when either tensor is per sample, Hm = H when either is per head, else 1: stride 0); rebuilt when
+        either tensor's storage or version counter, or the batch size, changes."""
         sig = lambda t: None if t is None else (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
-        key = (sig(attn_mask), sig(attn_bias))
+        key = (sig(attn_mask), sig(attn_bias), B)
         if key != self._mask_key:
-            ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
-            Hm = self.H if attn_bias is not None and attn_bias.dim() == 3 else 1
-            m = torch.zeros(Hm, T, ldm, device=self.device)
-            mt = torch.zeros(Hm, S, ldt, device=self.device)
-            # detached views: they share the storage (and the version counter) but not the autograd graph of a non-leaf bias
-            srcs = [t.detach() for t in (attn_mask, attn_bias) if t is not None]
-            m[:, :, :S].copy_(srcs[0])
-            if len(srcs) == 2:
-                m[:, :, :S].add_(srcs[1])
-            mt[:, :, :T].copy_(m[:, :, :S].transpose(1, 2))
-            hs, hst = (T * ldm, S * ldt) if Hm > 1 else (0, 0)
+            m, mt, ldm, ldt, hs, hst, bs, bst = effective_image(attn_mask, attn_bias, B, self.H, T, S)
+            # one image per sample: the 8-tuple form (the *_bmask / *_kbmask entries); otherwise the entries there always were
+            desc = (m, ldm, mt, ldt, hs, hst) + ((bs, bst) if bs else ())
             # the source tensors are held too: while they live, their addresses cannot name other tensors
-            self._mask = (ops.attn_amasks([(m, ldm, mt, ldt, hs, hst)]), m, mt, srcs)
+            srcs = [t.detach() for t in (attn_mask, attn_bias) if t is not None]
+            self._mask = (ops.attn_amasks([desc]), m, mt, srcs)
             self._mask_key = key
         return self._mask
 
@@ -189,7 +245,7 @@ class _Exec:
         pl = self.plan(T, S, B, form)
         pl.stamp += 1
         dt, ld, H, dh, dhp = self.dtype, self.ld, self.H, self.dh, self.dhp
-        pl.mask = None if attn_mask is None and attn_bias is None else self.mask_for(attn_mask, attn_bias, T, S)
+        pl.mask = None if attn_mask is None and attn_bias is None else self.mask_for(attn_mask, attn_bias, T, S, B)
         pl.kmask = None if key_padding_mask is None else self.kmask_for(key_padding_mask)
         pl.seed, pl.drop_p = seed, (mod.attn_dropout if training else 0.0)
         casts = [ops.cast_problem(query, d, T * B, d, dst_ct=pl.xq, ldd=ld)]
@@ -265,10 +321,14 @@ class _Exec:
         over samples and heads; [H, T, S]: over samples); a pair the effective image hides gets exactly 0, and a sample
         adds nothing at the keys its key_padding_mask hides."""
         T, S = pl.T, pl.S
-        nimg = self.H if len(bias_shape) == 3 else 1
+        # the form of the result follows from the bias alone: one image per sample and / or head that the bias has its own
+        Bb, Hb = image_lead(bias_shape, pl.B, self.H, T, S, "attn_bias")
+        nimg = (Bb, Hb)
         ldb = (S + 3) // 4 * 4
-        g = torch.empty(nimg, T, ldb, device=self.device)
-        outs = ops.attn_dbias([(g, ldb, T * ldb if nimg > 1 else 0)])
+        g = torch.empty(Bb, Hb, T, ldb, device=self.device)
+        hs = T * ldb if Hb > 1 else 0
+        # a per-sample result goes through bpm_attn_bwd_dbias_bmask (the 4-tuple form), as does any result under per-sample masks
+        outs = ops.attn_dbias([(g, ldb, hs, Hb * T * ldb) if Bb > 1 else (g, ldb, hs)])
         if nimg not in pl.dbias_ws:
             n = ops.attn_dbias_ws_bytes(ap, outs)
             pl.dbias_ws[nimg] = torch.empty((n + 3) // 4, device=self.device) if n else None
@@ -276,7 +336,7 @@ class _Exec:
             ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg])
         else:
             ops.attn_bwd_dbias(self.dtype, ap, pl.mask[0], outs, seed, ws=pl.dbias_ws[nimg], kmasks=pl.kmask[0])
-        g = g if ldb == S else g[:, :, :S].contiguous()
+        g = g if ldb == S else g[..., :S].contiguous()
         return g.reshape(bias_shape)
 
 class _MhaFn(torch.autograd.Function):
@@ -318,6 +378,14 @@ class MultiheadAttention(nn.Module):
     may require grad -- an nn.Parameter, or a non-leaf such as a gather from a relative-position table: its gradient (the
     score gradient summed over samples, and over heads for [T, S]; exactly 0 where the effective entry is -inf) comes back
     through autograd.  `weights` are taken under the same mask + bias.
+    Per-sample forms (attn_mask and attn_bias alike): [Bm, Hm, T, S] with Bm in {1, B} and Hm in {1, H}, and
+    torch.nn.MultiheadAttention's 3-D [B*H, T, S], read as [B, H, T, S] (index b*H + h); a 3-D tensor whose leading dimension
+    is H keeps the per-head meaning (for B = 1 the two readings coincide).  attn_mask may also be torch.bool in any of these
+    shapes, True hiding the pair (torch's convention).  The scores get the broadcast sum, per sample if either argument is
+    and per head if either is; the kernels' copy of it and of its transpose costs 2 * Bm * Hm * T * S * 4 bytes.  The
+    gradient of attn_bias comes back in the bias's own shape -- [B*H, T, S]: the score gradient; [B, 1, T, S]: summed over
+    the heads of the sample -- whatever the form of the mask beside it.  One spelling stays refused for attn_bias, as it
+    always was: the 4-D [B, H, T, S] with B > 1 and H > 1 (pass bias.reshape(B * H, T, S), a view).  Any other shape: ValueError naming these forms.
     key_padding_mask (the reference's docstring, :56-58): None or a torch.bool / torch.uint8 tensor [B, S] on the inputs'
     device; nonzero / True marks padding: that key is hidden for every head and query of its sample -- probability and
     `weights` exactly 0, d(key) / d(value) rows of a padded position exactly 0 -- alone or beside attn_mask / attn_bias.
@@ -398,16 +466,15 @@ class MultiheadAttention(nn.Module):
         same = lambda a, b: a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
         form = "qkv" if same(query, key) and same(key, value) else "kv" if same(key, value) else "sep"
         if attn_mask is not None:
-            if not torch.is_tensor(attn_mask) or not attn_mask.is_floating_point() or tuple(attn_mask.shape) != (T, S):
-                raise ValueError(f"MultiheadAttention: attn_mask must be a float tensor of shape [{T}, {S}]")
+            if not torch.is_tensor(attn_mask) or not (attn_mask.is_floating_point() or attn_mask.dtype == torch.bool):
+                raise ValueError(f"MultiheadAttention: attn_mask must be a float or torch.bool tensor of shape {_FORMS}")
+            image_lead(attn_mask.shape, B, self.num_heads, T, S, "attn_mask")
             if attn_mask.requires_grad:
                 raise ValueError("MultiheadAttention: attn_mask gets no gradient on the HIP path (requires_grad is set)")
         if attn_bias is not None:
             if not torch.is_tensor(attn_bias) or attn_bias.dtype != torch.float32:
                 raise ValueError("MultiheadAttention: attn_bias must be a float32 tensor")
-            if tuple(attn_bias.shape) not in ((T, S), (self.num_heads, T, S)):
-                raise ValueError(f"MultiheadAttention: attn_bias of shape {tuple(attn_bias.shape)}, expected [{T}, {S}] or "
-                                 f"[{self.num_heads}, {T}, {S}]")
+            image_lead(attn_bias.shape, B, self.num_heads, T, S, "attn_bias")
             if attn_bias.device != query.device:
                 raise ValueError(f"MultiheadAttention: attn_bias on {attn_bias.device}, the inputs on {query.device}")
             if config.is_x3(self.precision or config.precision()):

@@ -410,25 +410,43 @@ def attn_maps(dtype: int, probs) -> None:
 def attn_amasks(masks) -> "C.Array":
     """[(mask, ldm, maskT, ldt)] or [(mask, ldm, maskT, ldt, head_stride, head_strideT)] -> the host array of
     bpm_attn_hmask (bpm_attn_amask plus the two head strides; the attn_*_amask wrappers below launch through the *_hmask
-    entries, which are the *_amask entries at stride 0) that they take beside the problems.  mask: float32 device tensor [T, ldm] added to the scores
+    entries, which are the *_amask entries at stride 0) that they take beside the problems.  A third form, the 8-tuple
+    (mask, ldm, maskT, ldt, head_stride, head_strideT, batch_stride, batch_strideT), builds bpm_attn_bmask instead: sample b
+    reads the image(s) at mask + b * batch_stride (maskT + b * batch_strideT), and every wrapper that takes the array
+    launches through the *_bmask / *_kbmask entry of its family.  mask: float32 device tensor [T, ldm] added to the scores
     of every head (-inf hides the pair; AND the problem's mask_off rule), ldm >= S and a multiple of 4, 16-byte aligned;
     maskT: its transpose [S, ldt] under the same rules, which the dK / dV and maps entries read (None, 0 for forward / dQ
     only).  The head strides (elements; the 4-tuple form: 0) turn them into H images [H, T, ldm] / [H, S, ldt], head h of
     every sample reading its own.  Every query row needs a visible key (not checked)."""
-    arr = (_lib.AttnHMask * len(masks))()
+    per_sample = any(len(t) == 8 for t in masks)
+    arr = ((_lib.AttnBMask if per_sample else _lib.AttnHMask) * len(masks))()
     for a, t in zip(arr, masks):
         m, ldm, mt, ldt = t[:4]
-        hs, hst = t[4:] if len(t) == 6 else (0, 0)
+        hs, hst = t[4:6] if len(t) >= 6 else (0, 0)
         a.mask, a.ldm, a.maskT, a.ldt = _f32(m, "additive attention mask"), ldm, _f32(mt, "additive attention mask (transpose)"), ldt
         a.head_stride, a.head_strideT = hs, hst
+        if per_sample:
+            a.batch_stride, a.batch_strideT = t[6:] if len(t) == 8 else (0, 0)
     return arr
+
+
+def _per_sample(masks) -> bool:
+    """The array came from the 8-tuple form of attn_amasks() (bpm_attn_bmask) or the 4-tuple form of attn_dbias()."""
+    return getattr(masks, "_type_", None) in (_lib.AttnBMask, _lib.AttnDBiasB)
+
+
+def _mask_entry(name: str, masks) -> str:
+    """The entry that takes these additive masks: the *_hmask / *_kamask one, or its per-sample sibling *_bmask / *_kbmask."""
+    if _per_sample(masks):
+        return name.replace("_kamask", "_kbmask").replace("_hmask", "_bmask")
+    return name
 
 
 def _attn_amask(name: str, dtype: int, probs, masks, seed: int) -> None:
     arr = _as_array(AttnProblem, probs)
     if len(masks) != len(arr):
         raise ValueError(f"{name}: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
-    _grouped(name.replace("_amask", "_hmask"), arr, (dtype,), (_seed(seed),), beside=masks)
+    _grouped(_mask_entry(name.replace("_amask", "_hmask"), masks), arr, (dtype,), (_seed(seed),), beside=masks)
 
 
 def attn_fwd_amask(dtype: int, probs, masks, seed: int = 0) -> None:
@@ -448,7 +466,7 @@ def attn_maps_amask(dtype: int, probs, masks) -> None:
     arr = _as_array(AttnMapProblem, probs)
     if len(masks) != len(arr):
         raise ValueError(f"bpm_attn_maps_amask: one additive mask per problem ({len(arr)} problems, {len(masks)} masks)")
-    _grouped("bpm_attn_maps_hmask", arr, (dtype,), beside=masks)
+    _grouped(_mask_entry("bpm_attn_maps_hmask", masks), arr, (dtype,), beside=masks)
 
 
 def _attn_kamask(name: str, dtype: int, probs, kmasks, masks, seed: int) -> None:
@@ -456,7 +474,7 @@ def _attn_kamask(name: str, dtype: int, probs, kmasks, masks, seed: int) -> None
     if len(kmasks) != len(arr) or len(masks) != len(arr):
         raise ValueError(f"{name}: one key mask and one additive mask per problem ({len(arr)} problems, {len(kmasks)} key masks, "
                          f"{len(masks)} additive masks)")
-    _grouped(name, arr, (dtype,), (_seed(seed),), beside=(kmasks, masks))
+    _grouped(_mask_entry(name, masks), arr, (dtype,), (_seed(seed),), beside=(kmasks, masks))
 
 
 def attn_fwd_kamask(dtype: int, probs, kmasks, masks, seed: int = 0) -> None:
@@ -482,7 +500,7 @@ def attn_maps_kamask(dtype: int, probs, kmasks, masks) -> None:
     if _DRY_RUN:
         _DRY_LAUNCHES.append((attn_maps_kamask, dtype, arr, kmasks, masks))
         return
-    _grouped("bpm_attn_maps_kamask", arr, (dtype,), beside=(kmasks, masks))
+    _grouped(_mask_entry("bpm_attn_maps_kamask", masks), arr, (dtype,), beside=(kmasks, masks))
 
 
 def attn_head_map_problem(Q, K, lse, W, ldw, B, H, T, S, dh, dhp, mask_off, *, q_pos0=0, q_stride=1, head_stride=None,
@@ -508,6 +526,8 @@ def _attn_head_maps(fn, name: str, dtype: int, probs, *beside) -> None:
     if _DRY_RUN:
         _DRY_LAUNCHES.append((fn, dtype, arr, *beside))
         return
+    if beside:
+        name = _mask_entry(name, beside[-1])
     _grouped(name, arr, (dtype,), beside=beside if len(beside) > 1 else (beside[0] if beside else None))
 
 
@@ -538,10 +558,25 @@ def attn_dbias(outs) -> "C.Array":
     """[(dB, lddb, head_stride)] -> the host array of bpm_attn_dbias that bpm_attn_bwd_dbias takes beside the problems and
     their masks.  dB: float32 device tensor [T, lddb] (head_stride 0: the gradient summed over samples and heads) or
     [H, T, lddb] with head_stride elements between the images (summed over samples), lddb >= S and a multiple of 4,
-    16-byte aligned.  Columns >= S are left alone."""
-    arr = (_lib.AttnDBias * len(outs))()
-    for a, (dB, lddb, hs) in zip(arr, outs):
-        a.dB, a.lddb, a.head_stride = _f32(dB, "attention bias gradient"), lddb, hs
+    16-byte aligned.  Columns >= S are left alone.  The 4-tuple form (dB, lddb, head_stride, batch_stride) builds
+    bpm_attn_dbias_b: a non-zero batch_stride keeps the samples apart -- [B, H, T, lddb] (dB[b, h] = dS[b, h]) or, with
+    head_stride 0, [B, 1, T, lddb] (summed over the heads of sample b) -- through bpm_attn_bwd_dbias_bmask."""
+    per_sample = any(len(t) == 4 for t in outs)
+    arr = ((_lib.AttnDBiasB if per_sample else _lib.AttnDBias) * len(outs))()
+    for a, t in zip(arr, outs):
+        a.dB, a.lddb, a.head_stride = _f32(t[0], "attention bias gradient"), t[1], t[2]
+        if per_sample:
+            a.batch_stride = t[3] if len(t) == 4 else 0
+    return arr
+
+
+def _as_bmasks(masks) -> "C.Array":
+    """bpm_attn_hmask array -> the same masks as bpm_attn_bmask at batch stride 0 (for the per-sample bias gradient)."""
+    if _per_sample(masks):
+        return masks
+    arr = (_lib.AttnBMask * len(masks))()
+    for a, m in zip(arr, masks):
+        a.mask, a.ldm, a.maskT, a.ldt, a.head_stride, a.head_strideT = m.mask, m.ldm, m.maskT, m.ldt, m.head_stride, m.head_strideT
     return arr
 
 
@@ -552,6 +587,8 @@ def attn_dbias_ws_bytes(probs, outs) -> int:
         raise ValueError(f"bpm_attn_bwd_dbias_ws_bytes: one output per problem ({len(arr)} problems, {len(outs)} outputs)")
     if len(arr) > MAX_GROUP:
         raise ValueError(f"bpm_attn_bwd_dbias: at most {MAX_GROUP} problems per launch")
+    if _per_sample(outs):
+        return int(_lib.lib().bpm_attn_bwd_dbias_bmask_ws_bytes(arr, outs, len(arr)))
     return int(_lib.lib().bpm_attn_bwd_dbias_ws_bytes(arr, outs, len(arr)))
 
 
@@ -568,7 +605,16 @@ def attn_bwd_dbias(dtype: int, probs, masks, outs, seed: int = 0, ws=None, kmask
     if len(arr) > MAX_GROUP:
         raise ValueError(f"bpm_attn_bwd_dbias: at most {MAX_GROUP} problems per launch")
     nbytes = 0 if ws is None else ws.numel() * ws.element_size()
-    if kmasks is None:
+    if _per_sample(masks) or _per_sample(outs):
+        # per-sample masks or a per-sample result: the one entry that takes both (a shared form of either goes in at stride 0)
+        if not _per_sample(outs):
+            b = (_lib.AttnDBiasB * len(outs))()
+            for d, o in zip(b, outs):
+                d.dB, d.lddb, d.head_stride = o.dB, o.lddb, o.head_stride
+            outs = b
+        _lib.check(_lib.lib().bpm_attn_bwd_dbias_bmask(dtype, arr, _as_bmasks(masks), kmasks, outs, len(arr), _seed(seed), _p(ws), nbytes,
+                                                       _stream()), "bpm_attn_bwd_dbias_bmask")
+    elif kmasks is None:
         _lib.check(_lib.lib().bpm_attn_bwd_dbias(dtype, arr, masks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()), "bpm_attn_bwd_dbias")
     else:
         _lib.check(_lib.lib().bpm_attn_bwd_dbias_kmask(dtype, arr, masks, kmasks, outs, len(arr), _seed(seed), _p(ws), nbytes, _stream()),

@@ -234,7 +234,7 @@ int bpm_attn_maps_amask(int dtype, const bpm_attn_map_problem* probs /* host */,
  * [T, ldm] image for all heads -- the *_amask entries, which are these entries at stride 0 (same kernels, same bits).
  * Otherwise head h of every sample reads the image at mask + h*head_stride (maskT + h*head_strideT): H images under the
  * layout and alignment rules above, each of them -- head_stride % 4 == 0, head_stride >= T*ldm (head_strideT >= S*ldt) and
- * below 2^31, or BPM_ERR_ARG.  Per-sample masks do not exist.  The *_amask entries and their struct are unchanged, so
+ * below 2^31, or BPM_ERR_ARG.  Per-sample images: bpm_attn_bmask below.  The *_amask entries and their struct are unchanged, so
  * BPM_ABI_VERSION stays. */
 typedef struct bpm_attn_hmask {
     const float* mask;  int ldm;    /* as bpm_attn_amask */
@@ -342,6 +342,74 @@ int bpm_attn_head_maps_hmask(int dtype, const bpm_attn_head_map_problem* probs /
                              int nprob, void* stream);
 int bpm_attn_head_maps_kamask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
                               const bpm_attn_hmask* masks /* host */, int nprob, void* stream);
+
+/* PER-SAMPLE additive masks and biases (torch.nn.MultiheadAttention's 3-D attn_mask [B*H, T, S], index b*H + h; a
+ * cross-modal window or a time-distance bias over each sample's own time stamps): the *_hmask / *_kamask entries with a
+ * sample stride on the image.  bpm_attn_bmask is bpm_attn_hmask plus batch_stride / batch_strideT (elements, applied to
+ * mask / maskT).  Pair (sample b, head h, query i, key j) reads
+ *   mask [b*batch_stride  + h*head_stride  + i*ldm + j]      (forward, dQ, the bias gradient)
+ *   maskT[b*batch_strideT + h*head_strideT + j*ldt + i]      (dK / dV, both kinds of maps; required there)
+ * so the four combinations of zero and non-zero strides are images of shape [T,S], [H,T,S], [B,1,T,S] and [B,H,T,S].
+ * Every image obeys the layout and alignment rules of bpm_attn_amask (ldm >= S, ldm % 4 == 0, 16-byte aligned base, the
+ * transpose likewise), every head stride the rules of bpm_attn_hmask, and a non-zero batch stride is a multiple of 4, at
+ * least the images of one sample long (H*head_stride, or T*ldm when head_stride == 0; H*head_strideT or S*ldt for the
+ * transpose) and below 2^31.  Visibility, exact zeros, mask_off / q_pos0 / q_stride and the dropout element index
+ * ((b*H + h)*T + i)*S + j are those of the sibling entries, per image.
+ * EVERY QUERY ROW OF EVERY SAMPLE MUST KEEP AT LEAST ONE VISIBLE KEY under all rules together -- not checked; a row
+ * without one yields NaN.
+ * The *_kbmask entries take the key-padding bytes of the *_kamask entries beside the images.
+ * BPM_ERR_ARG, before anything is launched (and without a GPU): every rule of the *_hmask (*_kamask) sibling; a non-zero
+ * batch stride that is no multiple of 4, smaller than the images of one sample, or >= 2^31; dS / Pd set.
+ * Two bit-equalities: (1) at batch stride 0 every entry gives the bits of its *_hmask / *_kamask sibling, with and without
+ * dropout; (2) a [B,H,T,S] image that repeats one [H,T,S] image in every sample gives the bits of the shared-image launch.
+ * (The arithmetic of a sample does not depend on its neighbours: one launch over B samples equals B launches of one.)
+ * Kernels of their own; the existing entries launch what they always did.  New entries only: BPM_ABI_VERSION stays. */
+typedef struct bpm_attn_bmask {
+    const float* mask;  int ldm;    /* as bpm_attn_hmask */
+    const float* maskT; int ldt;
+    int64_t head_stride,  head_strideT;
+    int64_t batch_stride, batch_strideT;    /* elements between the images of consecutive samples; 0: the same image(s) for every sample */
+} bpm_attn_bmask;
+int bpm_attn_fwd_bmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_bmask* masks /* host */, int nprob,
+                       uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_bmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_bmask* masks /* host */, int nprob,
+                          uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_bmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_bmask* masks /* host */, int nprob,
+                           uint64_t seed, void* stream);
+int bpm_attn_maps_bmask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_bmask* masks /* host */, int nprob,
+                        void* stream);
+int bpm_attn_head_maps_bmask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_bmask* masks /* host */,
+                             int nprob, void* stream);
+int bpm_attn_fwd_kbmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                        const bpm_attn_bmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_bwd_dq_kbmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                           const bpm_attn_bmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_bwd_dkv_kbmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                            const bpm_attn_bmask* masks /* host */, int nprob, uint64_t seed, void* stream);
+int bpm_attn_maps_kbmask(int dtype, const bpm_attn_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                         const bpm_attn_bmask* masks /* host */, int nprob, void* stream);
+int bpm_attn_head_maps_kbmask(int dtype, const bpm_attn_head_map_problem* probs /* host */, const bpm_attn_kmask* kmasks /* host */,
+                              const bpm_attn_bmask* masks /* host */, int nprob, void* stream);
+
+/* The bias gradient with a PER-SAMPLE RESULT: bpm_attn_bwd_dbias[_kmask] under per-sample masks, and with two strides on
+ * the result, chosen independently of the mask's form:
+ *   batch_stride != 0, head_stride != 0   dB[b*batch_stride + h*head_stride + i*lddb + j] = dS[b,h,i,j]        ([B,H,T,S])
+ *   batch_stride != 0, head_stride == 0   dB[b*batch_stride + i*lddb + j] = sum over h of dS[b,h,i,j]           ([B,1,T,S])
+ *   batch_stride == 0                      the two forms of bpm_attn_dbias ([H,T,S] / [T,S]), in their order of addition
+ * A workgroup owns a 64 x 64 tile of one image and sums its terms in a fixed order (samples ascending, then heads); the
+ * split through the workspace and the second kernel add in index order: no float atomics, bit-reproducible.
+ * kmasks: the byte masks of a forward pass through bpm_attn_fwd_kbmask, or NULL.  At most BPM_MAX_GROUP problems.
+ * BPM_ERR_ARG: the rules of bpm_attn_bwd_dbias_kmask and of bpm_attn_bmask, and for dB a non-zero batch_stride that is no
+ * multiple of 4, smaller than one sample's images (H*head_stride, or T*lddb when head_stride == 0) or >= 2^31. */
+typedef struct bpm_attn_dbias_b {
+    float* dB; int lddb;            /* as bpm_attn_dbias */
+    int64_t head_stride;
+    int64_t batch_stride;           /* elements between the images of consecutive samples; 0: summed over the samples */
+} bpm_attn_dbias_b;
+size_t bpm_attn_bwd_dbias_bmask_ws_bytes(const bpm_attn_problem* probs /* host */, const bpm_attn_dbias_b* outs /* host */, int nprob);
+int bpm_attn_bwd_dbias_bmask(int dtype, const bpm_attn_problem* probs /* host */, const bpm_attn_bmask* masks /* host */,
+                             const bpm_attn_kmask* kmasks /* host, or NULL */, const bpm_attn_dbias_b* outs /* host */, int nprob,
+                             uint64_t seed, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
  * Row kernels.  All are grouped: `n` problems (<= BPM_MAX_GROUP) per launch,

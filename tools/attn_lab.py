@@ -27,6 +27,11 @@ made of, on the same inputs in the same run, the three alternating in each of th
 *_hmask entries with an all-zeros image, the *_kmask entries and the *_kamask entries with an all-ones byte mask, and the
 latter two again with the last third of every sample's keys padded.  --f32 times everything in float32.
 
+--bmask: the per-sample entries (bpm_attn_fwd_bmask / _bwd_dq_bmask / _bwd_dkv_bmask) beside the *_hmask entries at the same
+shape in the same run, alternating in three rounds: all-zeros images as [H,T,S] through *_hmask, the same through *_bmask at
+batch stride 0, [B,1,T,S] and [B,H,T,S] (one set of images per encoder).  Also prints the image bytes every pass reads,
+from the shapes: at T = S = 512, B = 8, H = 12 a [B,H,T,S] image is 100.7 MB per encoder, the shared [T,S] one 1 MB.
+
 Algorithmic FLOPs per visible (query, key) pair and head: forward 4 dh, dQ pass 6 dh (S, dP, dQ), dK/dV pass 8 dh."""
 import argparse
 import json
@@ -73,6 +78,7 @@ def main():
     ap.add_argument("--per-head", action="store_true", help="with --maps: also time bpm_attn_head_maps on the same buffers")
     ap.add_argument("--amask", action="store_true", help="also time the *_amask entries (all-zeros mask; the future mask as a tensor)")
     ap.add_argument("--kamask", action="store_true", help="also time the *_kamask entries beside the *_kmask and *_hmask entries")
+    ap.add_argument("--bmask", action="store_true", help="also time the *_bmask entries (one all-zeros image per sample) beside the *_hmask entries")
     ap.add_argument("--f32", action="store_true", help="float32 instead of bfloat16")
     ap.add_argument("--pair", type=int, default=-1, help="tuning hook: bit k = kernel k (fwd, dQ, dK/dV) takes two blocks per workgroup")
     a = ap.parse_args()
@@ -163,6 +169,29 @@ def main():
                 r[name] = {"hmask_us": round(uh, 1), "kmask_us": round(uk, 1), "kamask_us": round(uka, 1),
                            "kamask_over_hmask": round(uka / uh, 3), "kamask_over_kmask": round(uka / uk, 3),
                            "rounds_hmask_kmask_kamask_us": [[round(x, 1) for x in y] for y in rounds]}
+    if a.bmask:
+        # per-sample images (the *_bmask entries) beside the shared-image entries at the same shape: all-zeros images, one
+        # set per encoder (nothing is shared between the problems of a launch), three rounds, the middle one reported
+        ldm, ldt = (S + 3) // 4 * 4, (T + 3) // 4 * 4
+
+        def images(Bm, Hm, per_sample):
+            out = []
+            for _ in range(G):
+                m, mt = torch.zeros(Bm, Hm, T, ldm, device=dev), torch.zeros(Bm, Hm, S, ldt, device=dev)
+                hs, hst = (T * ldm, S * ldt) if Hm > 1 else (0, 0)
+                bs, bst = (Hm * T * ldm, Hm * S * ldt) if Bm > 1 else (0, 0)
+                out.append((m, ldm, mt, ldt, hs, hst) + ((bs, bst) if per_sample else ()))
+            return ops.attn_amasks(out), out
+
+        forms = (("hmask_HTS", images(1, H, False), H), ("bmask_HTS_stride0", images(1, H, True), H),
+                 ("bmask_B1TS", images(B, 1, True), B), ("bmask_BHTS", images(B, H, True), B * H))
+        res["bmask"] = {"image_mbytes_per_pass": {tag: round(G * n * T * S * 4 / 1e6, 1) for tag, _, n in forms}}
+        for name, fn in (("fwd", ops.attn_fwd_amask), ("bwd_dq", ops.attn_bwd_dq_amask), ("bwd_dkv", ops.attn_bwd_dkv_amask)):
+            rounds = [[_time(lambda: fn(DT, arr, am, 5), a.iters) for _, (am, _), _ in forms] for _ in range(3)]
+            mid = [sorted(r[i] for r in rounds)[1] for i in range(len(forms))]
+            res["bmask"][name] = {tag + "_us": round(u, 1) for (tag, _, _), u in zip(forms, mid)}
+            res["bmask"][name].update({tag + "_over_hmask": round(u / mid[0], 3) for (tag, _, _), u in list(zip(forms, mid))[1:]})
+            res["bmask"][name]["rounds_us"] = [[round(x, 1) for x in r] for r in rounds]
     if a.maps:
         # LSE of the last forward launch above is in place; maps and forward alternate in one timing loop each, three rounds
         wts = [torch.empty(B, T, S, device=dev) for _ in range(G)]
